@@ -15,11 +15,20 @@ GPU before the timed region and, identically, by the CPU baseline.
 
 One WINDOW is  reset() -> W untimed warm-up steps -> K timed steps  (reset again at every 64th step of a
 window, SURVEY.md 8d, so that the data-carrying phase stays in play).  The timed K steps are bracketed by
-barrier + torch.cuda.synchronize() on both sides.  Because K steps of a 7 us kernel are far too short to
-time once (the driver's --steps 20 is 0.2 ms), the window is REPEATED until >= 0.25 s of timed stream time
-have accumulated; every repeat starts from a reset, so every repeat times the same step indices after a
-reset (`timed_step_indices_after_reset`).  `value` = all env-steps of all timed regions / the sum over
-windows of the slowest rank's wall time.  Rank 0 prints ONE JSON line.
+barrier + torch.cuda.synchronize() on both sides.  Two untimed windows warm the process up first (first launches, first
+use of every pre-staged action tensor; the second also calibrates --repeats 0); then ONE window is timed, so --steps is
+the number of timed steps.
+--repeats R times R windows instead; --repeats 0 repeats the window until >= 0.25 s of timed stream time have
+accumulated (K steps of a 7 us kernel are short to time once).  Every repeat starts from a reset, so every repeat
+times the same step indices after a reset (`timed_step_indices_after_reset`).  `value` = all env-steps of all timed
+regions / the sum over windows of the slowest rank's wall time; `ms_per_step` = that wall time / timed steps.
+Rank 0 prints ONE JSON line.
+
+A plain run measures the headline and nothing else.  --full adds what takes runs of its own: the secondary
+measurements (fused rollout, hipGraph replay, steady state; at N > 1 the other gather forms and the kernel-only
+windows the roofline prices) and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned
+(obs, reward, done of rank 0's envs) as DIR/<name>.npy in float32 / float64; the inputs are a pure function of the
+arguments, so two builds can be compared output for output (not with --repeats 0, whose window count follows the timing).
 
 At N > 1 every env.step() of the timed region is followed by the end-of-step observation gather the north star names:
 ONE RCCL all-gather of the rank's 9*N-byte (obs, reward, done) record, ordered on the step's stream so that step k+1 is
@@ -81,6 +90,26 @@ def measured_traffic(D, N):
     except (OSError, ValueError, KeyError):
         pass
     return None, None
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: bound on what one run writes
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` (name -> 1-d numpy array, one entry per env; integers widened to float64, which holds them exactly)
+    as path/<name>.npy.  Above DUMP_MAX_BYTES in all, every array keeps the same fixed, seeded sample of env indices, written
+    beside them as `env_index`."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_env = sum(a.itemsize for a in arrays.values())
+    if n * per_env > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (per_env + 8), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def host_cores():
@@ -261,7 +290,12 @@ def main():
     ap.add_argument("--devices", type=int, default=4, help="senders per env (D)")
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4),
                     help="BASELINE.json config: 2 = CounterTraffic D=4 (the headline), 3 = D=16, 4 = pendulum env (builder-defined plant)")
-    ap.add_argument("--repeats", type=int, default=0, help="windows to time (0 = as many as give %.2f s of timed stream time)" % MIN_TIMED_S)
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="windows to time (default 1: --steps timed steps; 0 = as many as give %.2f s of timed stream time)" % MIN_TIMED_S)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="length of the CPU-baseline sample")
     ap.add_argument("--no-gather", action="store_true",
@@ -277,13 +311,15 @@ def main():
         rc = launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:],
                           timeout=float(os.environ.get("GW_BENCH_LAUNCH_TIMEOUT", "1700")))
         sys.exit(rc)
+    if not args.full:
+        args.no_secondaries = args.no_cpu_baseline = True
     if args.no_secondaries:
         args.no_rollout = args.no_graph = args.no_steady = True
     if args.config == 3:
         args.devices = 16
     if args.config == 4:
         import bench_pendulum                                    # tools-level module next to this file
-        return bench_pendulum.main(args, emit)
+        return bench_pendulum.main(args, emit, dump_outputs)
     if args.envs is None:
         args.envs = 65536
 
@@ -443,6 +479,9 @@ def main():
         if delta is not None:
             deltas.append(delta)
     env.check()
+    if args.dump_outputs and rank == 0:              # (before the secondaries below write the same record)
+        dump_outputs(args.dump_outputs, {"obs": rec.obs.cpu().numpy(), "reward": rec.reward.cpu().numpy(),
+                                         "done": rec.done.cpu().numpy()})
     env._fb = None                                   # (the secondaries below step without the gather's byte rows)
 
     # the job's time per window is the slowest rank's
@@ -456,7 +495,7 @@ def main():
     kern_how = ("HIP events on the launch stream around each window's K timed launches, summed over the %d windows, / (K * windows) "
                 "(upper bound on the kernel's own duration: includes inter-launch gaps and the reset kernel every %d steps)"
                 % (R, RESET_EVERY))
-    if step_gather is not None:
+    if step_gather is not None and args.full:
         # with a gather behind every step the stream time between the two events is step + collective; the KERNEL's average
         # duration (what the roofline prices) comes from extra windows of the same K steps without the gather
         saved, step_gather_saved = one, step_gather
@@ -717,9 +756,11 @@ def main():
                        "launches_per_step": 1, "stream_ms_per_step": kern_avg_s * 1e3},
             "roofline": roof,
         }
+        if step_gather is not None and not args.full:
+            del out["roofline"]                               # it prices the kernel-only windows that --full runs
         if ranks_info is not None:
             out["ranks"] = ranks_info
-        if multi:
+        if multi and args.full:
             out["gather_forms"] = {"headline": "per-step (value): observations of step k on every rank before step k+1 is launched",
                                    "no_gather": no_gather, "pipelined_gather": pipelined, "chunked_gather": chunked}
         if roll is not None:

@@ -79,7 +79,7 @@ def cpu_baseline(N_gpu, W, K, seconds):
                       "plant recurrence (oracle/plant_oracle.c, one thread), %.1f s" % (n_env - 1, W + K, cores, el)}
 
 
-def main(args, emit=print):
+def main(args, emit=print, dump=None):
     import torch
     from gymwipe_amd import VecInvertedPendulumEnv
     from gymwipe_amd.actions import actions_torch
@@ -132,6 +132,9 @@ def main(args, emit=print):
         if delta:
             deltas.append(delta)
     net.check()
+    if args.dump_outputs:
+        dump(args.dump_outputs, {"obs": penv._obs.cpu().numpy(), "reward": penv._rew.cpu().numpy(),
+                                 "done": penv._done.cpu().numpy(), "sensor_angle": penv._angle.cpu().numpy()})
     wall_total, stream_total = sum(walls), sum(streams)
     kern_avg_s = stream_total / (K * R)
     n_st = max(1, len(deltas))

@@ -3,7 +3,9 @@
 # the C-ABI library (table builder, fast-math validators, queue-encoding fuzz) under ASan + UBSan.
 set -e
 REPO=$(cd "$(dirname "$0")/.." && pwd)
-TMP=${TMPDIR:-/tmp}
+# a directory of this run's own: a fixed name under a shared /tmp may belong to another user or another run
+TMP=$(mktemp -d "${TMPDIR:-/tmp}/gw_sanitize.XXXXXX")
+trap 'rm -rf "$TMP"' EXIT
 gcc -O1 -g -std=c11 -D_GNU_SOURCE -ffp-contract=off -fno-fast-math -fopenmp -fsanitize=address,undefined \
     -fno-sanitize-recover=undefined -shared -fPIC -o $TMP/libct_oracle_san.so $REPO/oracle/ct_oracle.c -lm
 ASAN_OPTIONS=detect_leaks=0 LD_PRELOAD=$(gcc -print-file-name=libasan.so) python3 $REPO/tests/sanitize_oracle_run.py $TMP/libct_oracle_san.so

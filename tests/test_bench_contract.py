@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "128", "--warmup", "64",
-                          "--envs", "8192", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--envs", "8192", "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -42,7 +42,7 @@ def test_bench_prints_one_contract_line():
 @pytest.mark.gpu
 def test_bench_config4_prints_a_contract_line_with_one_launch_per_step():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--steps", "20", "--warmup", "5",
-                          "--envs", "4096", "--repeats", "20", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--envs", "4096", "--repeats", "20", "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -62,7 +62,7 @@ def test_bench_multi_gpu_code_path_runs_on_rccl_with_one_rank():
     the driver's multi-GPU runs make, on the one GPU this box has."""
     env = dict(os.environ, GW_BENCH_FORCE_GATHER="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                          "--envs", "8192", "--repeats", "30", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
+                          "--envs", "8192", "--repeats", "30", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600,
                          cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -89,7 +89,7 @@ def test_plain_bench_gpus_2_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["GW_BENCH_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                          "--envs", "8192", "--repeats", "10"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--envs", "8192", "--repeats", "10", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout[-1000:]
@@ -101,3 +101,60 @@ def test_plain_bench_gpus_2_starts_its_own_ranks():
     assert sorted(e["rank"] for e in r["per_rank"]) == [0, 1] and len({e["pid"] for e in r["per_rank"]}) == 2
     for form in ("no_gather", "pipelined_gather", "chunked_gather"):
         assert "error" not in d["gather_forms"][form], d["gather_forms"][form]
+
+
+def _one_line(out):
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_exactly_its_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """A plain run (no --full) times --steps steps once, reports the headline only, and --dump-outputs writes the outputs of
+    the last timed step: the oracle's after the same windows (two untimed warm-up windows + `repeats` timed ones; a reset
+    does not rewind the env clock, so every window counts) of the same action stream."""
+    import numpy as np
+    from gymwipe_amd.actions import actions_numpy
+    from oracle.ct_oracle import CtOracle
+    N, D, K, W = 1024, 4, 59, 5
+    runs = []
+    for repeats in ("1", "3"):
+        out_dir = tmp_path / ("r" + repeats)
+        d = _one_line(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K),
+                                      "--warmup", str(W), "--envs", str(N), "--repeats", repeats, "--dump-outputs", str(out_dir)],
+                                     capture_output=True, text=True, timeout=600, cwd=ROOT))
+        assert d["steps"] == K and d["warmup"] == W and d["repeats"] == int(repeats) and d["ms_per_step"] > 0
+        assert d["metric"] and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] - N / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for sec in ("cpu_baseline", "fused_rollout", "graph_replay", "steady_state_no_reset", "gather_forms"):
+            assert sec not in d, sec
+        dumped = {k: np.load(str(out_dir / (k + ".npy"))) for k in ("obs", "reward", "done")}
+        assert sorted(p.name for p in out_dir.iterdir()) == ["done.npy", "obs.npy", "reward.npy"]
+        for a in dumped.values():
+            assert a.shape == (N,) and a.dtype in (np.float32, np.float64)
+        runs.append((2 + int(repeats), dumped))
+    orc = CtOracle(N, D, nthreads=8)
+    dev, dur = actions_numpy(1234, 0, N, 0, W + K, D)
+    windows = 0
+    for n_windows, got in runs:
+        while windows < n_windows:
+            for i in range(W + K):
+                if i % 64 == 0:
+                    orc.reset()
+                o, r, dn = orc.step(dev[i], dur[i])
+            windows += 1
+        assert (got["obs"] == o).all() and (got["reward"] == r).all() and (got["done"] == dn).all()
+
+
+@pytest.mark.gpu
+def test_plain_bench_config4_dumps_the_pendulum_outputs(tmp_path):
+    d = _one_line(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--steps", "20", "--warmup", "5",
+                                  "--envs", "4096", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600,
+                                 cwd=ROOT))
+    assert d["steps"] == 20 and d["repeats"] == 1 and "cpu_baseline" not in d
+    import numpy as np
+    for k in ("obs", "reward", "done", "sensor_angle"):
+        a = np.load(str(tmp_path / (k + ".npy")))
+        assert a.shape == (4096,) and a.dtype in (np.float32, np.float64) and np.isfinite(a).all()

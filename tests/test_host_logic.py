@@ -181,6 +181,31 @@ def test_bench_algorithmic_byte_model():
     assert bench.HBM_PEAK == 8.0e12
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_bound(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 / float64 .npy per output (integers exactly, as float64); above the byte bound every
+    array keeps the same seeded sample of envs, written beside them as env_index."""
+    import bench
+    obs = np.arange(1000, dtype=np.int32) * 7919
+    rew = np.linspace(-1, 1, 1000).astype(np.float32)
+    done = (np.arange(1000) % 3 == 0).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "all"), {"obs": obs, "reward": rew, "done": done})
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in ("obs", "reward", "done")}
+    assert got["obs"].dtype == np.float64 and (got["obs"] == obs).all()
+    assert got["reward"].dtype == np.float32 and (got["reward"] == rew).all()
+    assert got["done"].dtype == np.float64 and (got["done"] == done).all()
+    assert not (tmp_path / "all" / "env_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2000)
+    samples = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"obs": obs, "reward": rew, "done": done})
+        idx = np.load(str(tmp_path / run / "env_index.npy")).astype(np.int64)
+        parts = {k: np.load(str(tmp_path / run / (k + ".npy"))) for k in ("obs", "reward", "done")}
+        assert sum(a.nbytes for a in parts.values()) + idx.nbytes <= 2000 and len(idx) > 0
+        assert (np.diff(idx) > 0).all() and (parts["obs"] == obs[idx]).all() and (parts["reward"] == rew[idx]).all()
+        samples.append(idx)
+    assert (samples[0] == samples[1]).all()
+
+
 def test_oracle_is_clean_under_asan_ubsan():
     """tests/sanitize_cpu.sh: the C oracle under AddressSanitizer + UBSan (CPU only; `--host` also runs the
     library's host side, which needs hipcc and takes longer)."""

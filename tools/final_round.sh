@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/final_$TAG
 mkdir -p $OUT
 cd $REPO
-B="python3 bench.py"
+B="python3 bench.py --full --repeats 0"
 run() { name=$1; shift; echo "== $name: $@"; "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "FAILED $name"; tail -5 $OUT/$name.err; }; }
 run bench_driver_cmd              $B --gpus 1 --steps 20 --warmup 5
 run bench_default                 $B

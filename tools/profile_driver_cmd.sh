@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--gpus 1 --steps 20 --warmup 5 $@"
+ARGS="--gpus 1 --steps 20 --warmup 5 --full --repeats 0 $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py $ARGS > $OUT/bench_trace.json 2> $OUT/trace.err
 echo "trace done"
 # counters in their own passes, fewer windows (every launch is serialised by the counter collection)
