@@ -29,7 +29,7 @@ EXPORTS = (
     "gw_abi_version", "gw_last_error", "gw_device_count", "gw_config_default", "gw_create",
     "gw_destroy", "gw_reset", "gw_step", "gw_step_fb", "gw_rollout", "gw_set_position", "gw_set_positions", "gw_received", "gw_delivered", "gw_enqueue", "gw_pack_feedback", "gw_unpack_feedback", "gw_get_state",
     "gw_stats_read", "gw_clear_flags", "gw_state_bytes", "gw_snapshot_bytes", "gw_get_snapshot", "gw_set_state", "gw_link_info", "gw_noise_states", "gw_selftest_queue", "gw_selftest_runq",
-    "gw_selftest_fastmath",
+    "gw_selftest_fastmath", "gw_selftest_launches",
     "gw_plant_config_default", "gw_plant_create", "gw_plant_destroy", "gw_plant_update", "gw_plant_set_input",
     "gw_plant_state_ptr", "gw_plant_get_state", "gw_plant_feedback", "gw_plant_update_feedback", "gw_now_ptr", "gw_pendulum_step",
     "gw_ctrl_config_default", "gw_ctrl_create", "gw_ctrl_destroy", "gw_ctrl_step", "gw_ctrl_get_state",
@@ -209,6 +209,7 @@ def lib():
     L.gw_selftest_runq.argtypes, L.gw_selftest_runq.restype = [C.c_uint64, i32, i32, i32], C.c_int
     L.gw_selftest_fastmath.argtypes = [C.POINTER(Config), C.POINTER(i32)]
     L.gw_selftest_fastmath.restype = C.c_int
+    L.gw_selftest_launches.argtypes, L.gw_selftest_launches.restype = [vp, C.c_char_p, i64], i64
     L.gw_plant_config_default.argtypes, L.gw_plant_config_default.restype = [C.POINTER(PlantConfig), i64], C.c_int
     L.gw_plant_create.argtypes, L.gw_plant_create.restype = [C.POINTER(PlantConfig), C.POINTER(vp)], C.c_int
     L.gw_plant_destroy.argtypes, L.gw_plant_destroy.restype = [vp], C.c_int

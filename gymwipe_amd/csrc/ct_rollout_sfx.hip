@@ -896,11 +896,12 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_kernel(GwState st, GwDevCo
 // the step-synchronous form: the caller's step-major arrays directly (no packing / expanding launches)
 template <int DT>
 int launch_rollout_sync(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
-                        int32_t* obs, float* reward, uint8_t* done, void* stream, bool below_limits)
+                        int32_t* obs, float* reward, uint8_t* done, void* stream, bool below_limits, uint64_t* rec)
 {
     const unsigned blk = 64;
     const unsigned grid = (unsigned)((st.N + blk - 1) / blk);
     const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.fast_ticks;
+    gw_note_launch(rec, GW_LS_ROLLOUT_SYNC + 3 * gw_ls_dt(DT) + (fast ? (below_limits ? 2 : 1) : 0));
     if (fast && below_limits)
         hipLaunchKernelGGL((ct_rollout_sync_kernel<DT, 2>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, cst, K, device, duration, obs, reward, done);
     else if (fast)
@@ -911,11 +912,13 @@ int launch_rollout_sync(const GwState& st, const GwDevConst& cst, int K, const i
 }
 
 template <int DT>
-int launch_rollout(const GwState& st, const GwDevConst& cst, int K, int Kp, const uint16_t* act, uint8_t* fb, void* stream, bool below_limits)
+int launch_rollout(const GwState& st, const GwDevConst& cst, int K, int Kp, const uint16_t* act, uint8_t* fb, void* stream, bool below_limits,
+                   uint64_t* rec)
 {
     const unsigned blk = 64;
     const unsigned grid = (unsigned)((st.N + blk - 1) / blk);
     const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.fast_ticks;
+    gw_note_launch(rec, GW_LS_ROLLOUT + 3 * gw_ls_dt(DT) + (fast ? (below_limits ? 2 : 1) : 0));
     if (fast && below_limits)
         hipLaunchKernelGGL((ct_rollout_sfx_kernel<DT, 2>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, cst, K, Kp, act, fb);
     else if (fast)
@@ -930,7 +933,7 @@ int launch_rollout(const GwState& st, const GwDevConst& cst, int K, int Kp, cons
 // Returns GW_EUNSUPPORTED when this (D, K) has no fused kernel: the caller falls back to K step launches.
 int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
                           int32_t* obs, float* reward, uint8_t* done, uint16_t* act_buf, uint8_t* fb_buf, int k_cap, void* stream,
-                          bool below_limits)
+                          bool below_limits, uint64_t* rec)
 {
     const int Kp = (K + 15) / 16 * 16;
     if (K <= 0 || Kp > k_cap) return GW_EUNSUPPORTED;
@@ -938,16 +941,16 @@ int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const
     const bool event_loop = getenv("GW_ROLLOUT_EVENT_LOOP") != nullptr && act_buf != nullptr && fb_buf != nullptr;
     if (!event_loop) {
         switch (st.D) {
-        case 2:  return launch_rollout_sync<2>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        case 3:  return launch_rollout_sync<3>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        case 4:  return launch_rollout_sync<4>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        case 5:  return launch_rollout_sync<5>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        case 6:  return launch_rollout_sync<6>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        case 7:  return launch_rollout_sync<7>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        case 8:  return launch_rollout_sync<8>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        case 16: return launch_rollout_sync<16>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        case 32: return launch_rollout_sync<32>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);
-        default: return launch_rollout_sync<0>(st, cst, K, device, duration, obs, reward, done, stream, below_limits);   // any other D: per-lane arrays in LDS
+        case 2:  return launch_rollout_sync<2>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        case 3:  return launch_rollout_sync<3>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        case 4:  return launch_rollout_sync<4>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        case 5:  return launch_rollout_sync<5>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        case 6:  return launch_rollout_sync<6>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        case 7:  return launch_rollout_sync<7>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        case 8:  return launch_rollout_sync<8>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        case 16: return launch_rollout_sync<16>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        case 32: return launch_rollout_sync<32>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
+        default: return launch_rollout_sync<0>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);   // any other D: per-lane arrays in LDS
         }
     }
     if (cst.max_duration > 0xfe) return GW_EUNSUPPORTED;  // (the event loop's packed action records hold a byte of duration)
@@ -956,14 +959,14 @@ int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const
     hipLaunchKernelGGL(pack_actions_kernel, dim3(g256), dim3(256), 0, (hipStream_t)stream, N, K, Kp, device, duration, act_buf);
     int rc;
     switch (st.D) {
-    case 2:  rc = launch_rollout<2>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits); break;
-    case 3:  rc = launch_rollout<3>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits); break;
-    case 4:  rc = launch_rollout<4>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits); break;
-    case 6:  rc = launch_rollout<6>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits); break;
-    case 8:  rc = launch_rollout<8>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits); break;
-    case 16: rc = launch_rollout<16>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits); break;
-    case 32: rc = launch_rollout<32>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits); break;
-    default: rc = launch_rollout<0>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits); break;   // any other D (5, 7, ..., 32): per-lane arrays in LDS
+    case 2:  rc = launch_rollout<2>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
+    case 3:  rc = launch_rollout<3>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
+    case 4:  rc = launch_rollout<4>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
+    case 6:  rc = launch_rollout<6>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
+    case 8:  rc = launch_rollout<8>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
+    case 16: rc = launch_rollout<16>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
+    case 32: rc = launch_rollout<32>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
+    default: rc = launch_rollout<0>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;   // any other D (5, 7, ..., 32): per-lane arrays in LDS
     }
     if (rc) return rc;
     hipLaunchKernelGGL(expand_feedback_kernel, dim3(g256), dim3(256), 0, (hipStream_t)stream, N, K, Kp, cst.counter_bound,

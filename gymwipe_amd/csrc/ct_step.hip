@@ -801,14 +801,15 @@ int gw_launch_reset(const GwState& st, const uint8_t* mask, int32_t* obs, void* 
 }
 
 int gw_launch_step(const GwState& st, const int32_t* device, const int32_t* duration,
-                   int32_t* obs, float* reward, uint8_t* done, void* stream)
+                   int32_t* obs, float* reward, uint8_t* done, void* stream, bool no_split, uint64_t* rec)
 {
     const unsigned blk = (unsigned)st.block;
     const unsigned grid = (unsigned)((st.N + blk - 1) / blk);
-    static const bool no_split = getenv("GW_NO_SPLIT") != nullptr;                      // A/B switch
-    const bool split = blk == 64u && !no_split;
+    const bool split = blk == 64u && !no_split;                                         // no_split: GW_NO_SPLIT at gw_create
+    const int pes = st.pe_stats ? 1 : 0;
 #define GW_LAUNCH_SPLIT(DT_)                                                                                     \
     do {                                                                                                        \
+        gw_note_launch(rec, GW_LS_GENERIC + 8 * gw_ls_dt(DT_) + 4 * pes + 1);                                   \
         if (st.pe_stats)                                                                                        \
             hipLaunchKernelGGL((ct_step_kernel<DT_, true, false, true>), dim3(grid), dim3(128), 0, (hipStream_t)stream, \
                                st, device, duration, obs, reward, done);                                        \
@@ -819,6 +820,7 @@ int gw_launch_step(const GwState& st, const int32_t* device, const int32_t* dura
 #define GW_LAUNCH_GENERIC(DT_)                                                                                   \
     do {                                                                                                        \
         if (split && (DT_) > 0) { constexpr int dts_ = ((DT_) > 0) ? (DT_) : 2; GW_LAUNCH_SPLIT(dts_); break; }      \
+        gw_note_launch(rec, GW_LS_GENERIC + 8 * gw_ls_dt(DT_) + 4 * pes);                                       \
         if (st.pe_stats)                                                                                        \
             hipLaunchKernelGGL((ct_step_kernel<DT_, true, false>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, \
                                st, device, duration, obs, reward, done);                                        \
@@ -829,6 +831,7 @@ int gw_launch_step(const GwState& st, const int32_t* device, const int32_t* dura
     if (st.rxp) {                                        // live PHY (open noise-state set / per-env geometry)
 #define GW_LAUNCH_DYN(DT_)                                                                                       \
     do {                                                                                                        \
+        gw_note_launch(rec, GW_LS_GENERIC + 8 * gw_ls_dt(DT_) + 4 * pes + 2);                                   \
         if (st.pe_stats)                                                                                        \
             hipLaunchKernelGGL((ct_step_kernel<DT_, true, true>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, device, duration, obs, reward, done); \
         else                                                                                                    \

@@ -670,9 +670,10 @@ inline int ok_or_ehip() { return hipGetLastError() == hipSuccess ? GW_OK : GW_EH
 
 template <int DT>
 int launch_live(const GwState& st, const int32_t* device, const int32_t* duration, int32_t* obs, float* reward, uint8_t* done,
-                hipStream_t stream)
+                hipStream_t stream, uint64_t* rec)
 {
     const unsigned grid = (unsigned)((st.N + 63) / 64);
+    gw_note_launch(rec, GW_LS_LIVE + 2 * gw_ls_dt(DT) + (st.prx_env ? 1 : 0));
     if (st.prx_env)
         hipLaunchKernelGGL((ct_step_live_kernel<DT, true>), dim3(grid), dim3(64), 0, stream, GW_LEAD_ARGS(st), obs, reward, done);
     else
@@ -683,19 +684,19 @@ int launch_live(const GwState& st, const int32_t* device, const int32_t* duratio
 } // namespace
 
 int gw_launch_step_dyn(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
-                       int32_t* obs, float* reward, uint8_t* done, void* stream)
+                       int32_t* obs, float* reward, uint8_t* done, void* stream, uint64_t* rec)
 {
     (void)cst;
     hipStream_t s = (hipStream_t)stream;
     switch (st.D) {
-    case 2:  return launch_live<2>(st, device, duration, obs, reward, done, s);
-    case 3:  return launch_live<3>(st, device, duration, obs, reward, done, s);
-    case 4:  return launch_live<4>(st, device, duration, obs, reward, done, s);
-    case 6:  return launch_live<6>(st, device, duration, obs, reward, done, s);
-    case 8:  return launch_live<8>(st, device, duration, obs, reward, done, s);
-    case 16: return launch_live<16>(st, device, duration, obs, reward, done, s);
-    case 32: return launch_live<32>(st, device, duration, obs, reward, done, s);
-    default: return launch_live<0>(st, device, duration, obs, reward, done, s);
+    case 2:  return launch_live<2>(st, device, duration, obs, reward, done, s, rec);
+    case 3:  return launch_live<3>(st, device, duration, obs, reward, done, s, rec);
+    case 4:  return launch_live<4>(st, device, duration, obs, reward, done, s, rec);
+    case 6:  return launch_live<6>(st, device, duration, obs, reward, done, s, rec);
+    case 8:  return launch_live<8>(st, device, duration, obs, reward, done, s, rec);
+    case 16: return launch_live<16>(st, device, duration, obs, reward, done, s, rec);
+    case 32: return launch_live<32>(st, device, duration, obs, reward, done, s, rec);
+    default: return launch_live<0>(st, device, duration, obs, reward, done, s, rec);
     }
 }
 

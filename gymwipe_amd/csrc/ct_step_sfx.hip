@@ -794,8 +794,9 @@ hipFunction_t step_function()
 
 template <int DT, int MODE>
 void launch_mode(const GwState& st, unsigned grid, const int32_t* device, const int32_t* duration,
-                 int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, hipStream_t stream)
+                 int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, hipStream_t stream, uint64_t* rec)
 {
+    gw_note_launch(rec, GW_LS_STEP_SFX + 3 * gw_ls_dt(DT) + MODE);
     const uint32_t dev_stage = (uint32_t)st.D | ((uint32_t)st.stage_chunks << 8);
     if (hipFunction_t f = step_function<DT, MODE>()) {
         StepArgs a = {st.ip, st.tw, st.tk, st.qb, device, duration, (uint32_t)st.N, dev_stage, obs, reward, done, fb};
@@ -810,16 +811,16 @@ void launch_mode(const GwState& st, unsigned grid, const int32_t* device, const 
 
 template <int DT>
 int launch(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
-           int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits)
+           int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits, uint64_t* rec)
 {
     const unsigned grid = (unsigned)((st.N + 63) / 64);  // the kernel's compile-time block size is 64
     // every exact fast form validated for this handle (gw_create): the instantiation without their fallbacks -- and, when
     // the host can rule out that any env reaches their validity limits in this launch, without the per-lane limit tests
     const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.idem_states && cst.fast_ticks;
     switch (fast ? (below_limits ? 2 : 1) : 0) {
-    case 2:  launch_mode<DT, 2>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream); break;
-    case 1:  launch_mode<DT, 1>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream); break;
-    default: launch_mode<DT, 0>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream); break;
+    case 2:  launch_mode<DT, 2>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec); break;
+    case 1:  launch_mode<DT, 1>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec); break;
+    default: launch_mode<DT, 0>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec); break;
     }
     return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP;
 }
@@ -829,19 +830,19 @@ inline int ok_or_ehip() { return hipGetLastError() == hipSuccess ? GW_OK : GW_EH
 } // namespace
 
 int gw_launch_step_sfx(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
-                       int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits)
+                       int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits, uint64_t* rec)
 {
     switch (st.D) {
-    case 2:  return launch<2>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    case 3:  return launch<3>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    case 4:  return launch<4>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    case 5:  return launch<5>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    case 6:  return launch<6>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    case 7:  return launch<7>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    case 8:  return launch<8>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    case 16: return launch<16>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    case 32: return launch<32>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
-    default: return launch<0>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits);
+    case 2:  return launch<2>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 3:  return launch<3>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 4:  return launch<4>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 5:  return launch<5>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 6:  return launch<6>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 7:  return launch<7>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 8:  return launch<8>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 16: return launch<16>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 32: return launch<32>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    default: return launch<0>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
     }
 }
 
@@ -874,14 +875,15 @@ int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream)
 }
 
 int gw_launch_pend_step(const GwState& st, const GwDevConst& cst, const GwPlantDev& p, const int32_t* device, const int32_t* duration,
-                        int32_t* obs, float* reward, double* angle_deg, void* stream, bool below_limits)
+                        int32_t* obs, float* reward, double* angle_deg, void* stream, bool below_limits, uint64_t* rec)
 {
     // 32 envs per wave while that still leaves SIMDs without a wave (1024 SIMDs: up to 32 768 envs), else 64
     const bool half = st.N <= 32 * 1024;
     const unsigned grid = (unsigned)((st.N + (half ? 31 : 63)) / (half ? 32 : 64));
     const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.idem_states && cst.fast_ticks;
     const int mode = fast ? (below_limits ? 2 : 1) : 0;
-#define GW_PEND(MODE_, HALF_) hipLaunchKernelGGL((pend_step_kernel<MODE_, HALF_>), dim3(grid), dim3(64), 0, (hipStream_t)stream, GW_LEAD_ARGS(st), p, obs, reward, angle_deg)
+#define GW_PEND(MODE_, HALF_) do { gw_note_launch(rec, GW_LS_PEND + 2 * (MODE_) + (HALF_));                                     \
+        hipLaunchKernelGGL((pend_step_kernel<MODE_, HALF_>), dim3(grid), dim3(64), 0, (hipStream_t)stream, GW_LEAD_ARGS(st), p, obs, reward, angle_deg); } while (0)
     if (half) { if (mode == 2) GW_PEND(2, true); else if (mode == 1) GW_PEND(1, true); else GW_PEND(0, true); }
     else      { if (mode == 2) GW_PEND(2, false); else if (mode == 1) GW_PEND(1, false); else GW_PEND(0, false); }
 #undef GW_PEND

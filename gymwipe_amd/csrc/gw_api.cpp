@@ -17,6 +17,8 @@
 #include <new>
 #include <vector>
 #include <deque>
+#include <atomic>
+#include <string>
 
 namespace {
 
@@ -70,6 +72,8 @@ struct gw_env {
     double       t_limit;     // below this clock value every validated fast form and certainty class holds
     int          captured;    // a launch was recorded into a hipGraph: its replays advance the clocks unseen by t_bound
     int          dyn;         // live-PHY mode (ct_step_dyn.hip): per-env geometry, or a geometry without a finite noise-state set
+    int          no_split;    // GW_NO_SPLIT at gw_create: the generic kernel's one-wave form at block 64
+    uint64_t     launches[GW_LS_COUNT];   // kernel instantiations launched by this handle (gw_selftest_launches)
 };
 
 namespace {
@@ -193,12 +197,13 @@ int launch_step(gw_env* env, const int32_t* device, const int32_t* duration,
                 int32_t* obs, float* reward, uint8_t* done, void* stream, uint8_t* fb, bool* fb_done)
 {
     if (fb_done) *fb_done = false;
-    if (env->dyn && env->st.tk) return gw_launch_step_dyn(env->st, env->cst_host, device, duration, obs, reward, done, stream);
+    if (env->dyn && env->st.tk) return gw_launch_step_dyn(env->st, env->cst_host, device, duration, obs, reward, done, stream, env->launches);
     if (env->st.tk) {
         if (fb_done) *fb_done = true;
-        return gw_launch_step_sfx(env->st, env->cst_host, device, duration, obs, reward, done, fb, stream, gw_env_below_limits(env, stream));
+        return gw_launch_step_sfx(env->st, env->cst_host, device, duration, obs, reward, done, fb, stream, gw_env_below_limits(env, stream),
+                                  env->launches);
     }
-    return gw_launch_step(env->st, device, duration, obs, reward, done, stream);
+    return gw_launch_step(env->st, device, duration, obs, reward, done, stream, env->no_split != 0, env->launches);
 }
 
 // Expand the suffix-encoded queue of one sender into packet byte sizes, head first (gw_queue.h).
@@ -293,6 +298,14 @@ static int derive_env_counts(gw_env* env, GwEnvCounts& c)
 }
 
 void gw_env_add_steps(gw_env* env, uint64_t n) { env->t_bound += (double)n * env->step_max; }
+uint64_t* gw_env_launch_record(gw_env* env) { return env->launches; }
+
+static std::atomic<uint64_t> g_launches[GW_LS_COUNT];     // the whole process's launch record
+void gw_note_launch(uint64_t* rec, int slot)
+{
+    if (rec) ++rec[slot];
+    g_launches[slot].fetch_add(1, std::memory_order_relaxed);
+}
 // May this launch skip the per-lane validity-limit tests of the fast forms?  Only while the host's bound on the simulated
 // time is good: a launch recorded into a hipGraph can be replayed any number of times behind the host's back, so the first
 // capture seen on a handle switches the shortcut off for good (and the captured launch itself keeps the tests).
@@ -419,6 +432,7 @@ int gw_create(const gw_config* cfg, gw_env** out)
                                                     // block size keeps the hidden-argument load off their first cycles)
         st.block = kb ? atoi(kb) : 64;
         if (st.block != 16 && st.block != 32 && st.block != 64 && st.block != 128 && st.block != 256) st.block = 64;
+        env->no_split = getenv("GW_NO_SPLIT") ? 1 : 0;     // A/B switch: the generic kernel's one-wave form at block 64
     }
     GwDevConst* d_cst = nullptr; uint8_t* d_trans = nullptr; double* d_ber = nullptr;
     const size_t tcount = (size_t)R * R * GW_MAX_NSTATES;
@@ -633,7 +647,8 @@ int gw_rollout(gw_env* env, int32_t steps, const int32_t* device_dev, const int3
         const int64_t o = (int64_t)s * N;
         rc = gw_launch_rollout_sfx(env->st, env->cst_host, chunk, device_dev + o, duration_dev + o, obs_dev + o,
                                    reward_dev + o, done_dev + o, env->st.ract, env->st.rfb, env->st.rcap, stream,
-                                   gw_env_below_limits(env, stream) && env->t_bound + (double)(chunk + 1) * env->step_max < env->t_limit);
+                                   gw_env_below_limits(env, stream) && env->t_bound + (double)(chunk + 1) * env->step_max < env->t_limit,
+                                   env->launches);
         if (rc == GW_EUNSUPPORTED) {
             if (getenv("GW_ROLLOUT_STRICT")) return fail(GW_EUNSUPPORTED, "no fused rollout for this handle (GW_ROLLOUT_STRICT is set)");
             break;                                               // (steps > rollout capacity 0, max_duration > 254)
@@ -798,6 +813,7 @@ struct GwSnapHeader {
     int32_t nblocks, dyn;
     uint64_t block_bytes[32];
     double t_bound;
+    int32_t captured, pad;      // the source's launches were recorded into a hipGraph: its t_bound does not bound its clocks
 };
 static const uint32_t kSnapMagic = 0x4e535747u;            // "GWSN"
 
@@ -824,6 +840,7 @@ int gw_get_snapshot(gw_env* env, void* dst, uint64_t bytes)
     h.magic = kSnapMagic; h.abi = GW_ABI_VERSION; h.total = need; h.cfg = env->cfg; h.nblocks = env->nblocks_create; h.dyn = env->dyn;
     for (int i = 0; i < env->nblocks_create; ++i) h.block_bytes[i] = env->block_bytes[i];
     h.t_bound = env->t_bound;
+    h.captured = env->captured;
     uint8_t* o = (uint8_t*)dst;
     memcpy(o, &h, sizeof h);
     o += sizeof h;
@@ -839,7 +856,10 @@ int gw_get_snapshot(gw_env* env, void* dst, uint64_t bytes)
 int gw_set_state(gw_env* env, const void* src, uint64_t bytes)
 {
     if (!env || !src) return fail(GW_EINVAL, "env/src is NULL");
-    if (bytes < sizeof(GwSnapHeader)) return fail(GW_EINVAL, "not a snapshot (too short)");
+    uint64_t need = 0;
+    int rc = gw_snapshot_bytes(env, &need);
+    if (rc) return rc;
+    if (bytes != need) return fail(GW_EINVAL, "a snapshot of this handle has %llu bytes, got %llu", (unsigned long long)need, (unsigned long long)bytes);
     GwSnapHeader h;
     memcpy(&h, src, sizeof h);
     if (h.magic != kSnapMagic || h.abi != (uint32_t)GW_ABI_VERSION || h.total != bytes) return fail(GW_EINVAL, "not a snapshot of this ABI");
@@ -849,8 +869,7 @@ int gw_set_state(gw_env* env, const void* src, uint64_t bytes)
         return fail(GW_EINVAL, "snapshot belongs to a handle with another configuration");
     for (int i = 0; i < h.nblocks; ++i)
         if (h.block_bytes[i] != env->block_bytes[i]) return fail(GW_EINVAL, "snapshot belongs to a handle with another layout");
-    int rc = select_device(env);
-    if (rc) return rc;
+    if ((rc = select_device(env))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     const uint8_t* in = (const uint8_t*)src + sizeof h;
     for (int i = 0; i < h.nblocks; ++i) {
@@ -865,6 +884,7 @@ int gw_set_state(gw_env* env, const void* src, uint64_t bytes)
         HIP_TRY(hipMemcpy(blob + gw_hdr_st_off(D), &env->st, sizeof env->st, hipMemcpyHostToDevice));
     }
     env->t_bound = h.t_bound > env->t_bound ? h.t_bound : env->t_bound;      // (an upper bound either way)
+    env->captured |= h.captured;                                             // ... unless graph replays moved the source's clocks
     HIP_TRY(hipDeviceSynchronize());
     return GW_OK;
 }
@@ -893,6 +913,48 @@ int gw_noise_states(gw_env* env, int32_t radio, int32_t* count, double* values)
     *count = env->tab.nstates[radio];
     if (values) for (int i = 0; i < GW_MAX_NSTATES; ++i) values[i] = i < *count ? env->tab.state_val[radio][i] : 0.0;
     return GW_OK;
+}
+
+// The kernel instantiation behind a launch-record slot (gw_internal.h), spelled as c++filt prints the kernel's symbol.
+static void launch_slot_name(int slot, char* out, size_t cap)
+{
+    static const int dts[GW_LS_NDT] = {2, 3, 4, 5, 6, 7, 8, 16, 32, 0};
+    static const char* const tf[2] = {"false", "true"};
+    if (slot < GW_LS_PEND) {
+        static const char* const fam[3] = {"ct_step_sfx_kernel", "ct_rollout_sync_kernel", "ct_rollout_sfx_kernel"};
+        const int f = slot / (3 * GW_LS_NDT), i = slot % (3 * GW_LS_NDT);
+        snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
+    } else if (slot < GW_LS_GENERIC) {
+        const int i = slot - GW_LS_PEND;
+        snprintf(out, cap, "pend_step_kernel<%d, %s>", i / 2, tf[i % 2]);
+    } else if (slot < GW_LS_LIVE) {
+        const int i = slot - GW_LS_GENERIC;
+        snprintf(out, cap, "ct_step_kernel<%d, %s, %s, %s>", dts[i / 8], tf[(i >> 2) & 1], tf[(i >> 1) & 1], tf[i & 1]);
+    } else {
+        const int i = slot - GW_LS_LIVE;
+        snprintf(out, cap, "ct_step_live_kernel<%d, %s>", dts[i / 2], tf[i % 2]);
+    }
+}
+
+int64_t gw_selftest_launches(gw_env* env, char* out, int64_t cap)
+{
+    if (cap < 0 || (cap > 0 && !out)) return fail(GW_EINVAL, "gw_selftest_launches: bad buffer");
+    std::string text;
+    for (int s = 0; s < GW_LS_COUNT; ++s) {
+        const uint64_t n = env ? env->launches[s] : g_launches[s].load(std::memory_order_relaxed);
+        if (!n) continue;
+        char line[96];
+        launch_slot_name(s, line, sizeof line);
+        text += line;
+        snprintf(line, sizeof line, " %llu\n", (unsigned long long)n);
+        text += line;
+    }
+    if (cap > 0) {
+        const size_t k = text.size() < (size_t)cap ? text.size() : (size_t)cap - 1;
+        memcpy(out, text.data(), k);
+        out[k] = 0;
+    }
+    return (int64_t)text.size();
 }
 
 // Host-only: which exact fast paths gw_create would enable for cfg (bit 0 fmod, 1 division,

@@ -269,21 +269,22 @@ int gw_build_tables(const gw_config& cfg, GwHostTables& out, char* msg, size_t m
 int gw_launch_init(const GwState& st, void* stream);
 int gw_launch_reset(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream);
 int gw_launch_step(const GwState& st, const int32_t* device, const int32_t* duration,
-                   int32_t* obs, float* reward, uint8_t* done, void* stream);
+                   int32_t* obs, float* reward, uint8_t* done, void* stream, bool no_split, uint64_t* rec);
 int gw_launch_received(const GwState& st, int32_t* out, void* stream);
 int gw_launch_enqueue(const GwState& st, int sender, const int32_t* payload_bytes, void* stream);
 int gw_launch_step_sfx(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
-                       int32_t* obs, float* reward, uint8_t* done, uint8_t* feedback_byte, void* stream, bool below_limits);
+                       int32_t* obs, float* reward, uint8_t* done, uint8_t* feedback_byte, void* stream, bool below_limits,
+                       uint64_t* rec);
 int gw_launch_reset_sfx(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream);
 int gw_launch_init_sfx(const GwState& st, void* stream);
 int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
                           int32_t* obs, float* reward, uint8_t* done, uint16_t* act_buf, uint8_t* fb_buf, int k_cap, void* stream,
-                          bool below_limits);
+                          bool below_limits, uint64_t* rec);
 int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream);
 int gw_launch_delivered_sfx(const GwState& st, uint32_t* out, void* stream);
 int gw_launch_clear_flags(const GwState& st, void* stream);          // ct_step_sfx.hip (both queue modes)
 int gw_launch_step_dyn(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
-                       int32_t* obs, float* reward, uint8_t* done, void* stream);
+                       int32_t* obs, float* reward, uint8_t* done, void* stream, uint64_t* rec);
 int gw_launch_init_dyn(const GwState& st, const GwDevConst& cst, double thermal, void* stream);
 int gw_launch_set_position(const GwState& st, const GwDevConst& cst, int radio, const double* xs, const double* ys,
                            const double* all_pos, const uint8_t* mask, void* stream);
@@ -297,3 +298,23 @@ int gw_launch_unpack_feedback(int64_t count, int center, int pv, const uint8_t* 
                                        // than 100 packets per tick only ever leaves the last 100 in the queue).  gw_ceil_div's
                                        // reciprocal is exact for len <= 100 up to multiplicity 256 (checked exhaustively by
                                        // tests/test_host_logic.py), the kernels' 24-bit multiplies far beyond.
+
+// Launch record (gw_selftest_launches): one slot per instantiation of the step / rollout kernel families, counted by the
+// launcher that picks the instantiation -- in the handle's own array (rec, may be null) and in the process-wide one (a relaxed
+// atomic).  Slot = family base + sender-count index (gw_ls_dt) x the family's template combinations + their index; names are
+// formatted only by the query (gw_api.cpp).
+enum {
+    GW_LS_NDT = 10,                                        // DT in {2, 3, 4, 5, 6, 7, 8, 16, 32, 0 = any D}
+    GW_LS_STEP_SFX = 0,                                    // ct_step_sfx_kernel<DT, MODE>: 3 per DT
+    GW_LS_ROLLOUT_SYNC = GW_LS_STEP_SFX + 3 * GW_LS_NDT,   // ct_rollout_sync_kernel<DT, MODE>
+    GW_LS_ROLLOUT = GW_LS_ROLLOUT_SYNC + 3 * GW_LS_NDT,    // ct_rollout_sfx_kernel<DT, MODE> (event loop)
+    GW_LS_PEND = GW_LS_ROLLOUT + 3 * GW_LS_NDT,            // pend_step_kernel<MODE, HALF>: 6
+    GW_LS_GENERIC = GW_LS_PEND + 6,                        // ct_step_kernel<DT, PER_ENV_STATS, DYN, SPLIT>: 8 per DT
+    GW_LS_LIVE = GW_LS_GENERIC + 8 * GW_LS_NDT,            // ct_step_live_kernel<DT, PER_ENV>: 2 per DT
+    GW_LS_COUNT = GW_LS_LIVE + 2 * GW_LS_NDT
+};
+constexpr int gw_ls_dt(int DT)
+{
+    return DT == 2 ? 0 : DT == 3 ? 1 : DT == 4 ? 2 : DT == 5 ? 3 : DT == 6 ? 4 : DT == 7 ? 5 : DT == 8 ? 6 : DT == 16 ? 7 : DT == 32 ? 8 : 9;
+}
+void gw_note_launch(uint64_t* rec, int slot);              // gw_api.cpp

@@ -385,6 +385,13 @@ int gw_selftest_runq(uint64_t seed, int32_t operations, int32_t mult, int32_t co
  * noise-state map, 16 counter ticks counted in one jump); negative on error.  max_noise_states may be NULL. */
 int gw_selftest_fastmath(const gw_config* cfg, int32_t* max_noise_states);
 
+/* Test hook: the step / rollout kernel instantiations launched by this handle since gw_create (env != NULL), or by the whole
+ * process (env == NULL), one line each: "<kernel><template args> <count>\n", spelled as c++filt prints the kernel's symbol,
+ * e.g. "ct_step_sfx_kernel<4, 2> 37".  A launch captured into a hipGraph counts once, however often it is replayed.
+ * Writes at most cap bytes incl. the NUL (out may be NULL when cap is 0); returns the length needed without the NUL,
+ * negative on error. */
+int64_t gw_selftest_launches(gw_env* env, char* out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

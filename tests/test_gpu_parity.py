@@ -716,6 +716,9 @@ def test_generic_kernel_two_wave_form_ragged_sizes_bad_actions_and_totals(D, N):
                             ("popped", "n_popped"), ("dropped", "n_dropped")):
                 assert st[name] == int(orc.get(f).sum()), name
             results.append({f: env.get_state(f).copy() for f in ("now", "queue", "rx_power", "counter")})
+            # the launch record says which form ran: walker + helper waves, then (GW_NO_SPLIT) the one-wave form
+            from test_kernel_variants import launches
+            assert set(launches(env)) == {"ct_step_kernel<%d, true, false, %s>" % (D, "false" if no_split else "true")}, launches(env)
         finally:
             os.environ.pop("GW_NO_SPLIT", None)
     for f in results[0]:
@@ -914,6 +917,63 @@ def test_snapshot_and_restore_continue_bit_for_bit(kw):
     other = VecCounterTrafficEnv(N, num_devices=D, multiplicity=[1, 1, 1, 1], **kw)   # another configuration refuses it
     with pytest.raises(Exception):
         other.restore(snap)
+
+
+def test_restore_after_graph_replays_keeps_the_limit_tests():
+    """A handle whose steps were captured into a hipGraph and replayed has clocks its host-side time bound never saw.  A
+    fresh handle restored from its snapshot must not trust that bound: past 10^6 s it launches the default step kernel
+    WITH the per-lane limit tests (MODE 1), never the form without them (MODE 2), and stays equal to the oracle."""
+    import torch
+    from gymwipe_amd import VecCounterTrafficEnv
+    from test_kernel_variants import launches
+    N, D, G, R = 1000, 4, 8, 12
+    env, orc = _mk(N, D, start_time=999999.5)          # the bound counts the 8 captured steps: 999999.5 + 8 x ~21 ms
+    dev, dur = action_stream(123, G * R + 8, N, D)
+    assert (env.reset().cpu().numpy() == orc.reset()).all()
+    a_dev = torch.zeros((G, N), dtype=torch.int32, device="cuda")
+    a_dur = torch.zeros((G, N), dtype=torch.int32, device="cuda")
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for j in range(G):
+            env.step({"device": a_dev[j], "duration": a_dur[j]})
+    for rep in range(R):
+        a_dev.copy_(torch.from_numpy(dev[rep * G:(rep + 1) * G]))
+        a_dur.copy_(torch.from_numpy(dur[rep * G:(rep + 1) * G]))
+        graph.replay()
+        torch.cuda.synchronize()
+        for j in range(G):
+            orc.step(dev[rep * G + j], dur[rep * G + j])
+    assert (env.get_state("now") > 1e6).mean() > 0.5                 # most clocks are past the fast forms' limit
+    snap = env.snapshot()
+    fresh = VecCounterTrafficEnv(N, num_devices=D, per_env_stats=True, start_time=999999.5)
+    fresh.restore(snap)
+    assert_state_equal(fresh, orc, STATE_FIELDS + STAT_FIELDS, where="after the restore")
+    for k in range(G * R, G * R + 8):
+        o, r, d, _ = fresh.step({"device": torch.from_numpy(dev[k]), "duration": torch.from_numpy(dur[k])})
+        oo, orr, od = orc.step(dev[k], dur[k])
+        assert (o.cpu().numpy() == oo).all() and (r.cpu().numpy() == orr).all() and (d.cpu().numpy() == od).all(), k
+    assert launches(fresh) == {"ct_step_sfx_kernel<4, 1>": 8}, launches(fresh)
+    assert_state_equal(fresh, orc, STATE_FIELDS + STAT_FIELDS, where="after steps on the restored handle")
+
+
+def test_restore_refuses_a_blob_shorter_than_the_snapshot():
+    """gw_set_state takes exactly gw_snapshot_bytes of this handle: a shorter blob whose header has been patched to claim
+    that length is refused with EINVAL before anything is copied.  (The blob is a prefix view of the full snapshot, so a
+    copy past its end would still read allocated memory.)"""
+    import ctypes as C
+    from gymwipe_amd import VecCounterTrafficEnv, _native as nat
+    env = VecCounterTrafficEnv(1000, num_devices=4)
+    env.reset()
+    snap = env.snapshot()
+    short = snap[:snap.nbytes - 4096]
+    assert short.base is snap or short.base is snap.base              # a view: its bytes stay inside the full buffer
+    total = np.frombuffer(short[8:16], dtype=np.uint64)               # GwSnapHeader.total (after magic and abi)
+    assert int(total[0]) == snap.nbytes
+    short[8:16] = np.array([short.nbytes], dtype=np.uint64).view(np.uint8)
+    rc = env._L.gw_set_state(env._h, short.ctypes.data, short.nbytes)
+    assert rc == nat.EINVAL, rc
+    short[8:16] = np.array([snap.nbytes], dtype=np.uint64).view(np.uint8)
+    assert env._L.gw_set_state(env._h, snap.ctypes.data, C.c_uint64(snap.nbytes)) == nat.OK
 
 
 def test_derived_event_counts_equal_counted_ones():

@@ -424,3 +424,76 @@ def test_bench_self_launch_happens_before_torch_is_imported():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
     assert out.returncode == 5, (out.stdout, out.stderr[-2000:])
+
+
+# ---- the kernel catalogue: every instantiation of the step / rollout families has a GPU parity recipe ----------------------
+KERNEL_FAMILIES = ("ct_step_sfx_kernel", "ct_rollout_sync_kernel", "ct_rollout_sfx_kernel", "pend_step_kernel",
+                   "ct_step_kernel", "ct_step_live_kernel")
+# templated kernels outside this catalogue, with checkers of their own (tests/test_grid.py, tests/test_control_loop.py)
+KERNELS_OUT_OF_SCOPE = ("grid_run_kernel",)
+
+
+def _library_kernel_instantiations(path):
+    """Every `<name>_kernel<...>` template instantiation in the library's symbol table, as c++filt spells it (no namespace,
+    no parameter list)."""
+    nm = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
+    dem = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True, check=True).stdout
+    names = set()
+    for line in dem.splitlines():
+        if "__device_stub__" in line:
+            continue
+        m = re.search(r"(?:^|[\s:])(\w+_kernel<[^()]*>)\(", line)
+        if m:
+            names.add(m.group(1))
+    return names
+
+
+def test_every_kernel_instantiation_has_a_gpu_recipe(native_lib):
+    """tests/test_kernel_variants.py runs one oracle-parity case per instantiation.  An instantiation added to the library
+    (a new `case 12:` in a launcher), or a new templated kernel family, fails here until a recipe -- or an explicit,
+    commented entry in UNREACHABLE / KERNELS_OUT_OF_SCOPE -- covers it."""
+    from gymwipe_amd import _native
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_kernel_variants as kv
+    names = _library_kernel_instantiations(_native.LIB_PATH)
+    families = {n.split("<")[0] for n in names}
+    assert families - set(KERNEL_FAMILIES) - set(KERNELS_OUT_OF_SCOPE) == set(), "templated kernel family without recipes"
+    lib_set = {n for n in names if n.split("<")[0] in KERNEL_FAMILIES}
+    assert len(lib_set) >= 134
+    covered = set(kv.RECIPES) | set(kv.UNREACHABLE)
+    assert not set(kv.RECIPES) & set(kv.UNREACHABLE)
+    assert sorted(lib_set - covered) == [], "instantiations without a recipe"
+    assert sorted(covered - lib_set) == [], "recipes for instantiations the library does not have"
+    for name, r in kv.RECIPES.items():
+        assert r["target"] == name and name in r["declared"] and r["declared"] <= lib_set, name
+
+
+def test_recorded_open_layouts_are_still_open(native_lib):
+    """The layouts test_kernel_variants.py gives ct_step_live_kernel<D, false> must still have no finite noise-state set at
+    that D (gw_selftest_fastmath reports MAX_NSTATES + 1), else their recipes would quietly test another kernel."""
+    from gymwipe_amd import _native
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_kernel_variants as kv
+    for D, seed in sorted(kv.OPEN_LAYOUT_SEEDS.items()):
+        pos, rrm, extra = kv.open_layout(D, seed)
+        cfg = _native.default_config(16, D)
+        for i, (x, y) in enumerate(pos):
+            cfg.pos[i][0], cfg.pos[i][1] = x, y
+        cfg.pos[D][0], cfg.pos[D][1] = rrm
+        for (a, b), db in extra.items():
+            cfg.extra_att_db[a][b] = cfg.extra_att_db[b][a] = db
+        mx = C.c_int32()
+        assert native_lib.gw_selftest_fastmath(C.byref(cfg), C.byref(mx)) >= 0, D
+        assert mx.value == _native.MAX_NSTATES + 1, (D, seed, mx.value)
+        assert kv.RECIPES["ct_step_live_kernel<%d, false>" % D]["kw"]["extra_attenuation"] == extra
+
+
+def test_launch_record_query_without_a_gpu(native_lib):
+    """gw_selftest_launches: the process-wide record is readable without a handle; the size query and the truncation rule
+    (cap bytes incl. the NUL) hold, and a bad buffer is refused."""
+    need = native_lib.gw_selftest_launches(None, None, 0)
+    assert need >= 0
+    buf = C.create_string_buffer(need + 1)
+    assert native_lib.gw_selftest_launches(None, buf, len(buf)) == need and len(buf.value) == need
+    assert native_lib.gw_selftest_launches(None, None, 8) < 0
+    assert native_lib.gw_selftest_launches(None, buf, -1) < 0
