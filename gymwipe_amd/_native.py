@@ -244,8 +244,10 @@ _fast = False
 
 def fast():
     """The CPython fast-call shim for the per-step entry points (csrc/gw_pyfast.c), bound to the loaded library's
-    gw_step / gw_pendulum_step -- or None when it has not been built (the callers then go through ctypes: same
-    library, same kernels, ~1 us more host time per call)."""
+    gw_step / gw_step_fb / gw_pendulum_step / gw_reset -- or None when it has not been built or GW_NO_PYFAST is set (the
+    callers then go through ctypes: same library, same kernels, ~1 us more host time per call).  Its ``Stepper`` type is
+    ``VecCounterTrafficEnv.step``'s common case as one native call (GW_NO_FASTSTEP=1 at env construction keeps the shim but
+    not the stepper: the A/B switch of tools/host_overhead.py)."""
     global _fast
     if _fast is False:
         _fast = None
@@ -260,7 +262,7 @@ def fast():
                 loader.exec_module(mod)
                 L = lib()
                 mod.bind(C.cast(L.gw_step, C.c_void_p).value, C.cast(L.gw_pendulum_step, C.c_void_p).value,
-                         C.cast(L.gw_step_fb, C.c_void_p).value)
+                         C.cast(L.gw_step_fb, C.c_void_p).value, C.cast(L.gw_reset, C.c_void_p).value)
                 _fast = mod
             except Exception:
                 _fast = None

@@ -190,6 +190,9 @@ __device__ __forceinline__ double& gw_rx(const GwState& st, int R, int j, int64_
 //    device-visible memory (tools/launch_floor.hip).
 #define GW_LEAD_PARAMS uint32_t* __restrict__ ip, double* __restrict__ tw, uint32_t* __restrict__ tk, uint8_t* __restrict__ qb, \
                        const int32_t* __restrict__ device, const int32_t* __restrict__ duration, uint32_t n_envs, uint32_t dev_stage
+// (the same block with the addresses declared as integers: ct_step_sfx_kernel)
+#define GW_LEAD_PARAMS_U64 uint64_t ip_a, uint64_t tw_a, uint64_t tk_a, uint64_t qb_a, uint64_t device_a, uint64_t duration_a, \
+                           uint32_t n_envs, uint32_t dev_stage
 // dev_stage: sender count | chunks of the tables to stage << 8 (one argument: the preload window holds 14 dwords)
 #define GW_LEAD_ARGS(st_) (st_).ip, (st_).tw, (st_).tk, (st_).qb, device, duration, (uint32_t)(st_).N, \
                           ((uint32_t)(st_).D | ((uint32_t)(st_).stage_chunks << 8))
@@ -216,6 +219,13 @@ template <class T>
 __device__ __forceinline__ T* gw_as_global(T* p)
 {
     return (T*)(__attribute__((address_space(1))) T*)p;
+}
+// The same for an address that arrives as an INTEGER (ct_step_sfx_kernel's arguments): converted straight to a global pointer.
+// (Through a generic pointer first, the two casts above cancel out and the accesses are flat again.)
+template <class T>
+__device__ __forceinline__ T* gw_global_at(uint64_t address)
+{
+    return (T*)(__attribute__((address_space(1))) T*)address;
 }
 template <int DT>
 __device__ __forceinline__ GwState hdr_state(uint32_t* ip, double* tw, uint32_t* tk, uint8_t* qb, uint32_t n_envs, int n_dev)

@@ -558,10 +558,24 @@ __device__ __forceinline__ void ct_step_sfx_body(const GwState& st, const GwDevC
 }
 
 // (kernel arguments and the header in front of the `ip` records: GW_LEAD_PARAMS, hdr_state, hdr_const in ct_common.hip.h)
+// The eleven addresses are declared as 64-bit INTEGERS (GW_LEAD_PARAMS_U64, same 88-byte block, same preloaded leading
+// arguments): for every parameter of pointer type the runtime looks the address up among its allocations on each launch, and
+// the host's enqueue rate is what limits the light phases (tools/launch_floor.hip measures both forms).
+// Converted straight to global-address-space pointers (gw_global_at): a kernel ARGUMENT of pointer type is known to be global,
+// an integer is not, and through a generic pointer the wave's first loads would become flat loads.
 template <int DT, int MODE>
-__global__ __launch_bounds__(64) void ct_step_sfx_kernel(GW_LEAD_PARAMS, int32_t* __restrict__ obs, float* __restrict__ reward,
-                                                        uint8_t* __restrict__ done, uint8_t* __restrict__ fb)
+__global__ __launch_bounds__(64) void ct_step_sfx_kernel(GW_LEAD_PARAMS_U64, uint64_t obs_a, uint64_t reward_a, uint64_t done_a, uint64_t fb_a)
 {
+    uint32_t* __restrict__ ip = gw_global_at<uint32_t>(ip_a);
+    double* __restrict__ tw = gw_global_at<double>(tw_a);
+    uint32_t* __restrict__ tk = gw_global_at<uint32_t>(tk_a);
+    uint8_t* __restrict__ qb = gw_global_at<uint8_t>(qb_a);
+    const int32_t* __restrict__ device = gw_global_at<const int32_t>(device_a);
+    const int32_t* __restrict__ duration = gw_global_at<const int32_t>(duration_a);
+    int32_t* __restrict__ obs = gw_global_at<int32_t>(obs_a);
+    float* __restrict__ reward = gw_global_at<float>(reward_a);
+    uint8_t* __restrict__ done = gw_global_at<uint8_t>(done_a);
+    uint8_t* __restrict__ fb = gw_global_at<uint8_t>(fb_a);
     const int n_dev = (int)(dev_stage & 0xffu);
     const GwState st = hdr_state<DT>(ip, tw, tk, qb, n_envs, n_dev);
     const GwDevConst c = hdr_const<DT>(ip, n_dev);
@@ -710,33 +724,43 @@ __global__ void ct_init_sfx_kernel(GwState st)
 
 // counter_traffic.py:135-144 + :69-73 -- counters and interpreter only; time is NOT rewound.
 // In the suffix encoding "counters <- 0" is a new breakpoint (tau, 0).
-__global__ void ct_reset_sfx_kernel(GwState st, const uint8_t* __restrict__ mask, int32_t* __restrict__ obs)
+// Arguments as the step kernel's (ct_common.hip.h): the `ip` address and what changes per call; the handle's GwState and
+// GwDevConst are read from the header in front of the `ip` records, the two constants through the constant address space.
+// bench.py's window resets every 64th step: with the whole GwState by value this launch cost the host what the step launch
+// did before it got the same treatment.
+__global__ void ct_reset_sfx_kernel(uint32_t* __restrict__ ip, uint32_t n_envs, uint32_t n_dev, const uint8_t* __restrict__ mask,
+                                    int32_t* __restrict__ obs)
 {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (uint32_t)st.N) return;
+    if (e >= n_envs) return;
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(ip) - gw_blob_header((int)n_dev);
+    const GW_AS_CONST GwState* hs = (const GW_AS_CONST GwState*)(base + gw_hdr_st_off((int)n_dev));
+    uint32_t* tkp = gw_as_global(hs->tk);
+    GwBp* bph = gw_as_global(hs->bph);
+    const GW_AS_CONST GwDevConst* c = (const GW_AS_CONST GwDevConst*)(base + gw_hdr_cst_off((int)n_dev));
     const uint32_t o16 = e << 4;
     uint32_t rvm;
     if (!mask || mask[e]) {
-        uint4 tk = ld<uint4>(st.tk, o16);
-        uint4 bp = ld<uint4>(st.ip, o16);          // {newest (t0, c0), second newest (t0, c0)}
+        uint4 tk = ld<uint4>(tkp, o16);
+        uint4 bp = ld<uint4>(ip, o16);             // {newest (t0, c0), second newest (t0, c0)}
         GwBp cur; cur.t0 = bp.x; cur.c0 = 0u;
         if (bp.x == tk.x) {                        // no tick since the newest breakpoint: overwrite it
-            st.bph[((size_t)e << 7) + ((tk.y - 1u) & GW_RING_MASK)] = cur;
+            bph[((size_t)e << 7) + ((tk.y - 1u) & GW_RING_MASK)] = cur;
             bp.y = 0u;
         } else {
             bp.z = bp.x; bp.w = bp.y;              // old newest becomes second newest
             cur.t0 = tk.x;
-            st.bph[((size_t)e << 7) + (tk.y & GW_RING_MASK)] = cur;
+            bph[((size_t)e << 7) + (tk.y & GW_RING_MASK)] = cur;
             tk.y += 1u; bp.x = cur.t0; bp.y = 0u;
         }
         tk.z = 0u; tk.w = 0u;                      // interpreter.reset(): receivedValues, lastAbs, done
-        st_(st.tk, o16, tk);
-        st_(st.ip, o16, bp);
+        st_(tkp, o16, tk);
+        st_(ip, o16, bp);
         rvm = 0u;
     } else {
-        rvm = ld<uint4>(st.tk, o16).z;
+        rvm = ld<uint4>(tkp, o16).z;
     }
-    if (obs) obs[e] = st.cst->payload_value * ((int)(rvm & 1u) - (int)((rvm >> 1) & 1u)) + st.cst->counter_bound;
+    if (obs) obs[e] = c->payload_value * ((int)(rvm & 1u) - (int)((rvm >> 1) & 1u)) + c->counter_bound;
 }
 
 __global__ void ct_received_sfx_kernel(GwState st, int32_t* __restrict__ out)
@@ -772,77 +796,101 @@ __global__ void ct_clear_flags_kernel(GwState st)
 // path looks the kernel up by its host address and copies twelve arguments one by one, 0.36 us more per launch on the host
 // (tools/launch_floor.hip: 3.31 -> 2.95 us) -- and the host's enqueue rate is what limits the light phases of a rollout.
 struct StepArgs {
-    uint32_t* ip; double* tw; uint32_t* tk; uint8_t* qb; const int32_t* device; const int32_t* duration;
+    uint64_t ip, tw, tk, qb, device, duration;         // addresses as integers: see ct_step_sfx_kernel
     uint32_t n_envs, dev_stage;
-    int32_t* obs; float* reward; uint8_t* done; uint8_t* fb;
+    uint64_t obs, reward, done, fb;
 };
 static_assert(sizeof(StepArgs) == 88, "StepArgs must mirror ct_step_sfx_kernel's parameter list");
 
-template <int DT, int MODE>
-hipFunction_t step_function()
+template <class K>
+void* function_of(K kernel)                            // for the CURRENT device; null when the runtime cannot tell
 {
-    static hipFunction_t fn[16] = {};                  // per device: a module's functions belong to the device it was loaded on
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    if (!fn[dev]) {
-        hipFunction_t f = nullptr;
-        if (hipGetFuncBySymbol(&f, reinterpret_cast<const void*>(&ct_step_sfx_kernel<DT, MODE>)) != hipSuccess) { (void)hipGetLastError(); f = nullptr; }
-        fn[dev] = f;
-    }
-    return fn[dev];
+    hipFunction_t f = nullptr;
+    if (hipGetFuncBySymbol(&f, reinterpret_cast<const void*>(kernel)) != hipSuccess) { (void)hipGetLastError(); f = nullptr; }
+    return f;
 }
 
 template <int DT, int MODE>
-void launch_mode(const GwState& st, unsigned grid, const int32_t* device, const int32_t* duration,
-                 int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, hipStream_t stream, uint64_t* rec)
+hipError_t launch_mode(const GwState& st, unsigned grid, const int32_t* device, const int32_t* duration,
+                       int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, hipStream_t stream, uint64_t* rec, void* fn)
 {
     gw_note_launch(rec, GW_LS_STEP_SFX + 3 * gw_ls_dt(DT) + MODE);
     const uint32_t dev_stage = (uint32_t)st.D | ((uint32_t)st.stage_chunks << 8);
-    if (hipFunction_t f = step_function<DT, MODE>()) {
-        StepArgs a = {st.ip, st.tw, st.tk, st.qb, device, duration, (uint32_t)st.N, dev_stage, obs, reward, done, fb};
+    if (fn) {
+        StepArgs a = {(uint64_t)st.ip, (uint64_t)st.tw, (uint64_t)st.tk, (uint64_t)st.qb, (uint64_t)device, (uint64_t)duration,
+                      (uint32_t)st.N, dev_stage, (uint64_t)obs, (uint64_t)reward, (uint64_t)done, (uint64_t)fb};
         size_t size = sizeof a;
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-        (void)hipModuleLaunchKernel(f, grid, 1, 1, 64, 1, 1, 0, stream, nullptr, extra);
-        return;
+        return hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, 64, 1, 1, 0, stream, nullptr, extra);
     }
-    hipLaunchKernelGGL((ct_step_sfx_kernel<DT, MODE>), dim3(grid), dim3(64), 0, stream, st.ip, st.tw, st.tk, st.qb, device, duration,
-                       (uint32_t)st.N, dev_stage, obs, reward, done, fb);
+    hipLaunchKernelGGL((ct_step_sfx_kernel<DT, MODE>), dim3(grid), dim3(64), 0, stream, (uint64_t)st.ip, (uint64_t)st.tw, (uint64_t)st.tk,
+                       (uint64_t)st.qb, (uint64_t)device, (uint64_t)duration, (uint32_t)st.N, dev_stage, (uint64_t)obs, (uint64_t)reward,
+                       (uint64_t)done, (uint64_t)fb);
+    return hipSuccess;
 }
 
 template <int DT>
 int launch(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
-           int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits, uint64_t* rec)
+           int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits, uint64_t* rec, const GwSfxFns* fns)
 {
     const unsigned grid = (unsigned)((st.N + 63) / 64);  // the kernel's compile-time block size is 64
     // every exact fast form validated for this handle (gw_create): the instantiation without their fallbacks -- and, when
     // the host can rule out that any env reaches their validity limits in this launch, without the per-lane limit tests
     const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.idem_states && cst.fast_ticks;
+    hipError_t e;
     switch (fast ? (below_limits ? 2 : 1) : 0) {
-    case 2:  launch_mode<DT, 2>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec); break;
-    case 1:  launch_mode<DT, 1>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec); break;
-    default: launch_mode<DT, 0>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec); break;
+    case 2:  e = launch_mode<DT, 2>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec, fns ? fns->step[2] : nullptr); break;
+    case 1:  e = launch_mode<DT, 1>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec, fns ? fns->step[1] : nullptr); break;
+    default: e = launch_mode<DT, 0>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec, fns ? fns->step[0] : nullptr); break;
     }
-    return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP;
+    // (the one error query of a step: it also takes a sticky error of an earlier asynchronous failure off the runtime)
+    return (hipGetLastError() == hipSuccess && e == hipSuccess) ? GW_OK : GW_EHIP;
+}
+
+template <int DT>
+void resolve(GwSfxFns* out)
+{
+    out->step[0] = function_of(&ct_step_sfx_kernel<DT, 0>);
+    out->step[1] = function_of(&ct_step_sfx_kernel<DT, 1>);
+    out->step[2] = function_of(&ct_step_sfx_kernel<DT, 2>);
+    out->reset = function_of(&ct_reset_sfx_kernel);
 }
 
 inline int ok_or_ehip() { return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP; }
 
 } // namespace
 
+void gw_resolve_sfx_functions(int D, GwSfxFns* out)
+{
+    switch (D) {
+    case 2:  resolve<2>(out); break;
+    case 3:  resolve<3>(out); break;
+    case 4:  resolve<4>(out); break;
+    case 5:  resolve<5>(out); break;
+    case 6:  resolve<6>(out); break;
+    case 7:  resolve<7>(out); break;
+    case 8:  resolve<8>(out); break;
+    case 16: resolve<16>(out); break;
+    case 32: resolve<32>(out); break;
+    default: resolve<0>(out); break;
+    }
+}
+
 int gw_launch_step_sfx(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
-                       int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits, uint64_t* rec)
+                       int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits, uint64_t* rec,
+                       const GwSfxFns* fns)
 {
     switch (st.D) {
-    case 2:  return launch<2>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    case 3:  return launch<3>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    case 4:  return launch<4>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    case 5:  return launch<5>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    case 6:  return launch<6>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    case 7:  return launch<7>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    case 8:  return launch<8>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    case 16: return launch<16>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    case 32: return launch<32>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
-    default: return launch<0>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec);
+    case 2:  return launch<2>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    case 3:  return launch<3>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    case 4:  return launch<4>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    case 5:  return launch<5>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    case 6:  return launch<6>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    case 7:  return launch<7>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    case 8:  return launch<8>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    case 16: return launch<16>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    case 32: return launch<32>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    default: return launch<0>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
     }
 }
 
@@ -853,10 +901,21 @@ int gw_launch_init_sfx(const GwState& st, void* stream)
     return ok_or_ehip();
 }
 
-int gw_launch_reset_sfx(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream)
+// (one argument block through hipModuleLaunchKernel, as the step launch: ResetArgs mirrors the kernel's parameter list)
+struct ResetArgs { uint32_t* ip; uint32_t n_envs, n_dev; const uint8_t* mask; int32_t* obs; };
+static_assert(sizeof(ResetArgs) == 32, "ResetArgs must mirror ct_reset_sfx_kernel's parameter list");
+
+int gw_launch_reset_sfx(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream, const GwSfxFns* fns)
 {
     const unsigned grid = (unsigned)((st.N + 255) / 256);
-    hipLaunchKernelGGL(ct_reset_sfx_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st, mask, obs);
+    if (fns && fns->reset) {
+        ResetArgs a = {st.ip, (uint32_t)st.N, (uint32_t)st.D, mask, obs};
+        size_t size = sizeof a;
+        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+        const hipError_t e = hipModuleLaunchKernel((hipFunction_t)fns->reset, grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra);
+        return (hipGetLastError() == hipSuccess && e == hipSuccess) ? GW_OK : GW_EHIP;
+    }
+    hipLaunchKernelGGL(ct_reset_sfx_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st.ip, (uint32_t)st.N, (uint32_t)st.D, mask, obs);
     return ok_or_ehip();
 }
 

@@ -74,6 +74,7 @@ struct gw_env {
     int          dyn;         // live-PHY mode (ct_step_dyn.hip): per-env geometry, or a geometry without a finite noise-state set
     int          no_split;    // GW_NO_SPLIT at gw_create: the generic kernel's one-wave form at block 64
     uint64_t     launches[GW_LS_COUNT];   // kernel instantiations launched by this handle (gw_selftest_launches)
+    GwSfxFns     fns;         // default mode: this handle's step / reset kernels on its device, resolved at gw_create
 };
 
 namespace {
@@ -96,8 +97,12 @@ int dev_alloc(gw_env* env, T** out, size_t count)
     return GW_OK;
 }
 
+// (hipGetDevice reads a thread-local; hipSetDevice takes the runtime's lock -- and in the one-process-per-GPU case the
+//  handle's device is already the current one)
 int select_device(const gw_env* env)
 {
+    int cur = -1;
+    if (hipGetDevice(&cur) == hipSuccess && cur == env->cfg.hip_device) return GW_OK;
     HIP_TRY(hipSetDevice(env->cfg.hip_device));
     return GW_OK;
 }
@@ -201,7 +206,7 @@ int launch_step(gw_env* env, const int32_t* device, const int32_t* duration,
     if (env->st.tk) {
         if (fb_done) *fb_done = true;
         return gw_launch_step_sfx(env->st, env->cst_host, device, duration, obs, reward, done, fb, stream, gw_env_below_limits(env, stream),
-                                  env->launches);
+                                  env->launches, &env->fns);
     }
     return gw_launch_step(env->st, device, duration, obs, reward, done, stream, env->no_split != 0, env->launches);
 }
@@ -313,11 +318,13 @@ bool gw_env_below_limits(gw_env* env, void* stream)
 {
     if (env->captured) return false;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-        env->captured = 1;
-        return false;
+    if (stream) {
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) (void)hipGetLastError();   // (a failed query only: the
+        else if (cs != hipStreamCaptureStatusNone) {                                                 //  launcher checks the launch)
+            env->captured = 1;
+            return false;
+        }
     }
-    (void)hipGetLastError();
     return env->t_bound + env->step_max < env->t_limit;
 }
 
@@ -411,6 +418,7 @@ int gw_create(const gw_config* cfg, gw_env** out)
     if (rc) { delete env; return fail(rc, "%s", msg); }
 
     if ((rc = select_device(env))) { delete env; return rc; }
+    if (!(cfg->flags & GW_CFG_EXPLICIT_QUEUE)) gw_resolve_sfx_functions(cfg->num_devices, &env->fns);
 
     const int D = cfg->num_devices, R = D + 1;
     const int64_t N = cfg->num_envs;
@@ -592,7 +600,7 @@ int gw_reset(gw_env* env, const uint8_t* mask_dev, int32_t* obs_dev, void* strea
     if (!env) return fail(GW_EINVAL, "env is NULL");
     int rc = select_device(env);
     if (rc) return rc;
-    if (env->st.tk ? gw_launch_reset_sfx(env->st, mask_dev, obs_dev, stream)
+    if (env->st.tk ? gw_launch_reset_sfx(env->st, mask_dev, obs_dev, stream, &env->fns)
                     : gw_launch_reset(env->st, mask_dev, obs_dev, stream))
         return fail(GW_EHIP, "reset kernel launch failed");
     return GW_OK;

@@ -272,10 +272,16 @@ int gw_launch_step(const GwState& st, const int32_t* device, const int32_t* dura
                    int32_t* obs, float* reward, uint8_t* done, void* stream, bool no_split, uint64_t* rec);
 int gw_launch_received(const GwState& st, int32_t* out, void* stream);
 int gw_launch_enqueue(const GwState& st, int sender, const int32_t* payload_bytes, void* stream);
+// The hipFunction_t (as void*) of a handle's per-call kernels on ITS device: ct_step_sfx_kernel<D, MODE> for MODE 0..2 and
+// ct_reset_sfx_kernel.  Resolved once, at gw_create with the handle's device current (a module's functions belong to the
+// device it was loaded on), so that a launch neither asks for the current device nor looks the kernel up.  A null entry
+// sends that launch through `<<< >>>`.
+struct GwSfxFns { void* step[3]; void* reset; };
+void gw_resolve_sfx_functions(int D, GwSfxFns* out);       // ct_step_sfx.hip
 int gw_launch_step_sfx(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
                        int32_t* obs, float* reward, uint8_t* done, uint8_t* feedback_byte, void* stream, bool below_limits,
-                       uint64_t* rec);
-int gw_launch_reset_sfx(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream);
+                       uint64_t* rec, const GwSfxFns* fns);
+int gw_launch_reset_sfx(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream, const GwSfxFns* fns);
 int gw_launch_init_sfx(const GwState& st, void* stream);
 int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
                           int32_t* obs, float* reward, uint8_t* done, uint16_t* act_buf, uint8_t* fb_buf, int k_cap, void* stream,

@@ -14,6 +14,7 @@ Reference behaviour kept on purpose:
     arguments, :57), so observations are 65534 / 65536 / 65538 and ``done`` never fires
 """
 import ctypes as C
+import os
 import weakref
 
 import numpy as np
@@ -206,6 +207,14 @@ class VecCounterTrafficEnv(BaseEnv):
             self.interpreter = interpreter
         else:
             self.interpreter = _DeviceInterpreter(self)
+        # env.step(action, out) as ONE native call (csrc/gw_pyfast.c: Stepper), installed over the method below as an instance
+        # attribute -- where the method's flat fast path applies at all (the shim is there, the built-in interpreter) and nothing
+        # overrides what it would skip (a subclass's step() or _info()).  Every other case is handed on to the method.
+        self._fast_native = self._fast is not None and not os.environ.get("GW_NO_FASTSTEP")   # (reset()'s short route too)
+        if (self._fast_native and interpreter is None
+                and type(self).step is VecCounterTrafficEnv.step and type(self)._info is VecCounterTrafficEnv._info):
+            self.step = self._fast.Stepper(self._hv, self._dev_index, self._seen, self._cuda_get_device, self._cuda_raw_stream,
+                                           self, self._step_py, nat.check, StepOutputs)
 
     # -- helpers ------------------------------------------------------------------------------
     def _stream(self):
@@ -246,9 +255,15 @@ class VecCounterTrafficEnv(BaseEnv):
             m = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).contiguous()
             assert m.shape == (self.num_envs,)
         obs = self._outputs()[0]
-        with torch.cuda.device(self.device):
-            nat.check(self._L.gw_reset(self._h, m.data_ptr() if m is not None else None,
-                                       obs.data_ptr(), self._stream()))
+        idx = self._dev_index
+        if self._fast_native and self._cuda_get_device() == idx:   # the one-process-per-GPU case, as in step(): no context
+            rc = self._fast.reset(self._hv, m.data_ptr() if m is not None else 0, obs.data_ptr(), self._cuda_raw_stream(idx))
+            if rc:                                                  # manager, no Stream object, no ctypes conversion
+                nat.check(rc)
+        else:
+            with torch.cuda.device(self.device):
+                nat.check(self._L.gw_reset(self._h, m.data_ptr() if m is not None else None,
+                                           obs.data_ptr(), self._stream()))
         if self._custom is not None:                      # counter_traffic.py:142-144
             self._custom.reset()
             return self._custom.getObservation()
@@ -275,7 +290,7 @@ class VecCounterTrafficEnv(BaseEnv):
         self._seen[id(t)] = (weakref.ref(t), t.data_ptr())
         return t
 
-    def step(self, action, out=None):
+    def _step_py(self, action, out=None):
         """One env.step() for all N envs: ``action = {"device": int32[N], "duration": int32[N]}``
         (torch tensors on the env's GPU are used in place).  Returns
         ``(obs int32[N], reward float32[N], done uint8[N], info)``; an action outside the action
@@ -285,7 +300,11 @@ class VecCounterTrafficEnv(BaseEnv):
         Aliasing contract of the fast path: an action tensor OBJECT that passed validation once, and the tensors inside a
         ``StepOutputs``, are taken at their word afterwards -- their device addresses, dtype, shape and device must not be
         changed behind the env's back (``set_()``, ``resize_()``, swapping ``.data``); writing new VALUES into them is what
-        they are for.  A ``StepOutputs`` on another GPU than the env is refused."""
+        they are for.  A ``StepOutputs`` on another GPU than the env is refused.
+
+        Where the CPython shim is built, an env with the built-in interpreter carries ``step`` as an instance attribute: a
+        native callable (``_gw_fast.Stepper``) that does the common case below -- cached action tensors, a ``StepOutputs``,
+        the caller on this env's device -- itself and hands every other call to this method."""
         # (this method is enqueued ~200 000 times a second: the common path -- pre-staged int32 tensors on this GPU, reused
         #  output buffers, the caller on this env's device -- is written out flat, without helper calls)
         dev = action["device"]
@@ -348,6 +367,8 @@ class VecCounterTrafficEnv(BaseEnv):
         self._last = (obs, rew, done)
         return obs, rew, done, self._info()
 
+    step = _step_py
+
     def feedback_bytes_into(self, row):
         """From now on every step() also writes its feedback in the one-byte exchange format of ``pack_feedback`` into
         ``row`` (uint8[N] on this env's GPU; ``None`` switches it off) -- the row a multi-GPU job gathers
@@ -400,6 +421,9 @@ class VecCounterTrafficEnv(BaseEnv):
             self._L.gw_destroy(self._h)
             self._h = C.c_void_p()
             self._hv = 0
+            stepper = self.__dict__.get("step")                # the native stepper holds the handle's address too
+            if stepper is not None and hasattr(stepper, "handle"):
+                stepper.handle = 0
 
     def __del__(self):
         try:

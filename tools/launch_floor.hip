@@ -61,6 +61,14 @@ __global__ __launch_bounds__(64) void k_small(unsigned* a, double* b, unsigned* 
 {
     if (n == 0xffffffffu && a) a[0] = (unsigned)nd;
 }
+// the same block with the nine addresses declared as 64-bit integers (cast to global pointers inside): does the runtime do work
+// per parameter of POINTER type?  (ct_step_sfx_kernel's signature follows the answer: DESIGN section 8)
+__global__ __launch_bounds__(64) void k_small_u64(unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long d,
+                                                  unsigned long long e, unsigned long long f, unsigned n, int nd,
+                                                  unsigned long long o, unsigned long long r, unsigned long long dn)
+{
+    if (n == 0xffffffffu && a) ((__attribute__((address_space(1))) unsigned*)a)[0] = (unsigned)nd;
+}
 __global__ __launch_bounds__(64) void k_one(unsigned* a) { if (a == (unsigned*)1) a[0] = 0; }
 
 template <class F> double enqueue_us(F launch, int n, hipStream_t s)
@@ -102,7 +110,9 @@ int main(int argc, char** argv)
     hipStream_t s; CK(hipStreamCreate(&s));
     const int n = 2000;
     uint4* a; CK(hipMalloc(&a, (size_t)8 * 65536 * 16)); CK(hipMemset(a, 0, (size_t)8 * 65536 * 16));
+    const bool only_enqueue = argc > 1 && !strcmp(argv[1], "enqueue");      // `launch_floor enqueue`: the host-side sections only
     for (int grid : {256, 1024, 4096}) {
+        if (only_enqueue) break;
         printf("grid %4d x 64: empty %.2f us/launch", grid, per_launch_us([&] { hipLaunchKernelGGL(k_empty, dim3(grid), dim3(64), 0, s); }, n, s));
         for (unsigned long long cyc : {0ull, 2000ull, 6500ull, 12500ull}) {
             const double t = per_launch_us([&] { hipLaunchKernelGGL(k_spin, dim3(grid), dim3(64), 0, s, cyc); }, n, s);
@@ -117,6 +127,7 @@ int main(int argc, char** argv)
                 printf("\n");
             }
     }
+    if (!only_enqueue) {
     printf("store policy (grid 1024 x 64, 4 x 16 B load/store per lane, 1/3 of the waves spin 12500 cycles, the rest 6250):\n");
     printf("   plain %.2f", per_launch_us([&] { hipLaunchKernelGGL(k_spin_mem_pol<0>, dim3(1024), dim3(64), 0, s, 12500ull, (u32x4*)a, 4); }, n, s));
     printf(" | nt %.2f", per_launch_us([&] { hipLaunchKernelGGL(k_spin_mem_pol<1>, dim3(1024), dim3(64), 0, s, 12500ull, (u32x4*)a, 4); }, n, s));
@@ -124,6 +135,7 @@ int main(int argc, char** argv)
     printf(" | sc0 sc1 %.2f us/launch\n", per_launch_us([&] { hipLaunchKernelGGL(k_spin_mem_pol<3>, dim3(1024), dim3(64), 0, s, 12500ull, (u32x4*)a, 4); }, n, s));
     printf("   all waves spin 12500:  plain %.2f", per_launch_us([&] { hipLaunchKernelGGL(k_spin_mem, dim3(1024), dim3(64), 0, s, 12500ull, a, 4); }, n, s));
     printf("\n");
+    }
     {   // host enqueue cost per launch (clock stopped before the synchronize; 64 launches so that the queue never fills)
         Big big; memset(&big, 1, sizeof big);
         unsigned* pa = (unsigned*)a;
@@ -159,6 +171,29 @@ int main(int argc, char** argv)
                 CK(hipGetLastError());
             }
         }
+        {   // pointer-typed against integer-typed addresses, same 80-byte block, hipModuleLaunchKernel + one buffer, measured
+            // ALTERNATELY so that drift of the box shows up as spread within a form and not as a difference between the forms
+            hipFunction_t fp = nullptr, fi = nullptr;
+            if (hipGetFuncBySymbol(&fp, (const void*)k_small) == hipSuccess && fp && hipGetFuncBySymbol(&fi, (const void*)k_small_u64) == hipSuccess && fi) {
+                struct PArgs { unsigned* a; double* b; unsigned* c; unsigned char* d; const int* e; const int* f; unsigned n; int nd; int* o; float* r; unsigned char* dn; } pa_;
+                struct IArgs { unsigned long long a, b, c, d, e, f; unsigned n; int nd; unsigned long long o, r, dn; } ia_;
+                static_assert(sizeof(PArgs) == sizeof(IArgs) && sizeof(IArgs) == 80, "same block");
+                pa_.a = pa; pa_.b = (double*)a; pa_.c = pa; pa_.d = (unsigned char*)a; pa_.e = (const int*)a; pa_.f = (const int*)a; pa_.n = 65536u; pa_.nd = 4;
+                pa_.o = (int*)a; pa_.r = (float*)a; pa_.dn = (unsigned char*)a;
+                memcpy(&ia_, &pa_, sizeof ia_);
+                size_t sz = 80;
+                void* exp_[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &pa_, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+                void* exi_[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ia_, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+                printf("host enqueue per launch, 80-byte block, nine addresses as pointers | as 64-bit integers (alternating):\n  ");
+                for (int round = 0; round < 6; ++round) {
+                    const double tp = enqueue_us([&] { (void)hipModuleLaunchKernel(fp, 1024, 1, 1, 64, 1, 1, 0, s, nullptr, exp_); }, 64, s);
+                    const double ti = enqueue_us([&] { (void)hipModuleLaunchKernel(fi, 1024, 1, 1, 64, 1, 1, 0, s, nullptr, exi_); }, 64, s);
+                    printf(" %.2f | %.2f us;", tp, ti);
+                }
+                printf("\n");
+                CK(hipGetLastError());
+            }
+        }
         printf("host enqueue per launch: one pointer argument %.2f us | 11 scalar arguments (80 B) %.2f us | the same through hipModuleLaunchKernel + one buffer %.2f us\n", t_one, t_small, t_small_mod);
         printf("host enqueue per launch: empty kernel %.2f us | 11 arguments, 1.2 KB, <<<>>> %.2f us | same through hipModuleLaunchKernel + one buffer %.2f us\n",
                t_empty, t_chevron, t_mod);
@@ -173,7 +208,7 @@ int main(int argc, char** argv)
                t([&] { (void)hipGetLastError(); }));
     }
     // the counter's rate: cycles per microsecond (spin a long while, time it)
-    {
+    if (!only_enqueue) {
         hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
         CK(hipEventRecord(e0, s));
         hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, s, 100000000ull);
