@@ -133,6 +133,49 @@ __device__ __forceinline__ void gw_store_wt(T* ptr, const T& v)
 #endif
 }
 
+// ---- typed access at a byte offset from the base of a record array.  Off is the call site's offset type, kept as it is:
+//      32-bit in the suffix step and rollout kernels (gw_create refuses what that cannot address), size_t in the live-PHY kernel
+template <class T, class Off>
+__device__ __forceinline__ T ld(const void* base, Off byte_off)
+{
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+// (through the GLOBAL address space, for a base pointer that was read from memory: gw_as_global below)
+template <class T, class Off>
+__device__ __forceinline__ T ld_global(const void* base, Off byte_off)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const __attribute__((address_space(1))) T*)(reinterpret_cast<const char*>(base) + byte_off);
+#else
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);       // (host pass: never executed)
+#endif
+}
+template <class T, class Off>
+__device__ __forceinline__ void st_(void* base, Off byte_off, const T& v)            // write-through: gw_store_wt
+{
+    gw_store_wt(reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off), v);
+}
+template <class T, class Off>
+__device__ __forceinline__ void st_plain(void* base, Off byte_off, const T& v)       // left to the L2's write-back
+{
+    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off) = v;
+}
+
+// byte `idx` (0..15) of a 16-byte record held in four registers, idx not known at compile time.  The words are
+// taken BY VALUE: selecting between the fields of a struct object is folded by the compiler into dynamic addressing
+// of a stack copy of it.
+__device__ __forceinline__ uint32_t byte_of(uint32_t x, uint32_t y, uint32_t z, uint32_t w, uint32_t idx)
+{
+    const uint32_t lo = (idx & 4u) ? y : x;
+    const uint32_t hi = (idx & 4u) ? w : z;
+    const uint32_t v = (idx & 8u) ? hi : lo;
+    return (v >> ((idx & 3u) * 8u)) & 0xffu;
+}
+__device__ __forceinline__ uint32_t word_of(const uint4& w, int i)          // i compile-time after unrolling
+{
+    return i == 0 ? w.x : (i == 1 ? w.y : (i == 2 ? w.z : w.w));
+}
+
 // Per-env event counters of the default-mode kernels: fire-and-forget atomics, issued only by lanes that have something to
 // add (a step without data pops nothing, flags are rare).  No load, no dependent store: nothing of it is on a wave's
 // critical path, and a quiet step moves no counter bytes at all.
@@ -312,3 +355,9 @@ __device__ __forceinline__ void publish_totals(unsigned long long* totals, const
 }
 
 } // namespace gwk
+
+// What a launcher returns.  (Its one error query: it also takes a sticky error of an earlier asynchronous failure off the runtime.)
+inline int gw_launch_status(hipError_t launched = hipSuccess)
+{
+    return (hipGetLastError() == hipSuccess && launched == hipSuccess) ? GW_OK : GW_EHIP;
+}

@@ -17,27 +17,14 @@
 // Results are bit-identical to K calls of the step kernel (tests compare both with the oracle).
 // The step semantics and reference citations are those of ct_step_sfx.hip / ct_common.hip.h.
 #include "ct_common.hip.h"
+#include "gw_dispatch.h"
 #include "gw_queue.h"
 
 using namespace gwk;
 
 namespace {
 
-template <class T>
-__device__ __forceinline__ T ld(const void* base, uint32_t byte_off)
-{
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-template <class T>
-__device__ __forceinline__ void st_(void* base, uint32_t byte_off, const T& v)
-{
-    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off) = v;
-}
-__device__ __forceinline__ uint32_t word_of(const uint4& w, int i)
-{
-    return i == 0 ? w.x : (i == 1 ? w.y : (i == 2 ? w.z : w.w));
-}
-
+// (ld, st_plain, word_of: ct_common.hip.h)
 
 // The rollout kernel wants each env's actions and feedback contiguous ([N][Kp]: one 16-byte load = 8 steps of
 // actions, one dword store = 4 steps of feedback); the C-ABI takes and returns step-major arrays ([K][N]).  Both
@@ -291,7 +278,7 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
 
     auto put_feedback = [&](uint32_t byte) {
         fbw |= byte << ((k & 3) * 8);
-        if ((k & 3) == 3 || k == K - 1) { st_(fbp, (uint32_t)(k & ~3), fbw); fbw = 0; }
+        if ((k & 3) == 3 || k == K - 1) { st_plain(fbp, (uint32_t)(k & ~3), fbw); fbw = 0; }
         k++;
         if ((k & 7) == 0 && k < K) aw = ld<uint4>(act, (uint32_t)k * 2u);                // next 8 actions
     };
@@ -520,11 +507,11 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
             o.y = nb[b + 4] | (nb[b + 5] << 8) | (nb[b + 6] << 16) | (nb[b + 7] << 24);
             o.z = nb[b + 8] | (nb[b + 9] << 8) | (nb[b + 10] << 16) | (nb[b + 11] << 24);
             o.w = nb[b + 12] | (nb[b + 13] << 8) | (nb[b + 14] << 16) | (nb[b + 15] << 24);
-            st_(st.qb, oq + 16u * w, o);
+            st_plain(st.qb, oq + 16u * w, o);
         }
     }
-    st_(st.tw, o16, make_double2(now, wake));
-    st_(st.tk, o16, make_uint4(tau, nbp, rvm, (uint32_t)last_abs | (dn << 31)));
+    st_plain(st.tw, o16, make_double2(now, wake));
+    st_plain(st.tk, o16, make_uint4(tau, nbp, rvm, (uint32_t)last_abs | (dn << 31)));
     publish_env_counters(st.sa, N, e, kt.pop, kt.deliv, k_bad, fl, (uint32_t)K);
 }
 
@@ -885,47 +872,12 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_kernel(GwState st, GwDevCo
             o.y = nb[b + 4] | (nb[b + 5] << 8) | (nb[b + 6] << 16) | (nb[b + 7] << 24);
             o.z = nb[b + 8] | (nb[b + 9] << 8) | (nb[b + 10] << 16) | (nb[b + 11] << 24);
             o.w = nb[b + 12] | (nb[b + 13] << 8) | (nb[b + 14] << 16) | (nb[b + 15] << 24);
-            st_(st.qb, oq + 16u * w, o);
+            st_plain(st.qb, oq + 16u * w, o);
         }
     }
-    st_(st.tw, o16, make_double2(now, wake));
-    st_(st.tk, o16, make_uint4(tau, nbp, rvm, (uint32_t)last_abs | (dn << 31)));
+    st_plain(st.tw, o16, make_double2(now, wake));
+    st_plain(st.tk, o16, make_uint4(tau, nbp, rvm, (uint32_t)last_abs | (dn << 31)));
     publish_env_counters(st.sa, N, e, kt.pop, kt.deliv, k_bad, fl, (uint32_t)K);
-}
-
-// the step-synchronous form: the caller's step-major arrays directly (no packing / expanding launches)
-template <int DT>
-int launch_rollout_sync(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
-                        int32_t* obs, float* reward, uint8_t* done, void* stream, bool below_limits, uint64_t* rec)
-{
-    const unsigned blk = 64;
-    const unsigned grid = (unsigned)((st.N + blk - 1) / blk);
-    const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.fast_ticks;
-    gw_note_launch(rec, GW_LS_ROLLOUT_SYNC + 3 * gw_ls_dt(DT) + (fast ? (below_limits ? 2 : 1) : 0));
-    if (fast && below_limits)
-        hipLaunchKernelGGL((ct_rollout_sync_kernel<DT, 2>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, cst, K, device, duration, obs, reward, done);
-    else if (fast)
-        hipLaunchKernelGGL((ct_rollout_sync_kernel<DT, 1>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, cst, K, device, duration, obs, reward, done);
-    else
-        hipLaunchKernelGGL((ct_rollout_sync_kernel<DT, 0>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, cst, K, device, duration, obs, reward, done);
-    return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP;
-}
-
-template <int DT>
-int launch_rollout(const GwState& st, const GwDevConst& cst, int K, int Kp, const uint16_t* act, uint8_t* fb, void* stream, bool below_limits,
-                   uint64_t* rec)
-{
-    const unsigned blk = 64;
-    const unsigned grid = (unsigned)((st.N + blk - 1) / blk);
-    const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.fast_ticks;
-    gw_note_launch(rec, GW_LS_ROLLOUT + 3 * gw_ls_dt(DT) + (fast ? (below_limits ? 2 : 1) : 0));
-    if (fast && below_limits)
-        hipLaunchKernelGGL((ct_rollout_sfx_kernel<DT, 2>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, cst, K, Kp, act, fb);
-    else if (fast)
-        hipLaunchKernelGGL((ct_rollout_sfx_kernel<DT, 1>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, cst, K, Kp, act, fb);
-    else
-        hipLaunchKernelGGL((ct_rollout_sfx_kernel<DT, 0>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, cst, K, Kp, act, fb);
-    return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP;
 }
 
 } // namespace
@@ -937,39 +889,34 @@ int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const
 {
     const int Kp = (K + 15) / 16 * 16;
     if (K <= 0 || Kp > k_cap) return GW_EUNSUPPORTED;
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    const int mode = gw_step_mode(cst, below_limits, false);
+    hipStream_t s = (hipStream_t)stream;
     // A/B switch: the older form -- for handles created while the switch was set (they have its scratch records)
     const bool event_loop = getenv("GW_ROLLOUT_EVENT_LOOP") != nullptr && act_buf != nullptr && fb_buf != nullptr;
-    if (!event_loop) {
-        switch (st.D) {
-        case 2:  return launch_rollout_sync<2>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        case 3:  return launch_rollout_sync<3>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        case 4:  return launch_rollout_sync<4>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        case 5:  return launch_rollout_sync<5>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        case 6:  return launch_rollout_sync<6>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        case 7:  return launch_rollout_sync<7>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        case 8:  return launch_rollout_sync<8>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        case 16: return launch_rollout_sync<16>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        case 32: return launch_rollout_sync<32>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);
-        default: return launch_rollout_sync<0>(st, cst, K, device, duration, obs, reward, done, stream, below_limits, rec);   // any other D: per-lane arrays in LDS
-        }
+    if (!event_loop) {                                    // the step-synchronous form: the caller's step-major arrays directly
+        gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {             // (any other D: per-lane arrays in LDS)
+            gw_with_mode(mode, [&](auto m) {
+                gw_note_launch(rec, GW_LS_ROLLOUT_SYNC + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
+                hipLaunchKernelGGL((ct_rollout_sync_kernel<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64), 0, s,
+                                   st, cst, K, device, duration, obs, reward, done);
+            });
+        });
+        return gw_launch_status();
     }
     if (cst.max_duration > 0xfe) return GW_EUNSUPPORTED;  // (the event loop's packed action records hold a byte of duration)
     const uint32_t N = (uint32_t)st.N;
     const unsigned g256 = (unsigned)((st.N + TP_ENVS - 1) / TP_ENVS);      // one block per 64-env tile
-    hipLaunchKernelGGL(pack_actions_kernel, dim3(g256), dim3(256), 0, (hipStream_t)stream, N, K, Kp, device, duration, act_buf);
-    int rc;
-    switch (st.D) {
-    case 2:  rc = launch_rollout<2>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
-    case 3:  rc = launch_rollout<3>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
-    case 4:  rc = launch_rollout<4>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
-    case 6:  rc = launch_rollout<6>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
-    case 8:  rc = launch_rollout<8>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
-    case 16: rc = launch_rollout<16>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
-    case 32: rc = launch_rollout<32>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;
-    default: rc = launch_rollout<0>(st, cst, K, Kp, act_buf, fb_buf, stream, below_limits, rec); break;   // any other D (5, 7, ..., 32): per-lane arrays in LDS
-    }
-    if (rc) return rc;
-    hipLaunchKernelGGL(expand_feedback_kernel, dim3(g256), dim3(256), 0, (hipStream_t)stream, N, K, Kp, cst.counter_bound,
+    hipLaunchKernelGGL(pack_actions_kernel, dim3(g256), dim3(256), 0, s, N, K, Kp, device, duration, act_buf);
+    gw_with_dt<GW_DTS_ROLLOUT_LOOP>(st.D, [&](auto dt) {                 // (any other D -- 5, 7, ...: per-lane arrays in LDS)
+        gw_with_mode(mode, [&](auto m) {
+            gw_note_launch(rec, GW_LS_ROLLOUT + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
+            hipLaunchKernelGGL((ct_rollout_sfx_kernel<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64), 0, s,
+                               st, cst, K, Kp, (const uint16_t*)act_buf, fb_buf);
+        });
+    });
+    if (const int rc = gw_launch_status()) return rc;
+    hipLaunchKernelGGL(expand_feedback_kernel, dim3(g256), dim3(256), 0, s, N, K, Kp, cst.counter_bound,
                        cst.payload_value, fb_buf, obs, reward, done);
-    return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP;
+    return gw_launch_status();
 }

@@ -24,6 +24,7 @@
 // Compile with -ffp-contract=off: every f64 result must be the IEEE result of the
 // reference's individual operations.
 #include "ct_common.hip.h"
+#include "gw_dispatch.h"
 #include "gw_runq.h"
 
 using namespace gwk;
@@ -779,25 +780,20 @@ __global__ void ct_received_kernel(GwState st, int32_t* __restrict__ out)
     out[idx] = ((st.xc[(size_t)e * 4 + 1] >> i) & 1u) ? st.cst->payload_value : 0;
 }
 
-inline int check_launch()
-{
-    return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP;
-}
-
 } // namespace
 
 int gw_launch_init(const GwState& st, void* stream)
 {
     const unsigned grid = (unsigned)((st.N + 255) / 256);
     hipLaunchKernelGGL(ct_init_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st);
-    return check_launch();
+    return gw_launch_status();
 }
 
 int gw_launch_reset(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream)
 {
     const unsigned grid = (unsigned)((st.N + 255) / 256);
     hipLaunchKernelGGL(ct_reset_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st, mask, obs);
-    return check_launch();
+    return gw_launch_status();
 }
 
 int gw_launch_step(const GwState& st, const int32_t* device, const int32_t* duration,
@@ -805,64 +801,38 @@ int gw_launch_step(const GwState& st, const int32_t* device, const int32_t* dura
 {
     const unsigned blk = (unsigned)st.block;
     const unsigned grid = (unsigned)((st.N + blk - 1) / blk);
-    const bool split = blk == 64u && !no_split;                                         // no_split: GW_NO_SPLIT at gw_create
-    const int pes = st.pe_stats ? 1 : 0;
-#define GW_LAUNCH_SPLIT(DT_)                                                                                     \
-    do {                                                                                                        \
-        gw_note_launch(rec, GW_LS_GENERIC + 8 * gw_ls_dt(DT_) + 4 * pes + 1);                                   \
-        if (st.pe_stats)                                                                                        \
-            hipLaunchKernelGGL((ct_step_kernel<DT_, true, false, true>), dim3(grid), dim3(128), 0, (hipStream_t)stream, \
-                               st, device, duration, obs, reward, done);                                        \
-        else                                                                                                    \
-            hipLaunchKernelGGL((ct_step_kernel<DT_, false, false, true>), dim3(grid), dim3(128), 0, (hipStream_t)stream, \
-                               st, device, duration, obs, reward, done);                                        \
-    } while (0)
-#define GW_LAUNCH_GENERIC(DT_)                                                                                   \
-    do {                                                                                                        \
-        if (split && (DT_) > 0) { constexpr int dts_ = ((DT_) > 0) ? (DT_) : 2; GW_LAUNCH_SPLIT(dts_); break; }      \
-        gw_note_launch(rec, GW_LS_GENERIC + 8 * gw_ls_dt(DT_) + 4 * pes);                                       \
-        if (st.pe_stats)                                                                                        \
-            hipLaunchKernelGGL((ct_step_kernel<DT_, true, false>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, \
-                               st, device, duration, obs, reward, done);                                        \
-        else                                                                                                    \
-            hipLaunchKernelGGL((ct_step_kernel<DT_, false, false>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, \
-                               st, device, duration, obs, reward, done);                                        \
-    } while (0)
-    if (st.rxp) {                                        // live PHY (open noise-state set / per-env geometry)
-#define GW_LAUNCH_DYN(DT_)                                                                                       \
-    do {                                                                                                        \
-        gw_note_launch(rec, GW_LS_GENERIC + 8 * gw_ls_dt(DT_) + 4 * pes + 2);                                   \
-        if (st.pe_stats)                                                                                        \
-            hipLaunchKernelGGL((ct_step_kernel<DT_, true, true>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, device, duration, obs, reward, done); \
-        else                                                                                                    \
-            hipLaunchKernelGGL((ct_step_kernel<DT_, false, true>), dim3(grid), dim3(blk), 0, (hipStream_t)stream, st, device, duration, obs, reward, done); \
-    } while (0)
-        switch (st.D) {                                  // the queue records in registers for the usual sender counts
-        case 4:  GW_LAUNCH_DYN(4); break;
-        case 16: GW_LAUNCH_DYN(16); break;
-        default: GW_LAUNCH_DYN(0); break;
+    hipStream_t s = (hipStream_t)stream;
+    // one launch of ct_step_kernel<DT, PER_ENV_STATS, DYN, SPLIT>; the record's slot spells the same four parameters
+    auto launch = [&](auto dt, auto dyn, auto split, unsigned threads) {
+        gw_with_flag(st.pe_stats != nullptr, [&](auto pes) {
+            constexpr int DT = decltype(dt)::value;
+            constexpr bool PES = decltype(pes)::value, DYN = decltype(dyn)::value, SPLIT = decltype(split)::value;
+            gw_note_launch(rec, GW_LS_GENERIC + 8 * gw_ls_dt(DT) + 4 * (PES ? 1 : 0) + 2 * (DYN ? 1 : 0) + (SPLIT ? 1 : 0));
+            hipLaunchKernelGGL((ct_step_kernel<DT, PES, DYN, SPLIT>), dim3(grid), dim3(threads), 0, s, st, device, duration, obs, reward, done);
+        });
+    };
+    if (st.rxp) {                                        // live PHY (open noise-state set / per-env geometry): the queue records
+        gw_with_dt<GW_DTS_GENERIC_LIVE>(st.D, [&](auto dt) {       // in registers for the usual sender counts
+            launch(dt, std::true_type{}, std::false_type{}, blk);
+        });
+        return gw_launch_status();
+    }
+    // the two-wave form (SPLIT) exists for compile-time sender counts, at block 64 (no_split: GW_NO_SPLIT at gw_create)
+    const bool split = blk == 64u && !no_split;
+    gw_with_dt<GW_DTS_GENERIC>(st.D, [&](auto dt) {
+        if constexpr (decltype(dt)::value > 0) {
+            if (split) { launch(dt, std::false_type{}, std::true_type{}, 128u); return; }
         }
-#undef GW_LAUNCH_DYN
-        return check_launch();
-    }
-    switch (st.D) {
-    case 2:  GW_LAUNCH_GENERIC(2); break;
-    case 3:  GW_LAUNCH_GENERIC(3); break;
-    case 4:  GW_LAUNCH_GENERIC(4); break;
-    case 8:  GW_LAUNCH_GENERIC(8); break;
-    case 16: GW_LAUNCH_GENERIC(16); break;
-    default: GW_LAUNCH_GENERIC(0); break;
-    }
-#undef GW_LAUNCH_GENERIC
-#undef GW_LAUNCH_SPLIT
-    return check_launch();
+        launch(dt, std::false_type{}, std::false_type{}, blk);
+    });
+    return gw_launch_status();
 }
 
 int gw_launch_enqueue(const GwState& st, int sender, const int32_t* payload_bytes, void* stream)
 {
     const unsigned grid = (unsigned)((st.N + 255) / 256);
     hipLaunchKernelGGL(ct_enqueue_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st, sender, payload_bytes);
-    return check_launch();
+    return gw_launch_status();
 }
 
 int gw_launch_received(const GwState& st, int32_t* out, void* stream)
@@ -870,5 +840,5 @@ int gw_launch_received(const GwState& st, int32_t* out, void* stream)
     const int64_t total = st.N * (int64_t)st.D;
     const unsigned grid = (unsigned)((total + 255) / 256);
     hipLaunchKernelGGL(ct_received_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st, out);
-    return check_launch();
+    return gw_launch_status();
 }

@@ -28,32 +28,16 @@
 // error sums that are rounded to integers, so decisions agree except on a measure-zero boundary; with the host's link
 // tables (no per-env geometry) the received powers themselves are exact sums and compare bit for bit.
 #include "ct_common.hip.h"
+#include "gw_dispatch.h"
 #include "gw_queue.h"
 
 using namespace gwk;
 
 namespace {
 
-// (through the GLOBAL address space: the pointers of this kernel's state come from the header in memory, and an access through
-//  a pointer read from memory is a FLAT instruction unless told otherwise -- ct_common.hip.h, hdr_state)
-template <class T>
-__device__ __forceinline__ T ld(const void* base, size_t byte_off)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return *(const __attribute__((address_space(1))) T*)(reinterpret_cast<const char*>(base) + byte_off);
-#else
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);       // (host pass: never executed)
-#endif
-}
-template <class T>
-__device__ __forceinline__ void st_(void* base, size_t byte_off, const T& v)
-{
-    gwk::gw_store_wt(reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off), v);
-}
-__device__ __forceinline__ uint32_t word_of(const uint4& w, int i)          // i compile-time after unrolling
-{
-    return i == 0 ? w.x : (i == 1 ? w.y : (i == 2 ? w.z : w.w));
-}
+// (ld_global, st_, word_of: ct_common.hip.h.  Loads go through the GLOBAL address space: the pointers of this kernel's state
+//  come from the header in memory, and an access through a pointer read from memory is a FLAT instruction unless told
+//  otherwise -- hdr_state)
 __device__ __forceinline__ double half_of(const double2& v, int i) { return i ? v.y : v.x; }
 
 // physical.py:25-58 (Eb/N0, Q approximation), :82-98 (dBm helpers), :208-212 (BPSK).  exp10 / exp instead of pow(10, .) /
@@ -138,23 +122,23 @@ __global__ __launch_bounds__(64) void ct_step_live_kernel(GW_LEAD_PARAMS, int32_
     // ---- loads, all issued before anything is waited for ---------------------------------------------------------------
     int d = device[el];
     int du = duration[el];
-    uint4 bp = ld<uint4>(st.ip, o16);
-    const double2 tw0 = ld<double2>(st.tw, o16);
-    const uint4 tk0 = ld<uint4>(st.tk, o16);
+    uint4 bp = ld_global<uint4>(st.ip, o16);
+    const double2 tw0 = ld_global<double2>(st.tw, o16);
+    const uint4 tk0 = ld_global<uint4>(st.tk, o16);
     uint4 qw[NWC];
 #pragma unroll
-    for (int w = 0; w < NWC; ++w) qw[w] = PACKED ? ld<uint4>(st.qb, oq + 16u * w) : make_uint4(0u, 0u, 0u, 0u);
+    for (int w = 0; w < NWC; ++w) qw[w] = PACKED ? ld_global<uint4>(st.qb, oq + 16u * w) : make_uint4(0u, 0u, 0u, 0u);
     double2 rxv[ROWS ? NH : 1], pav[ROWS && PER_ENV ? NH : 1], cav[ROWS ? DT : 1];
     if (ROWS) {
 #pragma unroll
-        for (int h = 0; h < NH; ++h) rxv[h] = ld<double2>(st.rxp, orx + 16u * h);
+        for (int h = 0; h < NH; ++h) rxv[h] = ld_global<double2>(st.rxp, orx + 16u * h);
         // all D "sender i hears the RRM" cache entries: which one the step needs depends on the action, and a load issued
         // only once the action has arrived is a second memory round trip in front of the announcement's decision
 #pragma unroll
-        for (int i = 0; i < DT; ++i) cav[i] = ld<double2>(st.bcache, ((size_t)el * 2 * DT + 2 * i) * 16u);
+        for (int i = 0; i < DT; ++i) cav[i] = ld_global<double2>(st.bcache, ((size_t)el * 2 * DT + 2 * i) * 16u);
         if (PER_ENV) {
 #pragma unroll
-            for (int h = 0; h < NH; ++h) pav[h] = ld<double2>(st.prx_env, olk + ((size_t)RRM * RP) * 8u + 16u * h);
+            for (int h = 0; h < NH; ++h) pav[h] = ld_global<double2>(st.prx_env, olk + ((size_t)RRM * RP) * 8u + 16u * h);
         }
     }
     asm volatile("" : "+v"(d), "+v"(du));
@@ -172,16 +156,16 @@ __global__ __launch_bounds__(64) void ct_step_live_kernel(GW_LEAD_PARAMS, int32_
 #pragma unroll
         for (int i = 1; i < DT; ++i) { ca.x = (i == dq) ? cav[i].x : ca.x; ca.y = (i == dq) ? cav[i].y : ca.y; }
     } else {
-        ca = ld<double2>(st.bcache, ((size_t)el * 2 * D + 2 * dq) * 16u);
+        ca = ld_global<double2>(st.bcache, ((size_t)el * 2 * D + 2 * dq) * 16u);
     }
-    double2 cx = ld<double2>(st.bcache, ((size_t)el * 2 * D + 2 * dq + 1) * 16u);   // (first needed at the first data packet)
+    double2 cx = ld_global<double2>(st.bcache, ((size_t)el * 2 * D + 2 * dq + 1) * 16u);   // (first needed at the first data packet)
     double2 pdv[ROWS && PER_ENV ? NH : 1];
     if (ROWS && PER_ENV) {
 #pragma unroll
-        for (int h = 0; h < NH; ++h) pdv[h] = ld<double2>(st.prx_env, olk + ((size_t)dq * RP) * 8u + 16u * h);
+        for (int h = 0; h < NH; ++h) pdv[h] = ld_global<double2>(st.prx_env, olk + ((size_t)dq * RP) * 8u + 16u * h);
     }
     auto link = [&](int from, int to) -> double {
-        return PER_ENV ? ld<double>(st.prx_env, (((size_t)el * R + from) * RP + to) * 8u) : s_prx[from * R + to];
+        return PER_ENV ? ld_global<double>(st.prx_env, (((size_t)el * R + from) * RP + to) * 8u) : s_prx[from * R + to];
     };
     double rx_d0, rx_r0, p_a, p_x;
     if (ROWS) {
@@ -196,8 +180,8 @@ __global__ __launch_bounds__(64) void ct_step_live_kernel(GW_LEAD_PARAMS, int32_
             p_a = link(RRM, dq);
         }
     } else {
-        rx_d0 = ld<double>(st.rxp, ((size_t)el * RP + dq) * 8u);
-        rx_r0 = RXR ? ld<double>(st.rxr, (size_t)el * 8u) : ld<double>(st.rxp, ((size_t)el * RP + RRM) * 8u);
+        rx_d0 = ld_global<double>(st.rxp, ((size_t)el * RP + dq) * 8u);
+        rx_r0 = RXR ? ld_global<double>(st.rxr, (size_t)el * 8u) : ld_global<double>(st.rxp, ((size_t)el * RP + RRM) * 8u);
         p_a = link(RRM, dq);
     }
     // the attenuation of a pair is one number (one model per unordered pair, physical.py:500-528; gw_create refuses an
@@ -232,10 +216,10 @@ __global__ __launch_bounds__(64) void ct_step_live_kernel(GW_LEAD_PARAMS, int32_
             c_on |= on ? (1ull << u) : 0ull;
             const uint32_t es = on ? src : 0u;                    // idle lanes read the wave's first env: a valid row
             c_off[u] = es * (uint32_t)RP + c_j;
-            c_a0[u] = ld<double>(rx_wave, (size_t)c_off[u] * 8u);
-            c_pa[u] = PER_ENV ? ld<double>(lk_wave, (size_t)((es * (uint32_t)R + (uint32_t)RRM) * (uint32_t)RP + c_j) * 8u) : s_prx[RRM * R + c_j];
+            c_a0[u] = ld_global<double>(rx_wave, (size_t)c_off[u] * 8u);
+            c_pa[u] = PER_ENV ? ld_global<double>(lk_wave, (size_t)((es * (uint32_t)R + (uint32_t)RRM) * (uint32_t)RP + c_j) * 8u) : s_prx[RRM * R + c_j];
             const uint32_t dr = on ? dsrc : 0u;
-            c_pd[u] = PER_ENV ? ld<double>(lk_wave, (size_t)((es * (uint32_t)R + dr) * (uint32_t)RP + c_j) * 8u) : s_prx[dr * R + c_j];
+            c_pd[u] = PER_ENV ? ld_global<double>(lk_wave, (size_t)((es * (uint32_t)R + dr) * (uint32_t)RP + c_j) * 8u) : s_prx[dr * R + c_j];
         }
     }
 
@@ -513,7 +497,7 @@ __global__ __launch_bounds__(64) void ct_step_live_kernel(GW_LEAD_PARAMS, int32_
             if (!COOP) {
                 for (int j = 0; j < D; ++j) {
                     if (j == d) continue;
-                    const double a0 = ld<double>(st.rxp, ((size_t)e * RP + j) * 8u);
+                    const double a0 = ld_global<double>(st.rxp, ((size_t)e * RP + j) * 8u);
                     const double a = heard(a0, link(RRM, j), link(d, j), n_data);
                     if (!(a >= 0.0)) fl |= GW_FLAG_REFEXC;
                     if (a != a0) st_(st.rxp, ((size_t)e * RP + j) * 8u, a);
@@ -666,44 +650,27 @@ __global__ void ct_init_dyn_kernel(GwState st, GwDevConst c, double thermal)
     }
 }
 
-inline int ok_or_ehip() { return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP; }
-
-template <int DT>
-int launch_live(const GwState& st, const int32_t* device, const int32_t* duration, int32_t* obs, float* reward, uint8_t* done,
-                hipStream_t stream, uint64_t* rec)
-{
-    const unsigned grid = (unsigned)((st.N + 63) / 64);
-    gw_note_launch(rec, GW_LS_LIVE + 2 * gw_ls_dt(DT) + (st.prx_env ? 1 : 0));
-    if (st.prx_env)
-        hipLaunchKernelGGL((ct_step_live_kernel<DT, true>), dim3(grid), dim3(64), 0, stream, GW_LEAD_ARGS(st), obs, reward, done);
-    else
-        hipLaunchKernelGGL((ct_step_live_kernel<DT, false>), dim3(grid), dim3(64), 0, stream, GW_LEAD_ARGS(st), obs, reward, done);
-    return ok_or_ehip();
-}
-
 } // namespace
 
 int gw_launch_step_dyn(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
                        int32_t* obs, float* reward, uint8_t* done, void* stream, uint64_t* rec)
 {
     (void)cst;
-    hipStream_t s = (hipStream_t)stream;
-    switch (st.D) {
-    case 2:  return launch_live<2>(st, device, duration, obs, reward, done, s, rec);
-    case 3:  return launch_live<3>(st, device, duration, obs, reward, done, s, rec);
-    case 4:  return launch_live<4>(st, device, duration, obs, reward, done, s, rec);
-    case 6:  return launch_live<6>(st, device, duration, obs, reward, done, s, rec);
-    case 8:  return launch_live<8>(st, device, duration, obs, reward, done, s, rec);
-    case 16: return launch_live<16>(st, device, duration, obs, reward, done, s, rec);
-    case 32: return launch_live<32>(st, device, duration, obs, reward, done, s, rec);
-    default: return launch_live<0>(st, device, duration, obs, reward, done, s, rec);
-    }
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    gw_with_dt<GW_DTS_LIVE>(st.D, [&](auto dt) {
+        gw_with_flag(st.prx_env != nullptr, [&](auto per_env) {
+            gw_note_launch(rec, GW_LS_LIVE + 2 * gw_ls_dt(decltype(dt)::value) + (decltype(per_env)::value ? 1 : 0));
+            hipLaunchKernelGGL((ct_step_live_kernel<decltype(dt)::value, decltype(per_env)::value>), dim3(grid), dim3(64), 0,
+                               (hipStream_t)stream, GW_LEAD_ARGS(st), obs, reward, done);
+        });
+    });
+    return gw_launch_status();
 }
 
 int gw_launch_init_dyn(const GwState& st, const GwDevConst& cst, double thermal, void* stream)
 {
     hipLaunchKernelGGL(ct_init_dyn_kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, st, cst, thermal);
-    return ok_or_ehip();
+    return gw_launch_status();
 }
 
 int gw_launch_set_position(const GwState& st, const GwDevConst& cst, int radio, const double* xs, const double* ys,
@@ -711,5 +678,5 @@ int gw_launch_set_position(const GwState& st, const GwDevConst& cst, int radio, 
 {
     hipLaunchKernelGGL(ct_set_position_kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        st, cst, radio, xs, ys, all_pos, mask);
-    return ok_or_ehip();
+    return gw_launch_status();
 }

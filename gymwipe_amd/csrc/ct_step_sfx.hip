@@ -20,6 +20,7 @@
 //   A.5  t_end = t_r + (slots+1)*slot; ticks every 1 ms (running f64 sum)   counter_traffic.py:53-61
 //   A.6  equal-time events: earlier-inserted first; process initialisation URGENT.
 #include "ct_common.hip.h"
+#include "gw_dispatch.h"
 #include "gw_queue.h"
 
 using namespace gwk;
@@ -28,32 +29,7 @@ using namespace gwk;
 
 namespace {
 
-template <class T>
-__device__ __forceinline__ T ld(const void* base, uint32_t byte_off)
-{
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-template <class T>
-__device__ __forceinline__ void st_(void* base, uint32_t byte_off, const T& v)
-{
-    gwk::gw_store_wt(reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off), v);
-}
-
-// byte `idx` (0..15) of a 16-byte record held in four registers, idx not known at compile time.  The words are
-// taken BY VALUE: selecting between the fields of a struct object is folded by the compiler into dynamic addressing
-// of a stack copy of it.
-__device__ __forceinline__ uint32_t byte_of(uint32_t x, uint32_t y, uint32_t z, uint32_t w, uint32_t idx)
-{
-    const uint32_t lo = (idx & 4u) ? y : x;
-    const uint32_t hi = (idx & 4u) ? w : z;
-    const uint32_t v = (idx & 8u) ? hi : lo;
-    return (v >> ((idx & 3u) * 8u)) & 0xffu;
-}
-__device__ __forceinline__ uint32_t word_of(const uint4& w, int i)          // i compile-time after unrolling
-{
-    return i == 0 ? w.x : (i == 1 ? w.y : (i == 2 ? w.z : w.w));
-}
-
+// (ld, st_, byte_of, word_of: ct_common.hip.h)
 
 // Step tables (GwStripeLayout, gw_internal.h; built by the host at gw_create: gw_api.cpp; state-major, so that only the
 // stripes of the noise states this handle's layout has are staged).  In LDS, because the step's first decisions wait on two
@@ -810,95 +786,51 @@ void* function_of(K kernel)                            // for the CURRENT device
     return f;
 }
 
-template <int DT, int MODE>
-hipError_t launch_mode(const GwState& st, unsigned grid, const int32_t* device, const int32_t* duration,
-                       int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, hipStream_t stream, uint64_t* rec, void* fn)
-{
-    gw_note_launch(rec, GW_LS_STEP_SFX + 3 * gw_ls_dt(DT) + MODE);
-    const uint32_t dev_stage = (uint32_t)st.D | ((uint32_t)st.stage_chunks << 8);
-    if (fn) {
-        StepArgs a = {(uint64_t)st.ip, (uint64_t)st.tw, (uint64_t)st.tk, (uint64_t)st.qb, (uint64_t)device, (uint64_t)duration,
-                      (uint32_t)st.N, dev_stage, (uint64_t)obs, (uint64_t)reward, (uint64_t)done, (uint64_t)fb};
-        size_t size = sizeof a;
-        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-        return hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, 64, 1, 1, 0, stream, nullptr, extra);
-    }
-    hipLaunchKernelGGL((ct_step_sfx_kernel<DT, MODE>), dim3(grid), dim3(64), 0, stream, (uint64_t)st.ip, (uint64_t)st.tw, (uint64_t)st.tk,
-                       (uint64_t)st.qb, (uint64_t)device, (uint64_t)duration, (uint32_t)st.N, dev_stage, (uint64_t)obs, (uint64_t)reward,
-                       (uint64_t)done, (uint64_t)fb);
-    return hipSuccess;
-}
-
-template <int DT>
-int launch(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
-           int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits, uint64_t* rec, const GwSfxFns* fns)
-{
-    const unsigned grid = (unsigned)((st.N + 63) / 64);  // the kernel's compile-time block size is 64
-    // every exact fast form validated for this handle (gw_create): the instantiation without their fallbacks -- and, when
-    // the host can rule out that any env reaches their validity limits in this launch, without the per-lane limit tests
-    const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.idem_states && cst.fast_ticks;
-    hipError_t e;
-    switch (fast ? (below_limits ? 2 : 1) : 0) {
-    case 2:  e = launch_mode<DT, 2>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec, fns ? fns->step[2] : nullptr); break;
-    case 1:  e = launch_mode<DT, 1>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec, fns ? fns->step[1] : nullptr); break;
-    default: e = launch_mode<DT, 0>(st, grid, device, duration, obs, reward, done, fb, (hipStream_t)stream, rec, fns ? fns->step[0] : nullptr); break;
-    }
-    // (the one error query of a step: it also takes a sticky error of an earlier asynchronous failure off the runtime)
-    return (hipGetLastError() == hipSuccess && e == hipSuccess) ? GW_OK : GW_EHIP;
-}
-
-template <int DT>
-void resolve(GwSfxFns* out)
-{
-    out->step[0] = function_of(&ct_step_sfx_kernel<DT, 0>);
-    out->step[1] = function_of(&ct_step_sfx_kernel<DT, 1>);
-    out->step[2] = function_of(&ct_step_sfx_kernel<DT, 2>);
-    out->reset = function_of(&ct_reset_sfx_kernel);
-}
-
-inline int ok_or_ehip() { return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP; }
-
 } // namespace
 
 void gw_resolve_sfx_functions(int D, GwSfxFns* out)
 {
-    switch (D) {
-    case 2:  resolve<2>(out); break;
-    case 3:  resolve<3>(out); break;
-    case 4:  resolve<4>(out); break;
-    case 5:  resolve<5>(out); break;
-    case 6:  resolve<6>(out); break;
-    case 7:  resolve<7>(out); break;
-    case 8:  resolve<8>(out); break;
-    case 16: resolve<16>(out); break;
-    case 32: resolve<32>(out); break;
-    default: resolve<0>(out); break;
-    }
+    gw_with_dt<GW_DTS_STEP>(D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        out->step[0] = function_of(&ct_step_sfx_kernel<DT, 0>);
+        out->step[1] = function_of(&ct_step_sfx_kernel<DT, 1>);
+        out->step[2] = function_of(&ct_step_sfx_kernel<DT, 2>);
+        out->step_slot = GW_LS_STEP_SFX + 3 * gw_ls_dt(DT);
+    });
+    out->reset = function_of(&ct_reset_sfx_kernel);
 }
 
 int gw_launch_step_sfx(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
                        int32_t* obs, float* reward, uint8_t* done, uint8_t* fb, void* stream, bool below_limits, uint64_t* rec,
                        const GwSfxFns* fns)
 {
-    switch (st.D) {
-    case 2:  return launch<2>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    case 3:  return launch<3>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    case 4:  return launch<4>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    case 5:  return launch<5>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    case 6:  return launch<6>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    case 7:  return launch<7>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    case 8:  return launch<8>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    case 16: return launch<16>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    case 32: return launch<32>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
-    default: return launch<0>(st, cst, device, duration, obs, reward, done, fb, stream, below_limits, rec, fns);
+    const unsigned grid = (unsigned)((st.N + 63) / 64);  // the kernel's compile-time block size is 64
+    const int mode = gw_step_mode(cst, below_limits, true);
+    const uint32_t dev_stage = (uint32_t)st.D | ((uint32_t)st.stage_chunks << 8);
+    if (fns && fns->step[mode]) {                        // the handle's resolved kernel: no dispatch, one argument block
+        gw_note_launch(rec, fns->step_slot + mode);
+        StepArgs a = {(uint64_t)st.ip, (uint64_t)st.tw, (uint64_t)st.tk, (uint64_t)st.qb, (uint64_t)device, (uint64_t)duration,
+                      (uint32_t)st.N, dev_stage, (uint64_t)obs, (uint64_t)reward, (uint64_t)done, (uint64_t)fb};
+        size_t size = sizeof a;
+        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+        return gw_launch_status(hipModuleLaunchKernel((hipFunction_t)fns->step[mode], grid, 1, 1, 64, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
     }
+    gw_with_dt<GW_DTS_STEP>(st.D, [&](auto dt) {
+        gw_with_mode(mode, [&](auto m) {
+            gw_note_launch(rec, GW_LS_STEP_SFX + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
+            hipLaunchKernelGGL((ct_step_sfx_kernel<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64), 0, (hipStream_t)stream,
+                               (uint64_t)st.ip, (uint64_t)st.tw, (uint64_t)st.tk, (uint64_t)st.qb, (uint64_t)device, (uint64_t)duration,
+                               (uint32_t)st.N, dev_stage, (uint64_t)obs, (uint64_t)reward, (uint64_t)done, (uint64_t)fb);
+        });
+    });
+    return gw_launch_status();
 }
 
 int gw_launch_init_sfx(const GwState& st, void* stream)
 {
     const unsigned grid = (unsigned)((st.N + 255) / 256);
     hipLaunchKernelGGL(ct_init_sfx_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st);
-    return ok_or_ehip();
+    return gw_launch_status();
 }
 
 // (one argument block through hipModuleLaunchKernel, as the step launch: ResetArgs mirrors the kernel's parameter list)
@@ -912,17 +844,16 @@ int gw_launch_reset_sfx(const GwState& st, const uint8_t* mask, int32_t* obs, vo
         ResetArgs a = {st.ip, (uint32_t)st.N, (uint32_t)st.D, mask, obs};
         size_t size = sizeof a;
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-        const hipError_t e = hipModuleLaunchKernel((hipFunction_t)fns->reset, grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra);
-        return (hipGetLastError() == hipSuccess && e == hipSuccess) ? GW_OK : GW_EHIP;
+        return gw_launch_status(hipModuleLaunchKernel((hipFunction_t)fns->reset, grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
     }
     hipLaunchKernelGGL(ct_reset_sfx_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st.ip, (uint32_t)st.N, (uint32_t)st.D, mask, obs);
-    return ok_or_ehip();
+    return gw_launch_status();
 }
 
 int gw_launch_delivered_sfx(const GwState& st, uint32_t* out, void* stream)
 {
     hipLaunchKernelGGL(ct_delivered_sfx_kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, st, out);
-    return ok_or_ehip();
+    return gw_launch_status();
 }
 
 int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream)
@@ -930,7 +861,7 @@ int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream)
     const int64_t total = st.N * (int64_t)st.D;
     const unsigned grid = (unsigned)((total + 255) / 256);
     hipLaunchKernelGGL(ct_received_sfx_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st, out);
-    return ok_or_ehip();
+    return gw_launch_status();
 }
 
 int gw_launch_pend_step(const GwState& st, const GwDevConst& cst, const GwPlantDev& p, const int32_t* device, const int32_t* duration,
@@ -939,19 +870,19 @@ int gw_launch_pend_step(const GwState& st, const GwDevConst& cst, const GwPlantD
     // 32 envs per wave while that still leaves SIMDs without a wave (1024 SIMDs: up to 32 768 envs), else 64
     const bool half = st.N <= 32 * 1024;
     const unsigned grid = (unsigned)((st.N + (half ? 31 : 63)) / (half ? 32 : 64));
-    const bool fast = cst.fast_fmod && cst.fast_div && cst.fast_decide && cst.idem_states && cst.fast_ticks;
-    const int mode = fast ? (below_limits ? 2 : 1) : 0;
-#define GW_PEND(MODE_, HALF_) do { gw_note_launch(rec, GW_LS_PEND + 2 * (MODE_) + (HALF_));                                     \
-        hipLaunchKernelGGL((pend_step_kernel<MODE_, HALF_>), dim3(grid), dim3(64), 0, (hipStream_t)stream, GW_LEAD_ARGS(st), p, obs, reward, angle_deg); } while (0)
-    if (half) { if (mode == 2) GW_PEND(2, true); else if (mode == 1) GW_PEND(1, true); else GW_PEND(0, true); }
-    else      { if (mode == 2) GW_PEND(2, false); else if (mode == 1) GW_PEND(1, false); else GW_PEND(0, false); }
-#undef GW_PEND
-    return ok_or_ehip();
+    gw_with_mode(gw_step_mode(cst, below_limits, true), [&](auto m) {
+        gw_with_flag(half, [&](auto h) {
+            gw_note_launch(rec, GW_LS_PEND + 2 * decltype(m)::value + (decltype(h)::value ? 1 : 0));
+            hipLaunchKernelGGL((pend_step_kernel<decltype(m)::value, decltype(h)::value>), dim3(grid), dim3(64), 0, (hipStream_t)stream,
+                               GW_LEAD_ARGS(st), p, obs, reward, angle_deg);
+        });
+    });
+    return gw_launch_status();
 }
 
 int gw_launch_clear_flags(const GwState& st, void* stream)
 {
     const int64_t n = st.N > st.n_slots ? st.N : st.n_slots;
     hipLaunchKernelGGL(ct_clear_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, st);
-    return ok_or_ehip();
+    return gw_launch_status();
 }

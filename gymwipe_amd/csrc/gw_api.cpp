@@ -229,7 +229,7 @@ void expand_sfx(uint32_t bound, uint32_t base, uint32_t mult, uint32_t len, uint
 int gw_fill_dev_const(const gw_config& cfg, const GwHostTables& tab, GwDevConst& k)
 {
     const int D = cfg.num_devices, R = D + 1;
-    k.D = D; k.R = R; k.S = GW_MAX_NSTATES;
+    k.D = D; k.R = R;
     k.counter_bound = cfg.counter_bound; k.payload_value = cfg.payload_value;
     k.mac_hdr = cfg.mac_header_bytes; k.net_hdr = cfg.net_header_bytes;
     k.duration_factor = cfg.duration_factor; k.max_duration = cfg.max_duration;
@@ -337,6 +337,155 @@ int gw_env_internals(gw_env* env, const GwState** st, const GwDevConst** cst, in
     return GW_OK;
 }
 
+namespace {
+
+// gw_create's one failure path: whatever the stages below have allocated goes with the handle
+struct EnvGuard {
+    gw_env* env;
+    ~EnvGuard() { if (env) gw_destroy(env); }
+};
+
+// stage 1 -- everything the host works out from the configuration: link tables, the kernels' constants, launch sizing
+int create_host_side(gw_env* env)
+{
+    const gw_config& cfg = env->cfg;
+    char msg[256] = "";
+    int rc = gw_build_tables(cfg, env->tab, msg, sizeof msg);
+    if (rc) return fail(rc, "%s", msg);
+    if ((rc = select_device(env))) return rc;
+    if (!(cfg.flags & GW_CFG_EXPLICIT_QUEUE)) gw_resolve_sfx_functions(cfg.num_devices, &env->fns);
+
+    GwDevConst& k = env->cst_host;
+    gw_fill_dev_const(cfg, env->tab, k);
+    // one env.step() advances an env's clock by at most: slot alignment + announcement + window + guard slot
+    const double max_slots = (double)(cfg.max_duration - 1) * cfg.duration_factor;
+    env->step_max = ((max_slots + 3.0) * cfg.slot + (double)(cfg.mac_header_bytes + 16) * 8.0 / env->tab.data_rate) * (1.0 + 1e-9) + 1e-9;
+    env->t_bound = cfg.start_time;
+    env->t_limit = (k.fast_fmod && k.cls_limit > 0.0) ? (k.fmod_limit < k.cls_limit ? k.fmod_limit : k.cls_limit) : 0.0;
+
+    GwState& st = env->st;
+    st.N = cfg.num_envs; st.D = cfg.num_devices; st.R = st.D + 1;
+    const char* kb = getenv("GW_BLOCK");            // tuning knob: threads per workgroup of the generic step kernel (the
+                                                    // suffix-queue kernels are fixed at 64: measured best, and a compile-time
+                                                    // block size keeps the hidden-argument load off their first cycles)
+    st.block = kb ? atoi(kb) : 64;
+    if (st.block != 16 && st.block != 32 && st.block != 64 && st.block != 128 && st.block != 256) st.block = 64;
+    env->no_split = getenv("GW_NO_SPLIT") ? 1 : 0;     // A/B switch: the generic kernel's one-wave form at block 64
+    env->dyn = ((cfg.flags & GW_CFG_PER_ENV_GEOMETRY) || env->tab.overflow) ? 1 : 0;
+    return GW_OK;
+}
+
+// stage 2 -- every device block of the handle, in the order the snapshot format records them (GwState says what each holds)
+int create_alloc(gw_env* env)
+{
+    const gw_config& cfg = env->cfg;
+    GwState& st = env->st;
+    const int64_t N = st.N;
+    const int D = st.D, R = st.R;
+    const bool explicit_q = (cfg.flags & GW_CFG_EXPLICIT_QUEUE) != 0;
+    const bool per_env_geo = (cfg.flags & GW_CFG_PER_ENV_GEOMETRY) != 0;
+    int rc = GW_OK;
+    auto alloc = [&](auto& ptr, size_t count) { if (!rc) rc = dev_alloc(env, &ptr, count); };   // (nothing after a failure)
+    if (explicit_q) {
+        st.XB = 16 * ((R + 15) / 16);
+        alloc(st.xw, N * 2);    alloc(st.xc, N * 4);    alloc(st.xs, N * st.XB);
+        alloc(st.qrec, N * D);  alloc(st.runs, N * D * GW_RING_PHYS);
+    } else {
+        st.RB = 16 * ((2 * D + 1 + 15) / 16);
+        alloc(st.tw, N * 2);   alloc(st.tk, N * 4);
+        alloc(st.blob, (size_t)gw_blob_header(D) + (size_t)N * 16);    // the step tables and the `ip` records share a block
+        if (!rc) st.ip = reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(st.blob) + gw_blob_header(D));
+        alloc(st.qb, N * st.RB);  alloc(st.bph, N * GW_RING_PHYS);
+        alloc(st.sa, N * GW_SA_WORDS + 2);
+        const char* rc_env = getenv("GW_ROLLOUT_CAP");      // steps per fused rollout launch
+        int cap = rc_env ? atoi(rc_env) : 64;
+        if (cap < 0) cap = 0;
+        st.rcap = (cap + 15) / 16 * 16;
+        // (scratch of the event-loop form only -- packed action / feedback records, 3 bytes per env and step of a chunk: an A/B
+        //  switch since the step-synchronous kernel reads and writes the caller's arrays; the switch is read here)
+        if (st.rcap > 0 && getenv("GW_ROLLOUT_EVENT_LOOP")) { alloc(st.ract, N * st.rcap);  alloc(st.rfb, N * st.rcap); }
+    }
+    if (env->dyn) {
+        const int RP = gw_rp(R);                            // rows of one env's radios, 16-byte aligned (gw_internal.h)
+        alloc(st.rxp, N * RP);  alloc(st.prx_tab, R * R);  alloc(st.pos_tab, R * 2);  alloc(st.extra_tab, R * R);
+        if (!explicit_q) { alloc(st.bcache, N * 2 * D * 2);  alloc(st.rxr, N); }
+        if (per_env_geo) { alloc(st.prx_env, N * R * RP);  alloc(st.pos_env, N * R * 2); }
+        if (per_env_geo && explicit_q) alloc(st.talk, N);   // (default queue mode: the mask lives in spare bytes of the qb record)
+    }
+    if (explicit_q && (cfg.flags & GW_CFG_PEER_RECEIVE)) alloc(st.peer_rx, N * D);
+    if (explicit_q && (cfg.flags & GW_CFG_PER_ENV_STATS)) alloc(st.pe_stats, N * 5);
+    st.n_slots = (N + 15) / 16 + 1;                   // one per wave; sized for the narrowest block (16) and for two waves per 64 envs
+    if (explicit_q) alloc(st.totals, st.n_slots * GW_T_COUNT);
+#ifdef GW_STAMPS
+    alloc(st.stamps, st.n_slots * 16);
+#endif
+    const size_t tcount = (size_t)R * R * GW_MAX_NSTATES;
+    alloc(st.cst, 1);  alloc(st.trans, tcount + 16);  alloc(st.ber, tcount);  alloc(st.cls, tcount);
+    alloc(st.ber2, 2 * D * GW_MAX_NSTATES + 2);  alloc(st.cls2, 2 * D * GW_MAX_NSTATES + 16);
+    if (explicit_q) alloc(st.blob, GwBlobLayout(D).total + 16);
+    return rc;
+}
+
+int upload(const void* dev, const void* host, size_t bytes)
+{
+    HIP_TRY(hipMemcpy(const_cast<void*>(dev), host, bytes, hipMemcpyHostToDevice));
+    return GW_OK;
+}
+
+// default mode: the two structs in the header of the `ip` block (gw_blob_header), which hold THIS handle's device pointers
+int upload_header_structs(const gw_env* env)
+{
+    const int D = env->st.D;
+    int rc = upload(env->st.blob + gw_hdr_cst_off(D), &env->cst_host, sizeof env->cst_host);
+    return rc ? rc : upload(env->st.blob + gw_hdr_st_off(D), &env->st, sizeof env->st);
+}
+
+// stage 3 -- constants, link tables and the step tables' image to the device; zeroes where the kernels expect them
+int create_upload(gw_env* env)
+{
+    GwState& st = env->st;
+    const GwHostTables& tab = env->tab;
+    const int64_t N = st.N;
+    const int D = st.D, R = st.R;
+    const size_t tcount = (size_t)R * R * GW_MAX_NSTATES;
+    int rc;
+    if ((rc = upload(st.cst, &env->cst_host, sizeof env->cst_host)) || (rc = upload(st.trans, tab.trans, tcount * sizeof(uint8_t))) ||
+        (rc = upload(st.ber, tab.ber, tcount * sizeof(double))) || (rc = upload(st.cls, tab.cls, tcount * sizeof(uint8_t))))
+        return rc;
+    std::vector<double> ber2;
+    std::vector<uint8_t> cls2;
+    gw_link_slices(tab, ber2, cls2);
+    if ((rc = upload(st.ber2, ber2.data(), ber2.size() * sizeof(double))) || (rc = upload(st.cls2, cls2.data(), cls2.size()))) return rc;
+    const std::vector<uint8_t> image = st.ip ? gw_stripe_image(tab, env->cst_host, &st.stage_chunks) : gw_blob_image(tab, env->cst_host);
+    if ((rc = upload(st.blob, image.data(), image.size()))) return rc;
+    if (st.totals) HIP_TRY(hipMemset(st.totals, 0, (size_t)st.n_slots * GW_T_COUNT * sizeof(unsigned long long)));
+    if (st.runs) HIP_TRY(hipMemset(st.runs, 0, (size_t)N * D * GW_RING_PHYS * sizeof(uint64_t)));
+    if (st.bph) HIP_TRY(hipMemset(st.bph, 0, (size_t)N * GW_RING_PHYS * sizeof(GwBp)));
+    if (env->dyn) {
+        std::vector<double> prx((size_t)R * R, 0.0), pos((size_t)R * 2), ext((size_t)R * R, 0.0);
+        for (int a = 0; a < R; ++a) {
+            pos[(size_t)a * 2] = env->cfg.pos[a][0]; pos[(size_t)a * 2 + 1] = env->cfg.pos[a][1];
+            for (int b = 0; b < R; ++b) { prx[(size_t)a * R + b] = tab.prx[a][b]; ext[(size_t)a * R + b] = env->cfg.extra_att_db[a][b]; }
+        }
+        if ((rc = upload(st.prx_tab, prx.data(), prx.size() * sizeof(double))) || (rc = upload(st.pos_tab, pos.data(), pos.size() * sizeof(double))) ||
+            (rc = upload(st.extra_tab, ext.data(), ext.size() * sizeof(double))))
+            return rc;
+    }
+    return st.ip ? upload_header_structs(env) : GW_OK;   // (last: GwState is complete only now)
+}
+
+// stage 4 -- fresh envs
+int create_init(gw_env* env)
+{
+    int rc = env->st.ip ? gw_launch_init_sfx(env->st, nullptr) : gw_launch_init(env->st, nullptr);
+    if (!rc && env->dyn) rc = gw_launch_init_dyn(env->st, env->cst_host, env->tab.thermal, nullptr);
+    if (rc) return fail(GW_EHIP, "init kernel launch failed");
+    HIP_TRY(hipDeviceSynchronize());
+    return GW_OK;
+}
+
+} // namespace
+
 extern "C" {
 
 int gw_abi_version(void) { return GW_ABI_VERSION; }
@@ -408,180 +557,14 @@ int gw_create(const gw_config* cfg, gw_env** out)
     if (cfg->hip_device < 0 || cfg->hip_device >= ndev)
         return fail(GW_EINVAL, "hip_device %d out of range (have %d)", cfg->hip_device, ndev);
 
-    gw_env* env = new (std::nothrow) gw_env();
+    EnvGuard guard = {new (std::nothrow) gw_env()};
+    gw_env* env = guard.env;
     if (!env) return fail(GW_ENOMEM, "out of host memory");
     memset(env, 0, sizeof *env);
     env->cfg = *cfg;
-
-    char msg[256] = "";
-    rc = gw_build_tables(env->cfg, env->tab, msg, sizeof msg);
-    if (rc) { delete env; return fail(rc, "%s", msg); }
-
-    if ((rc = select_device(env))) { delete env; return rc; }
-    if (!(cfg->flags & GW_CFG_EXPLICIT_QUEUE)) gw_resolve_sfx_functions(cfg->num_devices, &env->fns);
-
-    const int D = cfg->num_devices, R = D + 1;
-    const int64_t N = cfg->num_envs;
-    GwDevConst& k = env->cst_host;
-    gw_fill_dev_const(*cfg, env->tab, k);
-
-    {
-        // one env.step() advances an env's clock by at most: slot alignment + announcement + window + guard slot
-        const double max_slots = (double)(cfg->max_duration - 1) * cfg->duration_factor;
-        env->step_max = ((max_slots + 3.0) * cfg->slot + (double)(cfg->mac_header_bytes + 16) * 8.0 / env->tab.data_rate) * (1.0 + 1e-9) + 1e-9;
-        env->t_bound = cfg->start_time;
-        env->t_limit = (k.fast_fmod && k.cls_limit > 0.0) ? (k.fmod_limit < k.cls_limit ? k.fmod_limit : k.cls_limit) : 0.0;
-    }
-    GwState& st = env->st;
-    st.N = N; st.D = D; st.R = R;
-    {
-        const char* kb = getenv("GW_BLOCK");        // tuning knob: threads per workgroup of the generic step kernel (the
-                                                    // suffix-queue kernels are fixed at 64: measured best, and a compile-time
-                                                    // block size keeps the hidden-argument load off their first cycles)
-        st.block = kb ? atoi(kb) : 64;
-        if (st.block != 16 && st.block != 32 && st.block != 64 && st.block != 128 && st.block != 256) st.block = 64;
-        env->no_split = getenv("GW_NO_SPLIT") ? 1 : 0;     // A/B switch: the generic kernel's one-wave form at block 64
-    }
-    GwDevConst* d_cst = nullptr; uint8_t* d_trans = nullptr; double* d_ber = nullptr;
-    const size_t tcount = (size_t)R * R * GW_MAX_NSTATES;
-#define TRY_ALLOC(ptr, count) do { rc = dev_alloc(env, &(ptr), (size_t)(count)); if (rc) { gw_destroy(env); return rc; } } while (0)
-    const bool explicit_q = (cfg->flags & GW_CFG_EXPLICIT_QUEUE) != 0;
-    const bool per_env_geo = (cfg->flags & GW_CFG_PER_ENV_GEOMETRY) != 0;
-    env->dyn = (per_env_geo || env->tab.overflow) ? 1 : 0;
-    uint8_t* d_cls = nullptr; double* d_ber2 = nullptr; uint8_t* d_cls2 = nullptr; uint8_t* d_blob = nullptr;
-    if (explicit_q) {
-        st.XB = 16 * ((R + 15) / 16);
-        TRY_ALLOC(st.xw, N * 2);    TRY_ALLOC(st.xc, N * 4);    TRY_ALLOC(st.xs, N * st.XB);
-        TRY_ALLOC(st.qrec, N * D);  TRY_ALLOC(st.runs, N * D * GW_RING_PHYS);
-    } else {
-        st.RB = 16 * ((2 * D + 1 + 15) / 16);
-        TRY_ALLOC(st.tw, N * 2);   TRY_ALLOC(st.tk, N * 4);
-        {                                                   // the step tables and the `ip` records share a block: gw_blob_header()
-            uint8_t* blk = nullptr;
-            TRY_ALLOC(blk, (size_t)gw_blob_header(D) + (size_t)N * 16);
-            d_blob = blk;
-            st.ip = reinterpret_cast<uint32_t*>(blk + gw_blob_header(D));
-        }
-        TRY_ALLOC(st.qb, N * st.RB);  TRY_ALLOC(st.bph, N * GW_RING_PHYS);
-        TRY_ALLOC(st.sa, N * GW_SA_WORDS + 2);
-        {
-            const char* rc_env = getenv("GW_ROLLOUT_CAP");      // steps per fused rollout launch
-            int cap = rc_env ? atoi(rc_env) : 64;
-            if (cap < 0) cap = 0;
-            st.rcap = (cap + 15) / 16 * 16;
-            // (scratch of the event-loop form only -- packed action / feedback records, 3 bytes per env and step of a chunk: an A/B
-            //  switch since the step-synchronous kernel reads and writes the caller's arrays; the switch is read here)
-            if (st.rcap > 0 && getenv("GW_ROLLOUT_EVENT_LOOP")) { TRY_ALLOC(st.ract, N * st.rcap);  TRY_ALLOC(st.rfb, N * st.rcap); }
-        }
-    }
-    double *d_prx = nullptr, *d_pos = nullptr, *d_extra = nullptr;
-    if (env->dyn) {
-        const int RP = gw_rp(R);                            // rows of one env's radios, 16-byte aligned (gw_internal.h)
-        TRY_ALLOC(st.rxp, N * RP);  TRY_ALLOC(d_prx, R * R);  TRY_ALLOC(d_pos, R * 2);  TRY_ALLOC(d_extra, R * R);
-        if (!explicit_q) { TRY_ALLOC(st.bcache, N * 2 * D * 2);  TRY_ALLOC(st.rxr, N); }
-        if (per_env_geo) { TRY_ALLOC(st.prx_env, N * R * RP);  TRY_ALLOC(st.pos_env, N * R * 2); }
-        if (per_env_geo && explicit_q) TRY_ALLOC(st.talk, N);   // (default queue mode: the mask lives in spare bytes of the qb record)
-        st.prx_tab = d_prx; st.pos_tab = d_pos; st.extra_tab = d_extra;
-    }
-    if (explicit_q && (cfg->flags & GW_CFG_PEER_RECEIVE)) TRY_ALLOC(st.peer_rx, N * D);
-    if (explicit_q && (cfg->flags & GW_CFG_PER_ENV_STATS)) TRY_ALLOC(st.pe_stats, N * 5);
-    st.n_slots = (N + 15) / 16 + 1;                   // one per wave; sized for the narrowest block (16) and for two waves per 64 envs
-    if (explicit_q) TRY_ALLOC(st.totals, st.n_slots * GW_T_COUNT);
-#ifdef GW_STAMPS
-    TRY_ALLOC(st.stamps, st.n_slots * 16);
-#endif
-    TRY_ALLOC(d_cst, 1);       TRY_ALLOC(d_trans, tcount + 16);  TRY_ALLOC(d_ber, tcount);  TRY_ALLOC(d_cls, tcount);
-    TRY_ALLOC(d_ber2, 2 * D * GW_MAX_NSTATES + 2);  TRY_ALLOC(d_cls2, 2 * D * GW_MAX_NSTATES + 16);
-    if (!d_blob) TRY_ALLOC(d_blob, GwBlobLayout(D).total + 16);
-#undef TRY_ALLOC
-    st.cst = d_cst; st.trans = d_trans; st.ber = d_ber; st.cls = d_cls; st.ber2 = d_ber2; st.cls2 = d_cls2; st.blob = d_blob;
-
-#define HIP_TRY_D(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { rc = fail(GW_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); gw_destroy(env); return rc; } } while (0)
-    HIP_TRY_D(hipMemcpy(d_cst, &k, sizeof k, hipMemcpyHostToDevice));
-    HIP_TRY_D(hipMemcpy(d_trans, env->tab.trans, tcount * sizeof(uint8_t), hipMemcpyHostToDevice));
-    HIP_TRY_D(hipMemcpy(d_ber, env->tab.ber, tcount * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY_D(hipMemcpy(d_cls, env->tab.cls, tcount * sizeof(uint8_t), hipMemcpyHostToDevice));
-    {
-        std::vector<double> b2((size_t)2 * D * GW_MAX_NSTATES);
-        std::vector<uint8_t> c2((size_t)2 * D * GW_MAX_NSTATES);
-        for (int dd = 0; dd < D; ++dd)
-            for (int ss = 0; ss < GW_MAX_NSTATES; ++ss) {
-                const size_t ann = ((size_t)dd * R + D) * GW_MAX_NSTATES + ss;      // to = dd, from = RRM
-                const size_t dat = ((size_t)D * R + dd) * GW_MAX_NSTATES + ss;      // to = RRM, from = dd
-                b2[(size_t)dd * GW_MAX_NSTATES + ss] = env->tab.ber[ann];
-                c2[(size_t)dd * GW_MAX_NSTATES + ss] = env->tab.cls[ann];
-                b2[((size_t)D + dd) * GW_MAX_NSTATES + ss] = env->tab.ber[dat];
-                c2[((size_t)D + dd) * GW_MAX_NSTATES + ss] = env->tab.cls[dat];
-            }
-        HIP_TRY_D(hipMemcpy(d_ber2, b2.data(), b2.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY_D(hipMemcpy(d_cls2, c2.data(), c2.size(), hipMemcpyHostToDevice));
-        // the default step kernel's tables in one block (GwBlobLayout)
-        const GwBlobLayout L(D);
-        std::vector<uint8_t> blob((size_t)L.total, 0);
-        memcpy(blob.data() + L.ber, b2.data(), b2.size() * sizeof(double));
-        memcpy(blob.data() + L.cls, c2.data(), c2.size());
-        const uint8_t* tr = env->tab.trans;
-        const int S = GW_MAX_NSTATES;
-        for (int j = 0; j < D; ++j) {
-            const uint32_t mi[2] = {(uint32_t)k.mult[j], k.inv16[j]};
-            memcpy(blob.data() + L.mi + (size_t)j * 8, mi, 8);
-            for (int s0 = 0; s0 < S; ++s0) {
-                const uint8_t a = tr[((size_t)j * R + D) * S + s0];                 // j hears the RRM
-                blob[(size_t)L.h1 + (size_t)j * S + s0] = a;
-                blob[(size_t)L.r1 + (size_t)j * S + s0] = tr[((size_t)D * R + j) * S + s0];   // the RRM hears j
-                for (int dd = 0; dd < D; ++dd)
-                    blob[(size_t)L.h2 + ((size_t)j * D + dd) * S + s0] = (j == dd) ? a : tr[((size_t)j * R + dd) * S + a];
-            }
-        }
-        if (!st.ip) {                               // explicit mode: the generic kernel's tables (GwBlobLayout)
-            HIP_TRY_D(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-        } else {                                    // suffix mode: the same numbers state-major (GwStripeLayout), in the ip block's header
-            const GwStripeLayout T(D);
-            std::vector<uint8_t> sb((size_t)T.total, 0);
-            int nst = 1;
-            for (int r = 0; r < R; ++r) nst = env->tab.nstates[r] > nst ? env->tab.nstates[r] : nst;
-            if (nst > S) nst = S;
-            for (int j = 0; j < D; ++j) {
-                memcpy(sb.data() + T.mi + (size_t)j * 8, blob.data() + L.mi + (size_t)j * 8, 8);
-                for (int s0 = 0; s0 < S; ++s0) {
-                    uint8_t* stripe = sb.data() + T.s0 + (size_t)s0 * T.stripe;
-                    memcpy(stripe + T.ber0 + (size_t)j * 8, &b2[(size_t)j * S + s0], 8);
-                    memcpy(stripe + T.ber1 + (size_t)j * 8, &b2[((size_t)D + j) * S + s0], 8);
-                    stripe[T.h1 + j] = blob[(size_t)L.h1 + (size_t)j * S + s0];
-                    stripe[T.r1 + j] = blob[(size_t)L.r1 + (size_t)j * S + s0];
-                    stripe[T.cls0 + j] = c2[(size_t)j * S + s0];
-                    stripe[T.cls1 + j] = c2[((size_t)D + j) * S + s0];
-                    for (int dd = 0; dd < D; ++dd)
-                        sb[(size_t)T.h2 + ((size_t)s0 * D + j) * D + dd] = blob[(size_t)L.h2 + ((size_t)j * D + dd) * S + s0];
-                }
-            }
-            st.stage_chunks = T.staged_chunks(env->tab.overflow ? S : nst);
-            HIP_TRY_D(hipMemcpy(d_blob, sb.data(), sb.size(), hipMemcpyHostToDevice));
-        }
-    }
-    if (st.totals) HIP_TRY_D(hipMemset(st.totals, 0, (size_t)st.n_slots * GW_T_COUNT * sizeof(unsigned long long)));
-    if (st.runs) HIP_TRY_D(hipMemset(st.runs, 0, (size_t)N * D * GW_RING_PHYS * sizeof(uint64_t)));
-    if (st.bph) HIP_TRY_D(hipMemset(st.bph, 0, (size_t)N * GW_RING_PHYS * sizeof(GwBp)));
-    if (env->dyn) {
-        std::vector<double> prx((size_t)R * R, 0.0), pos((size_t)R * 2), ext((size_t)R * R, 0.0);
-        for (int a = 0; a < R; ++a) {
-            pos[(size_t)a * 2] = cfg->pos[a][0]; pos[(size_t)a * 2 + 1] = cfg->pos[a][1];
-            for (int b = 0; b < R; ++b) { prx[(size_t)a * R + b] = env->tab.prx[a][b]; ext[(size_t)a * R + b] = cfg->extra_att_db[a][b]; }
-        }
-        HIP_TRY_D(hipMemcpy(d_prx, prx.data(), prx.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY_D(hipMemcpy(d_pos, pos.data(), pos.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY_D(hipMemcpy(d_extra, ext.data(), ext.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (st.ip) {                                    // the per-step kernels read both structs from the header of the ip block
-        HIP_TRY_D(hipMemcpy(d_blob + gw_hdr_cst_off(D), &k, sizeof k, hipMemcpyHostToDevice));
-        HIP_TRY_D(hipMemcpy(d_blob + gw_hdr_st_off(D), &st, sizeof st, hipMemcpyHostToDevice));
-    }
-    rc = explicit_q ? gw_launch_init(st, nullptr) : gw_launch_init_sfx(st, nullptr);
-    if (!rc && env->dyn) rc = gw_launch_init_dyn(st, k, env->tab.thermal, nullptr);
-    if (rc) { rc = fail(GW_EHIP, "init kernel launch failed"); gw_destroy(env); return rc; }
-    HIP_TRY_D(hipDeviceSynchronize());
-#undef HIP_TRY_D
+    if ((rc = create_host_side(env)) || (rc = create_alloc(env)) || (rc = create_upload(env)) || (rc = create_init(env))) return rc;
     env->nblocks_create = env->nblocks;
+    guard.env = nullptr;
     *out = env;
     return GW_OK;
 }
@@ -885,12 +868,7 @@ int gw_set_state(gw_env* env, const void* src, uint64_t bytes)
         in += env->block_bytes[i];
     }
     // the header in front of the `ip` records holds THIS handle's device pointers: put them back
-    if (env->st.ip) {
-        uint8_t* blob = const_cast<uint8_t*>(env->st.blob);
-        const int D = env->st.D;
-        HIP_TRY(hipMemcpy(blob + gw_hdr_cst_off(D), &env->cst_host, sizeof env->cst_host, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(blob + gw_hdr_st_off(D), &env->st, sizeof env->st, hipMemcpyHostToDevice));
-    }
+    if (env->st.ip && (rc = upload_header_structs(env))) return rc;
     env->t_bound = h.t_bound > env->t_bound ? h.t_bound : env->t_bound;      // (an upper bound either way)
     env->captured |= h.captured;                                             // ... unless graph replays moved the source's clocks
     HIP_TRY(hipDeviceSynchronize());
@@ -926,7 +904,7 @@ int gw_noise_states(gw_env* env, int32_t radio, int32_t* count, double* values)
 // The kernel instantiation behind a launch-record slot (gw_internal.h), spelled as c++filt prints the kernel's symbol.
 static void launch_slot_name(int slot, char* out, size_t cap)
 {
-    static const int dts[GW_LS_NDT] = {2, 3, 4, 5, 6, 7, 8, 16, 32, 0};
+    static const int dts[GW_LS_NDT] = {GW_LS_DTS};
     static const char* const tf[2] = {"false", "true"};
     if (slot < GW_LS_PEND) {
         static const char* const fam[3] = {"ct_step_sfx_kernel", "ct_rollout_sync_kernel", "ct_rollout_sfx_kernel"};

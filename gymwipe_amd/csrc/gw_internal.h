@@ -1,8 +1,10 @@
-// gw_internal.h -- shared between the host side (gw_api.cpp, gw_tables.cpp) and the
-// HIP kernels (ct_step.hip).  Not part of the public C-ABI.
+// gw_internal.h -- what the host side (gw_*_api.cpp, gw_tables.cpp) and every kernel file (*.hip) share: the device-side
+// structs and table layouts, the launchers' prototypes, the launch record's slots.  Not part of the public C-ABI.
+// (Device helpers: ct_common.hip.h; picking a kernel instantiation: gw_dispatch.h.)
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include <vector>
 #include "../../include/gymwipe_amd.h"
 
 #define GW_RING_PHYS      128          // physical ring slots per (env, sender); logical capacity GW_QUEUE_CAP
@@ -14,7 +16,7 @@
 // Constants the kernels need, resident in device global memory (read through
 // the scalar cache: every field is wave-uniform).
 struct GwDevConst {
-    int32_t D, R, S;                    // senders, radios (D+1), states per radio (GW_MAX_NSTATES)
+    int32_t D, R;                       // senders, radios (D+1)
     int32_t counter_bound, payload_value, mac_hdr, net_hdr, duration_factor, max_duration;
     int32_t mult[GW_MAX_DEVICES];
     double  slot, data_rate, bit_rate, coded_factor, max_ber, counter_interval;
@@ -42,63 +44,70 @@ struct GwDevConst {
 struct GwBp { uint32_t t0, c0; };        // counting restarts at tick t0 with counter value c0
 struct alignas(16) GwRec { uint32_t x, y, z, w; };   // a run-length queue's 16-byte record (gw_runq.h)
 
-// Per-handle device state (structure of arrays; N = num_envs, D senders, R = D+1 radios).
+// Per-handle device state: sizes and device pointers (N = num_envs, D senders, R = D+1 radios), by value to the kernels that
+// are not launched per step and in the header in front of the `ip` records for those that are (gw_blob_header below).  A
+// pointer the handle's mode does not use is null.  Grouped by the gw_create branch that sets the fields -- but their ORDER is
+// part of the kernels' code (the compiler merges the scalar loads of neighbouring fields: moving a group changes the
+// instruction stream of every kernel that reads it), so the explicit-queue mode's fields and the common ones come in two
+// groups each, and `block` keeps peer_rx and pe_stats apart.
 struct GwState {
+    // ---- every mode: sizes (gw_create, before any branch) ----
     int64_t   N;
     int32_t   D, R;     // host-side copies of the constants (launch sizing)
-    int32_t   block;    // threads per workgroup of the step kernel
-    int32_t   stage_chunks;  // suffix mode: 16-byte chunks of the state-major tables a step kernel stages in LDS (GwStripeLayout)
-    double*   now;        // [N]        simulated time (SimMan.now)
-    double*   wake;       // [N]        next counter tick (all senders tick in lock-step)
-    uint32_t* counter;    // [N]        sender.counter (identical for all senders of an env)
-    // explicit-queue mode (GW_CFG_EXPLICIT_QUEUE), packed so that an env's scalars are three 16-byte loads and stores:
+    int32_t   stage_chunks;  // default mode: 16-byte chunks of the state-major tables a step kernel stages in LDS (GwStripeLayout)
+
+    // ---- explicit-queue mode (gw_create's GW_CFG_EXPLICIT_QUEUE branch), packed so that an env's scalars are three 16-byte
+    //      loads and stores; MAC queues (SimpleMac._packetQueue) as run-length deques, gw_runq.h ----
     double*   xw;         // [N][2]     {now, next counter tick}
     uint32_t* xc;         // [N][4]     {counter, rvmask, last_abs | done << 31, sticky GW_FLAG_* bits}
     uint8_t*  xs;         // [N][XB]    rx-power state index per radio 0..D (stands for phy._receivedPower), padded to 16 bytes
     int32_t   XB;         //            bytes per xs record: 16 * ceil((D + 1) / 16)
-    // MAC queue (SimpleMac._packetQueue), one of two encodings:
-    //  explicit (GW_CFG_EXPLICIT_QUEUE): run-length deques, gw_runq.h
     GwRec*    qrec;       // [D][N]     16-byte record: head run, tail run, bookkeeping
     uint64_t* runs;       // [N][D][GW_RING_PHYS]  the runs in between (touched only when a run is created or used up)
-    //  suffix (default): see gw_queue.h.  Packed so that one env costs four 16-byte loads:
+
+    // ---- default (suffix) mode (gw_create's branch without GW_CFG_EXPLICIT_QUEUE): MAC queues in the encoding of
+    //      gw_queue.h, packed so that one env costs four 16-byte loads ----
     double*   tw;         // [N][2]     {now, next counter tick}
     uint32_t* tk;         // [N][4]     {tau = ticks so far, nbp = breakpoints so far, rvmask, last_abs | done << 31}: stored whole per step
     uint32_t* ip;         // [N][4]     {newest breakpoint (t0, c0), second newest breakpoint (t0, c0)}: written by reset / init only
     uint8_t*  qb;         // [N][RB]    bytes: queue length of sender 0..D-1, rx-power state of radio 0..D, pad
     GwBp*     bph;        // [N][GW_RING_PHYS]  ring of all breakpoints, entry j at [j & 127] (read only after >2 resets/100 ticks)
     int32_t   RB;         //            bytes per qb record: 16 * ceil((2*D + 1) / 16)
-    uint16_t* ract;       // [N][rcap]  rollout scratch: packed actions (device | duration << 8)
-    uint8_t*  rfb;        // [N][rcap]  rollout scratch: packed feedback bytes
+    uint16_t* ract;       // [N][rcap]  event-loop rollout scratch: packed actions (device | duration << 8), or nullptr
+    uint8_t*  rfb;        // [N][rcap]  event-loop rollout scratch: packed feedback bytes, or nullptr
     int32_t   rcap;       //            steps per fused rollout launch (multiple of 16)
     uint32_t* sa;         // [4N + 2]   per-env event counters that cannot be derived from the state: {popped, delivered} bad
                           //            actions, sticky flags (layout: GW_SA_WORDS), bumped by no-return atomics only where
                           //            something happened; + the handle's step count.
                           //            (steps = launches - bad; transmissions = steps + popped; appended = tau * sum(mult);
                           //            dropped = appended - popped - sum(len): gw_api.cpp derives them)
-    uint32_t* rvmask;     // [N]        bit i set <=> receivedValues[i] == payload_value
-    int32_t*  last_abs;   // [N]        interpreter._lastAbsDifference
-    uint8_t*  done;       // [N]        interpreter._done
-    uint8_t*  rxs;        // [R][N]     rx-power state index per radio (stands for phy._receivedPower)
+
+    // ---- explicit-queue mode, continued: its event counters ----
     uint32_t* peer_rx;    // [D][N] or nullptr (GW_CFG_PEER_RECEIVE): packets a receive-mode MAC handed up
-    uint32_t* flags;      // [N]        sticky GW_FLAG_* bits
-    uint64_t* pe_stats;   // [5][N] or nullptr: n_tx, n_delivered, n_appended, n_popped, n_dropped
+    int32_t   block;      //            threads per workgroup of the generic step kernel (GW_BLOCK; host only)
+    uint64_t* pe_stats;   // [5][N] or nullptr (GW_CFG_PER_ENV_STATS): n_tx, n_delivered, n_appended, n_popped, n_dropped
     unsigned long long* totals;  // [n_slots][GW_T_COUNT], one 64-B slot per wave of the step launch:
                                  // steps, tx, delivered, appended, popped, dropped, flags_or, bad_actions
-    int64_t   n_slots;
-    unsigned long long* stamps;  // diagnostic build only (make STAMPS=1): [n_slots][8] s_memtime stamps of the last launch
+
+    // ---- every mode, continued: the link tables (gw_create, after the branches) ----
+    int64_t   n_slots;           // waves a step launch can have: slots of `totals` (and of `stamps`)
+    unsigned long long* stamps;  // diagnostic build only (make STAMPS=1): [n_slots][16] s_memtime stamps of the last launch
     const GwDevConst* cst;
     const uint8_t*    trans;     // [R to][R from][S]  state after hearing `from`
     const double*     ber;       // [R to][R from][S]  BER at `to` while hearing `from`, indexed by the NEW state
     const uint8_t*    cls;       // [R to][R from][S]  decode certainty at `to` hearing `from` (GW_CLS_*), by the NEW state
-    // compact slices of ber/cls the step actually needs, staged in LDS by the suffix kernel:
-    //   [0][d][s]: sender d hearing the RRM's announcement;  [1][d][s]: the RRM hearing sender d
+    // compact slices of ber/cls: [0][d][s] sender d hearing the RRM's announcement;  [1][d][s] the RRM hearing sender d
     const double*     ber2;      // [2][D][S]
     const uint8_t*    cls2;      // [2][D][S]
-    const uint8_t*    blob;      // GwBlobLayout: the default step kernel's tables in one block
-    // live-PHY mode (ct_step_dyn.hip): f64 received power per radio instead of the noise-state bytes.  One env's radios are
-    // CONTIGUOUS (rows of RP = gw_rp(R) doubles, 16-byte aligned): the all-pairs update of a step touches every radio of an
-    // env and one or two rows of its link matrix, so whole rows are what a lane -- or, for D >= 8, a group of D lanes -- reads.
-    double*   rxp;        // [N][RP]    phy._receivedPower, or nullptr (default mode)
+    const uint8_t*    blob;      // the step tables in one block: GwStripeLayout (default mode: the start of the `ip` block)
+                                 // or GwBlobLayout (explicit-queue mode)
+
+    // ---- live PHY (ct_step_dyn.hip; with either queue mode): gw_create's `dyn` branch (GW_CFG_PER_ENV_GEOMETRY, or a
+    //      geometry without a finite noise-state set).  f64 received power per radio instead of the noise-state bytes.  One
+    //      env's radios are CONTIGUOUS (rows of RP = gw_rp(R) doubles, 16-byte aligned): the all-pairs update of a step touches
+    //      every radio of an env and one or two rows of its link matrix, so whole rows are what a lane -- or, for D >= 8, a
+    //      group of D lanes -- reads ----
+    double*   rxp;        // [N][RP]    phy._receivedPower, or nullptr (table PHY)
     const double* prx_tab;   // [R][R]  link power from -> to, mW (host glibc tables)
     const double* pos_tab;   // [R][2]  the handle's geometry
     const double* extra_tab; // [R][R]  custom attenuation per pair, dB
@@ -161,8 +170,10 @@ struct GwStripeLayout {
 };
 
 // In the default (suffix-queue) mode the step tables, the handle's GwDevConst and its GwState live in the SAME allocation as
-// the `ip` records, in a header of gw_blob_header(D) bytes in front of them (gw_api.cpp fills it at gw_create):
-//     [ tables (GwStripeLayout) | GwDevConst at gw_hdr_cst_off | GwState at gw_hdr_st_off | pad to 256 ] [ ip records ... ]
+// the `ip` records, in a header of gw_blob_header(D) bytes in front of them (gw_create uploads it; gw_set_state puts the two
+// structs back after restoring the block):
+//     [ tables (GwStripeLayout, gw_stripe_image) | GwDevConst at gw_hdr_cst_off | GwState at gw_hdr_st_off | pad to 256 ] [ ip records ... ]
+// (sizeof both structs therefore shows in the block's size, gw_state_bytes and the snapshot layout.)
 // The per-step kernels get `ip` as a preloaded leading argument and derive everything else from it.  Their argument block
 // shrinks from 1.2 KB (both structs by value) to under 100 bytes: the runtime writes a launch's arguments into
 // device-visible memory, and for 1.2 KB that alone took 3.6 us of the host's 5.5 us per launch (tools/launch_floor.hip).
@@ -264,6 +275,12 @@ struct GwHostTables {
 
 // returns GW_OK or an error code; msg receives a description on failure
 int gw_build_tables(const gw_config& cfg, GwHostTables& out, char* msg, size_t msglen);
+// What gw_create uploads of them (gw_tables.cpp).  The two links a step uses per sender, [0][d][s] sender d hearing the RRM
+// and [1][d][s] the RRM hearing sender d (GwState::ber2 / cls2); and the step tables as one image: GwBlobLayout for the
+// generic kernel, GwStripeLayout for the suffix mode, whose *stage_chunks is GwState::stage_chunks.
+void gw_link_slices(const GwHostTables& tab, std::vector<double>& ber2, std::vector<uint8_t>& cls2);
+std::vector<uint8_t> gw_blob_image(const GwHostTables& tab, const GwDevConst& k);
+std::vector<uint8_t> gw_stripe_image(const GwHostTables& tab, const GwDevConst& k, int* stage_chunks);
 
 // kernel launchers (ct_step.hip); stream is a hipStream_t
 int gw_launch_init(const GwState& st, void* stream);
@@ -274,9 +291,9 @@ int gw_launch_received(const GwState& st, int32_t* out, void* stream);
 int gw_launch_enqueue(const GwState& st, int sender, const int32_t* payload_bytes, void* stream);
 // The hipFunction_t (as void*) of a handle's per-call kernels on ITS device: ct_step_sfx_kernel<D, MODE> for MODE 0..2 and
 // ct_reset_sfx_kernel.  Resolved once, at gw_create with the handle's device current (a module's functions belong to the
-// device it was loaded on), so that a launch neither asks for the current device nor looks the kernel up.  A null entry
-// sends that launch through `<<< >>>`.
-struct GwSfxFns { void* step[3]; void* reset; };
+// device it was loaded on), so that a launch neither asks for the current device nor looks the kernel up -- nor dispatches
+// on the sender count: step_slot is the launch-record slot of step[0].  A null entry sends that launch through `<<< >>>`.
+struct GwSfxFns { void* step[3]; void* reset; int step_slot; };
 void gw_resolve_sfx_functions(int D, GwSfxFns* out);       // ct_step_sfx.hip
 int gw_launch_step_sfx(const GwState& st, const GwDevConst& cst, const int32_t* device, const int32_t* duration,
                        int32_t* obs, float* reward, uint8_t* done, uint8_t* feedback_byte, void* stream, bool below_limits,
@@ -305,12 +322,22 @@ int gw_launch_unpack_feedback(int64_t count, int center, int pv, const uint8_t* 
                                        // reciprocal is exact for len <= 100 up to multiplicity 256 (checked exhaustively by
                                        // tests/test_host_logic.py), the kernels' 24-bit multiplies far beyond.
 
+// Sender counts with a kernel instantiation of their own (template parameter DT; every other count runs DT = 0), one list
+// per kernel family.  Each family's launcher dispatches over its list (gw_dispatch.h) and nothing else restates it.
+#define GW_DTS_STEP          2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_step_sfx_kernel
+#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel
+#define GW_DTS_ROLLOUT_LOOP  2, 3, 4, 6, 8, 16, 32          // ct_rollout_sfx_kernel (event loop)
+#define GW_DTS_LIVE          2, 3, 4, 6, 8, 16, 32          // ct_step_live_kernel
+#define GW_DTS_GENERIC       2, 3, 4, 8, 16                 // ct_step_kernel on the table PHY
+#define GW_DTS_GENERIC_LIVE  4, 16                          // ct_step_kernel on the live PHY (DYN)
+
 // Launch record (gw_selftest_launches): one slot per instantiation of the step / rollout kernel families, counted by the
 // launcher that picks the instantiation -- in the handle's own array (rec, may be null) and in the process-wide one (a relaxed
 // atomic).  Slot = family base + sender-count index (gw_ls_dt) x the family's template combinations + their index; names are
 // formatted only by the query (gw_api.cpp).
+#define GW_LS_DTS GW_DTS_STEP, 0                            // the record's sender-count order (every family's list is a subset); 0 = any D
 enum {
-    GW_LS_NDT = 10,                                        // DT in {2, 3, 4, 5, 6, 7, 8, 16, 32, 0 = any D}
+    GW_LS_NDT = 10,
     GW_LS_STEP_SFX = 0,                                    // ct_step_sfx_kernel<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_SYNC = GW_LS_STEP_SFX + 3 * GW_LS_NDT,   // ct_rollout_sync_kernel<DT, MODE>
     GW_LS_ROLLOUT = GW_LS_ROLLOUT_SYNC + 3 * GW_LS_NDT,    // ct_rollout_sfx_kernel<DT, MODE> (event loop)
@@ -319,8 +346,11 @@ enum {
     GW_LS_LIVE = GW_LS_GENERIC + 8 * GW_LS_NDT,            // ct_step_live_kernel<DT, PER_ENV>: 2 per DT
     GW_LS_COUNT = GW_LS_LIVE + 2 * GW_LS_NDT
 };
-constexpr int gw_ls_dt(int DT)
+constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {
-    return DT == 2 ? 0 : DT == 3 ? 1 : DT == 4 ? 2 : DT == 5 ? 3 : DT == 6 ? 4 : DT == 7 ? 5 : DT == 8 ? 6 : DT == 16 ? 7 : DT == 32 ? 8 : 9;
+    constexpr int dts[GW_LS_NDT] = {GW_LS_DTS};
+    int i = 0;
+    while (i < GW_LS_NDT - 1 && dts[i] != DT) ++i;
+    return i;
 }
 void gw_note_launch(uint64_t* rec, int slot);              // gw_api.cpp

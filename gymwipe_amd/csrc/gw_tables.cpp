@@ -146,3 +146,85 @@ int gw_build_tables(const gw_config& cfg, GwHostTables& t, char* msg, size_t msg
     }
     return GW_OK;
 }
+
+// ---- what gw_create uploads of the tables ----
+namespace {
+constexpr int S = GW_MAX_NSTATES;
+// index into trans / ber / cls of: sender d hearing the RRM's announcement; the RRM hearing sender d
+size_t ann_at(const GwHostTables& t, int d, int s) { return ((size_t)d * t.R + t.D) * S + s; }
+size_t dat_at(const GwHostTables& t, int d, int s) { return ((size_t)t.D * t.R + d) * S + s; }
+// state of sender j after the announcement AND >= 1 data packet of sender d, from state s (the kernels use it when hearing
+// the same talker twice changes nothing more: GwDevConst::idem_states)
+uint8_t h2_of(const GwHostTables& t, int j, int d, int s)
+{
+    const uint8_t a = t.trans[ann_at(t, j, s)];
+    return j == d ? a : t.trans[((size_t)j * t.R + d) * S + a];
+}
+void put_mi(uint8_t* at, const GwDevConst& k, int j)
+{
+    const uint32_t mi[2] = {(uint32_t)k.mult[j], k.inv16[j]};
+    memcpy(at, mi, 8);
+}
+} // namespace
+
+void gw_link_slices(const GwHostTables& t, std::vector<double>& ber2, std::vector<uint8_t>& cls2)
+{
+    const int D = t.D;
+    ber2.assign((size_t)2 * D * S, 0.0);
+    cls2.assign((size_t)2 * D * S, 0);
+    for (int d = 0; d < D; ++d)
+        for (int s = 0; s < S; ++s) {
+            ber2[(size_t)d * S + s] = t.ber[ann_at(t, d, s)];
+            cls2[(size_t)d * S + s] = t.cls[ann_at(t, d, s)];
+            ber2[((size_t)D + d) * S + s] = t.ber[dat_at(t, d, s)];
+            cls2[((size_t)D + d) * S + s] = t.cls[dat_at(t, d, s)];
+        }
+}
+
+// GwBlobLayout: sender-major, [ ber f64[2][D][S] | mi u32[D][2] | h1 u8[D][S] | r1 u8[D][S] | cls u8[2][D][S] | h2 u8[D][D][S] ]
+std::vector<uint8_t> gw_blob_image(const GwHostTables& t, const GwDevConst& k)
+{
+    const int D = t.D;
+    const GwBlobLayout L(D);
+    std::vector<uint8_t> img((size_t)L.total, 0);
+    std::vector<double> ber2;
+    std::vector<uint8_t> cls2;
+    gw_link_slices(t, ber2, cls2);
+    memcpy(img.data() + L.ber, ber2.data(), ber2.size() * sizeof(double));
+    memcpy(img.data() + L.cls, cls2.data(), cls2.size());
+    for (int j = 0; j < D; ++j) {
+        put_mi(img.data() + L.mi + (size_t)j * 8, k, j);
+        for (int s = 0; s < S; ++s) {
+            img[(size_t)L.h1 + (size_t)j * S + s] = t.trans[ann_at(t, j, s)];
+            img[(size_t)L.r1 + (size_t)j * S + s] = t.trans[dat_at(t, j, s)];
+            for (int d = 0; d < D; ++d) img[(size_t)L.h2 + ((size_t)j * D + d) * S + s] = h2_of(t, j, d, s);
+        }
+    }
+    return img;
+}
+
+// GwStripeLayout: the same numbers state-major.  *stage_chunks: the 16-byte chunks that cover the states this handle's
+// layout has (all of them when the closure is open).
+std::vector<uint8_t> gw_stripe_image(const GwHostTables& t, const GwDevConst& k, int* stage_chunks)
+{
+    const int D = t.D;
+    const GwStripeLayout T(D);
+    std::vector<uint8_t> img((size_t)T.total, 0);
+    for (int j = 0; j < D; ++j) {
+        put_mi(img.data() + T.mi + (size_t)j * 8, k, j);
+        for (int s = 0; s < S; ++s) {
+            uint8_t* stripe = img.data() + T.s0 + (size_t)s * T.stripe;
+            memcpy(stripe + T.ber0 + (size_t)j * 8, &t.ber[ann_at(t, j, s)], 8);
+            memcpy(stripe + T.ber1 + (size_t)j * 8, &t.ber[dat_at(t, j, s)], 8);
+            stripe[T.h1 + j] = t.trans[ann_at(t, j, s)];
+            stripe[T.r1 + j] = t.trans[dat_at(t, j, s)];
+            stripe[T.cls0 + j] = t.cls[ann_at(t, j, s)];
+            stripe[T.cls1 + j] = t.cls[dat_at(t, j, s)];
+            for (int d = 0; d < D; ++d) img[(size_t)T.h2 + ((size_t)s * D + j) * D + d] = h2_of(t, j, d, s);
+        }
+    }
+    int nst = 1;
+    for (int r = 0; r < t.R; ++r) nst = t.nstates[r] > nst ? t.nstates[r] : nst;
+    *stage_chunks = T.staged_chunks((t.overflow || nst > S) ? S : nst);
+    return img;
+}
