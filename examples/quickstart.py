@@ -37,6 +37,13 @@ dur = torch.randint(0, 20, (64, N), dtype=torch.int32, device="cuda")
 o, r, d = venv.rollout(dev, dur)
 print("rollout:", tuple(o.shape), float(r.float().mean()))
 
+# 3b. the same with the policy inside the launch: each env draws its action from the observation it just got.  A policy over
+#     the last observation is three rows of probabilities (below / at / above COUNTER_BOUND) over the 4 * 20 flat actions.
+from gymwipe_amd.actions import policy_cdf
+table = policy_cdf(torch.softmax(torch.randn(3, 4 * 20, device="cuda"), dim=-1))
+a_dev, a_dur, o, r, d = venv.rollout_policy(table, 64, seed=1)          # acts on the last observation first; step0 += 64 next time
+print("rollout_policy:", tuple(a_dev.shape), float(r.float().mean()))
+
 
 # 4. your own Interpreter (envs/core.py:59-159), fed with what the RRM sniffed each step
 class CountDeliveries(VecInterpreter):

@@ -57,3 +57,68 @@ def actions_torch(seed, env_lo, env_hi, step_lo, step_hi, num_devices, max_durat
     dev = ((z & 0xffffffff) % num_devices).to(torch.int32)
     dur = (lsr(z, 32) % max_duration).to(torch.int32)
     return dev.contiguous(), dur.contiguous()
+
+
+# ---- policies over the last observation (gw_rollout_policy, include/gymwipe_amd.h) -------------------------------------------
+# The agent sees counter_bound + payload_value * {-1, 0, +1}, so a policy over the last observation is three rows of
+# probabilities over the A = num_devices * max_duration flat actions (agents/dqn_counter_traffic.py:25-31).  The kernels draw
+# from a table of cumulative sums in 32-bit fixed point:
+#     u = min(h & 0xffffffff, 0xfffffffe)      h: the stream above, at (seed, env, step)
+#     a = min(A - 1, #{ j : cdf[cls][j] <= u })
+def policy_cdf(p):
+    """Probabilities ``[..., A]`` (numpy array or torch tensor, on whichever device it lives) -> the table of
+    :func:`policy_sample_numpy` / ``gw_rollout_policy``: ``floor(2^32 * cumsum_f64(p))`` clipped to ``2^32 - 1``, and
+    ``0xffffffff`` from the last action with ``p > 0`` onwards.  An action with ``p == 0`` gets ``cdf[j] == cdf[j - 1]``
+    (0 for ``j == 0``) and is never drawn; ``u <= 0xfffffffe`` never reaches past the last action with ``p > 0``.
+    numpy's cumsum adds in sequence, which gives both properties by itself.  ``torch.cumsum`` on a GPU is a parallel scan:
+    two neighbouring prefixes may be summed in different orders and differ by an ulp, so there the entries of ``p == 0``
+    actions are taken from their predecessor and the row is made non-decreasing explicitly (a running maximum); an entry with
+    ``p > 0`` may still differ by 1 from the numpy table's.
+    numpy in: uint32 out.  torch in: int64 out on the same device (no host sync; ``rollout_policy`` stores it as 32-bit words)."""
+    if isinstance(p, np.ndarray) or not hasattr(p, "cumsum") or not hasattr(p, "device"):
+        p = np.asarray(p, dtype=np.float64)
+        A = p.shape[-1]
+        v = np.minimum(np.floor(np.cumsum(p, axis=-1, dtype=np.float64) * 4294967296.0), 4294967295.0)
+        idx = np.arange(A)
+        last = np.where(p > 0, idx, -1).max(axis=-1, keepdims=True)
+        return np.where(idx >= last, 4294967295.0, v).astype(np.uint32)
+    import torch
+    A = p.shape[-1]
+    v = torch.floor(torch.cumsum(p.to(torch.float64), dim=-1) * 4294967296.0).clamp(max=4294967295.0)
+    v = torch.cummax(torch.where(p > 0, v, torch.zeros_like(v)), dim=-1).values     # p == 0: the predecessor's entry
+    idx = torch.arange(A, device=p.device)
+    last = torch.where(p > 0, idx, torch.full_like(idx, -1)).max(dim=-1, keepdim=True).values
+    return torch.where(idx >= last, torch.full_like(v, 4294967295.0), v).to(torch.int64)
+
+
+def policy_u_numpy(seed, env_lo, env_hi, step):
+    """The draw's uniform 32-bit number for envs [env_lo, env_hi) at stream position ``step``."""
+    e = np.arange(env_lo, env_hi, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = np.uint64(seed & _M64) ^ (e * np.uint64(_G1)) ^ (np.uint64(step & _M64) * np.uint64(_G2))
+        z = z + np.uint64(_G1)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(_C1)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(_C2)
+        z = z ^ (z >> np.uint64(31))
+    return np.minimum(z & np.uint64(0xffffffff), np.uint64(0xfffffffe)).astype(np.uint32)
+
+
+def policy_count_numpy(cdf, cls, u):
+    """``min(A - 1, #{ j : cdf[cls[i]][j] <= u[i] })`` for every i (rows non-decreasing)."""
+    cdf = np.asarray(cdf, dtype=np.uint32)
+    A = cdf.shape[-1]
+    a = np.empty(len(u), np.int64)
+    for c in range(cdf.shape[0]):
+        sel = cls == c
+        a[sel] = np.searchsorted(cdf[c], u[sel], side="right")
+    return np.minimum(a, A - 1)
+
+
+def policy_sample_numpy(seed, env_lo, env_hi, step, cdf, obs, counter_bound, max_duration):
+    """CPU restatement of the kernels' draw: ``(device, duration)`` int32[envs] for envs [env_lo, env_hi) at stream position
+    ``step`` (= step0 + k), acting on the observations ``obs`` int32[envs] with the table ``cdf`` uint32[3][A]."""
+    obs = np.asarray(obs).astype(np.int64)
+    cls = np.sign(obs - int(counter_bound)).astype(np.int64) + 1
+    a = policy_count_numpy(cdf, cls, policy_u_numpy(seed, env_lo, env_hi, step))
+    dev = a // int(max_duration)
+    return dev.astype(np.int32), (a - dev * int(max_duration)).astype(np.int32)

@@ -71,6 +71,7 @@ class DqnCounterTrafficAgent:
         self.m_done = torch.zeros(self.cap, device=self.dev)
         self.m_pos, self.m_len, self.steps = 0, 0, 0
         self.center = float(env.COUNTER_BOUND)
+        self.seed, self.stream_pos = int(seed), 0             # collect(): the draws' stream and how far it has been used
 
     def _features(self, obs):
         return (obs.to(self.torch.float32) - self.center).unsqueeze(-1)   # the observation is centred on COUNTER_BOUND
@@ -82,6 +83,44 @@ class DqnCounterTrafficAgent:
             qv = self.q(self._features(obs))
             p = torch.softmax(torch.clamp(qv / self.tau, -500.0, 500.0), dim=-1)
             return torch.multinomial(p, 1).squeeze(-1)
+
+    def policy_cdf(self):
+        """The policy of ``act()`` as the table ``env.rollout_policy`` draws from: Q at the three values an observation takes
+        (COUNTER_BOUND + payload_value * {-1, 0, +1}), the same clip and softmax, ``actions.policy_cdf`` -- built on the GPU,
+        no host sync."""
+        from .actions import policy_cdf
+        torch = self.torch
+        pv = float(self.env.config.payload_value)
+        with torch.no_grad():
+            obs = torch.tensor([self.center - pv, self.center, self.center + pv], device=self.dev)
+            qv = self.q(self._features(obs))
+            return policy_cdf(torch.softmax(torch.clamp(qv / self.tau, -500.0, 500.0), dim=-1))
+
+    def collect(self, steps):
+        """``steps`` env steps of all N envs under the current policy in ONE ``env.rollout_policy`` call -- observation ->
+        policy -> step inside the launch -- and their transitions into the replay memory.  Returns the rollout's
+        ``(device, duration, obs, reward, done)``."""
+        torch = self.torch
+        steps = int(steps)
+        if self.env._last[0] is None:
+            self.env.reset()
+        first = self.env._last[0].clone()
+        dev, dur, obs, rew, done = self.env.rollout_policy(self.policy_cdf(), steps, self.seed, step0=self.stream_pos)
+        self.stream_pos += steps
+        self.steps += steps
+        keep = min(steps, self.cap // self.n)                  # (more steps than the memory holds: the last ones)
+        if keep:
+            seen = torch.cat([first.unsqueeze(0), obs[:-1]])[steps - keep:]
+            flat = (dev.to(torch.int64) * self.processor.max_duration + dur.to(torch.int64))[steps - keep:]
+            at = (self.m_pos + torch.arange(keep * self.n, device=self.dev)) % self.cap
+            self.m_obs[at] = seen.reshape(-1).to(torch.float32)
+            self.m_next[at] = obs[steps - keep:].reshape(-1).to(torch.float32)
+            self.m_act[at] = flat.reshape(-1)
+            self.m_rew[at] = rew[steps - keep:].reshape(-1)
+            self.m_done[at] = done[steps - keep:].reshape(-1).to(torch.float32)
+            self.m_pos = (self.m_pos + keep * self.n) % self.cap
+            self.m_len = min(self.m_len + keep * self.n, self.cap)
+        return dev, dur, obs, rew, done
 
     def remember(self, obs, act, rew, nxt, done):
         i = self.m_pos

@@ -524,363 +524,189 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
 // the env's state in registers across all K steps, queue lengths of the senders not addressed and the ticks behind a window
 // lazy exactly as above; DT == 0 = any sender count, the per-lane arrays as LDS columns.  Same results bit for bit (the tests
 // run both forms against the oracle; GW_ROLLOUT_EVENT_LOOP=1 selects the event loop).
+//
+// Where a step's action comes from is the loop's one parameter, so that its body exists once (ct_rollout_sync_body.h):
+//   ct_rollout_sync_kernel  gw_rollout: the caller's pre-staged rows, step k + 1's action loaded while step k is walked;
+//   ct_rollout_policy       gw_rollout_policy: drawn at the step boundary from a three-row table over the observation the
+//                           env just produced (PolicyActions), and stored with that step's outputs.
+// The policy's draw (include/gymwipe_amd.h, gw_rollout_policy): the first 32 bits of the action stream's hash
+// (gymwipe_amd/actions.py) against the observation class's row of the table.
+__device__ __forceinline__ uint32_t gw_policy_u(uint64_t seed, uint64_t env_term, uint64_t step)
+{
+    uint64_t z = seed ^ env_term ^ (step * 0xD1B54A32D192ED03ull);
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return gw_min_u32((uint32_t)z, 0xfffffffeu);
+}
+// #{ j in [0, A) : row[j] <= u } for a non-decreasing row: the upper bound by halving.  Every index read lies in [0, A),
+// whatever the row holds.  gw_policy_count: the draw's action, that count clamped to A - 1.
+template <class ROW>
+__device__ __forceinline__ uint32_t gw_policy_upper(ROW row, uint32_t A, uint32_t u)
+{
+    uint32_t lo = 0, n = A;
+    while (n != 0u) {
+        const uint32_t half = n >> 1;
+        const bool le = row[lo + half] <= u;
+        lo = le ? lo + half + 1u : lo;
+        n = le ? n - half - 1u : half;
+    }
+    return lo;
+}
+template <class ROW>
+__device__ __forceinline__ uint32_t gw_policy_count(ROW row, uint32_t A, uint32_t u)
+{
+    return gw_min_u32(gw_policy_upper(row, A, u), A - 1u);
+}
+__device__ __forceinline__ uint32_t gw_policy_cls(int32_t obs, int32_t center)        // sign(obs - center) + 1
+{
+    return (uint32_t)((int)(obs > center) - (int)(obs < center) + 1);
+}
+
+constexpr int GW_POLICY_A_MAX = GW_MAX_DEVICES * 20;     // flat actions the fused form stages (3 rows of them in LDS)
+
+struct PolicyActions {
+    const uint32_t* __restrict__ cdf;                    // [3][A]
+    const int32_t* __restrict__ obs_prev;                // [N], apart from every output (the C-ABI's rule: the outputs are
+                                                         // __restrict__ too; rollout_policy() copies a row of its own `out`)
+    int32_t* __restrict__ device_out;
+    int32_t* __restrict__ duration_out;
+    uint64_t seed, step0, env0;
+    uint32_t* s_cdf;                                     // the table in LDS (the launch's dynamic part: 3 * A words)
+    uint32_t A, md, inv20;                               // inv20 = ceil(2^20 / md): a / md == (a * inv20) >> 20 for a < A <= 640
+    int32_t center;
+    uint64_t env_term;
+    int d_cur, du_cur;
+    __device__ __forceinline__ void stage() const
+    {
+        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
+    }
+    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
+    {
+        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
+        // exact: inv20 * md = 2^20 + r with 0 <= r < md, and a * r < 640 * 320 < 2^20 (md <= A / 2: at least two senders)
+        const uint32_t dv = (a * inv20) >> 20;
+        d_cur = (int)dv;
+        du_cur = (int)(a - dv * md);
+    }
+    __device__ __forceinline__ void first(uint32_t e)
+    {
+        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;
+        draw(gw_policy_cls(obs_prev[e], center), step0);
+    }
+    // step k is over: its action goes out with its outputs, the next one is drawn from what the agent now sees
+    __device__ __forceinline__ void stepped(size_t at, int k, int K, int32_t latest)
+    {
+        device_out[at] = d_cur;
+        duration_out[at] = du_cur;
+        if (k + 1 < K) draw((uint32_t)((int)(latest > 0) - (int)(latest < 0) + 1), step0 + (uint64_t)(k + 1));
+    }
+};
+
 template <int DT, int MODE>
 __global__ __launch_bounds__(64) void ct_rollout_sync_kernel(GwState st, GwDevConst c, int K,
                                                             const int32_t* __restrict__ device, const int32_t* __restrict__ duration,
                                                             int32_t* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done)
 {
-    // Actions and outputs in the C-ABI's own step-major layout ([K][N]: a step's row is coalesced across the wave's lanes), read
-    // and written by this kernel itself: step k + 1's action is loaded while step k is walked, a step's three outputs are
-    // stores nothing waits for.  (The event loop reads packed per-env action records and writes feedback bytes, with a
-    // transposing kernel on either side: 15 us per 64 steps x 65 536 envs, an eighth of this kernel's own time.)
-    constexpr bool GEN = DT == 0;                        // any sender count: per-lane arrays in LDS columns (as in the event loop)
-    constexpr int DM = GEN ? GW_MAX_DEVICES : DT;        // capacity
-    constexpr int NWC = (2 * DM + 1 + 15) / 16;
-    constexpr int S = GW_MAX_NSTATES;
-    const int D = GEN ? c.D : DT, R = D + 1, RRM = D;
-    const uint32_t N = (uint32_t)st.N;
+#define GW_ROLLOUT_SRC_STAGE
+#define GW_ROLLOUT_SRC_FIRST int d_next = device[e], du_next = duration[e];
+#define GW_ROLLOUT_SRC_TAKE /* the next step's action is requested now */                                                        \
+    const int d = d_next, du = du_next;                                                                                          \
+    if (k + 1 < K) { d_next = device[(size_t)(k + 1) * N + e]; du_next = duration[(size_t)(k + 1) * N + e]; }
+#define GW_ROLLOUT_SRC_CHECKED(bad) (bad)                /* a staged action may lie outside the action space (GW_FLAG_BADACT) */
+#define GW_ROLLOUT_SRC_STEPPED(at, latest)
+#include "ct_rollout_sync_body.h"
+#undef GW_ROLLOUT_SRC_STAGE
+#undef GW_ROLLOUT_SRC_FIRST
+#undef GW_ROLLOUT_SRC_TAKE
+#undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_STEPPED
+}
+
+// What gw_rollout_policy passes on to the kernels below besides the outputs.
+struct GwPolicyArgs {
+    const uint32_t* cdf;          // [3][A], A = D * max_duration
+    const int32_t* obs_prev;      // [N] what each env's agent saw last
+    uint64_t seed, step0, env0;
+};
+
+// The closed loop in one launch: the same K steps, each env's action drawn from the table's row for the observation its own
+// previous step produced (obs_prev for step 0).  No `_kernel` suffix: the catalogue of tests/test_kernel_variants.py is about
+// the families it lists; this one's cases are tests/test_rollout_policy.py's.
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_policy(GwState st, GwDevConst c, int K, GwPolicyArgs p,
+                                                       int32_t* __restrict__ device_out, int32_t* __restrict__ duration_out,
+                                                       int32_t* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done)
+{
+    extern __shared__ uint32_t s_policy_cdf[];
+    PolicyActions src;
+    src.cdf = p.cdf; src.obs_prev = p.obs_prev; src.device_out = device_out; src.duration_out = duration_out;
+    src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
+    src.s_cdf = s_policy_cdf;
+    src.md = (uint32_t)c.max_duration;
+    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
+    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
+    src.center = c.counter_bound;
+    src.env_term = 0; src.d_cur = 0; src.du_cur = 0;
+#define GW_ROLLOUT_SRC_STAGE src.stage();
+#define GW_ROLLOUT_SRC_FIRST src.first(e);
+#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
+#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
+#define GW_ROLLOUT_SRC_STEPPED(at, latest) src.stepped(at, k, K, latest);
+#include "ct_rollout_sync_body.h"
+#undef GW_ROLLOUT_SRC_STAGE
+#undef GW_ROLLOUT_SRC_FIRST
+#undef GW_ROLLOUT_SRC_TAKE
+#undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_STEPPED
+}
+
+// The unfused form's draw, for handles without a fused rollout: one step's actions for every env from the observations `obs_in`.
+__global__ __launch_bounds__(256) void policy_sample_kernel(uint32_t N, uint32_t A, uint32_t md, int32_t center, GwPolicyArgs p,
+                                                            int32_t* __restrict__ device_out, int32_t* __restrict__ duration_out)
+{
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-
-    constexpr int TRANS_B = ((DM + 1) * (DM + 1) * S + 15) / 16 * 16;
-    __shared__ __attribute__((aligned(16))) uint8_t s_trans[TRANS_B];
-    __shared__ __attribute__((aligned(16))) double  s_ber[2 * DM * S];
-    __shared__ __attribute__((aligned(16))) uint8_t s_cls[2 * DM * S];
-    __shared__ uint32_t s_cols[GEN ? (3 * DM + 1) * 64 : 1];     // GEN: len[D], tb[D], sta[R] columns per lane
-    __shared__ uint2 s_mi[GEN ? DM : 1];                 // GEN: {mult, ceil(65536/mult)} and terminal-state masks, indexed by
-    __shared__ uint32_t s_term[GEN ? DM : 1];            //      the lane's own addressed sender
-    if constexpr (GEN) {
-        for (int i = threadIdx.x; i < D; i += blockDim.x) {
-            s_mi[i] = make_uint2((uint32_t)st.cst->mult[i], st.cst->inv16[i]);
-            s_term[i] = st.cst->term[i];
-        }
-    }
-    {
-        const int n_tr = (R * R * S + 15) >> 4, n_be = (2 * D * S * 8) >> 4, n_cl = (2 * D * S) >> 4;
-        for (int i = threadIdx.x; i < n_tr; i += blockDim.x) *reinterpret_cast<uint4*>(s_trans + ((uint32_t)i << 4)) = ld<uint4>(st.trans, (uint32_t)i << 4);
-        for (int i = threadIdx.x; i < n_be; i += blockDim.x) *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_ber) + ((uint32_t)i << 4)) = ld<uint4>(st.ber2, (uint32_t)i << 4);
-        for (int i = threadIdx.x; i < n_cl; i += blockDim.x) *reinterpret_cast<uint4*>(s_cls + ((uint32_t)i << 4)) = ld<uint4>(st.cls2, (uint32_t)i << 4);
-    }
-    __syncthreads();
     if (e >= N) return;
-
-    // ---- state -> registers ----
-    const uint32_t RB = GEN ? (uint32_t)st.RB : 16u * NWC;
-    const uint32_t o16 = e << 4, oq = e * RB;
-    const uint4 ip = ld<uint4>(st.ip, o16);
-    const double2 tw = ld<double2>(st.tw, o16);
-    const uint4 tk = ld<uint4>(st.tk, o16);
-    typename ArrSel<GEN, DM>::rw len, tb;
-    typename ArrSel<GEN, DM + 1>::rw sta;
-    if constexpr (GEN) {
-        uint32_t* col = s_cols + (threadIdx.x & 63);
-        len.p = col; tb.p = col + DM * 64; sta.p = col + 2 * DM * 64;
-        for (int i = 0; i < D; ++i) len[i] = st.qb[oq + (uint32_t)i];
-        for (int j = 0; j < R; ++j) sta[j] = st.qb[oq + (uint32_t)(D + j)];
-    } else {
-        uint4 qw[NWC];
-#pragma unroll
-        for (int w = 0; w < NWC; ++w) qw[w] = ld<uint4>(st.qb, oq + 16u * w);
-#pragma unroll
-        for (int i = 0; i < DT; ++i) len[i] = (word_of(qw[i >> 4], (i >> 2) & 3) >> ((i & 3) * 8)) & 0xffu;
-#pragma unroll
-        for (int j = 0; j < DT + 1; ++j) sta[j] = (word_of(qw[(DT + j) >> 4], ((DT + j) >> 2) & 3) >> (((DT + j) & 3) * 8)) & 0xffu;
-    }
-    double now = tw.x, wake = tw.y;
-    uint32_t tau = tk.x;
-    const uint32_t nbp = tk.y;
-    GwBp bpc, bpp;
-    bpc.t0 = ip.x; bpc.c0 = ip.y;
-    bpp.t0 = ip.z; bpp.c0 = ip.w;
-    const GwBp* hist = st.bph + ((size_t)e << 7);
-    uint32_t rvm = tk.z;
-    int32_t last_abs = (int32_t)(tk.w & 0x7fffffffu);
-    uint32_t dn = tk.w >> 31;
-
-    constexpr bool FAST = MODE >= 1, NOLIM = MODE == 2;
-    const StepMathT<FAST, NOLIM> m(c);
-    const double slot = c.slot, br = c.bit_rate, hd = c.hdr_dur, hdr_bits = c.hdr_bits, interval = c.counter_interval;
-    const double inv_interval = c.inv_interval, tie_filter = c.tie_filter, coded_factor = c.coded_factor;
-    const bool fast_ticks = FAST || c.fast_ticks != 0;
-    const bool idem = c.idem_states != 0;
-    const uint32_t bound = (uint32_t)c.counter_bound, base_bytes = (uint32_t)(c.mac_hdr + c.net_hdr);
-    const int mh = c.mac_hdr, pv = c.payload_value;
-    uint32_t live_mask = 0u;                             // any-D kernel: bit i = sender i is in a non-terminal noise state
-    if constexpr (GEN) {
-        for (int i = 0; i < D; ++i) live_mask |= ((s_term[i] >> sta[i]) & 1u) ? 0u : (1u << i);
-    }
-    typename ArrSel<GEN, DM>::ro mult, term, inv16;
-    if constexpr (GEN) {
-        mult.p = st.cst->mult; mult.shift16 = 0; term.p = st.cst->term; term.shift16 = 1; inv16.p = st.cst->inv16; inv16.shift16 = 0;
-    } else {
-#pragma unroll
-        for (int i = 0; i < DT; ++i) { mult.v[i] = (uint32_t)c.mult[i]; term.v[i] = c.term[i]; inv16.v[i] = c.inv16[i]; }
-    }
-#pragma unroll
-    for (int i = 0; i < D; ++i) tb[i] = tau;
-
-    Tally kt = {0, 0, 0, 0, 0};
-    uint32_t k_bad = 0, fl = 0;
-    int k = 0;
-    int d_next = device[e], du_next = duration[e];              // step 0's action
-    auto put_feedback = [&](int32_t latest, int32_t r) {
-        const size_t at = (size_t)k * N + e;
-        obs[at] = latest + c.counter_bound;
-        reward[at] = (float)r;
-        done[at] = (uint8_t)dn;
-        k++;
-    };
-
-    while (k < K) {
-        // ---- start of step k (counter_traffic.py:146-158); the next step's action is requested now ----
-        const int d = d_next, du = du_next;
-        if (k + 1 < K) { d_next = device[(size_t)(k + 1) * N + e]; du_next = duration[(size_t)(k + 1) * N + e]; }
-        if ((unsigned)d >= (unsigned)D || (unsigned)du >= (unsigned)c.max_duration) {
-            fl |= GW_FLAG_BADACT;                    // env untouched, feedback repeats the current values
-            k_bad++;
-            put_feedback(pv * ((int)(rvm & 1u) - (int)((rvm >> 1) & 1u)), 0);
-            continue;
-        }
-        uint32_t l0 = 0, t0 = 0, s_d_old = 0, mult_d = 0, inv16_d = 65536u;
-        if constexpr (GEN) {
-            l0 = len[d]; t0 = tb[d]; s_d_old = sta[d];
-            mult_d = s_mi[d].x; inv16_d = s_mi[d].y;
-        } else {
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-                if (i == d) { l0 = len[i]; t0 = tb[i]; mult_d = mult[i]; inv16_d = inv16[i]; s_d_old = sta[i]; }
-        }
-        uint32_t len_d = gw_len_after_ticks(l0, tau - t0, mult_d, kt);          // the addressed queue, up to date
-        const int slots = du * c.duration_factor;                               // counter_traffic.py:149
-        const int Ld = ndigits(slots);
-        const bool cls_valid = NOLIM || now < c.cls_limit;
-        const uint32_t s_d = s_trans[(uint32_t)((d * R + RRM) * S) + s_d_old];  // d after hearing the RRM
-#pragma unroll
-        for (int i = 0; i < (GEN ? 0 : D); ++i) if (i == d) sta[i] = s_d;
-        if constexpr (GEN) {
-            sta[d] = s_d;
-            live_mask = ((s_term[d] >> s_d) & 1u) ? (live_mask & ~(1u << d)) : (live_mask | (1u << d));
-        }
-        // ---- A.1 / A.2: announcement ----
-        const TxTimes an = tx_times(m, now, hd, m.over_rate((double)(Ld * 8)));
-        kt.tx++;
-        const bool granted = decode(m, (uint32_t)s_cls[(uint32_t)(d * S) + s_d], cls_valid, s_ber[(uint32_t)(d * S) + s_d], an, br, hdr_bits,
-                                    (double)(Ld * 8) * coded_factor, fl);
-        const double t_r = an.t_e;
-        const double t_end = t_r + (double)(slots + 1) * slot;                  // simple_stack.py:557-558
-        uint32_t s_r = sta[RRM];
-        uint32_t n_data = 0;
-
-        // counter ticks with wake < t (or <= t): the running sum four at a time, or one jump where the step qualifies
-        auto ticks_to = [&](double t, bool inclusive) {
-            uint32_t kk = 0;
-            for (;;) {
-                const double w1 = wake + interval, w2 = w1 + interval, w3 = w2 + interval, w4 = w3 + interval;
-                const bool b0 = inclusive ? (wake <= t) : (wake < t);
-                const bool b1 = inclusive ? (w1 <= t) : (w1 < t);
-                const bool b2 = inclusive ? (w2 <= t) : (w2 < t);
-                const bool b3 = inclusive ? (w3 <= t) : (w3 < t);
-                const double last = b3 ? w3 : (b2 ? w2 : (b1 ? w1 : wake));
-                if (inclusive && b0 && last == t) fl |= GW_FLAG_TIE;
-                kk += (uint32_t)b0 + (uint32_t)b1 + (uint32_t)b2 + (uint32_t)b3;
-                wake = b3 ? w4 : (b2 ? w3 : (b1 ? w2 : (b0 ? w1 : wake)));
-                if (!b3) break;
-            }
-            tau += kk;
-            len_d = gw_len_after_ticks(len_d, kk, mult_d, kt);
-        };
-        double delta = 0.0;
-        const bool span_ok = fast_ticks && gw_tick_span_ok(wake, t_end, interval, &delta);
-        auto ticks_upto = [&](double t, bool inclusive) {
-            uint32_t nj = 0;
-            double wj = wake;
-            bool tiej = false, sane = false;
-            gw_tick_jump_lo(wake, t, delta, c.inv_interval_lo, inclusive, &nj, &wj, &tiej, &sane);
-            if (span_ok && sane) {
-                wake = wj;
-                tau += nj;
-                if (tiej) fl |= GW_FLAG_TIE;
-                len_d = gw_len_after_ticks(len_d, nj, mult_d, kt);
-            } else {
-                ticks_to(t, inclusive);
-            }
-        };
-
-        if (granted) {
-            // ---- A.3 / A.4: window at sender d (simple_stack.py:397-434) ----
-            const double stopw = t_r + (double)slots * slot;                    // :400-401
-            double cur = t_r;
-            ticks_upto(cur, false);                   // (covers the ticks since the previous window closed too: counting is cumulative)
-            const uint32_t s_r1 = s_trans[(uint32_t)((RRM * R + d) * S) + s_r];            // the RRM after one packet of d
-            const double ber_x1 = s_ber[(uint32_t)((D + d) * S) + s_r1];
-            const uint32_t cls_x1 = s_cls[(uint32_t)((D + d) * S) + s_r1];
-            bool more = true;
-            uint32_t pops = 0;
-            {
-                // the straight-line form: preconditions and reasoning in ct_step_sfx.hip
-                const double span = t_end - t_r;
-                const bool straight = span_ok && mult_d != 0u && idem && cls_valid && cls_x1 != (uint32_t)GW_CLS_COMPUTE &&
-                                      (FAST || (m.fast_fmod && m.fast_div)) && (NOLIM || t_end < m.fmod_limit) && t_r >= span + span;
-                if (straight && len_d != 0u) {
-                    auto head = [&](uint32_t ln, uint32_t tk_now, bool& deep) {
-                        const uint32_t age = __umul24(ln + mult_d - 1u, inv16_d) >> 16;   // gw_ceil_div
-                        const uint32_t ht = tk_now - age;
-                        const bool older = ht < bpc.t0;
-                        deep = older && ht < bpp.t0;
-                        return base_bytes + gw_min_u32((older ? bpp.c0 : bpc.c0) + (ht - (older ? bpp.t0 : bpc.t0)), bound);
-                    };
-                    bool deep = false;
-                    uint32_t chk = 0;
-                    uint32_t sz = head(len_d, tau, deep);
-                    bool go = !deep && (stopw - cur) > gw_fast_div((double)(sz * 8u), m.dr, m.rcp_dr);
-                    while (go) {
-                        const double pd = gw_fast_div((double)(((int)sz - mh) * 8), m.dr, m.rcp_dr);
-                        const double t_s = cur + (m.slot - gw_fast_fmod_lo(cur, m.slot, c.inv_slot_lo));
-                        const double t_e = t_s + (hd + pd);
-                        uint32_t nj = 0;
-                        double wj = wake;
-                        bool tiej = false, sane = false;
-                        gw_tick_jump_lo(wake, t_e, delta, c.inv_interval_lo, true, &nj, &wj, &tiej, &sane);
-                        chk |= (sane ? 0u : (uint32_t)GW_FLAG_INTERNAL) | (tiej ? (uint32_t)GW_FLAG_TIE : 0u);
-                        len_d = gw_min_u32(len_d - 1u + __umul24(nj, mult_d), (uint32_t)GW_QUEUE_CAP);
-                        tau += nj;
-                        wake = wj;
-                        cur = t_e;
-                        pops++;
-                        bool deep_n = false;
-                        sz = head(len_d, tau, deep_n);
-                        go = cur < stopw && len_d != 0u && !deep_n && (stopw - cur) > gw_fast_div((double)(sz * 8u), m.dr, m.rcp_dr);
-                    }
-                    (void)head(len_d, tau, deep);
-                    more = cur < stopw && (len_d == 0u || deep);
-                    fl |= chk | ((pops && !(cur < t_end)) ? (uint32_t)GW_FLAG_CARRY : 0u);
-                }
-            }
-            if (pops) {                                                         // devices.py:163-168, counter_traffic.py:75-80
-                const bool okx = cls_x1 == (uint32_t)GW_CLS_OK;
-                kt.pop += pops;
-                kt.tx += pops;
-                n_data += pops;
-                s_r = s_r1;
-                kt.deliv += okx ? pops : 0u;
-                rvm |= okx ? (1u << d) : 0u;
-                dn = (okx && pv == c.counter_bound) ? 1u : dn;
-            }
-            if (more)
-            for (;;) {
-                if (len_d == 0u) {                                              // :409-416
-                    if (mult_d != 0u && wake < stopw) {
-                        cur = wake;
-                        wake = wake + interval;
-                        tau++;
-                        len_d = gw_len_after_ticks(0u, 1u, mult_d, kt);
-                    } else break;
-                }
-                const uint32_t age = gw_ceil_div(len_d, mult_d, inv16_d);
-                const uint32_t sz = base_bytes + gw_tick_value(tau - age, bpc, bpp, nbp, hist, bound);
-                const double need = m.over_rate((double)(sz * 8u));             // messages.py:67-75
-                if (!((stopw - cur) > need)) break;                             // :418-420
-                len_d--;                                                        // :425
-                kt.pop++;
-                const int pay = (int)sz - mh;
-                const TxTimes x = tx_times(m, cur, hd, m.over_rate((double)(pay * 8)));
-                kt.tx++;
-                n_data++;
-                s_r = s_trans[(uint32_t)((RRM * R + d) * S) + s_r];             // the RRM hears sender d (again)
-                const bool ok = decode(m, (uint32_t)s_cls[(uint32_t)((D + d) * S) + s_r], cls_valid, s_ber[(uint32_t)((D + d) * S) + s_r], x, br,
-                                       hdr_bits, (double)(pay * 8) * coded_factor, fl);
-                kt.deliv += ok ? 1u : 0u;
-                rvm |= ok ? (1u << d) : 0u;
-                dn = (ok && pv == c.counter_bound) ? 1u : dn;
-                fl |= !(x.t_e < t_end) ? (uint32_t)GW_FLAG_CARRY : 0u;
-                ticks_upto(x.t_e, true);                                        // ticks are older events than the MAC's resume
-                cur = x.t_e;
-                if (!(cur < stopw)) break;                                      // window timeout already processed
-            }
-        }
-
-        // ---- close the step: A.5 lazily (the ticks up to t_end are counted by the next step's first count); what must not be
-        //      lost is the diagnostic bit for a tick falling EXACTLY on t_end (see the event loop above) ----
-        {
-            const double dd = t_end - wake;
-            if (dd >= 0.0) {
-                const double q = dd * inv_interval;
-                if (!(fabs(q - rint(q)) > tie_filter) || !(wake >= 0.0625) || !(wake < 2097152.0)) {
-                    for (double w = wake; w <= t_end; w = w + interval)
-                        if (w == t_end) fl |= GW_FLAG_TIE;
-                }
-            }
-        }
-        bool all_term = true;
-        if constexpr (GEN) {
-            all_term = (live_mask & ~(1u << d)) == 0u;
-            len[d] = len_d; tb[d] = tau;
-        } else {
-#pragma unroll
-            for (int i = 0; i < D; ++i) all_term = all_term && (i == d || ((term[i] >> sta[i]) & 1u));
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-                if (i == d) { len[i] = len_d; tb[i] = tau; }
-        }
-        if (!all_term) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                if (i == d) continue;
-                uint32_t si = s_trans[(uint32_t)((i * R + RRM) * S) + sta[i]];  // heard the announcement
-                for (uint32_t n = 0; n < n_data; ++n) {                          // ... and d's data
-                    const uint32_t s2 = s_trans[(uint32_t)((i * R + d) * S) + si];
-                    if (s2 == si) break;
-                    si = s2;
-                }
-                sta[i] = si;
-                if constexpr (GEN) live_mask = ((term[i] >> si) & 1u) ? (live_mask & ~(1u << i)) : (live_mask | (1u << i));
-            }
-        }
-        sta[RRM] = s_r;
-        const int32_t latest = pv * ((int)(rvm & 1u) - (int)((rvm >> 1) & 1u));
-        const int32_t abs_d = latest < 0 ? -latest : latest;
-        int32_t r = last_abs - abs_d;
-        last_abs = abs_d;
-        r = r > 10 ? 10 : (r < -10 ? -10 : r);
-        now = t_end;
-        put_feedback(latest, r);
-    }
-
-    // ---- catch up: ticks up to the end of the last step, every queue to the final tick ----
-    {
-        uint32_t kk = 0;
-        while (wake <= now) { if (wake == now) fl |= GW_FLAG_TIE; wake = wake + interval; kk++; }
-        tau += kk;
-#pragma unroll
-        for (int i = 0; i < D; ++i) len[i] = gw_len_after_ticks(len[i], tau - tb[i], mult[i], kt);
-    }
-    if constexpr (GEN) {
-        for (int i = 0; i < D; ++i) st.qb[oq + (uint32_t)i] = (uint8_t)len[i];
-        for (int j = 0; j < R; ++j) st.qb[oq + (uint32_t)(D + j)] = (uint8_t)sta[j];
-    } else {
-        uint32_t nb[16 * NWC];
-#pragma unroll
-        for (int b = 0; b < 16 * NWC; ++b) nb[b] = 0u;
-#pragma unroll
-        for (int i = 0; i < DT; ++i) nb[i] = len[i];
-#pragma unroll
-        for (int j = 0; j < DT + 1; ++j) nb[DT + j] = sta[j];
-#pragma unroll
-        for (int w = 0; w < NWC; ++w) {
-            const int b = 16 * w;
-            uint4 o;
-            o.x = nb[b + 0] | (nb[b + 1] << 8) | (nb[b + 2] << 16) | (nb[b + 3] << 24);
-            o.y = nb[b + 4] | (nb[b + 5] << 8) | (nb[b + 6] << 16) | (nb[b + 7] << 24);
-            o.z = nb[b + 8] | (nb[b + 9] << 8) | (nb[b + 10] << 16) | (nb[b + 11] << 24);
-            o.w = nb[b + 12] | (nb[b + 13] << 8) | (nb[b + 14] << 16) | (nb[b + 15] << 24);
-            st_plain(st.qb, oq + 16u * w, o);
-        }
-    }
-    st_plain(st.tw, o16, make_double2(now, wake));
-    st_plain(st.tk, o16, make_uint4(tau, nbp, rvm, (uint32_t)last_abs | (dn << 31)));
-    publish_env_counters(st.sa, N, e, kt.pop, kt.deliv, k_bad, fl, (uint32_t)K);
+    const uint32_t cls = gw_policy_cls(p.obs_prev[e], center);
+    const uint32_t a = gw_policy_count(p.cdf + (size_t)cls * A, A, gw_policy_u(p.seed, (p.env0 + e) * 0x9E3779B97F4A7C15ull, p.step0));
+    const uint32_t dv = a / md;
+    device_out[e] = (int32_t)dv;
+    duration_out[e] = (int32_t)(a - dv * md);
 }
 
 } // namespace
+
+// One step's draw of gw_rollout_policy's unfused form (every queue mode): row `step` of the action outputs from `obs_in`.
+int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const uint32_t* cdf, uint64_t seed, uint64_t step,
+                            uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, void* stream)
+{
+    const GwPolicyArgs p = {cdf, obs_in, seed, step, env_id0};
+    hipLaunchKernelGGL(policy_sample_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
+                       (uint32_t)D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound, p, device_out, duration_out);
+    return gw_launch_status();
+}
+
+// The fused form of gw_rollout_policy.  GW_EUNSUPPORTED where there is none -- more steps than the handle's capacity, a handle
+// created for the event-loop form, an action space larger than the table's LDS copy: the caller draws and steps per step.
+int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
+                                 uint64_t env_id0, const int32_t* obs_prev, int32_t* device_out, int32_t* duration_out, int32_t* obs,
+                                 float* reward, uint8_t* done, void* stream, bool below_limits, uint64_t* rec)
+{
+    const int64_t A = (int64_t)st.D * cst.max_duration;
+    if (K <= 0 || K > st.rcap || st.ract != nullptr || A > GW_POLICY_A_MAX) return GW_EUNSUPPORTED;
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    const int mode = gw_step_mode(cst, below_limits, false);
+    const GwPolicyArgs p = {cdf, obs_prev, seed, step0, env_id0};
+    gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
+        gw_with_mode(mode, [&](auto m) {
+            gw_note_launch(rec, GW_LS_ROLLOUT_POLICY + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
+            hipLaunchKernelGGL((ct_rollout_policy<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64),
+                               (size_t)(3 * A) * sizeof(uint32_t), (hipStream_t)stream, st, cst, K, p, device_out, duration_out, obs, reward, done);
+        });
+    });
+    return gw_launch_status();
+}
 
 // Returns GW_EUNSUPPORTED when this (D, K) has no fused kernel: the caller falls back to K step launches.
 int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,

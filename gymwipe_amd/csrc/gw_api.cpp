@@ -328,6 +328,28 @@ bool gw_env_below_limits(gw_env* env, void* stream)
     return env->t_bound + env->step_max < env->t_limit;
 }
 
+// The fused part of a rollout (ct_rollout_sfx.hip), shared by gw_rollout and gw_rollout_policy: chunks of up to rcap steps
+// through launch(first step, steps in the chunk, below_limits) while the handle has a fused form; *s = the steps done.  A
+// launcher's GW_EUNSUPPORTED ends it (steps > rollout capacity 0, max_duration > 254, ...): the caller goes on step by step,
+// or, under GW_ROLLOUT_STRICT, fails.
+template <class F>
+static int fused_chunks(gw_env* env, int32_t steps, void* stream, int32_t* s, F&& launch)
+{
+    while (env->st.tk && !env->dyn && env->st.rcap > 0 && *s < steps) {
+        const int32_t chunk = steps - *s < env->st.rcap ? steps - *s : env->st.rcap;
+        const int rc = launch(*s, chunk,
+                              gw_env_below_limits(env, stream) && env->t_bound + (double)(chunk + 1) * env->step_max < env->t_limit);
+        if (rc == GW_EUNSUPPORTED) {
+            if (getenv("GW_ROLLOUT_STRICT")) return fail(GW_EUNSUPPORTED, "no fused rollout for this handle (GW_ROLLOUT_STRICT is set)");
+            break;
+        }
+        if (rc) return fail(GW_EHIP, "rollout kernel launch failed at step %d", *s);
+        *s += chunk;
+        gw_env_add_steps(env, (uint64_t)chunk);
+    }
+    return GW_OK;
+}
+
 // for the entry points that drive a gw_env together with another handle (gw_plant_api.cpp: gw_pendulum_step)
 int gw_env_internals(gw_env* env, const GwState** st, const GwDevConst** cst, int* hip_device)
 {
@@ -633,24 +655,54 @@ int gw_rollout(gw_env* env, int32_t steps, const int32_t* device_dev, const int3
     const int64_t N = env->st.N;
     int32_t s = 0;
     // fused persistent rollout (ct_rollout_sfx.hip) in chunks of up to rcap steps, when this D has one
-    while (env->st.tk && !env->dyn && env->st.rcap > 0 && s < steps) {
-        const int32_t chunk = steps - s < env->st.rcap ? steps - s : env->st.rcap;
-        const int64_t o = (int64_t)s * N;
-        rc = gw_launch_rollout_sfx(env->st, env->cst_host, chunk, device_dev + o, duration_dev + o, obs_dev + o,
-                                   reward_dev + o, done_dev + o, env->st.ract, env->st.rfb, env->st.rcap, stream,
-                                   gw_env_below_limits(env, stream) && env->t_bound + (double)(chunk + 1) * env->step_max < env->t_limit,
-                                   env->launches);
-        if (rc == GW_EUNSUPPORTED) {
-            if (getenv("GW_ROLLOUT_STRICT")) return fail(GW_EUNSUPPORTED, "no fused rollout for this handle (GW_ROLLOUT_STRICT is set)");
-            break;                                               // (steps > rollout capacity 0, max_duration > 254)
-        }
-        if (rc) return fail(GW_EHIP, "rollout kernel launch failed at step %d", s);
-        s += chunk;
-        gw_env_add_steps(env, (uint64_t)chunk);
-    }
+    rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
+        const int64_t o = (int64_t)s0 * N;
+        return gw_launch_rollout_sfx(env->st, env->cst_host, chunk, device_dev + o, duration_dev + o, obs_dev + o,
+                                     reward_dev + o, done_dev + o, env->st.ract, env->st.rfb, env->st.rcap, stream, below,
+                                     env->launches);
+    });
+    if (rc) return rc;
     for (; s < steps; ++s) {                                   // generic path: one step launch per step
         const int64_t o = (int64_t)s * N;
         if (launch_step(env, device_dev + o, duration_dev + o, obs_dev + o, reward_dev + o, done_dev + o, stream))
+            return fail(GW_EHIP, "step kernel launch failed at step %d", s);
+        gw_env_add_steps(env, 1);
+    }
+    return GW_OK;
+}
+
+int gw_rollout_policy(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                      const int32_t* obs_prev_dev, int32_t* device_out_dev, int32_t* duration_out_dev,
+                      int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!cdf_dev || !obs_prev_dev || !device_out_dev || !duration_out_dev || !obs_dev || !reward_dev || !done_dev)
+        return fail(GW_EINVAL, "gw_rollout_policy: NULL device pointer");
+    if (steps == 0) return GW_OK;
+    int rc = select_device(env);
+    if (rc) return rc;
+    const int64_t N = env->st.N;
+    // step s acts on the observations of step s - 1: the caller's for the call's first step, this call's own rows afterwards
+    auto seen_before = [&](int32_t s) { return s ? obs_dev + (int64_t)(s - 1) * N : obs_prev_dev; };
+    int32_t s = 0;
+    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (A/B switch: every step through the unfused form)
+        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
+            const int64_t o = (int64_t)s0 * N;
+            return gw_launch_rollout_policy_sfx(env->st, env->cst_host, chunk, cdf_dev, seed, step0 + (uint64_t)s0, env_id0,
+                                                seen_before(s0), device_out_dev + o, duration_out_dev + o, obs_dev + o,
+                                                reward_dev + o, done_dev + o, stream, below, env->launches);
+        });
+        if (rc) return rc;
+    }
+    if (s < steps && getenv("GW_ROLLOUT_STRICT"))
+        return fail(GW_EUNSUPPORTED, "no fused policy rollout for this handle (GW_ROLLOUT_STRICT is set)");
+    for (; s < steps; ++s) {                                   // every other handle: draw, then one step launch, per step
+        const int64_t o = (int64_t)s * N;
+        if (gw_launch_policy_sample(N, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, cdf_dev, seed,
+                                    step0 + (uint64_t)s, env_id0, seen_before(s), device_out_dev + o, duration_out_dev + o, stream))
+            return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
+        if (launch_step(env, device_out_dev + o, duration_out_dev + o, obs_dev + o, reward_dev + o, done_dev + o, stream))
             return fail(GW_EHIP, "step kernel launch failed at step %d", s);
         gw_env_add_steps(env, 1);
     }
@@ -916,9 +968,12 @@ static void launch_slot_name(int slot, char* out, size_t cap)
     } else if (slot < GW_LS_LIVE) {
         const int i = slot - GW_LS_GENERIC;
         snprintf(out, cap, "ct_step_kernel<%d, %s, %s, %s>", dts[i / 8], tf[(i >> 2) & 1], tf[(i >> 1) & 1], tf[i & 1]);
-    } else {
+    } else if (slot < GW_LS_ROLLOUT_POLICY) {
         const int i = slot - GW_LS_LIVE;
         snprintf(out, cap, "ct_step_live_kernel<%d, %s>", dts[i / 2], tf[i % 2]);
+    } else {
+        const int i = slot - GW_LS_ROLLOUT_POLICY;
+        snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     }
 }
 

@@ -303,6 +303,12 @@ int gw_launch_init_sfx(const GwState& st, void* stream);
 int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
                           int32_t* obs, float* reward, uint8_t* done, uint16_t* act_buf, uint8_t* fb_buf, int k_cap, void* stream,
                           bool below_limits, uint64_t* rec);
+// gw_rollout_policy (ct_rollout_sfx.hip): the fused form, and one step's draw of the unfused one
+int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
+                                 uint64_t env_id0, const int32_t* obs_prev, int32_t* device_out, int32_t* duration_out, int32_t* obs,
+                                 float* reward, uint8_t* done, void* stream, bool below_limits, uint64_t* rec);
+int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const uint32_t* cdf, uint64_t seed, uint64_t step,
+                            uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, void* stream);
 int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream);
 int gw_launch_delivered_sfx(const GwState& st, uint32_t* out, void* stream);
 int gw_launch_clear_flags(const GwState& st, void* stream);          // ct_step_sfx.hip (both queue modes)
@@ -325,7 +331,7 @@ int gw_launch_unpack_feedback(int64_t count, int center, int pv, const uint8_t* 
 // Sender counts with a kernel instantiation of their own (template parameter DT; every other count runs DT = 0), one list
 // per kernel family.  Each family's launcher dispatches over its list (gw_dispatch.h) and nothing else restates it.
 #define GW_DTS_STEP          2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_step_sfx_kernel
-#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel
+#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy
 #define GW_DTS_ROLLOUT_LOOP  2, 3, 4, 6, 8, 16, 32          // ct_rollout_sfx_kernel (event loop)
 #define GW_DTS_LIVE          2, 3, 4, 6, 8, 16, 32          // ct_step_live_kernel
 #define GW_DTS_GENERIC       2, 3, 4, 8, 16                 // ct_step_kernel on the table PHY
@@ -344,7 +350,8 @@ enum {
     GW_LS_PEND = GW_LS_ROLLOUT + 3 * GW_LS_NDT,            // pend_step_kernel<MODE, HALF>: 6
     GW_LS_GENERIC = GW_LS_PEND + 6,                        // ct_step_kernel<DT, PER_ENV_STATS, DYN, SPLIT>: 8 per DT
     GW_LS_LIVE = GW_LS_GENERIC + 8 * GW_LS_NDT,            // ct_step_live_kernel<DT, PER_ENV>: 2 per DT
-    GW_LS_COUNT = GW_LS_LIVE + 2 * GW_LS_NDT
+    GW_LS_ROLLOUT_POLICY = GW_LS_LIVE + 2 * GW_LS_NDT,     // ct_rollout_policy<DT, MODE>: 3 per DT (appended: the slots above keep
+    GW_LS_COUNT = GW_LS_ROLLOUT_POLICY + 3 * GW_LS_NDT     //                              their numbers)
 };
 constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {

@@ -267,6 +267,7 @@ class VecCounterTrafficEnv(BaseEnv):
         if self._custom is not None:                      # counter_traffic.py:142-144
             self._custom.reset()
             return self._custom.getObservation()
+        self._last = (obs,) + tuple(self._last[1:])       # the observation the agent acts on next (rollout_policy)
         return obs
 
     def _ready(self, t):
@@ -411,6 +412,69 @@ class VecCounterTrafficEnv(BaseEnv):
         if K:
             self._last = (obs[-1], rew[-1], done[-1])
         return obs, rew, done
+
+    def _policy_table(self, cdf):
+        """``cdf`` as the 32-bit words gw_rollout_policy reads: [3][A] on this env's GPU (a tensor that already is, is used in
+        place, so a caller may keep rewriting it on the same stream)."""
+        torch = _torch()
+        A = self.num_devices * int(self.config.max_duration)
+        if isinstance(cdf, torch.Tensor):
+            t = cdf
+            if t.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                t = t.to(self.device).contiguous()
+            else:                                         # actions.policy_cdf's int64: keep the low 32 bits, bit for bit
+                t = (t.to(self.device).to(torch.int64) & 0xffffffff)
+                t = torch.where(t >= (1 << 31), t - (1 << 32), t).to(torch.int32).contiguous()
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(cdf, dtype=np.uint32).view(np.int32)).to(self.device)
+        if tuple(t.shape) != (3, A):
+            raise ValueError("policy table must have shape (3, %d), got %s" % (A, tuple(t.shape)))
+        return t
+
+    def rollout_policy(self, cdf, steps, seed, step0=0, env_id0=0, obs_prev=None, out=None):
+        """``steps`` consecutive steps with the policy inside the launch (gw_rollout_policy): every env draws its action from
+        row ``sign(obs - COUNTER_BOUND) + 1`` of ``cdf`` (``actions.policy_cdf``, [3][num_devices * max_duration]) for the
+        observation it got last -- ``obs_prev`` int32[N] before the first step (default: what the env returned last), its own
+        afterwards -- with the counter-based stream of ``actions.policy_sample_numpy`` at ``(seed, env_id0 + e, step0 + k)``.
+        Returns ``(device, duration, obs, reward, done)``, each ``[steps][N]``: the transitions a replay memory wants; the two
+        action arrays can be replayed through ``rollout``.  Advance ``step0`` by ``steps`` from call to call.  Not for
+        hipGraph capture: ``step0`` would be baked in and every replay would repeat the same draws.
+        The native call wants ``obs_prev`` apart from its outputs.  With the same ``out`` buffers call after call the default
+        ``obs_prev`` is the last row of ``out``'s own ``obs``; an ``obs_prev`` inside any of ``out`` is copied first."""
+        torch = _torch()
+        if self._custom is not None:
+            raise ValueError("rollout_policy needs the built-in interpreter: a custom interpreter's observations are not "
+                             "the ones the kernel draws from")
+        K, n = int(steps), self.num_envs
+        if obs_prev is None:
+            obs_prev = self._last[0]
+            if obs_prev is None:
+                raise ValueError("rollout_policy: no observation yet -- reset() or step() first, or pass obs_prev")
+        prev = torch.as_tensor(obs_prev).to(device=self.device, dtype=torch.int32).contiguous()
+        if prev.shape != (n,):
+            raise ValueError("obs_prev must have shape (%d,), got %s" % (n, tuple(prev.shape)))
+        table = self._policy_table(cdf)
+        if out is None:
+            out = (torch.empty((K, n), dtype=torch.int32, device=self.device),
+                   torch.empty((K, n), dtype=torch.int32, device=self.device),
+                   torch.empty((K, n), dtype=torch.int32, device=self.device),
+                   torch.empty((K, n), dtype=torch.float32, device=self.device),
+                   torch.empty((K, n), dtype=torch.uint8, device=self.device))
+        dev, dur, obs, rew, done = out
+        for t, dt in ((dev, torch.int32), (dur, torch.int32), (obs, torch.int32), (rew, torch.float32), (done, torch.uint8)):
+            assert t.dtype is dt and tuple(t.shape) == (K, n) and t.is_contiguous() and t.device == self.device
+        if K:
+            lo, hi = prev.data_ptr(), prev.data_ptr() + 4 * n
+            if any(lo < t.data_ptr() + t.numel() * t.element_size() and t.data_ptr() < hi for t in out):
+                prev = prev.clone()
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_rollout_policy(self._h, K, table.data_ptr(), int(seed) & (2 ** 64 - 1),
+                                                int(step0) & (2 ** 64 - 1), int(env_id0) & (2 ** 64 - 1), prev.data_ptr(),
+                                                dev.data_ptr(), dur.data_ptr(), obs.data_ptr(), rew.data_ptr(),
+                                                done.data_ptr(), self._stream()))
+        if K:
+            self._last = (obs[-1], rew[-1], done[-1])
+        return dev, dur, obs, rew, done
 
     def render(self, mode='human', close=False):          # counter_traffic.py:160-162
         values = self.received()[0].tolist()

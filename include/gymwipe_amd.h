@@ -190,6 +190,30 @@ int gw_unpack_feedback(gw_env* env, int64_t count, const uint8_t* packed_dev, in
 int gw_rollout(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
                int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream);
 
+/* gw_rollout with the policy inside: `steps` env.step() calls in which every env's action is drawn from the observation it
+ * just got, as the reference's caller does between two steps (agents/dqn_counter_traffic.py:63-70: a policy over
+ * window_length = 1 observations; :25-31 flat action -> device, duration).  The agent sees one of three values,
+ * counter_bound + payload_value * {-1, 0, +1}, so any such policy is a table of three rows over the A = num_devices *
+ * max_duration flat actions -- cdf_dev: uint32[3][A], row-major, non-decreasing per row (gymwipe_amd/actions.py policy_cdf).
+ * Env e at step k of the call acts on obs_prev_dev[e] (int32[N]) for k = 0 and on its own observation of step k - 1 afterwards:
+ *     cls = sign(obs - counter_bound) + 1
+ *     h   = splitmix64(seed ^ ((env_id0 + e) * 0x9E3779B97F4A7C15) ^ ((step0 + k) * 0xD1B54A32D192ED03))     (actions.py)
+ *     u   = min(h & 0xffffffff, 0xfffffffe)
+ *     a   = min(A - 1, #{ j in [0, A) : cdf[cls][j] <= u });   device = a / max_duration, duration = a % max_duration
+ * The five outputs are [steps][N] and none may be NULL; device_out_dev / duration_out_dev have the layout gw_rollout takes, so
+ * a recorded closed loop can be replayed through it.  obs_prev_dev and cdf_dev overlap none of the outputs: to continue from
+ * the last row of an earlier call's obs_dev while writing the same buffer again, copy that row first.  The table is read stream-ordered (rewrite it on the same stream between
+ * calls), never validated or read back: the clamp keeps any content memory-safe, and a drawn action is always inside the
+ * action space (no GW_FLAG_BADACT).  Continue a stream of draws by advancing step0 by `steps`; shard it by env_id0.
+ * Default mode: ONE launch per 64 steps (ct_rollout_policy in ct_rollout_sfx.hip), the draw at each step boundary inside it.
+ * Every other handle (explicit queues, live PHY, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0), or any
+ * handle while GW_ROLLOUT_POLICY_UNFUSED is set: a sampling launch and a step launch per step, same results;
+ * GW_ROLLOUT_STRICT turns that into GW_EUNSUPPORTED.  steps == 0 is GW_OK; a NULL pointer or steps < 0 is GW_EINVAL before
+ * any HIP call.  Not for hipGraph capture: step0 is baked into the recorded launch, so every replay repeats the same draws. */
+int gw_rollout_policy(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                      const int32_t* obs_prev_dev, int32_t* device_out_dev, int32_t* duration_out_dev,
+                      int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream);
+
 /* Cumulative number of data packets the RRM has decoded per env since gw_create: uint32[N], device pointer
  * (default mode).  A custom Interpreter (envs/core.py:59-159) differences this across a step to learn how many
  * packets of the assigned sender the RRM sniffed (networking/devices.py:163-168). */

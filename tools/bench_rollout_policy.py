@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""
+Closed-loop rollout: what the policy inside the launch buys (profiles/rollout_policy/README.md).
+
+Windows of K steps at N envs x D senders, a reset between windows, three forms of the same work:
+  a  env.rollout             pre-staged actions, one persistent launch per window (no policy at all: the ceiling)
+  b  per-step closed loop    what a caller does without gw_rollout_policy: per step, the observation's class, a draw,
+                             torch.searchsorted on the same table, the flat action split, env.step()
+  c  env.rollout_policy      the draw inside the launch; with GW_ROLLOUT_POLICY_UNFUSED=1 its unfused form
+Each form is timed `--repeats` times over `--windows` windows (wall clock around a device synchronize); one JSON line with the
+best, the median and the spread.  GW_TREE names the checkout whose gymwipe_amd package (and built library) is measured --
+default: this file's own -- so one job can run a and b on the parent commit's build and c on this one's; a form the measured
+checkout lacks is reported as null.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.environ.get("GW_TREE") or os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--devices", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=64, help="steps per window (K)")
+    ap.add_argument("--windows", type=int, default=8)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--forms", default="a,b,c")
+    ap.add_argument("--label", default="")
+    args = ap.parse_args()
+
+    import torch
+    from gymwipe_amd import VecCounterTrafficEnv, actions
+    from gymwipe_amd import _native as nat
+
+    N, D, K, W = args.envs, args.devices, args.steps, args.windows
+    dev = torch.device("cuda:0")
+    env = VecCounterTrafficEnv(N, num_devices=D, device=dev)
+    md = int(env.config.max_duration)
+    A = D * md
+    center = int(env.config.counter_bound)
+    rng = np.random.default_rng(7)
+    p = rng.dirichlet(np.full(A, 0.3), size=3)
+    cdf = actions.policy_cdf(p) if hasattr(actions, "policy_cdf") else \
+        np.minimum(np.floor(np.cumsum(p, axis=1) * 2.0 ** 32), 2.0 ** 32 - 1).astype(np.uint32)
+    cdf[:, -1] = 0xffffffff
+    table32 = torch.from_numpy(cdf.view(np.int32)).to(dev)
+    # form b's table: the three rows as one sorted int64 vector (row r offset by r << 32), one searchsorted per step
+    flat = (torch.from_numpy(cdf.astype(np.int64)).to(dev) + (torch.arange(3, device=dev)[:, None] << 32)).reshape(-1).contiguous()
+    a_dev, a_dur = actions.actions_torch(3, 0, N, 0, K, D, md, device=dev)
+    out3 = (torch.empty((K, N), dtype=torch.int32, device=dev), torch.empty((K, N), dtype=torch.float32, device=dev),
+            torch.empty((K, N), dtype=torch.uint8, device=dev))
+    out5 = (torch.empty((K, N), dtype=torch.int32, device=dev), torch.empty((K, N), dtype=torch.int32, device=dev)) + out3
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(11)
+
+    def form_a():
+        for _ in range(W):
+            env.reset()
+            env.rollout(a_dev, a_dur, out=out3)
+
+    def form_b():
+        for _ in range(W):
+            obs = env.reset()
+            for _k in range(K):
+                cls = (torch.sign(obs - center) + 1).to(torch.int64)
+                u = torch.randint(0, 0xffffffff, (N,), device=dev, generator=gen)
+                a = torch.searchsorted(flat, u + (cls << 32), right=True) - cls * A
+                a = torch.clamp(a, max=A - 1)
+                d = torch.div(a, md, rounding_mode="floor")
+                obs, _, _, _ = env.step({"device": d.to(torch.int32), "duration": (a - d * md).to(torch.int32)})
+
+    def form_c():
+        s = 0
+        for _ in range(W):
+            env.reset()
+            env.rollout_policy(table32, K, 5, step0=s, out=out5)
+            s += K
+
+    have_c = hasattr(nat.lib(), "gw_rollout_policy") and hasattr(env, "rollout_policy")
+    forms = {"a": form_a, "b": form_b, "c": form_c if have_c else None}
+    res = {"label": args.label, "tree": "GW_TREE" if os.environ.get("GW_TREE") else "own", "envs": N, "devices": D, "steps": K, "windows": W,
+           "repeats": args.repeats, "unfused_switch": bool(os.environ.get("GW_ROLLOUT_POLICY_UNFUSED"))}
+    for name in args.forms.split(","):
+        fn = forms[name]
+        if fn is None:
+            res[name] = None
+            continue
+        fn()                                                   # warm-up (first launches, allocator)
+        torch.cuda.synchronize(dev)
+        times = []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            times.append(time.perf_counter() - t0)
+        env.check()
+        rate = [N * K * W / t / 1e9 for t in times]
+        res[name] = {"G_env_steps_per_s_best": round(max(rate), 3), "median": round(float(np.median(rate)), 3),
+                     "min": round(min(rate), 3), "us_per_step_best": round(min(times) / (K * W) * 1e6, 3)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
