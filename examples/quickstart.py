@@ -44,6 +44,12 @@ table = policy_cdf(torch.softmax(torch.randn(3, 4 * 20, device="cuda"), dim=-1))
 a_dev, a_dur, o, r, d = venv.rollout_policy(table, 64, seed=1)          # acts on the last observation first; step0 += 64 next time
 print("rollout_policy:", tuple(a_dev.shape), float(r.float().mean()))
 
+# 3c. ... and for a caller that wants the tally, not the transitions: int64[3][A][7] over (observation class, action) with
+#     n, reward sum, reward-square sum, next observation below / at / above the bound, done -- no [steps][N] array at all
+stats = venv.rollout_policy_stats(table, 64, seed=1, step0=64)          # continues from the observations 3b ended on
+n, r_sum = int(stats[..., 0].sum()), int(stats[..., 1].sum())
+print("rollout_policy_stats:", tuple(stats.shape), n, r_sum / n)
+
 
 # 4. your own Interpreter (envs/core.py:59-159), fed with what the RRM sniffed each step
 class CountDeliveries(VecInterpreter):

@@ -122,3 +122,42 @@ def policy_sample_numpy(seed, env_lo, env_hi, step, cdf, obs, counter_bound, max
     a = policy_count_numpy(cdf, cls, policy_u_numpy(seed, env_lo, env_hi, step))
     dev = a // int(max_duration)
     return dev.astype(np.int32), (a - dev * int(max_duration)).astype(np.int32)
+
+
+# ---- the table of a closed loop (gw_rollout_policy_stats / gw_transition_stats, include/gymwipe_amd.h) -----------------------
+TS_COLS = 7                     # n, r_sum, r_sq, next below / at / above the bound, done
+
+
+def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center, max_duration, num_devices):
+    """CPU restatement of both entry points' table: ``int64[3][A][TS_COLS]`` over (observation class, flat action) from
+    recorded transitions ``[steps][N]``.  Step k's observation seen is ``obs_prev`` for k = 0 and row k - 1 of ``obs``
+    afterwards; ``cls = sign(obs_seen - center) + 1``, ``a = device * max_duration + duration``.  Columns: transitions,
+    reward sum, reward-square sum, next observation below / at / above ``center``, ``done != 0``.  A row whose action lies
+    outside the action space is skipped (the env did nothing in that step); a reward is rounded to nearest (ties to even) and
+    clamped to [-10, 10], anything that is not a number counting as -10."""
+    md, D = int(max_duration), int(num_devices)
+    A = D * md
+    dev = np.asarray(device).astype(np.int64)
+    dur = np.asarray(duration).astype(np.int64)
+    nxt = np.asarray(obs).astype(np.int64)
+    steps = dev.shape[0]
+    table = np.zeros((3, A, TS_COLS), np.int64)
+    if steps == 0:
+        return table
+    seen = np.concatenate([np.asarray(obs_prev).astype(np.int64).reshape(1, -1), nxt[:-1]])
+    with np.errstate(invalid="ignore"):
+        x = np.rint(np.asarray(reward, dtype=np.float64))
+        x = np.where(x >= -10.0, x, -10.0)               # (a NaN fails the comparison)
+        r = np.where(x <= 10.0, x, 10.0).astype(np.int64)
+    ok = (dev >= 0) & (dev < D) & (dur >= 0) & (dur < md)
+    row = ((np.sign(seen - int(center)) + 1) * A + dev * md + dur)[ok]
+    ncl = (np.sign(nxt - int(center)) + 1)[ok]
+    r = r[ok]
+    dn = (np.asarray(done)[ok] != 0).astype(np.int64)
+    flat = table.reshape(3 * A, TS_COLS)
+    np.add.at(flat[:, 0], row, 1)
+    np.add.at(flat[:, 1], row, r)
+    np.add.at(flat[:, 2], row, r * r)
+    np.add.at(flat, (row, 3 + ncl), 1)
+    np.add.at(flat[:, 6], row, dn)
+    return table

@@ -163,3 +163,70 @@ class DqnCounterTrafficAgent:
             if self.steps * self.n >= self.warmup and self.m_len >= self.batch_size:
                 loss = self.learn()
         return loss
+
+
+class TabularCounterTrafficAgent:
+    """The agent this env admits exactly: it sees one of three observation values and picks one of A = num_devices *
+    max_duration flat actions, so its Q function is a ``[3][A]`` table and everything it learns from is the table of
+    ``env.rollout_policy_stats`` -- visits, reward sums, where the next observation landed, how often ``done`` fired, per
+    (observation class, action).  ``collect`` is one launch per 64 steps and no per-env array; ``learn`` and ``evaluate`` are
+    arithmetic on ``[3][A]`` tensors on the GPU.  Nothing here is sized by the number of envs."""
+
+    def __init__(self, env, gamma=0.99, tau=1.0, seed=123):
+        import torch
+        self.torch = torch
+        self.env = env
+        self.dev = env.device
+        self.nb_actions = int(env.num_devices) * int(env.config.max_duration)
+        self.gamma, self.tau = float(gamma), float(tau)
+        self.q = torch.zeros((3, self.nb_actions), dtype=torch.float64, device=self.dev)
+        self.table = torch.zeros((3, self.nb_actions, 7), dtype=torch.int64, device=self.dev)     # everything collected so far
+        self.seed, self.stream_pos = int(seed), 0
+
+    def policy_cdf(self):
+        """Boltzmann policy over Q (``DqnCounterTrafficAgent.act``'s rule: exp(clip(q / tau, -500, 500)), normalised) as the
+        table ``env.rollout_policy_stats`` draws from; built where Q lives, no host sync."""
+        from .actions import policy_cdf
+        torch = self.torch
+        return policy_cdf(torch.softmax(torch.clamp(self.q / self.tau, -500.0, 500.0), dim=-1))
+
+    def _rollout(self, steps, table):
+        steps = int(steps)
+        if self.env._last[0] is None:
+            self.env.reset()
+        self.env.rollout_policy_stats(self.policy_cdf(), steps, self.seed, step0=self.stream_pos, table=table)
+        self.stream_pos += steps
+        return table
+
+    def collect(self, steps):
+        """``steps`` env steps of all N envs under the current policy, their transitions added into ``self.table``."""
+        return self._rollout(steps, self.table)
+
+    @staticmethod
+    def q_iteration(q, table, gamma, sweeps=1):
+        """``sweeps`` sweeps of Q-iteration on the empirical model of the visited pairs of ``table`` (int64[3][A][7]):
+        ``Q[s,a] <- r_sum/n + gamma * (1 - done/n) * sum_s' next[s']/n * max_a' Q[s',a']``; unvisited pairs keep their value.
+        Returns the new Q (float64[3][A], same device)."""
+        import torch
+        t = table.to(torch.float64)
+        n = t[..., 0]
+        visited = n > 0
+        nn = torch.clamp(n, min=1.0)
+        r_mean, cont, p_next = t[..., 1] / nn, 1.0 - t[..., 6] / nn, t[..., 3:6] / nn.unsqueeze(-1)
+        for _ in range(int(sweeps)):
+            v = q.max(dim=1).values                            # [3]: the value of each observation class
+            q = torch.where(visited, r_mean + gamma * cont * (p_next * v).sum(dim=-1), q)
+        return q
+
+    def learn(self, sweeps=1):
+        self.q = self.q_iteration(self.q, self.table, self.gamma, sweeps)
+        return self.q
+
+    def evaluate(self, steps):
+        """Mean reward per env-step under the current policy over ``steps`` further steps of all N envs, and its standard
+        error: ``(mean, stderr)`` from n, r_sum and r_sq of a table of this call's own (``self.table`` is not touched)."""
+        torch = self.torch
+        t = self._rollout(steps, torch.zeros_like(self.table)).to(torch.float64)
+        n, r_sum, r_sq = (float(x) for x in t[..., :3].sum(dim=(0, 1)).cpu())
+        mean = r_sum / n
+        return mean, (max(r_sq / n - mean * mean, 0.0) / n) ** 0.5

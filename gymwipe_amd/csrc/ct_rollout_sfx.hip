@@ -529,6 +529,8 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
 //   ct_rollout_sync_kernel  gw_rollout: the caller's pre-staged rows, step k + 1's action loaded while step k is walked;
 //   ct_rollout_policy       gw_rollout_policy: drawn at the step boundary from a three-row table over the observation the
 //                           env just produced (PolicyActions), and stored with that step's outputs.
+//   ct_rollout_pstats       gw_rollout_policy_stats: the same draw, nothing stored per step -- the transition is counted into a
+//                           table over (observation class, action) instead (StatsActions).
 // The policy's draw (include/gymwipe_amd.h, gw_rollout_policy): the first 32 bits of the action stream's hash
 // (gymwipe_amd/actions.py) against the observation class's row of the table.
 __device__ __forceinline__ uint32_t gw_policy_u(uint64_t seed, uint64_t env_term, uint64_t step)
@@ -565,6 +567,7 @@ __device__ __forceinline__ uint32_t gw_policy_cls(int32_t obs, int32_t center)  
 }
 
 constexpr int GW_POLICY_A_MAX = GW_MAX_DEVICES * 20;     // flat actions the fused form stages (3 rows of them in LDS)
+constexpr size_t GW_LDS_PER_BLOCK = 65536;               // what one workgroup may allocate, static and dynamic together
 
 struct PolicyActions {
     const uint32_t* __restrict__ cdf;                    // [3][A]
@@ -604,6 +607,12 @@ struct PolicyActions {
     }
 };
 
+// step k's three outputs as the C-ABI lays them out: what GW_ROLLOUT_SRC_OUTPUT is for a kernel with obs, reward and done arrays
+#define GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)                                                                              \
+    obs[at] = latest + c.counter_bound;                                                                                          \
+    reward[at] = (float)r;                                                                                                       \
+    done[at] = (uint8_t)dn;
+
 template <int DT, int MODE>
 __global__ __launch_bounds__(64) void ct_rollout_sync_kernel(GwState st, GwDevConst c, int K,
                                                             const int32_t* __restrict__ device, const int32_t* __restrict__ duration,
@@ -615,12 +624,14 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_kernel(GwState st, GwDevCo
     const int d = d_next, du = du_next;                                                                                          \
     if (k + 1 < K) { d_next = device[(size_t)(k + 1) * N + e]; du_next = duration[(size_t)(k + 1) * N + e]; }
 #define GW_ROLLOUT_SRC_CHECKED(bad) (bad)                /* a staged action may lie outside the action space (GW_FLAG_BADACT) */
+#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
 #define GW_ROLLOUT_SRC_STEPPED(at, latest)
 #include "ct_rollout_sync_body.h"
 #undef GW_ROLLOUT_SRC_STAGE
 #undef GW_ROLLOUT_SRC_FIRST
 #undef GW_ROLLOUT_SRC_TAKE
 #undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_OUTPUT
 #undef GW_ROLLOUT_SRC_STEPPED
 }
 
@@ -653,13 +664,210 @@ __global__ __launch_bounds__(64) void ct_rollout_policy(GwState st, GwDevConst c
 #define GW_ROLLOUT_SRC_FIRST src.first(e);
 #define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
 #define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
+#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
 #define GW_ROLLOUT_SRC_STEPPED(at, latest) src.stepped(at, k, K, latest);
 #include "ct_rollout_sync_body.h"
 #undef GW_ROLLOUT_SRC_STAGE
 #undef GW_ROLLOUT_SRC_FIRST
 #undef GW_ROLLOUT_SRC_TAKE
 #undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_OUTPUT
 #undef GW_ROLLOUT_SRC_STEPPED
+}
+
+// ---- the tally: gw_rollout_policy_stats and gw_transition_stats (include/gymwipe_amd.h: int64 table[3][A][GW_TS_COLS]) --------
+// Everything a learner or an evaluator takes from a transition of this env is a function of (observation class, flat action):
+// the kernels below count into a per-block histogram in LDS and add its non-empty bins to the caller's table once per block.
+// A bin is two 64-bit words, each updated by ONE LDS atomic add per transition:
+//     word 0   bits  0-12 / 13-25 / 26-38   transitions whose next observation was below / at / above counter_bound
+//              bits 39-51                   transitions with done != 0                      (n = the sum of the first three)
+//     word 1   bits  0-16  sum of (reward + 10)        bits 17-35  sum of reward^2
+// Bit budget: between zeroing and flush a histogram takes at most TS_EVENTS transitions -- one wave of 64 envs over at most
+// TS_STEPS = 64 steps in ct_rollout_pstats, a tile of TS_EVENTS rows in transition_stats_rows -- and a reward is an integer in
+// [-10, 10] (ct_rollout_sync_body.h clamps it; transition_stats_rows rounds and clamps what it reads).  So a count is at most
+// 4 096 < 2^13, sum(reward + 10) at most 20 * 4 096 < 2^17, sum(reward^2) at most 100 * 4 096 < 2^19: no field carries into
+// its neighbour.  Integer adds commute, in LDS and in the table alike: the result does not depend on the order of arrival.
+constexpr uint32_t TS_STEPS = GW_TS_STEPS, TS_EVENTS = 64 * TS_STEPS;
+constexpr int TS_CNT_BITS = 13, TS_RS_BITS = 17, TS_RQ_BITS = 19;
+constexpr int TS_RMAX = 10;
+static_assert(TS_EVENTS < (1u << TS_CNT_BITS), "a count field overflows into its neighbour");
+static_assert(2 * TS_RMAX * TS_EVENTS < (1u << TS_RS_BITS), "the reward-sum field overflows");
+static_assert(TS_RMAX * TS_RMAX * TS_EVENTS < (1u << TS_RQ_BITS), "the reward-square-sum field overflows");
+static_assert(4 * TS_CNT_BITS <= 64 && TS_RS_BITS + TS_RQ_BITS <= 64, "a bin is two 64-bit words");
+constexpr uint32_t TS_BIN_BYTES = 16;
+
+// one transition into the LDS histogram: bin = cls * A + a, next_cls in [0, 3), r in [-TS_RMAX, TS_RMAX]
+__device__ __forceinline__ void gw_ts_count(uint64_t* hist, uint32_t bin, uint32_t next_cls, int32_t r, uint32_t dn)
+{
+    const uint64_t w0 = (1ull << (TS_CNT_BITS * next_cls)) | ((uint64_t)(dn != 0u ? 1u : 0u) << (3 * TS_CNT_BITS));
+    const uint64_t w1 = (uint64_t)(uint32_t)(r + TS_RMAX) | ((uint64_t)(uint32_t)(r * r) << TS_RS_BITS);
+    __hip_atomic_fetch_add(hist + 2u * bin, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(hist + 2u * bin + 1u, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void gw_ts_add(int64_t* cell, uint64_t v)      // a 64-bit global atomic add, nothing returned
+{
+    __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the seven columns of one (cls, a) pair into the table (a zero adds nothing and is not sent)
+__device__ __forceinline__ void gw_ts_row(int64_t* row, uint64_t n0, uint64_t n1, uint64_t n2, uint64_t dn, int64_t rs, uint64_t rq)
+{
+    gw_ts_add(row + 0, n0 + n1 + n2);
+    if (rs != 0) gw_ts_add(row + 1, (uint64_t)rs);
+    if (rq != 0u) gw_ts_add(row + 2, rq);
+    if (n0 != 0u) gw_ts_add(row + 3, n0);
+    if (n1 != 0u) gw_ts_add(row + 4, n1);
+    if (n2 != 0u) gw_ts_add(row + 5, n2);
+    if (dn != 0u) gw_ts_add(row + 6, dn);
+}
+// The histogram's non-empty bins into the table: lane `first` of `stride` takes every stride-th bin.  The caller has ordered
+// the LDS adds before this (a barrier, or a fence within the one wave that made them).
+__device__ __forceinline__ void gw_ts_flush(const uint64_t* hist, uint32_t bins, uint32_t first, uint32_t stride, int64_t* table)
+{
+    constexpr uint64_t CM = (1ull << TS_CNT_BITS) - 1u;
+    for (uint32_t b = first; b < bins; b += stride) {
+        const uint64_t w0 = hist[2u * b];
+        if (w0 == 0u) continue;                          // every transition sets one of the next-observation counts
+        const uint64_t w1 = hist[2u * b + 1u];
+        const uint64_t n0 = w0 & CM, n1 = (w0 >> TS_CNT_BITS) & CM, n2 = (w0 >> (2 * TS_CNT_BITS)) & CM;
+        const int64_t rs = (int64_t)(w1 & ((1ull << TS_RS_BITS) - 1u)) - (int64_t)TS_RMAX * (int64_t)(n0 + n1 + n2);
+        gw_ts_row(table + (size_t)b * GW_TS_COLS, n0, n1, n2, (w0 >> (3 * TS_CNT_BITS)) & CM, rs,
+                  (w1 >> TS_RS_BITS) & ((1ull << TS_RQ_BITS) - 1u));
+    }
+}
+
+// What gw_rollout_policy_stats passes on to ct_rollout_pstats.  obs_prev and obs_last may be one array (an env reads its own
+// element before the step loop and writes it after).
+struct GwStatsArgs {
+    const uint32_t* cdf;          // [3][A]
+    const int32_t* obs_prev;      // [N]
+    int32_t* obs_last;            // [N]
+    int32_t* ret;                 // [N] += the env's reward sum, or nullptr
+    int64_t* table;               // [3][A][GW_TS_COLS]
+    uint64_t seed, step0, env0;
+};
+
+// PolicyActions' draw without the action stores, and the step's outcome into the histogram instead of three output arrays.
+struct StatsActions {
+    const uint32_t* __restrict__ cdf;
+    uint64_t seed, step0, env0;
+    uint64_t* s_hist;                                    // [3 * A] bins of two words (the launch's dynamic LDS, in front of
+    uint32_t* s_cdf;                                     //  the table's 3 * A words)
+    uint32_t A, md, inv20;
+    int32_t center;
+    uint64_t env_term;
+    uint32_t bin_cur;                                    // cls * A + a of the action being taken
+    int d_cur, du_cur;
+    int32_t ret, latest_last;
+    __device__ __forceinline__ void stage() const
+    {
+        for (uint32_t i = threadIdx.x; i < 6u * A; i += blockDim.x) s_hist[i] = 0u;
+        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
+    }
+    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
+    {
+        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
+        const uint32_t dv = (a * inv20) >> 20;           // (exact: PolicyActions::draw)
+        bin_cur = cls * A + a;
+        d_cur = (int)dv;
+        du_cur = (int)(a - dv * md);
+    }
+    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen)
+    {
+        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;
+        draw(gw_policy_cls(obs_seen, center), step0);
+    }
+    // step k is over: one transition of the bin its action was drawn for; the next action from what the agent now sees
+    __device__ __forceinline__ void stepped(int k, int K, int32_t latest, int32_t r, uint32_t dn)
+    {
+        const uint32_t next_cls = (uint32_t)((int)(latest > 0) - (int)(latest < 0) + 1);
+        gw_ts_count(s_hist, bin_cur, next_cls, r, dn);
+        ret += r;
+        latest_last = latest;
+        if (k + 1 < K) draw(next_cls, step0 + (uint64_t)(k + 1));
+    }
+};
+
+// gw_rollout_policy_stats: ct_rollout_policy's closed loop with none of its five output streams.  A block is one wave, so the
+// histogram's adds and the flush's reads are LDS operations of the same wave, which the hardware keeps in order; the fences
+// keep the compiler from moving them, and no block barrier is needed (or possible: lanes beyond N have left).
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_pstats(GwState st, GwDevConst c, int K, GwStatsArgs p)
+{
+    extern __shared__ uint64_t s_stats_dyn[];
+    StatsActions src;
+    src.cdf = p.cdf; src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
+    src.md = (uint32_t)c.max_duration;
+    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
+    src.s_hist = s_stats_dyn;
+    src.s_cdf = reinterpret_cast<uint32_t*>(s_stats_dyn + 6u * src.A);
+    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
+    src.center = c.counter_bound;
+    src.env_term = 0; src.bin_cur = 0; src.d_cur = 0; src.du_cur = 0; src.ret = 0; src.latest_last = 0;
+#define GW_ROLLOUT_SRC_STAGE src.stage();
+#define GW_ROLLOUT_SRC_FIRST src.first(e, p.obs_prev[e]);
+#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
+#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
+#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) (void)at; src.stepped(k, K, latest, r, dn);
+#define GW_ROLLOUT_SRC_STEPPED(at, latest)
+#include "ct_rollout_sync_body.h"
+#undef GW_ROLLOUT_SRC_STAGE
+#undef GW_ROLLOUT_SRC_FIRST
+#undef GW_ROLLOUT_SRC_TAKE
+#undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_OUTPUT
+#undef GW_ROLLOUT_SRC_STEPPED
+    p.obs_last[e] = src.latest_last + c.counter_bound;
+    if (p.ret) p.ret[e] += src.ret;
+    // the wave's lanes that have an env (all 64 but in the last block) share the bins out among themselves
+    const uint32_t lanes = gw_min_u32(64u, N - blockIdx.x * 64u);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    gw_ts_flush(src.s_hist, 3u * src.A, threadIdx.x, lanes, p.table);
+}
+
+// gw_transition_stats: the same table from recorded [K][N] transitions.  A block takes tiles of TS_EVENTS consecutive
+// elements (the histogram's bit budget), 16 per thread, and flushes after each.  Any content is safe: a row whose action lies
+// outside the action space is skipped, a reward is rounded to nearest and clamped (NaN counts as -10), done is != 0.
+// LDS = false (a histogram of 3 * A bins would not fit): every row's seven columns straight into the table.
+template <bool LDS>
+__global__ __launch_bounds__(256) void transition_stats_rows(uint64_t total, uint32_t N, uint32_t D, uint32_t md, int32_t center,
+                                                            const int32_t* __restrict__ obs_prev, const int32_t* __restrict__ device,
+                                                            const int32_t* __restrict__ duration, const int32_t* __restrict__ obs,
+                                                            const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                            int64_t* __restrict__ table)
+{
+    extern __shared__ uint64_t s_stats_dyn[];
+    const uint64_t A = (uint64_t)D * md;
+    const uint64_t tiles = (total + TS_EVENTS - 1u) / TS_EVENTS;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        if constexpr (LDS) {
+            for (uint32_t i = threadIdx.x; i < 6u * (uint32_t)A; i += blockDim.x) s_stats_dyn[i] = 0u;
+            __syncthreads();
+        }
+#pragma unroll 4
+        for (uint32_t j = 0; j < TS_EVENTS / 256u; ++j) {
+            const uint64_t i = tile * TS_EVENTS + j * 256u + threadIdx.x;
+            if (i >= total) break;
+            const uint32_t dv = (uint32_t)device[i], du = (uint32_t)duration[i];
+            if (dv >= D || du >= md) continue;                                  // a GW_FLAG_BADACT step: the env did nothing
+            const int32_t seen = i < N ? obs_prev[i] : obs[i - N];              // row k - 1 of obs, same env
+            const float x = rintf(reward[i]);
+            const int32_t r = (int32_t)(x >= (float)-TS_RMAX ? (x <= (float)TS_RMAX ? x : (float)TS_RMAX) : (float)-TS_RMAX);
+            const uint32_t next_cls = gw_policy_cls(obs[i], center), dn = done[i];
+            const uint64_t bin = (uint64_t)gw_policy_cls(seen, center) * A + (uint64_t)dv * md + du;
+            if constexpr (LDS) {
+                gw_ts_count(s_stats_dyn, (uint32_t)bin, next_cls, r, dn);
+            } else {
+                gw_ts_row(table + bin * GW_TS_COLS, next_cls == 0u, next_cls == 1u, next_cls == 2u, dn != 0u, r, (uint64_t)(r * r));
+            }
+        }
+        if constexpr (LDS) {
+            __syncthreads();
+            gw_ts_flush(s_stats_dyn, 3u * (uint32_t)A, threadIdx.x, blockDim.x, table);
+            __syncthreads();
+        }
+    }
 }
 
 // The unfused form's draw, for handles without a fused rollout: one step's actions for every env from the observations `obs_in`.
@@ -705,6 +913,53 @@ int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, int K
                                (size_t)(3 * A) * sizeof(uint32_t), (hipStream_t)stream, st, cst, K, p, device_out, duration_out, obs, reward, done);
         });
     });
+    return gw_launch_status();
+}
+
+// The fused form of gw_rollout_policy_stats; GW_EUNSUPPORTED as above, and where the histogram beside the kernel's own tables
+// does not fit a workgroup's LDS (decided by the handle alone, never by K: a call is refused before its first launch).
+int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
+                                 uint64_t env_id0, const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table,
+                                 void* stream, bool below_limits, uint64_t* rec)
+{
+    const int64_t A = (int64_t)st.D * cst.max_duration;
+    if (K <= 0 || K > st.rcap || K > (int)TS_STEPS || st.ract != nullptr || A > GW_POLICY_A_MAX) return GW_EUNSUPPORTED;
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    const int mode = gw_step_mode(cst, below_limits, false);
+    const GwStatsArgs p = {cdf, obs_prev, obs_last, ret, table, seed, step0, env_id0};
+    const size_t dyn = (size_t)(3 * A) * (TS_BIN_BYTES + sizeof(uint32_t));
+    return gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
+        return gw_with_mode(mode, [&](auto m) {
+            constexpr int DT = decltype(dt)::value, MODE = decltype(m)::value;
+            static const int fixed = [] {                // the instantiation's own LDS (asked once; the same on every device)
+                hipFuncAttributes fa;
+                return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&ct_rollout_pstats<DT, MODE>)) == hipSuccess
+                           ? (int)fa.sharedSizeBytes : -1;
+            }();
+            if (fixed < 0) return gw_launch_status(hipErrorInvalidDeviceFunction);
+            if ((size_t)fixed + dyn > GW_LDS_PER_BLOCK) return (int)GW_EUNSUPPORTED;
+            gw_note_launch(rec, GW_LS_ROLLOUT_PSTATS + 3 * gw_ls_dt(DT) + MODE);
+            hipLaunchKernelGGL((ct_rollout_pstats<DT, MODE>), dim3(grid), dim3(64), dyn, (hipStream_t)stream, st, cst, K, p);
+            return gw_launch_status();
+        });
+    });
+}
+
+int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
+                               const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
+                               const uint8_t* done, int64_t* table, void* stream)
+{
+    const uint64_t total = (uint64_t)N * (uint64_t)K, tiles = (total + TS_EVENTS - 1u) / TS_EVENTS;
+    if (total == 0u) return GW_OK;
+    const uint64_t A = (uint64_t)D * (uint64_t)max_duration;
+    const size_t dyn = (size_t)(3u * A) * TS_BIN_BYTES;
+    const unsigned grid = (unsigned)(tiles < 4096u ? tiles : 4096u);
+    if (dyn <= GW_LDS_PER_BLOCK / 2)
+        hipLaunchKernelGGL(transition_stats_rows<true>, dim3(grid), dim3(256), dyn, (hipStream_t)stream, total, (uint32_t)N, (uint32_t)D,
+                           (uint32_t)max_duration, counter_bound, obs_prev, device, duration, obs, reward, done, table);
+    else
+        hipLaunchKernelGGL(transition_stats_rows<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, total, (uint32_t)N, (uint32_t)D,
+                           (uint32_t)max_duration, counter_bound, obs_prev, device, duration, obs, reward, done, table);
     return gw_launch_status();
 }
 

@@ -1,17 +1,21 @@
 // ct_rollout_sync_body.h -- the body of the step-synchronous rollout kernels (ct_rollout_sfx.hip), included once per kernel:
-// ct_rollout_sync_kernel (actions staged by the caller) and ct_rollout_policy (actions drawn in the kernel).  It is text
+// ct_rollout_sync_kernel (actions staged by the caller), ct_rollout_policy (actions drawn in the kernel) and ct_rollout_pstats
+// (drawn in the kernel, the transitions tallied instead of stored).  It is text
 // with macro hooks, not a function, on purpose.  As a __forceinline__ template over an action-source type the compiler
 // optimised the callee on its own before inlining it, and all 30 instantiations of ct_rollout_sync_kernel came out different
 // (up to 31 more VGPRs at D = 16 and 32, SGPRs parked in VGPR lanes at D = 4); with the source as an object whose members hold
 // the action pointers, 28 still differed in instruction order.  Included, with the staged source's statements spelled as they
 // were, every one of them is instruction for instruction what it was.
-// The including kernel provides: template parameters DT and MODE; st (GwState), c (GwDevConst), K; obs, reward, done; and
+// The including kernel provides: template parameters DT and MODE; st (GwState), c (GwDevConst), K; and
 //   GW_ROLLOUT_SRC_STAGE            statements before the block's barrier (tables of the source's own -> LDS)
 //   GW_ROLLOUT_SRC_FIRST            statements once per lane, before step 0
 //   GW_ROLLOUT_SRC_TAKE             statements at the start of step k that define `const int d, du`, the step's action
 //   GW_ROLLOUT_SRC_CHECKED(bad)     `bad` if an action can lie outside the action space, else false
+//   GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn)   statements that put step k's outcome (index `at` of [K][N] outputs) where the
+//                                   kernel wants it: GW_ROLLOUT_STORE_OUTPUTS, the three stores into the kernel's obs, reward
+//                                   and done, or a tally
 //   GW_ROLLOUT_SRC_STEPPED(at, latest)   statements when step k is over (outputs at index `at`; k not yet advanced)
-// The hooks share the body's scope.  Of its names they read only e, N, k and K, and they define only d and du; whatever else a
+// The hooks share the body's scope.  Of its names they read only e, N, k, K and c, and they define only d and du; whatever else a
 // source keeps lives in names the body leaves free: `src` and anything ending in `_next`.  A new local of the body takes
 // neither form.
     // Actions and outputs in the C-ABI's own step-major layout ([K][N]: a step's row is coalesced across the wave's lanes), read
@@ -110,9 +114,7 @@
     GW_ROLLOUT_SRC_FIRST                                        // step 0's action
     auto put_feedback = [&](int32_t latest, int32_t r) {
         const size_t at = (size_t)k * N + e;
-        obs[at] = latest + c.counter_bound;
-        reward[at] = (float)r;
-        done[at] = (uint8_t)dn;
+        GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn)
         GW_ROLLOUT_SRC_STEPPED(at, latest)
         k++;
     };

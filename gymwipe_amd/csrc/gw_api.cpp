@@ -333,10 +333,11 @@ bool gw_env_below_limits(gw_env* env, void* stream)
 // launcher's GW_EUNSUPPORTED ends it (steps > rollout capacity 0, max_duration > 254, ...): the caller goes on step by step,
 // or, under GW_ROLLOUT_STRICT, fails.
 template <class F>
-static int fused_chunks(gw_env* env, int32_t steps, void* stream, int32_t* s, F&& launch)
+static int fused_chunks(gw_env* env, int32_t steps, void* stream, int32_t* s, F&& launch, int32_t longest = INT32_MAX)
 {
-    while (env->st.tk && !env->dyn && env->st.rcap > 0 && *s < steps) {
-        const int32_t chunk = steps - *s < env->st.rcap ? steps - *s : env->st.rcap;
+    const int32_t cap = env->st.rcap < longest ? env->st.rcap : longest;       // (a launcher may take fewer steps than rcap)
+    while (env->st.tk && !env->dyn && cap > 0 && *s < steps) {
+        const int32_t chunk = steps - *s < cap ? steps - *s : cap;
         const int rc = launch(*s, chunk,
                               gw_env_below_limits(env, stream) && env->t_bound + (double)(chunk + 1) * env->step_max < env->t_limit);
         if (rc == GW_EUNSUPPORTED) {
@@ -709,6 +710,47 @@ int gw_rollout_policy(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint6
     return GW_OK;
 }
 
+int gw_rollout_policy_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                            const int32_t* obs_prev_dev, int32_t* obs_last_dev, int32_t* return_dev, int64_t* table_dev, void* stream)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!cdf_dev || !obs_prev_dev || !obs_last_dev || !table_dev)
+        return fail(GW_EINVAL, "gw_rollout_policy_stats: NULL device pointer");
+    if (steps == 0) return GW_OK;
+    int rc = select_device(env);
+    if (rc) return rc;
+    int32_t s = 0;
+    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (the A/B switch leaves no fused form: the caller composes)
+        // a chunk acts on what the one before it left in obs_last_dev
+        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
+            return gw_launch_rollout_pstats_sfx(env->st, env->cst_host, chunk, cdf_dev, seed, step0 + (uint64_t)s0, env_id0,
+                                                s0 ? obs_last_dev : obs_prev_dev, obs_last_dev, return_dev, table_dev, stream,
+                                                below, env->launches);
+        }, GW_TS_STEPS);
+        if (rc) return rc;
+    }
+    // (what keeps a handle from the fused form does not depend on the chunk: s is 0 here, nothing was launched)
+    if (s < steps) return fail(GW_EUNSUPPORTED, "no fused policy rollout for this handle: gw_rollout_policy, then gw_transition_stats");
+    return GW_OK;
+}
+
+int gw_transition_stats(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev, const int32_t* duration_dev,
+                        const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev, int64_t* table_dev, void* stream)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!obs_prev_dev || !device_dev || !duration_dev || !obs_dev || !reward_dev || !done_dev || !table_dev)
+        return fail(GW_EINVAL, "gw_transition_stats: NULL device pointer");
+    if (steps == 0) return GW_OK;
+    int rc = select_device(env);
+    if (rc) return rc;
+    if (gw_launch_transition_stats(env->st.N, steps, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, obs_prev_dev,
+                                   device_dev, duration_dev, obs_dev, reward_dev, done_dev, table_dev, stream))
+        return fail(GW_EHIP, "transition statistics kernel launch failed");
+    return GW_OK;
+}
+
 int gw_delivered(gw_env* env, uint32_t* out_dev, void* stream)
 {
     if (!env || !out_dev) return fail(GW_EINVAL, "env/out is NULL");
@@ -971,9 +1013,12 @@ static void launch_slot_name(int slot, char* out, size_t cap)
     } else if (slot < GW_LS_ROLLOUT_POLICY) {
         const int i = slot - GW_LS_LIVE;
         snprintf(out, cap, "ct_step_live_kernel<%d, %s>", dts[i / 2], tf[i % 2]);
-    } else {
+    } else if (slot < GW_LS_ROLLOUT_PSTATS) {
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
+    } else {
+        const int i = slot - GW_LS_ROLLOUT_PSTATS;
+        snprintf(out, cap, "ct_rollout_pstats<%d, %d>", dts[i / 3], i % 3);
     }
 }
 

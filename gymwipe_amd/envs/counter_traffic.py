@@ -197,6 +197,8 @@ class VecCounterTrafficEnv(BaseEnv):
         self._seen = {}                                   # action tensor objects already validated (step())
         self._dev_index = self.device.index or 0
         self._last = (None, None, None)
+        self._stats_last = None                           # rollout_policy_stats: the last observations, and the fallback's
+        self._stats_buf = None                            # 64-step transition buffers (both allocated on first use)
         self._custom = interpreter
         if interpreter is not None:                       # a user-supplied Interpreter replaces the fused one
             if explicit_queue:
@@ -475,6 +477,90 @@ class VecCounterTrafficEnv(BaseEnv):
         if K:
             self._last = (obs[-1], rew[-1], done[-1])
         return dev, dur, obs, rew, done
+
+    def _stats_table(self, table):
+        """The ``int64[3][A][TS_COLS]`` table on this env's GPU: the caller's (added into) or a new one of zeros."""
+        torch = _torch()
+        from ..actions import TS_COLS
+        shape = (3, self.num_devices * int(self.config.max_duration), TS_COLS)
+        if table is None:
+            return torch.zeros(shape, dtype=torch.int64, device=self.device)
+        if not (type(table) is torch.Tensor and table.dtype is torch.int64 and table.device == self.device
+                and tuple(table.shape) == shape and table.is_contiguous()):
+            raise ValueError("table must be a contiguous int64 tensor of shape %s on %s" % (shape, self.device))
+        return table
+
+    def transition_stats(self, obs_prev, device, duration, obs, reward, done, table=None):
+        """Recorded transitions ``[steps][N]`` (what ``rollout_policy`` returns; ``obs_prev`` int32[N] is what step 0 acted on)
+        added into ``table`` (gw_transition_stats; ``actions.transition_stats_numpy`` restates it): ``int64[3][A][7]`` over
+        (observation class, flat action).  Returns the table (a new one of zeros when none is passed)."""
+        torch = _torch()
+        table = self._stats_table(table)
+        K, n = int(obs.shape[0]), self.num_envs
+        args = []
+        for t, dt in ((obs_prev, torch.int32), (device, torch.int32), (duration, torch.int32), (obs, torch.int32),
+                      (reward, torch.float32), (done, torch.uint8)):
+            t = torch.as_tensor(t).to(device=self.device, dtype=dt).contiguous()
+            if tuple(t.shape) != ((n,) if not args else (K, n)):
+                raise ValueError("transition_stats: obs_prev is [N], the five arrays [steps][N]; got %s" % (tuple(t.shape),))
+            args.append(t)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_transition_stats(self._h, K, *[t.data_ptr() for t in args], table.data_ptr(), self._stream()))
+        return table
+
+    def rollout_policy_stats(self, cdf, steps, seed, step0=0, env_id0=0, obs_prev=None, table=None, returns=None):
+        """``rollout_policy`` for a caller that wants the tally, not the transitions (gw_rollout_policy_stats): the same
+        ``steps`` steps, draws and state changes, and every transition ADDED into ``table`` -- ``int64[3][A][7]`` over
+        (observation class ``sign(obs_seen - COUNTER_BOUND) + 1``, flat action ``device * max_duration + duration``) with the
+        columns n, reward sum, reward-square sum, next observation below / at / above the bound, done.  Returns the table (a
+        new one of zeros when none is passed).  ``returns`` (int32[N], optional) gets each env's reward sum added.  The last
+        observation is kept as ``reset()`` keeps its own, so a following ``rollout_policy`` / ``rollout_policy_stats``
+        continues from it; advance ``step0`` by ``steps``.  Nothing here is sized by ``steps * N``.
+        A handle without the fused form (explicit queues, live PHY, ...) runs ``rollout_policy`` in chunks of at most 64 steps
+        into buffers the env keeps, then ``transition_stats``: the same table."""
+        torch = _torch()
+        if self._custom is not None:
+            raise ValueError("rollout_policy_stats needs the built-in interpreter")
+        K, n = int(steps), self.num_envs
+        if obs_prev is None:
+            obs_prev = self._last[0]
+            if obs_prev is None:
+                raise ValueError("rollout_policy_stats: no observation yet -- reset() or step() first, or pass obs_prev")
+        prev = torch.as_tensor(obs_prev).to(device=self.device, dtype=torch.int32).contiguous()
+        if prev.shape != (n,):
+            raise ValueError("obs_prev must have shape (%d,), got %s" % (n, tuple(prev.shape)))
+        cdf_t = self._policy_table(cdf)
+        table = self._stats_table(table)
+        if returns is not None and not (type(returns) is torch.Tensor and returns.dtype is torch.int32 and returns.device == self.device
+                                        and tuple(returns.shape) == (n,) and returns.is_contiguous()):
+            raise ValueError("returns must be a contiguous int32[N] tensor on the env's GPU")
+        if K == 0:
+            return table
+        last = self._stats_last
+        if last is None:
+            last = self._stats_last = torch.empty(n, dtype=torch.int32, device=self.device)
+        seed, step0, env_id0 = int(seed) & (2 ** 64 - 1), int(step0), int(env_id0) & (2 ** 64 - 1)
+        with torch.cuda.device(self.device):
+            rc = self._L.gw_rollout_policy_stats(self._h, K, cdf_t.data_ptr(), seed, step0 & (2 ** 64 - 1), env_id0, prev.data_ptr(),
+                                                 last.data_ptr(), returns.data_ptr() if returns is not None else None,
+                                                 table.data_ptr(), self._stream())
+        if rc == nat.EUNSUPPORTED and not os.environ.get("GW_ROLLOUT_STRICT"):
+            last.copy_(prev)
+            for s in range(0, K, 64):                      # refused before anything ran: compose it from the two other calls
+                k = min(64, K - s)
+                if self._stats_buf is None:
+                    self._stats_buf = tuple(torch.empty((64, n), dtype=t, device=self.device)
+                                            for t in (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8))
+                out = tuple(b[:k] for b in self._stats_buf)
+                self.rollout_policy(cdf_t, k, seed, step0=step0 + s, env_id0=env_id0, obs_prev=last, out=out)
+                self.transition_stats(last, *out, table=table)
+                if returns is not None:
+                    returns += out[3].sum(dim=0).to(torch.int32)
+                last.copy_(out[2][k - 1])
+        else:
+            nat.check(rc)
+        self._last = (last,) + tuple(self._last[1:])
+        return table
 
     def render(self, mode='human', close=False):          # counter_traffic.py:160-162
         values = self.received()[0].tolist()

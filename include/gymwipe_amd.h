@@ -214,6 +214,36 @@ int gw_rollout_policy(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint6
                       const int32_t* obs_prev_dev, int32_t* device_out_dev, int32_t* duration_out_dev,
                       int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream);
 
+/* The table of a closed loop: everything a learner or an evaluator takes from a transition of this env is a function of the
+ * observation class the agent saw and the flat action it took. */
+#define GW_TS_COLS 7
+/* int64 table[3][A][GW_TS_COLS], row-major; cls = sign(obs_seen - counter_bound) + 1, a = device * max_duration + duration
+ *   0 n          transitions taken from (cls, a)
+ *   1 r_sum      sum of rewards (signed)          2 r_sq   sum of reward^2
+ *   3,4,5 next   transitions whose resulting observation was below / at / above counter_bound (columns 3 + 4 + 5 == column 0)
+ *   6 done       transitions whose step returned done != 0 */
+
+/* gw_rollout_policy without its five [steps][N] outputs: the env trajectory, the draws and the state changes are exactly those
+ * of gw_rollout_policy with the same arguments, and every transition is ADDED into table_dev (the caller zeroes it; calls
+ * accumulate).  obs_last_dev[e] (int32[N]) receives the env's last observation; it may be obs_prev_dev itself (an env reads its
+ * own element before it writes it), which is how a caller continues: obs in place, step0 += steps.  return_dev (int32[N], may
+ * be NULL): return_dev[e] += the env's reward sum over the call.  Allocates nothing, stream-ordered, the tables never
+ * validated.  Default mode only (ct_rollout_pstats in ct_rollout_sfx.hip, one launch per 64 steps, the tally in LDS).  A handle
+ * without that form -- explicit queues, live PHY, created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0, A > 640, a
+ * histogram of 3 * A bins that does not fit LDS beside the kernel's tables (sender counts without a kernel of their own from
+ * 12 up at max_duration 20), or any handle while GW_ROLLOUT_POLICY_UNFUSED is set -- gets GW_EUNSUPPORTED before anything is
+ * launched: call gw_rollout_policy and gw_transition_stats instead.  steps == 0 is GW_OK; a NULL pointer other than return_dev /
+ * stream, or steps < 0, is GW_EINVAL before any HIP call. */
+int gw_rollout_policy_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                            const int32_t* obs_prev_dev, int32_t* obs_last_dev, int32_t* return_dev, int64_t* table_dev, void* stream);
+
+/* The same table from recorded transitions ([steps][N] arrays as gw_rollout_policy returns them), ADDED into table_dev.  Step
+ * k's observation seen is obs_prev_dev for k = 0 and row k - 1 of obs_dev afterwards.  Every handle (it reads the configuration
+ * only).  Memory-safe for any content: a row whose action lies outside the action space is skipped (a GW_FLAG_BADACT step: the
+ * env did nothing), a reward is rounded to nearest and clamped to [-10, 10], done counts where != 0. */
+int gw_transition_stats(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev, const int32_t* duration_dev,
+                        const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev, int64_t* table_dev, void* stream);
+
 /* Cumulative number of data packets the RRM has decoded per env since gw_create: uint32[N], device pointer
  * (default mode).  A custom Interpreter (envs/core.py:59-159) differences this across a step to learn how many
  * packets of the assigned sender the RRM sniffed (networking/devices.py:163-168). */

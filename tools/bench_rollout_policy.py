@@ -7,6 +7,14 @@ Windows of K steps at N envs x D senders, a reset between windows, three forms o
   b  per-step closed loop    what a caller does without gw_rollout_policy: per step, the observation's class, a draw,
                              torch.searchsorted on the same table, the flat action split, env.step()
   c  env.rollout_policy      the draw inside the launch; with GW_ROLLOUT_POLICY_UNFUSED=1 its unfused form
+The stats leg (profiles/rollout_stats/README.md) -- the same closed loop for a caller that wants the table over (observation
+class, action), not the transitions:
+  t  rollout_policy + torch  c, then the table built with torch (bincount per column): what a caller without
+                             gw_rollout_policy_stats writes
+  r  rollout_policy + env.transition_stats   c, then the table by gw_transition_stats
+  s  env.rollout_policy_stats                the tally inside the launch, no [K][N] array at all
+Each of t, r and s must count every transition (checked once, before the timing; that they produce the same table from the
+same steps is tests/test_rollout_stats.py's business).
 Each form is timed `--repeats` times over `--windows` windows (wall clock around a device synchronize); one JSON line with the
 best, the median and the spread.  GW_TREE names the checkout whose gymwipe_amd package (and built library) is measured --
 default: this file's own -- so one job can run a and b on the parent commit's build and c on this one's; a form the measured
@@ -82,10 +90,54 @@ def main():
             env.rollout_policy(table32, K, 5, step0=s, out=out5)
             s += K
 
+    def torch_table(first, out, table):
+        d, u, obs, rew, done = out
+        seen = torch.cat([first.unsqueeze(0), obs[:-1]])
+        row = ((torch.sign(seen - center) + 1).to(torch.int64) * A + d.to(torch.int64) * md + u.to(torch.int64)).reshape(-1)
+        r = rew.reshape(-1).to(torch.int64)
+        col = (torch.sign(obs - center) + 1).reshape(-1).to(torch.int64)
+        flat = table.view(3 * A, 7)
+        flat[:, 0] += torch.bincount(row, minlength=3 * A)
+        flat[:, 1].index_add_(0, row, r)
+        flat[:, 2].index_add_(0, row, r * r)
+        flat.view(-1).index_add_(0, row * 7 + 3 + col, torch.ones_like(row))
+        flat[:, 6].index_add_(0, row, (done.reshape(-1) != 0).to(torch.int64))
+
+    stats = torch.zeros((3, A, 7), dtype=torch.int64, device=dev)
+
+    def form_t(table=stats):
+        s = 0
+        for _ in range(W):
+            first = env.reset().clone()
+            torch_table(first, env.rollout_policy(table32, K, 5, step0=s, out=out5), table)
+            s += K
+
+    def form_r(table=stats):
+        s = 0
+        for _ in range(W):
+            first = env.reset().clone()
+            env.transition_stats(first, *env.rollout_policy(table32, K, 5, step0=s, out=out5), table=table)
+            s += K
+
+    def form_s(table=stats):
+        s = 0
+        for _ in range(W):
+            env.reset()
+            env.rollout_policy_stats(table32, K, 5, step0=s, table=table)
+            s += K
+
     have_c = hasattr(nat.lib(), "gw_rollout_policy") and hasattr(env, "rollout_policy")
-    forms = {"a": form_a, "b": form_b, "c": form_c if have_c else None}
+    have_s = hasattr(nat.lib(), "gw_rollout_policy_stats") and hasattr(env, "rollout_policy_stats")
+    forms = {"a": form_a, "b": form_b, "c": form_c if have_c else None, "t": form_t if have_c else None,
+             "r": form_r if have_s else None, "s": form_s if have_s else None}
+    for f in args.forms.split(","):                            # every stats form counts every transition (the forms do not walk
+        if f in "trs" and forms[f] is not None:                #  the same steps: an env's clock and queues outlive reset())
+            check = torch.zeros_like(stats)
+            forms[f](check)
+            assert int(check[..., 0].sum()) == int(check[..., 3:6].sum()) == N * K * W, f
     res = {"label": args.label, "tree": "GW_TREE" if os.environ.get("GW_TREE") else "own", "envs": N, "devices": D, "steps": K, "windows": W,
-           "repeats": args.repeats, "unfused_switch": bool(os.environ.get("GW_ROLLOUT_POLICY_UNFUSED"))}
+           "repeats": args.repeats, "unfused_switch": bool(os.environ.get("GW_ROLLOUT_POLICY_UNFUSED")),
+           "lib": os.path.basename(os.environ.get("GW_LIB") or "")}
     for name in args.forms.split(","):
         fn = forms[name]
         if fn is None:
