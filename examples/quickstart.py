@@ -50,6 +50,12 @@ stats = venv.rollout_policy_stats(table, 64, seed=1, step0=64)          # contin
 n, r_sum = int(stats[..., 0].sum()), int(stats[..., 1].sum())
 print("rollout_policy_stats:", tuple(stats.shape), n, r_sum / n)
 
+# 3d. episodes inside the launch: an env is reset after 8 steps (or when a step returns done) and acts on the reset's
+#     observation next -- without this an env soon sits in its absorbing state, where every reward is 0.  `ended` marks the
+#     terminal steps (1 done, 2 step limit); the env keeps each env's age and return and tallies the ended episodes.
+a_dev, a_dur, o, r, d, ended = venv.rollout_episodes(table, 64, seed=1, max_steps=8, step0=128)
+print("rollout_episodes:", int((ended != 0).sum()), "episodes ended,", venv.episode_stats())
+
 
 # 4. your own Interpreter (envs/core.py:59-159), fed with what the RRM sniffed each step
 class CountDeliveries(VecInterpreter):

@@ -128,10 +128,12 @@ def policy_sample_numpy(seed, env_lo, env_hi, step, cdf, obs, counter_bound, max
 TS_COLS = 7                     # n, r_sum, r_sq, next below / at / above the bound, done
 
 
-def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center, max_duration, num_devices):
+def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center, max_duration, num_devices, ended=None):
     """CPU restatement of both entry points' table: ``int64[3][A][TS_COLS]`` over (observation class, flat action) from
     recorded transitions ``[steps][N]``.  Step k's observation seen is ``obs_prev`` for k = 0 and row k - 1 of ``obs``
-    afterwards; ``cls = sign(obs_seen - center) + 1``, ``a = device * max_duration + duration``.  Columns: transitions,
+    afterwards -- or, with ``ended`` (``[steps][N]``, what ``rollout_episodes`` records: gw_transition_stats_ep), ``center``
+    where ``ended[k - 1] != 0``: the env was reset and acted on the reset's observation.
+    ``cls = sign(obs_seen - center) + 1``, ``a = device * max_duration + duration``.  Columns: transitions,
     reward sum, reward-square sum, next observation below / at / above ``center``, ``done != 0``.  A row whose action lies
     outside the action space is skipped (the env did nothing in that step); a reward is rounded to nearest (ties to even) and
     clamped to [-10, 10], anything that is not a number counting as -10."""
@@ -144,7 +146,8 @@ def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center
     table = np.zeros((3, A, TS_COLS), np.int64)
     if steps == 0:
         return table
-    seen = np.concatenate([np.asarray(obs_prev).astype(np.int64).reshape(1, -1), nxt[:-1]])
+    after = nxt[:-1] if ended is None else np.where(np.asarray(ended)[:-1] != 0, int(center), nxt[:-1])
+    seen = np.concatenate([np.asarray(obs_prev).astype(np.int64).reshape(1, -1), after])
     with np.errstate(invalid="ignore"):
         x = np.rint(np.asarray(reward, dtype=np.float64))
         x = np.where(x >= -10.0, x, -10.0)               # (a NaN fails the comparison)
@@ -161,3 +164,26 @@ def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center
     np.add.at(flat, (row, 3 + ncl), 1)
     np.add.at(flat[:, 6], row, dn)
     return table
+
+
+# ---- episodes inside a closed loop (gw_rollout_episodes, include/gymwipe_amd.h) -------------------------------------------------
+EP_COLS = 5                     # episodes ended, of those by done, sum of lengths, sum of returns, sum of returns^2
+
+
+def episodes_numpy(state, reward, done, max_steps, on_done):
+    """The per-step bookkeeping of ``gw_rollout_episodes`` after one step of every env: ``state`` int32[N][2] ``{age, ret}``
+    is updated in place (``age += 1; ret += reward``, both back to 0 where the episode ended); returns ``(ended, tally)`` --
+    ``ended`` uint8[N]: 1 where the step returned ``done`` and ``on_done`` is set, else 2 where ``max_steps > 0`` and the
+    episode has reached ``max_steps`` steps, else 0 (done wins over the step limit); ``tally`` int64[EP_COLS]: what the ended
+    episodes add.  The caller resets the envs with ``ended != 0``; they act on the reset's observation next."""
+    assert state.dtype == np.int32 and state.ndim == 2 and state.shape[1] == 2
+    state[:, 0] += 1
+    state[:, 1] += np.asarray(reward).astype(np.int32)
+    by_done = (np.asarray(done) != 0) if on_done else np.zeros(len(state), bool)
+    by_limit = (state[:, 0] >= int(max_steps)) if int(max_steps) > 0 else np.zeros(len(state), bool)
+    ended = np.where(by_done, 1, np.where(by_limit, 2, 0)).astype(np.uint8)
+    over = ended != 0
+    age, ret = state[over, 0].astype(np.int64), state[over, 1].astype(np.int64)
+    tally = np.array([over.sum(), (ended == 1).sum(), age.sum(), ret.sum(), (ret * ret).sum()], np.int64)
+    state[over] = 0
+    return ended, tally

@@ -96,21 +96,32 @@ class DqnCounterTrafficAgent:
             qv = self.q(self._features(obs))
             return policy_cdf(torch.softmax(torch.clamp(qv / self.tau, -500.0, 500.0), dim=-1))
 
-    def collect(self, steps):
+    def collect(self, steps, episode_steps=None):
         """``steps`` env steps of all N envs under the current policy in ONE ``env.rollout_policy`` call -- observation ->
         policy -> step inside the launch -- and their transitions into the replay memory.  Returns the rollout's
-        ``(device, duration, obs, reward, done)``."""
+        ``(device, duration, obs, reward, done)``.
+        ``episode_steps``: episodes of at most that many steps, ended by ``done`` too, through ``env.rollout_episodes`` (the
+        reference's caller: keras-rl resets on done and after nb_max_episode_steps).  The memory then holds the observation
+        each step acted on -- the reset's after an episode's end -- as ``m_obs`` and the terminal observation as ``m_next``;
+        the return value gains ``ended``."""
         torch = self.torch
         steps = int(steps)
         if self.env._last[0] is None:
             self.env.reset()
         first = self.env._last[0].clone()
-        dev, dur, obs, rew, done = self.env.rollout_policy(self.policy_cdf(), steps, self.seed, step0=self.stream_pos)
+        if episode_steps is None:
+            rows = self.env.rollout_policy(self.policy_cdf(), steps, self.seed, step0=self.stream_pos)
+            after = rows[2][:-1]
+        else:
+            rows = self.env.rollout_episodes(self.policy_cdf(), steps, self.seed, max_steps=int(episode_steps), on_done=True,
+                                             step0=self.stream_pos)
+            after = torch.where(rows[5][:-1] != 0, torch.full_like(rows[2][:-1], int(self.center)), rows[2][:-1])
+        dev, dur, obs, rew, done = rows[:5]
         self.stream_pos += steps
         self.steps += steps
         keep = min(steps, self.cap // self.n)                  # (more steps than the memory holds: the last ones)
         if keep:
-            seen = torch.cat([first.unsqueeze(0), obs[:-1]])[steps - keep:]
+            seen = torch.cat([first.unsqueeze(0), after])[steps - keep:]
             flat = (dev.to(torch.int64) * self.processor.max_duration + dur.to(torch.int64))[steps - keep:]
             at = (self.m_pos + torch.arange(keep * self.n, device=self.dev)) % self.cap
             self.m_obs[at] = seen.reshape(-1).to(torch.float32)
@@ -120,7 +131,7 @@ class DqnCounterTrafficAgent:
             self.m_done[at] = done[steps - keep:].reshape(-1).to(torch.float32)
             self.m_pos = (self.m_pos + keep * self.n) % self.cap
             self.m_len = min(self.m_len + keep * self.n, self.cap)
-        return dev, dur, obs, rew, done
+        return rows
 
     def remember(self, obs, act, rew, nxt, done):
         i = self.m_pos
@@ -172,10 +183,11 @@ class TabularCounterTrafficAgent:
     (observation class, action).  ``collect`` is one launch per 64 steps and no per-env array; ``learn`` and ``evaluate`` are
     arithmetic on ``[3][A]`` tensors on the GPU.  Nothing here is sized by the number of envs."""
 
-    def __init__(self, env, gamma=0.99, tau=1.0, seed=123):
+    def __init__(self, env, gamma=0.99, tau=1.0, seed=123, episode_steps=None):
         import torch
         self.torch = torch
         self.env = env
+        self.episode_steps = None if episode_steps is None else int(episode_steps)   # episodes inside the launch (see _rollout)
         self.dev = env.device
         self.nb_actions = int(env.num_devices) * int(env.config.max_duration)
         self.gamma, self.tau = float(gamma), float(tau)
@@ -191,10 +203,16 @@ class TabularCounterTrafficAgent:
         return policy_cdf(torch.softmax(torch.clamp(self.q / self.tau, -500.0, 500.0), dim=-1))
 
     def _rollout(self, steps, table):
+        """``episode_steps`` set: ``env.rollout_episodes_stats`` -- an env is reset inside the launch on done and after that
+        many steps, so no caller-side ``env.reset()`` is needed to keep the envs out of their absorbing state."""
         steps = int(steps)
         if self.env._last[0] is None:
             self.env.reset()
-        self.env.rollout_policy_stats(self.policy_cdf(), steps, self.seed, step0=self.stream_pos, table=table)
+        if self.episode_steps is None:
+            self.env.rollout_policy_stats(self.policy_cdf(), steps, self.seed, step0=self.stream_pos, table=table)
+        else:
+            self.env.rollout_episodes_stats(self.policy_cdf(), steps, self.seed, max_steps=self.episode_steps, on_done=True,
+                                            step0=self.stream_pos, table=table)
         self.stream_pos += steps
         return table
 

@@ -531,6 +531,9 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
 //                           env just produced (PolicyActions), and stored with that step's outputs.
 //   ct_rollout_pstats       gw_rollout_policy_stats: the same draw, nothing stored per step -- the transition is counted into a
 //                           table over (observation class, action) instead (StatsActions).
+//   ct_rollout_policy_ep    gw_rollout_episodes: ct_rollout_policy with episodes -- an env whose step returned done, or whose
+//   ct_rollout_pstats_ep    episode reached its step limit, is reset in registers at the step boundary and draws its next
+//                           action from the reset's observation; gw_rollout_episodes_stats: the same with ct_rollout_pstats' tally.
 // The policy's draw (include/gymwipe_amd.h, gw_rollout_policy): the first 32 bits of the action stream's hash
 // (gymwipe_amd/actions.py) against the observation class's row of the table.
 __device__ __forceinline__ uint32_t gw_policy_u(uint64_t seed, uint64_t env_term, uint64_t step)
@@ -626,6 +629,7 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_kernel(GwState st, GwDevCo
 #define GW_ROLLOUT_SRC_CHECKED(bad) (bad)                /* a staged action may lie outside the action space (GW_FLAG_BADACT) */
 #define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
 #define GW_ROLLOUT_SRC_STEPPED(at, latest)
+#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)
 #include "ct_rollout_sync_body.h"
 #undef GW_ROLLOUT_SRC_STAGE
 #undef GW_ROLLOUT_SRC_FIRST
@@ -633,6 +637,7 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_kernel(GwState st, GwDevCo
 #undef GW_ROLLOUT_SRC_CHECKED
 #undef GW_ROLLOUT_SRC_OUTPUT
 #undef GW_ROLLOUT_SRC_STEPPED
+#undef GW_ROLLOUT_SRC_EPISODE
 }
 
 // What gw_rollout_policy passes on to the kernels below besides the outputs.
@@ -666,6 +671,7 @@ __global__ __launch_bounds__(64) void ct_rollout_policy(GwState st, GwDevConst c
 #define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
 #define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
 #define GW_ROLLOUT_SRC_STEPPED(at, latest) src.stepped(at, k, K, latest);
+#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)
 #include "ct_rollout_sync_body.h"
 #undef GW_ROLLOUT_SRC_STAGE
 #undef GW_ROLLOUT_SRC_FIRST
@@ -673,6 +679,7 @@ __global__ __launch_bounds__(64) void ct_rollout_policy(GwState st, GwDevConst c
 #undef GW_ROLLOUT_SRC_CHECKED
 #undef GW_ROLLOUT_SRC_OUTPUT
 #undef GW_ROLLOUT_SRC_STEPPED
+#undef GW_ROLLOUT_SRC_EPISODE
 }
 
 // ---- the tally: gw_rollout_policy_stats and gw_transition_stats (include/gymwipe_amd.h: int64 table[3][A][GW_TS_COLS]) --------
@@ -809,6 +816,7 @@ __global__ __launch_bounds__(64) void ct_rollout_pstats(GwState st, GwDevConst c
 #define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
 #define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) (void)at; src.stepped(k, K, latest, r, dn);
 #define GW_ROLLOUT_SRC_STEPPED(at, latest)
+#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)
 #include "ct_rollout_sync_body.h"
 #undef GW_ROLLOUT_SRC_STAGE
 #undef GW_ROLLOUT_SRC_FIRST
@@ -816,6 +824,7 @@ __global__ __launch_bounds__(64) void ct_rollout_pstats(GwState st, GwDevConst c
 #undef GW_ROLLOUT_SRC_CHECKED
 #undef GW_ROLLOUT_SRC_OUTPUT
 #undef GW_ROLLOUT_SRC_STEPPED
+#undef GW_ROLLOUT_SRC_EPISODE
     p.obs_last[e] = src.latest_last + c.counter_bound;
     if (p.ret) p.ret[e] += src.ret;
     // the wave's lanes that have an env (all 64 but in the last block) share the bins out among themselves
@@ -826,16 +835,290 @@ __global__ __launch_bounds__(64) void ct_rollout_pstats(GwState st, GwDevConst c
     gw_ts_flush(src.s_hist, 3u * src.A, threadIdx.x, lanes, p.table);
 }
 
+// ---- episodes inside the closed loop: gw_rollout_episodes / gw_rollout_episodes_stats (include/gymwipe_amd.h) --------------
+// What both calls pass on besides their parents' arguments: the caller's gw_episodes, and where the observation each env acts
+// on next goes.  obs_prev and obs_next may be one array (an env reads its element before the step loop and writes it after).
+struct GwEpisodeArgs {
+    int32_t max_steps, on_done;
+    int32_t* state;               // [N][2] {age, ret}
+    int64_t* tally;               // [GW_EP_COLS], or nullptr
+    int32_t* obs_next;            // [N]
+};
+
+// One env's episode bookkeeping over a launch: {age, ret} in registers, the episodes it ended summed per lane (a launch is at
+// most 64 steps, so the two counts fit 32 bits; lengths and returns are sums of int32 values).
+struct EpisodeBook {
+    int32_t max_steps, on_done;
+    int32_t age, ret;
+    uint32_t n, n_done;
+    int64_t len_sum, ret_sum, ret_sq;
+    __device__ __forceinline__ void load(const GwEpisodeArgs& a, uint32_t e)
+    {
+        max_steps = a.max_steps; on_done = a.on_done;
+        const int2 s = *reinterpret_cast<const int2*>(a.state + 2 * (size_t)e);
+        age = s.x; ret = s.y;
+        n = 0; n_done = 0; len_sum = 0; ret_sum = 0; ret_sq = 0;
+    }
+    // a step returned (r, dn): 0 the episode goes on, 1 it ended by done, 2 by the step limit (done wins)
+    __device__ __forceinline__ uint32_t stepped(int32_t r, uint32_t dn)
+    {
+        age += 1; ret += r;
+        const uint32_t cause = (on_done != 0 && dn != 0u) ? 1u : ((max_steps > 0 && age >= max_steps) ? 2u : 0u);
+        if (cause) {
+            n += 1u; n_done += cause == 1u ? 1u : 0u;
+            len_sum += age; ret_sum += ret; ret_sq += (int64_t)ret * (int64_t)ret;
+            age = 0; ret = 0;
+        }
+        return cause;
+    }
+    // {age, ret} back, and the lane's episodes into the block's tally in LDS
+    __device__ __forceinline__ void store(const GwEpisodeArgs& a, uint32_t e, unsigned long long* s_ep) const
+    {
+        *reinterpret_cast<int2*>(a.state + 2 * (size_t)e) = make_int2(age, ret);
+        if (!a.tally || !n) return;
+        const unsigned long long v[GW_EP_COLS] = {n, n_done, (unsigned long long)len_sum, (unsigned long long)ret_sum,
+                                                  (unsigned long long)ret_sq};
+#pragma unroll
+        for (int j = 0; j < GW_EP_COLS; ++j)
+            if (v[j]) __hip_atomic_fetch_add(s_ep + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+};
+// The block is one wave (as in ct_rollout_pstats): its LDS adds and the flush's reads are operations of the same wave, kept in
+// order by the hardware; the fences keep the compiler from moving them.  Then GW_EP_COLS global adds per block at most.
+__device__ __forceinline__ void gw_wave_lds_order()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ void gw_ep_flush(const unsigned long long* s_ep, uint32_t first, uint32_t stride, int64_t* tally)
+{
+    if (!tally) return;
+    for (uint32_t j = first; j < (uint32_t)GW_EP_COLS; j += stride)
+        if (s_ep[j]) gw_ts_add(tally + j, s_ep[j]);
+}
+
+// the `ip` record of an env that may have been reset in the launch (the body's bpc / bpp), behind the body
+#define GW_ROLLOUT_STORE_IP st_plain(st.ip, o16, make_uint4(bpc.t0, bpc.c0, bpp.t0, bpp.c0));
+
+// ct_rollout_policy's source without its __restrict__ on obs_prev (it may be obs_next), and with the episode's book: the draw
+// after a step that ended an episode is for the reset's observation, counter_bound (class 1).
+struct EpisodeActions {
+    const uint32_t* __restrict__ cdf;
+    int32_t* device_out;
+    int32_t* duration_out;
+    uint8_t* ended;
+    uint64_t seed, step0, env0;
+    uint32_t* s_cdf;
+    uint32_t A, md, inv20;
+    uint64_t env_term;
+    int d_cur, du_cur;
+    int32_t latest_next;                                 // what the env acts on next, minus counter_bound
+    EpisodeBook ep;
+    __device__ __forceinline__ void stage(unsigned long long* s_ep) const
+    {
+        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
+        if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
+    }
+    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
+    {
+        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
+        const uint32_t dv = (a * inv20) >> 20;           // (exact: PolicyActions::draw)
+        d_cur = (int)dv;
+        du_cur = (int)(a - dv * md);
+    }
+    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen, int32_t center)
+    {
+        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;
+        latest_next = obs_seen - center;
+        draw(gw_policy_cls(obs_seen, center), step0);
+    }
+    __device__ __forceinline__ void stepped(size_t at, int k, int K, int32_t latest, uint32_t cause)
+    {
+        device_out[at] = d_cur;
+        duration_out[at] = du_cur;
+        ended[at] = (uint8_t)cause;
+        latest_next = cause ? 0 : latest;
+        if (k + 1 < K) draw((uint32_t)((int)(latest_next > 0) - (int)(latest_next < 0) + 1), step0 + (uint64_t)(k + 1));
+    }
+};
+
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_policy_ep(GwState st, GwDevConst c, int K, GwPolicyArgs p, GwEpisodeArgs ea,
+                                                          int32_t* device_out, int32_t* duration_out, int32_t* obs, float* reward,
+                                                          uint8_t* done, uint8_t* ended)
+{
+    extern __shared__ uint32_t s_policy_cdf[];
+    __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
+    EpisodeActions src;
+    src.cdf = p.cdf; src.device_out = device_out; src.duration_out = duration_out; src.ended = ended;
+    src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
+    src.s_cdf = s_policy_cdf;
+    src.md = (uint32_t)c.max_duration;
+    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
+    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
+    src.env_term = 0; src.d_cur = 0; src.du_cur = 0; src.latest_next = 0;
+#define GW_ROLLOUT_SRC_RESETS
+#define GW_ROLLOUT_SRC_STAGE src.stage(s_ep_tally);
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.first(e, p.obs_prev[e], c.counter_bound);
+#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
+#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
+#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest)
+#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)                                                                                \
+    {                                                                                                                            \
+        const uint32_t cause_next = src.ep.stepped(r, dn);                                                                       \
+        if (cause_next) reset_env();                                                                                             \
+        src.stepped(at, k, K, latest, cause_next);                                                                               \
+    }
+#include "ct_rollout_sync_body.h"
+#undef GW_ROLLOUT_SRC_RESETS
+#undef GW_ROLLOUT_SRC_STAGE
+#undef GW_ROLLOUT_SRC_FIRST
+#undef GW_ROLLOUT_SRC_TAKE
+#undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_OUTPUT
+#undef GW_ROLLOUT_SRC_STEPPED
+#undef GW_ROLLOUT_SRC_EPISODE
+    GW_ROLLOUT_STORE_IP
+    ea.obs_next[e] = src.latest_next + c.counter_bound;
+    src.ep.store(ea, e, s_ep_tally);
+    gw_wave_lds_order();
+    gw_ep_flush(s_ep_tally, threadIdx.x, gw_min_u32(64u, N - blockIdx.x * 64u), ea.tally);
+}
+
+// ct_rollout_pstats' source with the episode's book.  A transition is counted under the class the env acted on (the reset's
+// observation after an episode's end), with the next observation and done the step returned.
+struct EpisodeStatsActions {
+    const uint32_t* __restrict__ cdf;
+    uint64_t seed, step0, env0;
+    uint64_t* s_hist;
+    uint32_t* s_cdf;
+    uint32_t A, md, inv20;
+    uint64_t env_term;
+    uint32_t bin_cur;
+    int d_cur, du_cur;
+    int32_t latest_next;
+    EpisodeBook ep;
+    __device__ __forceinline__ void stage(unsigned long long* s_ep) const
+    {
+        for (uint32_t i = threadIdx.x; i < 6u * A; i += blockDim.x) s_hist[i] = 0u;
+        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
+        if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
+    }
+    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
+    {
+        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
+        const uint32_t dv = (a * inv20) >> 20;           // (exact: PolicyActions::draw)
+        bin_cur = cls * A + a;
+        d_cur = (int)dv;
+        du_cur = (int)(a - dv * md);
+    }
+    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen, int32_t center)
+    {
+        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;
+        latest_next = obs_seen - center;
+        draw(gw_policy_cls(obs_seen, center), step0);
+    }
+    __device__ __forceinline__ void stepped(int k, int K, int32_t latest, int32_t r, uint32_t dn, uint32_t cause)
+    {
+        gw_ts_count(s_hist, bin_cur, (uint32_t)((int)(latest > 0) - (int)(latest < 0) + 1), r, dn);
+        latest_next = cause ? 0 : latest;
+        if (k + 1 < K) draw((uint32_t)((int)(latest_next > 0) - (int)(latest_next < 0) + 1), step0 + (uint64_t)(k + 1));
+    }
+};
+
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_pstats_ep(GwState st, GwDevConst c, int K, GwPolicyArgs p, GwEpisodeArgs ea, int64_t* table)
+{
+    extern __shared__ uint64_t s_stats_dyn[];
+    __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
+    EpisodeStatsActions src;
+    src.cdf = p.cdf; src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
+    src.md = (uint32_t)c.max_duration;
+    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
+    src.s_hist = s_stats_dyn;
+    src.s_cdf = reinterpret_cast<uint32_t*>(s_stats_dyn + 6u * src.A);
+    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
+    src.env_term = 0; src.bin_cur = 0; src.d_cur = 0; src.du_cur = 0; src.latest_next = 0;
+#define GW_ROLLOUT_SRC_RESETS
+#define GW_ROLLOUT_SRC_STAGE src.stage(s_ep_tally);
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.first(e, p.obs_prev[e], c.counter_bound);
+#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
+#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
+#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) (void)at;
+#define GW_ROLLOUT_SRC_STEPPED(at, latest)
+#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)                                                                                \
+    {                                                                                                                            \
+        const uint32_t dn_step = dn, cause_next = src.ep.stepped(r, dn_step);                                                    \
+        if (cause_next) reset_env();                                                                                             \
+        src.stepped(k, K, latest, r, dn_step, cause_next);                                                                       \
+    }
+#include "ct_rollout_sync_body.h"
+#undef GW_ROLLOUT_SRC_RESETS
+#undef GW_ROLLOUT_SRC_STAGE
+#undef GW_ROLLOUT_SRC_FIRST
+#undef GW_ROLLOUT_SRC_TAKE
+#undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_OUTPUT
+#undef GW_ROLLOUT_SRC_STEPPED
+#undef GW_ROLLOUT_SRC_EPISODE
+    GW_ROLLOUT_STORE_IP
+    ea.obs_next[e] = src.latest_next + c.counter_bound;
+    src.ep.store(ea, e, s_ep_tally);
+    // the wave's lanes that have an env (all 64 but in the last block) share the bins out among themselves
+    const uint32_t lanes = gw_min_u32(64u, N - blockIdx.x * 64u);
+    gw_wave_lds_order();
+    gw_ep_flush(s_ep_tally, threadIdx.x, lanes, ea.tally);
+    gw_ts_flush(src.s_hist, 3u * src.A, threadIdx.x, lanes, table);
+}
+
+// The per-step form's bookkeeping, for handles without the fused kernels: after a step's launch, steps 1-4 and 6 of the
+// semantics for every env -- {age, ret}, ended, the tally, the observation acted on next -- and the mask gw_reset's launch takes.
+__global__ __launch_bounds__(256) void episodes_step_kernel(uint32_t N, int32_t center, GwEpisodeArgs ea, const int32_t* obs,
+                                                           const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask)
+{
+    __shared__ unsigned long long s_ep[GW_EP_COLS];
+    if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < N) {
+        int2 s = *reinterpret_cast<const int2*>(ea.state + 2 * (size_t)e);
+        const int32_t r = (int32_t)reward[e];
+        s.x += 1; s.y += r;
+        const uint32_t cause = (ea.on_done != 0 && done[e] != 0) ? 1u : ((ea.max_steps > 0 && s.x >= ea.max_steps) ? 2u : 0u);
+        if (cause) {
+            if (ea.tally) {
+                const unsigned long long v[GW_EP_COLS] = {1ull, cause == 1u ? 1ull : 0ull, (unsigned long long)(int64_t)s.x,
+                                                          (unsigned long long)(int64_t)s.y,
+                                                          (unsigned long long)((int64_t)s.y * (int64_t)s.y)};
+#pragma unroll
+                for (int j = 0; j < GW_EP_COLS; ++j)
+                    if (v[j]) __hip_atomic_fetch_add(s_ep + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            s.x = 0; s.y = 0;
+        }
+        *reinterpret_cast<int2*>(ea.state + 2 * (size_t)e) = s;
+        ended[e] = (uint8_t)cause;
+        mask[e] = (uint8_t)(cause != 0u);
+        ea.obs_next[e] = cause ? center : obs[e];
+    }
+    __syncthreads();
+    if (ea.tally && threadIdx.x < (uint32_t)GW_EP_COLS && s_ep[threadIdx.x]) gw_ts_add(ea.tally + threadIdx.x, s_ep[threadIdx.x]);
+}
+
 // gw_transition_stats: the same table from recorded [K][N] transitions.  A block takes tiles of TS_EVENTS consecutive
 // elements (the histogram's bit budget), 16 per thread, and flushes after each.  Any content is safe: a row whose action lies
 // outside the action space is skipped, a reward is rounded to nearest and clamped (NaN counts as -10), done is != 0.
 // LDS = false (a histogram of 3 * A bins would not fit): every row's seven columns straight into the table.
-template <bool LDS>
+// EP (gw_transition_stats_ep): rows recorded by gw_rollout_episodes -- where ended[k - 1] != 0 step k acted on the reset's
+// observation, counter_bound.
+template <bool LDS, bool EP>
 __global__ __launch_bounds__(256) void transition_stats_rows(uint64_t total, uint32_t N, uint32_t D, uint32_t md, int32_t center,
                                                             const int32_t* __restrict__ obs_prev, const int32_t* __restrict__ device,
                                                             const int32_t* __restrict__ duration, const int32_t* __restrict__ obs,
                                                             const float* __restrict__ reward, const uint8_t* __restrict__ done,
-                                                            int64_t* __restrict__ table)
+                                                            const uint8_t* __restrict__ ended, int64_t* __restrict__ table)
 {
     extern __shared__ uint64_t s_stats_dyn[];
     const uint64_t A = (uint64_t)D * md;
@@ -851,7 +1134,8 @@ __global__ __launch_bounds__(256) void transition_stats_rows(uint64_t total, uin
             if (i >= total) break;
             const uint32_t dv = (uint32_t)device[i], du = (uint32_t)duration[i];
             if (dv >= D || du >= md) continue;                                  // a GW_FLAG_BADACT step: the env did nothing
-            const int32_t seen = i < N ? obs_prev[i] : obs[i - N];              // row k - 1 of obs, same env
+            int32_t seen = i < N ? obs_prev[i] : obs[i - N];                    // row k - 1 of obs, same env
+            if constexpr (EP) seen = (i >= N && ended[i - N] != 0) ? center : seen;
             const float x = rintf(reward[i]);
             const int32_t r = (int32_t)(x >= (float)-TS_RMAX ? (x <= (float)TS_RMAX ? x : (float)TS_RMAX) : (float)-TS_RMAX);
             const uint32_t next_cls = gw_policy_cls(obs[i], center), dn = done[i];
@@ -947,19 +1231,82 @@ int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, int K
 
 int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
                                const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
-                               const uint8_t* done, int64_t* table, void* stream)
+                               const uint8_t* done, const uint8_t* ended, int64_t* table, void* stream)
 {
     const uint64_t total = (uint64_t)N * (uint64_t)K, tiles = (total + TS_EVENTS - 1u) / TS_EVENTS;
     if (total == 0u) return GW_OK;
     const uint64_t A = (uint64_t)D * (uint64_t)max_duration;
     const size_t dyn = (size_t)(3u * A) * TS_BIN_BYTES;
     const unsigned grid = (unsigned)(tiles < 4096u ? tiles : 4096u);
-    if (dyn <= GW_LDS_PER_BLOCK / 2)
-        hipLaunchKernelGGL(transition_stats_rows<true>, dim3(grid), dim3(256), dyn, (hipStream_t)stream, total, (uint32_t)N, (uint32_t)D,
-                           (uint32_t)max_duration, counter_bound, obs_prev, device, duration, obs, reward, done, table);
-    else
-        hipLaunchKernelGGL(transition_stats_rows<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, total, (uint32_t)N, (uint32_t)D,
-                           (uint32_t)max_duration, counter_bound, obs_prev, device, duration, obs, reward, done, table);
+    const bool lds = dyn <= GW_LDS_PER_BLOCK / 2;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds ? dyn : 0, (hipStream_t)stream, total, (uint32_t)N, (uint32_t)D,
+                           (uint32_t)max_duration, counter_bound, obs_prev, device, duration, obs, reward, done, ended, table);
+    };
+    if (ended) { if (lds) launch(transition_stats_rows<true, true>); else launch(transition_stats_rows<false, true>); }
+    else       { if (lds) launch(transition_stats_rows<true, false>); else launch(transition_stats_rows<false, false>); }
+    return gw_launch_status();
+}
+
+// The fused forms of gw_rollout_episodes / gw_rollout_episodes_stats: their parents' launchers and availability rules, with
+// the caller's gw_episodes and obs_next passed on.
+int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
+                                    uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
+                                    int32_t* device_out, int32_t* duration_out, int32_t* obs, float* reward, uint8_t* done,
+                                    uint8_t* ended, void* stream, bool below_limits, uint64_t* rec)
+{
+    const int64_t A = (int64_t)st.D * cst.max_duration;
+    if (K <= 0 || K > st.rcap || st.ract != nullptr || A > GW_POLICY_A_MAX) return GW_EUNSUPPORTED;
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    const int mode = gw_step_mode(cst, below_limits, false);
+    const GwPolicyArgs p = {cdf, obs_prev, seed, step0, env_id0};
+    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
+    gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
+        gw_with_mode(mode, [&](auto m) {
+            gw_note_launch(rec, GW_LS_ROLLOUT_POLICY_EP + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
+            hipLaunchKernelGGL((ct_rollout_policy_ep<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64),
+                               (size_t)(3 * A) * sizeof(uint32_t), (hipStream_t)stream, st, cst, K, p, ea, device_out, duration_out, obs,
+                               reward, done, ended);
+        });
+    });
+    return gw_launch_status();
+}
+
+int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
+                                    uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
+                                    int64_t* table, void* stream, bool below_limits, uint64_t* rec)
+{
+    const int64_t A = (int64_t)st.D * cst.max_duration;
+    if (K <= 0 || K > st.rcap || K > (int)TS_STEPS || st.ract != nullptr || A > GW_POLICY_A_MAX) return GW_EUNSUPPORTED;
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    const int mode = gw_step_mode(cst, below_limits, false);
+    const GwPolicyArgs p = {cdf, obs_prev, seed, step0, env_id0};
+    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
+    const size_t dyn = (size_t)(3 * A) * (TS_BIN_BYTES + sizeof(uint32_t));
+    return gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
+        return gw_with_mode(mode, [&](auto m) {
+            constexpr int DT = decltype(dt)::value, MODE = decltype(m)::value;
+            static const int fixed = [] {                // the instantiation's own LDS (asked once; the same on every device)
+                hipFuncAttributes fa;
+                return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&ct_rollout_pstats_ep<DT, MODE>)) == hipSuccess
+                           ? (int)fa.sharedSizeBytes : -1;
+            }();
+            if (fixed < 0) return gw_launch_status(hipErrorInvalidDeviceFunction);
+            if ((size_t)fixed + dyn > GW_LDS_PER_BLOCK) return (int)GW_EUNSUPPORTED;
+            gw_note_launch(rec, GW_LS_ROLLOUT_PSTATS_EP + 3 * gw_ls_dt(DT) + MODE);
+            hipLaunchKernelGGL((ct_rollout_pstats_ep<DT, MODE>), dim3(grid), dim3(64), dyn, (hipStream_t)stream, st, cst, K, p, ea, table);
+            return gw_launch_status();
+        });
+    });
+}
+
+// One step's episode bookkeeping of gw_rollout_episodes' per-step form (every queue mode): row `step`'s ended, the mask.
+int gw_launch_episodes_step(int64_t N, int counter_bound, const gw_episodes& ep, int32_t* obs_next, const int32_t* obs,
+                            const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask, void* stream)
+{
+    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
+    hipLaunchKernelGGL(episodes_step_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
+                       counter_bound, ea, obs, reward, done, ended, mask);
     return gw_launch_status();
 }
 

@@ -1,6 +1,7 @@
 // ct_rollout_sync_body.h -- the body of the step-synchronous rollout kernels (ct_rollout_sfx.hip), included once per kernel:
-// ct_rollout_sync_kernel (actions staged by the caller), ct_rollout_policy (actions drawn in the kernel) and ct_rollout_pstats
-// (drawn in the kernel, the transitions tallied instead of stored).  It is text
+// ct_rollout_sync_kernel (actions staged by the caller), ct_rollout_policy (actions drawn in the kernel), ct_rollout_pstats
+// (drawn in the kernel, the transitions tallied instead of stored) and their episodic forms ct_rollout_policy_ep /
+// ct_rollout_pstats_ep (an env that ends an episode is reset inside the launch).  It is text
 // with macro hooks, not a function, on purpose.  As a __forceinline__ template over an action-source type the compiler
 // optimised the callee on its own before inlining it, and all 30 instantiations of ct_rollout_sync_kernel came out different
 // (up to 31 more VGPRs at D = 16 and 32, SGPRs parked in VGPR lanes at D = 4); with the source as an object whose members hold
@@ -15,6 +16,10 @@
 //                                   kernel wants it: GW_ROLLOUT_STORE_OUTPUTS, the three stores into the kernel's obs, reward
 //                                   and done, or a tally
 //   GW_ROLLOUT_SRC_STEPPED(at, latest)   statements when step k is over (outputs at index `at`; k not yet advanced)
+//   GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)   the last statements of step k: empty, or the episodic kernels' bookkeeping
+//                                   (ended[at], the next draw).  An includer that defines GW_ROLLOUT_SRC_RESETS may call
+//                                   reset_env() here: gw_reset for this one env, in registers (see there).  Such a kernel
+//                                   stores the env's `ip` record behind the body (GW_ROLLOUT_STORE_IP), which no other does.
 // The hooks share the body's scope.  Of its names they read only e, N, k, K and c, and they define only d and du; whatever else a
 // source keeps lives in names the body leaves free: `src` and anything ending in `_next`.  A new local of the body takes
 // neither form.
@@ -77,7 +82,7 @@
     }
     double now = tw.x, wake = tw.y;
     uint32_t tau = tk.x;
-    const uint32_t nbp = tk.y;
+    uint32_t nbp = tk.y;                                 // (changes only where an includer resets: reset_env below)
     GwBp bpc, bpp;
     bpc.t0 = ip.x; bpc.c0 = ip.y;
     bpp.t0 = ip.z; bpp.c0 = ip.w;
@@ -112,10 +117,36 @@
     uint32_t k_bad = 0, fl = 0;
     int k = 0;
     GW_ROLLOUT_SRC_FIRST                                        // step 0's action
+#ifdef GW_ROLLOUT_SRC_RESETS
+    // gw_reset for this env between step k and step k + 1, on the registers (ct_reset_sfx_kernel, ct_step_sfx.hip): counters to 0
+    // from the current tick, the interpreter cleared, the clock not rewound.  That kernel takes tau as current, so the ticks
+    // up to `now` are counted first, as the tail below counts them (its GW_FLAG_TIE rule included); the queues stay lazy -- a
+    // reset leaves the queued packets alone and changes only the tick -> counter-value map, and tb[] still says how far each
+    // length has been brought.  The ring slot written here may be read back by this lane in a later step (gw_tick_value's
+    // deep path, through `hist`): both go through st.bph with plain accesses, so the compiler orders them.
+    auto reset_env = [&]() {
+        uint32_t kk = 0;
+        while (wake <= now) { if (wake == now) fl |= GW_FLAG_TIE; wake = wake + interval; kk++; }
+        tau += kk;
+        GwBp* ring = st.bph + ((size_t)e << 7);
+        GwBp cur; cur.t0 = bpc.t0; cur.c0 = 0u;
+        if (bpc.t0 == tau) {                                    // no tick since the newest breakpoint: overwrite it
+            ring[(nbp - 1u) & GW_RING_MASK] = cur;
+        } else {                                                // the newest becomes the second newest
+            bpp = bpc;
+            cur.t0 = tau;
+            ring[nbp & GW_RING_MASK] = cur;
+            nbp += 1u;
+        }
+        bpc = cur;
+        rvm = 0u; last_abs = 0; dn = 0u;                        // interpreter.reset(): receivedValues, lastAbs, done
+    };
+#endif
     auto put_feedback = [&](int32_t latest, int32_t r) {
         const size_t at = (size_t)k * N + e;
         GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn)
         GW_ROLLOUT_SRC_STEPPED(at, latest)
+        GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)
         k++;
     };
 

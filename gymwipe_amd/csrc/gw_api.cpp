@@ -75,6 +75,7 @@ struct gw_env {
     int          no_split;    // GW_NO_SPLIT at gw_create: the generic kernel's one-wave form at block 64
     uint64_t     launches[GW_LS_COUNT];   // kernel instantiations launched by this handle (gw_selftest_launches)
     GwSfxFns     fns;         // default mode: this handle's step / reset kernels on its device, resolved at gw_create
+    uint8_t*     ep_mask;     // [N] gw_rollout_episodes' per-step form: the envs to reset after the step (scratch, not state)
 };
 
 namespace {
@@ -587,6 +588,7 @@ int gw_create(const gw_config* cfg, gw_env** out)
     env->cfg = *cfg;
     if ((rc = create_host_side(env)) || (rc = create_alloc(env)) || (rc = create_upload(env)) || (rc = create_init(env))) return rc;
     env->nblocks_create = env->nblocks;
+    if ((rc = dev_alloc(env, &env->ep_mask, (size_t)cfg->num_envs))) return rc;   // (scratch: behind the snapshot's blocks)
     guard.env = nullptr;
     *out = env;
     return GW_OK;
@@ -746,7 +748,104 @@ int gw_transition_stats(gw_env* env, int32_t steps, const int32_t* obs_prev_dev,
     int rc = select_device(env);
     if (rc) return rc;
     if (gw_launch_transition_stats(env->st.N, steps, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, obs_prev_dev,
-                                   device_dev, duration_dev, obs_dev, reward_dev, done_dev, table_dev, stream))
+                                   device_dev, duration_dev, obs_dev, reward_dev, done_dev, nullptr, table_dev, stream))
+        return fail(GW_EHIP, "transition statistics kernel launch failed");
+    return GW_OK;
+}
+
+static int check_episodes(const gw_episodes* ep, const char* who)
+{
+    if (!ep || !ep->state_dev) return fail(GW_EINVAL, "%s: NULL device pointer", who);
+    if (ep->max_steps < 0) return fail(GW_EINVAL, "%s: max_steps < 0", who);
+    return GW_OK;
+}
+
+int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                        const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                        int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
+                        uint8_t* done_dev, uint8_t* ended_dev, void* stream)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!cdf_dev || !obs_prev_dev || !obs_next_dev || !device_out_dev || !duration_out_dev || !obs_dev || !reward_dev || !done_dev ||
+        !ended_dev)
+        return fail(GW_EINVAL, "gw_rollout_episodes: NULL device pointer");
+    int rc = check_episodes(ep, "gw_rollout_episodes");
+    if (rc) return rc;
+    if (steps == 0) return GW_OK;
+    if ((rc = select_device(env))) return rc;
+    const int64_t N = env->st.N;
+    // step s acts on what obs_next_dev holds after step s - 1 (the caller's obs_prev_dev for the call's first step)
+    auto seen_before = [&](int32_t s) { return s ? (const int32_t*)obs_next_dev : obs_prev_dev; };
+    int32_t s = 0;
+    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (A/B switch: every step through the per-step form)
+        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
+            const int64_t o = (int64_t)s0 * N;
+            return gw_launch_rollout_policy_ep_sfx(env->st, env->cst_host, chunk, cdf_dev, seed, step0 + (uint64_t)s0, env_id0, *ep,
+                                                   seen_before(s0), obs_next_dev, device_out_dev + o, duration_out_dev + o,
+                                                   obs_dev + o, reward_dev + o, done_dev + o, ended_dev + o, stream, below,
+                                                   env->launches);
+        });
+        if (rc) return rc;
+    }
+    if (s < steps && getenv("GW_ROLLOUT_STRICT"))
+        return fail(GW_EUNSUPPORTED, "no fused episodic rollout for this handle (GW_ROLLOUT_STRICT is set)");
+    for (; s < steps; ++s) {                                   // every other handle: draw, step, bookkeeping, masked reset
+        const int64_t o = (int64_t)s * N;
+        if (gw_launch_policy_sample(N, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, cdf_dev, seed,
+                                    step0 + (uint64_t)s, env_id0, seen_before(s), device_out_dev + o, duration_out_dev + o, stream))
+            return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
+        if (launch_step(env, device_out_dev + o, duration_out_dev + o, obs_dev + o, reward_dev + o, done_dev + o, stream))
+            return fail(GW_EHIP, "step kernel launch failed at step %d", s);
+        gw_env_add_steps(env, 1);
+        if (gw_launch_episodes_step(N, env->cst_host.counter_bound, *ep, obs_next_dev, obs_dev + o, reward_dev + o, done_dev + o,
+                                    ended_dev + o, env->ep_mask, stream))
+            return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
+        if ((rc = gw_reset(env, env->ep_mask, nullptr, stream))) return rc;
+    }
+    return GW_OK;
+}
+
+int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                              const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                              int64_t* table_dev, void* stream)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!cdf_dev || !obs_prev_dev || !obs_next_dev || !table_dev)
+        return fail(GW_EINVAL, "gw_rollout_episodes_stats: NULL device pointer");
+    int rc = check_episodes(ep, "gw_rollout_episodes_stats");
+    if (rc) return rc;
+    if (steps == 0) return GW_OK;
+    if ((rc = select_device(env))) return rc;
+    int32_t s = 0;
+    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (the A/B switch leaves no fused form: the caller composes)
+        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
+            return gw_launch_rollout_pstats_ep_sfx(env->st, env->cst_host, chunk, cdf_dev, seed, step0 + (uint64_t)s0, env_id0, *ep,
+                                                   s0 ? (const int32_t*)obs_next_dev : obs_prev_dev, obs_next_dev, table_dev, stream,
+                                                   below, env->launches);
+        }, GW_TS_STEPS);
+        if (rc) return rc;
+    }
+    // (what keeps a handle from the fused form does not depend on the chunk: s is 0 here, nothing was launched)
+    if (s < steps)
+        return fail(GW_EUNSUPPORTED, "no fused episodic rollout for this handle: gw_rollout_episodes, then gw_transition_stats_ep");
+    return GW_OK;
+}
+
+int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev,
+                           const int32_t* duration_dev, const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                           const uint8_t* ended_dev, int64_t* table_dev, void* stream)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!obs_prev_dev || !device_dev || !duration_dev || !obs_dev || !reward_dev || !done_dev || !ended_dev || !table_dev)
+        return fail(GW_EINVAL, "gw_transition_stats_ep: NULL device pointer");
+    if (steps == 0) return GW_OK;
+    int rc = select_device(env);
+    if (rc) return rc;
+    if (gw_launch_transition_stats(env->st.N, steps, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, obs_prev_dev,
+                                   device_dev, duration_dev, obs_dev, reward_dev, done_dev, ended_dev, table_dev, stream))
         return fail(GW_EHIP, "transition statistics kernel launch failed");
     return GW_OK;
 }
@@ -1017,8 +1116,9 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        const int i = slot - GW_LS_ROLLOUT_PSTATS;
-        snprintf(out, cap, "ct_rollout_pstats<%d, %d>", dts[i / 3], i % 3);
+        static const char* const fam[3] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep"};
+        const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
+        snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }
 }
 

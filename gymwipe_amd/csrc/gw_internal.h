@@ -314,7 +314,19 @@ int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, int K
                                  void* stream, bool below_limits, uint64_t* rec);
 int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
                                const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
-                               const uint8_t* done, int64_t* table, void* stream);
+                               const uint8_t* done, const uint8_t* ended, int64_t* table, void* stream);   // ended: nullptr, or
+                                                                                    // gw_transition_stats_ep's rows
+// gw_rollout_episodes / gw_rollout_episodes_stats (ct_rollout_sfx.hip): the fused forms, and one step's bookkeeping of the
+// per-step form (ended, the handle's reset mask, obs_next)
+int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
+                                    uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
+                                    int32_t* device_out, int32_t* duration_out, int32_t* obs, float* reward, uint8_t* done,
+                                    uint8_t* ended, void* stream, bool below_limits, uint64_t* rec);
+int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
+                                    uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
+                                    int64_t* table, void* stream, bool below_limits, uint64_t* rec);
+int gw_launch_episodes_step(int64_t N, int counter_bound, const gw_episodes& ep, int32_t* obs_next, const int32_t* obs,
+                            const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask, void* stream);
 int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const uint32_t* cdf, uint64_t seed, uint64_t step,
                             uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, void* stream);
 int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream);
@@ -339,7 +351,7 @@ int gw_launch_unpack_feedback(int64_t count, int center, int pv, const uint8_t* 
 // Sender counts with a kernel instantiation of their own (template parameter DT; every other count runs DT = 0), one list
 // per kernel family.  Each family's launcher dispatches over its list (gw_dispatch.h) and nothing else restates it.
 #define GW_DTS_STEP          2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_step_sfx_kernel
-#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats
+#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats, their _ep forms
 #define GW_DTS_ROLLOUT_LOOP  2, 3, 4, 6, 8, 16, 32          // ct_rollout_sfx_kernel (event loop)
 #define GW_DTS_LIVE          2, 3, 4, 6, 8, 16, 32          // ct_step_live_kernel
 #define GW_DTS_GENERIC       2, 3, 4, 8, 16                 // ct_step_kernel on the table PHY
@@ -360,7 +372,9 @@ enum {
     GW_LS_LIVE = GW_LS_GENERIC + 8 * GW_LS_NDT,            // ct_step_live_kernel<DT, PER_ENV>: 2 per DT
     GW_LS_ROLLOUT_POLICY = GW_LS_LIVE + 2 * GW_LS_NDT,     // ct_rollout_policy<DT, MODE>: 3 per DT (appended: the slots above keep
     GW_LS_ROLLOUT_PSTATS = GW_LS_ROLLOUT_POLICY + 3 * GW_LS_NDT,   // ct_rollout_pstats<DT, MODE>: 3 per DT    their numbers)
-    GW_LS_COUNT = GW_LS_ROLLOUT_PSTATS + 3 * GW_LS_NDT
+    GW_LS_ROLLOUT_POLICY_EP = GW_LS_ROLLOUT_PSTATS + 3 * GW_LS_NDT,      // ct_rollout_policy_ep<DT, MODE>: 3 per DT
+    GW_LS_ROLLOUT_PSTATS_EP = GW_LS_ROLLOUT_POLICY_EP + 3 * GW_LS_NDT,   // ct_rollout_pstats_ep<DT, MODE>: 3 per DT
+    GW_LS_COUNT = GW_LS_ROLLOUT_PSTATS_EP + 3 * GW_LS_NDT
 };
 constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {

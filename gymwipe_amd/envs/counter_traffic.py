@@ -199,6 +199,8 @@ class VecCounterTrafficEnv(BaseEnv):
         self._last = (None, None, None)
         self._stats_last = None                           # rollout_policy_stats: the last observations, and the fallback's
         self._stats_buf = None                            # 64-step transition buffers (both allocated on first use)
+        self._ep_state = self._ep_tally = self._ep_next = None   # rollout_episodes: {age, ret}[N], the episode tally, the
+        self._ep_buf = None                               # observations acted on next; the fallback's ended rows (first use)
         self._custom = interpreter
         if interpreter is not None:                       # a user-supplied Interpreter replaces the fused one
             if explicit_queue:
@@ -269,6 +271,11 @@ class VecCounterTrafficEnv(BaseEnv):
         if self._custom is not None:                      # counter_traffic.py:142-144
             self._custom.reset()
             return self._custom.getObservation()
+        if self._ep_state is not None:                    # rollout_episodes' {age, ret}: a reset env starts a new episode
+            if m is None:
+                self._ep_state.zero_()
+            else:
+                self._ep_state.masked_fill_(m.bool().unsqueeze(1), 0)
         self._last = (obs,) + tuple(self._last[1:])       # the observation the agent acts on next (rollout_policy)
         return obs
 
@@ -490,22 +497,26 @@ class VecCounterTrafficEnv(BaseEnv):
             raise ValueError("table must be a contiguous int64 tensor of shape %s on %s" % (shape, self.device))
         return table
 
-    def transition_stats(self, obs_prev, device, duration, obs, reward, done, table=None):
+    def transition_stats(self, obs_prev, device, duration, obs, reward, done, table=None, ended=None):
         """Recorded transitions ``[steps][N]`` (what ``rollout_policy`` returns; ``obs_prev`` int32[N] is what step 0 acted on)
         added into ``table`` (gw_transition_stats; ``actions.transition_stats_numpy`` restates it): ``int64[3][A][7]`` over
-        (observation class, flat action).  Returns the table (a new one of zeros when none is passed)."""
+        (observation class, flat action).  Returns the table (a new one of zeros when none is passed).
+        ``ended`` (uint8[steps][N], what ``rollout_episodes`` returns; gw_transition_stats_ep): an env whose step k - 1 ended
+        an episode acted on the reset's observation at step k."""
         torch = _torch()
         table = self._stats_table(table)
         K, n = int(obs.shape[0]), self.num_envs
         args = []
-        for t, dt in ((obs_prev, torch.int32), (device, torch.int32), (duration, torch.int32), (obs, torch.int32),
-                      (reward, torch.float32), (done, torch.uint8)):
+        rows = [(obs_prev, torch.int32), (device, torch.int32), (duration, torch.int32), (obs, torch.int32),
+                (reward, torch.float32), (done, torch.uint8)] + ([(ended, torch.uint8)] if ended is not None else [])
+        for t, dt in rows:
             t = torch.as_tensor(t).to(device=self.device, dtype=dt).contiguous()
             if tuple(t.shape) != ((n,) if not args else (K, n)):
-                raise ValueError("transition_stats: obs_prev is [N], the five arrays [steps][N]; got %s" % (tuple(t.shape),))
+                raise ValueError("transition_stats: obs_prev is [N], the other arrays [steps][N]; got %s" % (tuple(t.shape),))
             args.append(t)
+        call = self._L.gw_transition_stats if ended is None else self._L.gw_transition_stats_ep
         with torch.cuda.device(self.device):
-            nat.check(self._L.gw_transition_stats(self._h, K, *[t.data_ptr() for t in args], table.data_ptr(), self._stream()))
+            nat.check(call(self._h, K, *[t.data_ptr() for t in args], table.data_ptr(), self._stream()))
         return table
 
     def rollout_policy_stats(self, cdf, steps, seed, step0=0, env_id0=0, obs_prev=None, table=None, returns=None):
@@ -561,6 +572,127 @@ class VecCounterTrafficEnv(BaseEnv):
             nat.check(rc)
         self._last = (last,) + tuple(self._last[1:])
         return table
+
+    # -- episodes inside the closed loop (gw_rollout_episodes) -----------------------------------------
+    def _episode_tensors(self):
+        if self._ep_state is None:                        # (first use: an env that never runs episodes pays nothing in reset())
+            torch = _torch()
+            from ..actions import EP_COLS
+            self._ep_state = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
+            self._ep_tally = torch.zeros(EP_COLS, dtype=torch.int64, device=self.device)
+            self._ep_next = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+
+    @property
+    def episode_state(self):
+        """int32[N][2] on the GPU: each env's ``{age, ret}`` -- steps and reward sum since its last reset -- as
+        ``rollout_episodes`` keeps them; ``reset()`` zeroes the envs it resets."""
+        self._episode_tensors()
+        return self._ep_state
+
+    @property
+    def episode_tally(self):
+        """int64[5] on the GPU, added into by ``rollout_episodes`` / ``rollout_episodes_stats``: episodes ended, of those by
+        done, sum of lengths, sum of returns, sum of squared returns (``episode_stats()``); the caller may zero it."""
+        self._episode_tensors()
+        return self._ep_tally
+
+    def _episodes(self, max_steps, on_done, obs_prev, who):
+        """What both episodic calls share: the env's own ``{age, ret}`` / tally / next-observation tensors (first use), the
+        gw_episodes record and the checked ``obs_prev``."""
+        torch = _torch()
+        if self._custom is not None:
+            raise ValueError("%s needs the built-in interpreter" % who)
+        if int(max_steps) < 0:
+            raise ValueError("%s: max_steps must be >= 0" % who)
+        n = self.num_envs
+        self._episode_tensors()
+        if obs_prev is None:
+            obs_prev = self._last[0]
+            if obs_prev is None:
+                raise ValueError("%s: no observation yet -- reset() or step() first, or pass obs_prev" % who)
+        prev = torch.as_tensor(obs_prev).to(device=self.device, dtype=torch.int32).contiguous()
+        if prev.shape != (n,):
+            raise ValueError("obs_prev must have shape (%d,), got %s" % (n, tuple(prev.shape)))
+        ep = nat.Episodes(int(max_steps), 1 if on_done else 0, self._ep_state.data_ptr(), self._ep_tally.data_ptr())
+        return ep, prev
+
+    def rollout_episodes(self, cdf, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, out=None):
+        """``rollout_policy`` with episodes (gw_rollout_episodes): an env whose step returned ``done`` (``on_done``), or whose
+        episode has reached ``max_steps`` steps (0: no limit), is reset inside the launch exactly as ``reset(mask)`` would reset
+        it between two steps, and draws its next action from the reset's observation.  Returns ``(device, duration, obs,
+        reward, done, ended)``, each ``[steps][N]``: row k is what step k returned (``obs[k]`` the terminal observation where
+        ``ended[k]`` is 1 = done or 2 = step limit).  The env keeps each env's ``{age, ret}`` since its last reset, adds every
+        ended episode into its tally (``episode_stats()``) and remembers the observation each env acts on next, so calls
+        continue one another; advance ``step0`` by ``steps``.  The draws are ``rollout_policy``'s: resets do not shift the
+        stream.  ``out``: six ``[steps][N]`` tensors to write into.  Not for hipGraph capture (``step0`` would be baked in)."""
+        torch = _torch()
+        ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_episodes")
+        K, n = int(steps), self.num_envs
+        table = self._policy_table(cdf)
+        kinds = (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8, torch.uint8)
+        if out is None:
+            out = tuple(torch.empty((K, n), dtype=dt, device=self.device) for dt in kinds)
+        for t, dt in zip(out, kinds):
+            assert t.dtype is dt and tuple(t.shape) == (K, n) and t.is_contiguous() and t.device == self.device
+        if K:
+            lo, hi = prev.data_ptr(), prev.data_ptr() + 4 * n
+            if any(lo < t.data_ptr() + t.numel() * t.element_size() and t.data_ptr() < hi for t in out):
+                prev = prev.clone()
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_rollout_episodes(self._h, K, table.data_ptr(), int(seed) & (2 ** 64 - 1),
+                                                  int(step0) & (2 ** 64 - 1), int(env_id0) & (2 ** 64 - 1), C.byref(ep),
+                                                  prev.data_ptr(), self._ep_next.data_ptr(), *[t.data_ptr() for t in out],
+                                                  self._stream()))
+        if K:
+            self._last = (self._ep_next, out[3][-1], out[4][-1])
+        return tuple(out)
+
+    def rollout_episodes_stats(self, cdf, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, table=None):
+        """``rollout_episodes`` for a caller that wants the tally, not the transitions (gw_rollout_episodes_stats): the same
+        steps, draws, resets and episode bookkeeping, every transition ADDED into ``table`` (``rollout_policy_stats``' table)
+        under the class of the observation the env acted on -- the reset's after an episode's end.  Returns the table.  A
+        handle without the fused form runs ``rollout_episodes`` in chunks of at most 64 steps into buffers the env keeps, then
+        ``transition_stats(..., ended=...)``: the same table."""
+        torch = _torch()
+        ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_episodes_stats")
+        K, n = int(steps), self.num_envs
+        cdf_t = self._policy_table(cdf)
+        table = self._stats_table(table)
+        if K == 0:
+            return table
+        seed, step0, env_id0 = int(seed) & (2 ** 64 - 1), int(step0), int(env_id0) & (2 ** 64 - 1)
+        with torch.cuda.device(self.device):
+            rc = self._L.gw_rollout_episodes_stats(self._h, K, cdf_t.data_ptr(), seed, step0 & (2 ** 64 - 1), env_id0, C.byref(ep),
+                                                   prev.data_ptr(), self._ep_next.data_ptr(), table.data_ptr(), self._stream())
+        if rc == nat.EUNSUPPORTED and not os.environ.get("GW_ROLLOUT_STRICT"):
+            if self._stats_buf is None:
+                self._stats_buf = tuple(torch.empty((64, n), dtype=t, device=self.device)
+                                        for t in (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8))
+            if self._ep_buf is None:
+                self._ep_buf = torch.empty((64, n), dtype=torch.uint8, device=self.device)
+            seen = prev.clone()
+            for s in range(0, K, 64):                      # refused before anything ran: compose it from the two other calls
+                k = min(64, K - s)
+                out = tuple(b[:k] for b in self._stats_buf + (self._ep_buf,))
+                self.rollout_episodes(cdf_t, k, seed, max_steps, on_done, step0=step0 + s, env_id0=env_id0, obs_prev=seen, out=out)
+                self.transition_stats(seen, *out[:5], table=table, ended=out[5])
+                seen.copy_(self._ep_next)
+        else:
+            nat.check(rc)
+        self._last = (self._ep_next,) + tuple(self._last[1:])
+        return table
+
+    def episode_stats(self):
+        """The episodes ``rollout_episodes`` / ``rollout_episodes_stats`` have ended on this env so far, from the tally:
+        ``{"episodes", "by_done", "mean_length", "mean_return", "return_stderr"}`` (the means are ``nan`` before the first
+        episode ends).  Reads five numbers back: a host sync."""
+        n, by_done, length, ret, sq = (int(x) for x in self._ep_tally.cpu()) if self._ep_tally is not None else (0,) * 5
+        if n == 0:
+            nan = float("nan")
+            return {"episodes": 0, "by_done": 0, "mean_length": nan, "mean_return": nan, "return_stderr": nan}
+        mean = ret / n
+        return {"episodes": n, "by_done": by_done, "mean_length": length / n, "mean_return": mean,
+                "return_stderr": (max(sq / n - mean * mean, 0.0) / n) ** 0.5}
 
     def render(self, mode='human', close=False):          # counter_traffic.py:160-162
         values = self.received()[0].tolist()

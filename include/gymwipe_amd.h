@@ -244,6 +244,56 @@ int gw_rollout_policy_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev,
 int gw_transition_stats(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev, const int32_t* duration_dev,
                         const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev, int64_t* table_dev, void* stream);
 
+/* Episodes inside the closed loop.  gw_rollout_policy cannot end an episode: an env is reset only by gw_reset between calls.
+ * Here each env carries two caller-owned int32 values {age, ret} -- the steps and the reward sum since its last reset -- and
+ * after step k of env e has produced its (obs, reward, done), in this order:
+ *   1. age += 1; ret += reward
+ *   2. cause = (on_done && done) ? 1 : (max_steps > 0 && age >= max_steps) ? 2 : 0        (done wins over the step limit)
+ *   3. ended[k][e] = cause
+ *   4. cause != 0: {1, cause == 1, age, ret, ret * ret} is added into the episode tally
+ *   5. cause != 0: the env is reset exactly as gw_reset with mask[e] != 0 would reset it between step k and step k + 1
+ *      (counters to 0 from the current tick, interpreter cleared, simulated time not rewound)
+ *   6. cause != 0: age = ret = 0, and at step k + 1 the env acts on the reset's observation, counter_bound (class 1)
+ * Row k of obs / reward / done stays what the step returned (obs[k] is the terminal observation). */
+#define GW_EP_COLS 5   /* int64 tally: episodes ended, of those by done, sum of lengths, sum of returns, sum of returns^2 */
+typedef struct gw_episodes {
+    int32_t  max_steps;     /* > 0: reset after the max_steps-th step since the env's last reset; 0: no time limit */
+    int32_t  on_done;       /* != 0: reset after a step that returned done */
+    int32_t* state_dev;     /* int32[N][2] {age, ret}, in/out, never NULL (the caller zeroes it after its own gw_reset) */
+    int64_t* tally_dev;     /* int64[GW_EP_COLS], ADDED into; may be NULL */
+} gw_episodes;
+
+/* gw_rollout_policy with episodes: the same draws -- the hash of (seed, env_id0 + e, step0 + k); a reset does not shift the
+ * stream -- and the same five [steps][N] outputs, plus ended_dev (uint8[steps][N]) and obs_next_dev (int32[N]): the observation
+ * each env acts on next, its last one or counter_bound where it has just been reset.  Pass obs_next_dev as the next call's
+ * obs_prev_dev; it may be the same array (an env reads its element before writing it), but neither overlaps the [steps][N]
+ * outputs.  max_steps == 0 && on_done == 0 gives exactly gw_rollout_policy's outputs and state, ended all zero.
+ * Default mode: ONE launch per 64 steps (ct_rollout_policy_ep in ct_rollout_sfx.hip), the reset in registers at the step
+ * boundary.  Every other handle (as for gw_rollout_policy), or any handle while GW_ROLLOUT_POLICY_UNFUSED is set: per step a
+ * sampling launch, a step launch, a bookkeeping launch and gw_reset's launch with a mask the handle owns -- same results;
+ * GW_ROLLOUT_STRICT turns that into GW_EUNSUPPORTED.  steps == 0 is GW_OK; a NULL pointer other than tally_dev / stream,
+ * steps < 0 or max_steps < 0 is GW_EINVAL before any HIP call.  Allocates nothing, stream-ordered, the table never validated.
+ * Not for hipGraph capture: step0 is baked into the recorded launch, so every replay repeats the same draws. */
+int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                        const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                        int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
+                        uint8_t* done_dev, uint8_t* ended_dev, void* stream);
+
+/* gw_rollout_episodes without its [steps][N] outputs: every transition ADDED into table_dev (gw_rollout_policy_stats' table)
+ * under the class of the observation the env acted on -- counter_bound after a reset, otherwise its last observation; the
+ * next-observation and done columns are what the step returned.  Default mode only (ct_rollout_pstats_ep), available where
+ * gw_rollout_policy_stats is; elsewhere GW_EUNSUPPORTED before anything is launched: call gw_rollout_episodes and
+ * gw_transition_stats_ep instead.  Argument rules and the hipGraph caveat as above. */
+int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                              const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                              int64_t* table_dev, void* stream);
+
+/* gw_transition_stats for rows recorded by gw_rollout_episodes: step k's observation seen is counter_bound where
+ * ended_dev[k - 1] != 0; row 0 uses obs_prev_dev as it is. */
+int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev,
+                           const int32_t* duration_dev, const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                           const uint8_t* ended_dev, int64_t* table_dev, void* stream);
+
 /* Cumulative number of data packets the RRM has decoded per env since gw_create: uint32[N], device pointer
  * (default mode).  A custom Interpreter (envs/core.py:59-159) differences this across a step to learn how many
  * packets of the assigned sender the RRM sniffed (networking/devices.py:163-168). */

@@ -13,6 +13,15 @@ class, action), not the transitions:
                              gw_rollout_policy_stats writes
   r  rollout_policy + env.transition_stats   c, then the table by gw_transition_stats
   s  env.rollout_policy_stats                the tally inside the launch, no [K][N] array at all
+The episodes leg (--episodes T; profiles/rollout_episodes/README.md) -- episodes of T steps inside the launch against the only
+way to get the same trajectory without gw_rollout_episodes, a launch per T steps and a reset() in between:
+  e0 env.rollout_episodes, both limits off   against c: what the hook at the end of a step costs when it never fires
+  p  rollout_policy(T) + reset()             K / T calls of each per window
+  e  env.rollout_episodes(max_steps=T)       one call per window
+  q  rollout_policy_stats(T) + reset()       the same two for the tally
+  f  env.rollout_episodes_stats(max_steps=T)
+p/e and q/f walk the same steps (checked once, before the timing: the same reward sum, the same table).  Every leg reports the
+share of its env-steps with a non-zero reward beside its rate: what the steps are worth.
 Each of t, r and s must count every transition (checked once, before the timing; that they produce the same table from the
 same steps is tests/test_rollout_stats.py's business).
 Each form is timed `--repeats` times over `--windows` windows (wall clock around a device synchronize); one JSON line with the
@@ -40,6 +49,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--forms", default="a,b,c")
     ap.add_argument("--label", default="")
+    ap.add_argument("--episodes", type=int, default=0, help="episode length T of the forms p, e, q, f (must divide --steps)")
     args = ap.parse_args()
 
     import torch
@@ -126,16 +136,81 @@ def main():
             env.rollout_policy_stats(table32, K, 5, step0=s, table=table)
             s += K
 
+    T = args.episodes
+    out6 = out5 + (torch.empty((K, N), dtype=torch.uint8, device=dev),)
+    rewards_of = {"c": out5[3], "p": out5[3], "e0": out6[3], "e": out6[3]}    # form -> the rewards its last window stored
+
+    def form_e0():
+        s = 0
+        for _ in range(W):
+            env.reset()
+            env.rollout_episodes(table32, K, 5, max_steps=0, on_done=False, step0=s, out=out6)
+            s += K
+
+    def form_p():                                              # T steps, reset, T steps, ...: the parent's only way
+        s = 0
+        for _ in range(W):
+            for k in range(0, K, T):
+                env.reset()
+                env.rollout_policy(table32, T, 5, step0=s, out=tuple(t[k:k + T] for t in out5))
+                s += T
+
+    def form_e():
+        s = 0
+        env.reset()
+        for _ in range(W):
+            env.rollout_episodes(table32, K, 5, max_steps=T, on_done=True, step0=s, out=out6)
+            s += K
+
+    def form_q(table=stats):
+        s = 0
+        for _ in range(W):
+            for k in range(0, K, T):
+                env.reset()
+                env.rollout_policy_stats(table32, T, 5, step0=s, table=table)
+                s += T
+
+    def form_f(table=stats):
+        s = 0
+        env.reset()
+        for _ in range(W):
+            env.rollout_episodes_stats(table32, K, 5, max_steps=T, on_done=True, step0=s, table=table)
+            s += K
+
+    have_e = hasattr(nat.lib(), "gw_rollout_episodes") and hasattr(env, "rollout_episodes")
+    if T:
+        assert T > 0 and K % T == 0, "--episodes must divide --steps"
+    if T and have_e and any(f in args.forms.split(",") for f in "peqf"):
+        # the same trajectory both ways, each from a fresh handle (an env's clock and queues outlive reset()): the rewards of p
+        # and e, the tables of q and f.  (Default configuration: done never fires, every episode ends by the step limit.)
+        def fresh():
+            return VecCounterTrafficEnv(N, num_devices=D, device=dev)
+        env = fresh()
+        form_p()
+        rew_p = out5[3].double().sum().item()
+        env = fresh()
+        form_e()
+        assert out6[3].double().sum().item() == rew_p and int((out6[5] != 0).sum()) == N * K // T, "p and e walk different steps"
+        tq, tf = torch.zeros_like(stats), torch.zeros_like(stats)
+        env = fresh()
+        form_q(tq)
+        env = fresh()
+        form_f(tf)
+        assert bool((tq == tf).all()) and int(tq[..., 0].sum()) == N * K * W, "q and f build different tables"
+        env = fresh()
     have_c = hasattr(nat.lib(), "gw_rollout_policy") and hasattr(env, "rollout_policy")
     have_s = hasattr(nat.lib(), "gw_rollout_policy_stats") and hasattr(env, "rollout_policy_stats")
     forms = {"a": form_a, "b": form_b, "c": form_c if have_c else None, "t": form_t if have_c else None,
-             "r": form_r if have_s else None, "s": form_s if have_s else None}
+             "r": form_r if have_s else None, "s": form_s if have_s else None,
+             "e0": form_e0 if have_e else None, "p": form_p if T and have_c else None, "e": form_e if T and have_e else None,
+             "q": form_q if T and have_s else None, "f": form_f if T and have_e else None}
     for f in args.forms.split(","):                            # every stats form counts every transition (the forms do not walk
-        if f in "trs" and forms[f] is not None:                #  the same steps: an env's clock and queues outlive reset())
+        if f in ("t", "r", "s") and forms[f] is not None:                #  the same steps: an env's clock and queues outlive reset())
             check = torch.zeros_like(stats)
             forms[f](check)
             assert int(check[..., 0].sum()) == int(check[..., 3:6].sum()) == N * K * W, f
     res = {"label": args.label, "tree": "GW_TREE" if os.environ.get("GW_TREE") else "own", "envs": N, "devices": D, "steps": K, "windows": W,
+           "episodes": T,
            "repeats": args.repeats, "unfused_switch": bool(os.environ.get("GW_ROLLOUT_POLICY_UNFUSED")),
            "lib": os.path.basename(os.environ.get("GW_LIB") or "")}
     for name in args.forms.split(","):
@@ -155,6 +230,8 @@ def main():
         rate = [N * K * W / t / 1e9 for t in times]
         res[name] = {"G_env_steps_per_s_best": round(max(rate), 3), "median": round(float(np.median(rate)), 3),
                      "min": round(min(rate), 3), "us_per_step_best": round(min(times) / (K * W) * 1e6, 3)}
+        if name in rewards_of:                                 # what the steps are worth: the share with a non-zero reward
+            res[name]["nonzero_reward_share"] = round(float((rewards_of[name] != 0).float().mean()), 4)
     print(json.dumps(res))
 
 
