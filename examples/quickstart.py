@@ -56,6 +56,10 @@ print("rollout_policy_stats:", tuple(stats.shape), n, r_sum / n)
 a_dev, a_dur, o, r, d, ended = venv.rollout_episodes(table, 64, seed=1, max_steps=8, step0=128)
 print("rollout_episodes:", int((ended != 0).sum()), "episodes ended,", venv.episode_stats())
 
+# 3e. ... and when you choose the actions yourself: one step with autoreset (a rollout_autoreset of one step; `nxt` is what to act on)
+o, r, d, ended, nxt = venv.step_autoreset(action, max_steps=8)
+print("step_autoreset:", int((ended != 0).sum()), "episodes ended,", int((nxt != o).sum()), "envs act on the reset's observation")
+
 
 # 4. your own Interpreter (envs/core.py:59-159), fed with what the RRM sniffed each step
 class CountDeliveries(VecInterpreter):

@@ -27,7 +27,7 @@ CFG_PER_ENV_GEOMETRY = 32
 
 EXPORTS = (
     "gw_abi_version", "gw_last_error", "gw_device_count", "gw_config_default", "gw_create",
-    "gw_destroy", "gw_reset", "gw_step", "gw_step_fb", "gw_rollout", "gw_rollout_policy", "gw_rollout_policy_stats", "gw_transition_stats", "gw_rollout_episodes", "gw_rollout_episodes_stats", "gw_transition_stats_ep", "gw_set_position", "gw_set_positions", "gw_received", "gw_delivered", "gw_enqueue", "gw_pack_feedback", "gw_unpack_feedback", "gw_get_state",
+    "gw_destroy", "gw_reset", "gw_step", "gw_step_fb", "gw_rollout", "gw_rollout_policy", "gw_rollout_policy_stats", "gw_transition_stats", "gw_rollout_episodes", "gw_rollout_episodes_stats", "gw_transition_stats_ep", "gw_rollout_autoreset", "gw_set_position", "gw_set_positions", "gw_received", "gw_delivered", "gw_enqueue", "gw_pack_feedback", "gw_unpack_feedback", "gw_get_state",
     "gw_stats_read", "gw_clear_flags", "gw_state_bytes", "gw_snapshot_bytes", "gw_get_snapshot", "gw_set_state", "gw_link_info", "gw_noise_states", "gw_selftest_queue", "gw_selftest_runq",
     "gw_selftest_fastmath", "gw_selftest_launches",
     "gw_plant_config_default", "gw_plant_create", "gw_plant_destroy", "gw_plant_update", "gw_plant_set_input",
@@ -204,6 +204,8 @@ def lib():
     L.gw_rollout_episodes_stats.restype = C.c_int
     L.gw_transition_stats_ep.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gw_transition_stats_ep.restype = C.c_int
+    L.gw_rollout_autoreset.argtypes = [vp, i32, vp, vp, C.POINTER(Episodes), vp, vp, vp, vp, vp, vp]
+    L.gw_rollout_autoreset.restype = C.c_int
     L.gw_received.argtypes, L.gw_received.restype = [vp, vp, vp], C.c_int
     L.gw_enqueue.argtypes, L.gw_enqueue.restype = [vp, i32, vp, vp], C.c_int
     L.gw_pack_feedback.argtypes, L.gw_pack_feedback.restype = [vp, C.c_int64, vp, vp, vp, vp, i32, vp], C.c_int
@@ -261,7 +263,7 @@ _fast = False
 
 def fast():
     """The CPython fast-call shim for the per-step entry points (csrc/gw_pyfast.c), bound to the loaded library's
-    gw_step / gw_step_fb / gw_pendulum_step / gw_reset -- or None when it has not been built or GW_NO_PYFAST is set (the
+    gw_step / gw_step_fb / gw_pendulum_step / gw_reset / gw_rollout_autoreset -- or None when it has not been built or GW_NO_PYFAST is set (the
     callers then go through ctypes: same library, same kernels, ~1 us more host time per call).  Its ``Stepper`` type is
     ``VecCounterTrafficEnv.step``'s common case as one native call (GW_NO_FASTSTEP=1 at env construction keeps the shim but
     not the stepper: the A/B switch of tools/host_overhead.py)."""
@@ -280,6 +282,7 @@ def fast():
                 L = lib()
                 mod.bind(C.cast(L.gw_step, C.c_void_p).value, C.cast(L.gw_pendulum_step, C.c_void_p).value,
                          C.cast(L.gw_step_fb, C.c_void_p).value, C.cast(L.gw_reset, C.c_void_p).value)
+                mod.bind_autoreset(C.cast(L.gw_rollout_autoreset, C.c_void_p).value)
                 _fast = mod
             except Exception:
                 _fast = None

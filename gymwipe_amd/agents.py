@@ -159,10 +159,25 @@ class DqnCounterTrafficAgent:
                 pt.mul_(1.0 - self.target_update).add_(p, alpha=self.target_update)
         return loss
 
-    def fit(self, nb_steps, reset_every=64):
-        """Vectorised dqn.fit(): nb_steps env.step() calls of all N envs; returns the last loss (tensor)."""
+    def fit(self, nb_steps, reset_every=64, episode_steps=None):
+        """Vectorised dqn.fit(): nb_steps env.step() calls of all N envs; returns the last loss (tensor).
+        ``episode_steps``: per-env episodes of at most that many steps, ended by ``done`` too, through
+        ``env.step_autoreset`` (keras-rl's reset on done and nb_max_episode_steps) instead of the global reset every
+        ``reset_every`` steps: the memory gets the terminal observation as ``m_next``, and the next action is for the
+        observation the env acts on next -- the reset's where the step ended an episode."""
         obs = self.env.reset().clone()
         loss = None
+        if episode_steps is not None:
+            for k in range(nb_steps):
+                flat = self.act(obs)
+                o, r, d, _, nxt = self.env.step_autoreset(self.processor.process_action(flat), max_steps=int(episode_steps),
+                                                          on_done=True)
+                self.remember(obs, flat, r, o, d)
+                obs = nxt.clone()
+                self.steps += 1
+                if self.steps * self.n >= self.warmup and self.m_len >= self.batch_size:
+                    loss = self.learn()
+            return loss
         for k in range(nb_steps):
             if k and reset_every and k % reset_every == 0:
                 obs = self.env.reset().clone()

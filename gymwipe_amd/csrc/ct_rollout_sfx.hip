@@ -534,6 +534,8 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
 //   ct_rollout_policy_ep    gw_rollout_episodes: ct_rollout_policy with episodes -- an env whose step returned done, or whose
 //   ct_rollout_pstats_ep    episode reached its step limit, is reset in registers at the step boundary and draws its next
 //                           action from the reset's observation; gw_rollout_episodes_stats: the same with ct_rollout_pstats' tally.
+//   ct_rollout_sync_ep      gw_rollout_autoreset: ct_rollout_sync_kernel's staged rows with the same episodes -- the caller's
+//                           actions, the launch's resets.
 // The policy's draw (include/gymwipe_amd.h, gw_rollout_policy): the first 32 bits of the action stream's hash
 // (gymwipe_amd/actions.py) against the observation class's row of the table.
 __device__ __forceinline__ uint32_t gw_policy_u(uint64_t seed, uint64_t env_term, uint64_t step)
@@ -1073,6 +1075,57 @@ __global__ __launch_bounds__(64) void ct_rollout_pstats_ep(GwState st, GwDevCons
     gw_ts_flush(src.s_hist, 3u * src.A, threadIdx.x, lanes, table);
 }
 
+// gw_rollout_autoreset: ct_rollout_sync_kernel's staged source with the episode's book -- the caller chooses the actions, the
+// launch ends the episodes.  Nothing of the call is baked into the launch (no step0), so it may be recorded into a hipGraph.
+// A rejected action (GW_FLAG_BADACT) leaves the env alone and repeats the current values, and is still a step of the episode:
+// the body's put_feedback runs the hook below for it with reward 0 and the current done, as episodes_step_kernel sees such a row.
+struct StagedEpisodes {
+    uint8_t* ended;
+    int32_t latest_next;                                 // what the env acts on next, minus counter_bound
+    EpisodeBook ep;
+};
+
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_sync_ep(GwState st, GwDevConst c, int K, GwEpisodeArgs ea,
+                                                        const int32_t* __restrict__ device, const int32_t* __restrict__ duration,
+                                                        int32_t* obs, float* reward, uint8_t* done, uint8_t* ended)
+{
+    __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
+    StagedEpisodes src;
+    src.ended = ended;
+    src.latest_next = 0;
+#define GW_ROLLOUT_SRC_RESETS
+#define GW_ROLLOUT_SRC_STAGE if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep_tally[threadIdx.x] = 0ull;
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); int d_next = device[e], du_next = duration[e];
+#define GW_ROLLOUT_SRC_TAKE /* the next step's action is requested now */                                                        \
+    const int d = d_next, du = du_next;                                                                                          \
+    if (k + 1 < K) { d_next = device[(size_t)(k + 1) * N + e]; du_next = duration[(size_t)(k + 1) * N + e]; }
+#define GW_ROLLOUT_SRC_CHECKED(bad) (bad)                /* a staged action may lie outside the action space (GW_FLAG_BADACT) */
+#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest)
+#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)                                                                                \
+    {                                                                                                                            \
+        const uint32_t cause_next = src.ep.stepped(r, dn);                                                                       \
+        if (cause_next) reset_env();                                                                                             \
+        src.ended[at] = (uint8_t)cause_next;                                                                                     \
+        src.latest_next = cause_next ? 0 : latest;                                                                               \
+    }
+#include "ct_rollout_sync_body.h"
+#undef GW_ROLLOUT_SRC_RESETS
+#undef GW_ROLLOUT_SRC_STAGE
+#undef GW_ROLLOUT_SRC_FIRST
+#undef GW_ROLLOUT_SRC_TAKE
+#undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_OUTPUT
+#undef GW_ROLLOUT_SRC_STEPPED
+#undef GW_ROLLOUT_SRC_EPISODE
+    GW_ROLLOUT_STORE_IP
+    ea.obs_next[e] = src.latest_next + c.counter_bound;
+    src.ep.store(ea, e, s_ep_tally);
+    gw_wave_lds_order();
+    gw_ep_flush(s_ep_tally, threadIdx.x, gw_min_u32(64u, N - blockIdx.x * 64u), ea.tally);
+}
+
 // The per-step form's bookkeeping, for handles without the fused kernels: after a step's launch, steps 1-4 and 6 of the
 // semantics for every env -- {age, ret}, ended, the tally, the observation acted on next -- and the mask gw_reset's launch takes.
 __global__ __launch_bounds__(256) void episodes_step_kernel(uint32_t N, int32_t center, GwEpisodeArgs ea, const int32_t* obs,
@@ -1298,6 +1351,26 @@ int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, in
             return gw_launch_status();
         });
     });
+}
+
+// The fused form of gw_rollout_autoreset: gw_launch_rollout_policy_ep_sfx's availability rules without the table's (there is
+// no table), and no dynamic LDS.
+int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
+                                    const gw_episodes& ep, int32_t* obs_next, int32_t* obs, float* reward, uint8_t* done,
+                                    uint8_t* ended, void* stream, bool below_limits, uint64_t* rec)
+{
+    if (K <= 0 || K > st.rcap || st.ract != nullptr) return GW_EUNSUPPORTED;
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    const int mode = gw_step_mode(cst, below_limits, false);
+    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
+    gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
+        gw_with_mode(mode, [&](auto m) {
+            gw_note_launch(rec, GW_LS_ROLLOUT_SYNC_EP + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
+            hipLaunchKernelGGL((ct_rollout_sync_ep<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64), 0,
+                               (hipStream_t)stream, st, cst, K, ea, device, duration, obs, reward, done, ended);
+        });
+    });
+    return gw_launch_status();
 }
 
 // One step's episode bookkeeping of gw_rollout_episodes' per-step form (every queue mode): row `step`'s ended, the mask.

@@ -1,7 +1,7 @@
 // ct_rollout_sync_body.h -- the body of the step-synchronous rollout kernels (ct_rollout_sfx.hip), included once per kernel:
 // ct_rollout_sync_kernel (actions staged by the caller), ct_rollout_policy (actions drawn in the kernel), ct_rollout_pstats
 // (drawn in the kernel, the transitions tallied instead of stored) and their episodic forms ct_rollout_policy_ep /
-// ct_rollout_pstats_ep (an env that ends an episode is reset inside the launch).  It is text
+// ct_rollout_pstats_ep / ct_rollout_sync_ep (an env that ends an episode is reset inside the launch).  It is text
 // with macro hooks, not a function, on purpose.  As a __forceinline__ template over an action-source type the compiler
 // optimised the callee on its own before inlining it, and all 30 instantiations of ct_rollout_sync_kernel came out different
 // (up to 31 more VGPRs at D = 16 and 32, SGPRs parked in VGPR lanes at D = 4); with the source as an object whose members hold

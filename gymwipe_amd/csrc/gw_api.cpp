@@ -760,6 +760,20 @@ static int check_episodes(const gw_episodes* ep, const char* who)
     return GW_OK;
 }
 
+// Step s of the per-step episodic forms, behind its action: the step's launch on one row of the outputs, the bookkeeping
+// launch (ended, obs_next, the tally, the handle's reset mask) and gw_reset's launch with that mask.
+static int episode_step(gw_env* env, int32_t s, const int32_t* device_row, const int32_t* duration_row, const gw_episodes* ep,
+                        int32_t* obs_next_dev, int32_t* obs_row, float* reward_row, uint8_t* done_row, uint8_t* ended_row, void* stream)
+{
+    if (launch_step(env, device_row, duration_row, obs_row, reward_row, done_row, stream))
+        return fail(GW_EHIP, "step kernel launch failed at step %d", s);
+    gw_env_add_steps(env, 1);
+    if (gw_launch_episodes_step(env->st.N, env->cst_host.counter_bound, *ep, obs_next_dev, obs_row, reward_row, done_row, ended_row,
+                                env->ep_mask, stream))
+        return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
+    return gw_reset(env, env->ep_mask, nullptr, stream);
+}
+
 int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                         const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
                         int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
@@ -795,13 +809,41 @@ int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uin
         if (gw_launch_policy_sample(N, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, cdf_dev, seed,
                                     step0 + (uint64_t)s, env_id0, seen_before(s), device_out_dev + o, duration_out_dev + o, stream))
             return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
-        if (launch_step(env, device_out_dev + o, duration_out_dev + o, obs_dev + o, reward_dev + o, done_dev + o, stream))
-            return fail(GW_EHIP, "step kernel launch failed at step %d", s);
-        gw_env_add_steps(env, 1);
-        if (gw_launch_episodes_step(N, env->cst_host.counter_bound, *ep, obs_next_dev, obs_dev + o, reward_dev + o, done_dev + o,
-                                    ended_dev + o, env->ep_mask, stream))
-            return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
-        if ((rc = gw_reset(env, env->ep_mask, nullptr, stream))) return rc;
+        if ((rc = episode_step(env, s, device_out_dev + o, duration_out_dev + o, ep, obs_next_dev, obs_dev + o, reward_dev + o,
+                               done_dev + o, ended_dev + o, stream)))
+            return rc;
+    }
+    return GW_OK;
+}
+
+int gw_rollout_autoreset(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
+                         const gw_episodes* ep, int32_t* obs_next_dev,
+                         int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, void* stream)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!device_dev || !duration_dev || !obs_next_dev || !obs_dev || !reward_dev || !done_dev || !ended_dev)
+        return fail(GW_EINVAL, "gw_rollout_autoreset: NULL device pointer");
+    int rc = check_episodes(ep, "gw_rollout_autoreset");
+    if (rc) return rc;
+    if (steps == 0) return GW_OK;
+    if ((rc = select_device(env))) return rc;
+    const int64_t N = env->st.N;
+    int32_t s = 0;
+    rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
+        const int64_t o = (int64_t)s0 * N;
+        return gw_launch_rollout_autoreset_sfx(env->st, env->cst_host, chunk, device_dev + o, duration_dev + o, *ep, obs_next_dev,
+                                               obs_dev + o, reward_dev + o, done_dev + o, ended_dev + o, stream, below,
+                                               env->launches);
+    });
+    if (rc) return rc;
+    if (s < steps && getenv("GW_ROLLOUT_STRICT"))
+        return fail(GW_EUNSUPPORTED, "no fused autoreset rollout for this handle (GW_ROLLOUT_STRICT is set)");
+    for (; s < steps; ++s) {                                   // every other handle: step, bookkeeping, masked reset
+        const int64_t o = (int64_t)s * N;
+        if ((rc = episode_step(env, s, device_dev + o, duration_dev + o, ep, obs_next_dev, obs_dev + o, reward_dev + o, done_dev + o,
+                               ended_dev + o, stream)))
+            return rc;
     }
     return GW_OK;
 }
@@ -1116,7 +1158,7 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        static const char* const fam[3] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep"};
+        static const char* const fam[4] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep"};
         const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
         snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }

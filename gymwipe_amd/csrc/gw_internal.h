@@ -327,6 +327,10 @@ int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, in
                                     int64_t* table, void* stream, bool below_limits, uint64_t* rec);
 int gw_launch_episodes_step(int64_t N, int counter_bound, const gw_episodes& ep, int32_t* obs_next, const int32_t* obs,
                             const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask, void* stream);
+// gw_rollout_autoreset (ct_rollout_sfx.hip): the fused form -- staged actions, episodes inside the launch
+int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
+                                    const gw_episodes& ep, int32_t* obs_next, int32_t* obs, float* reward, uint8_t* done,
+                                    uint8_t* ended, void* stream, bool below_limits, uint64_t* rec);
 int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const uint32_t* cdf, uint64_t seed, uint64_t step,
                             uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, void* stream);
 int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream);
@@ -374,7 +378,8 @@ enum {
     GW_LS_ROLLOUT_PSTATS = GW_LS_ROLLOUT_POLICY + 3 * GW_LS_NDT,   // ct_rollout_pstats<DT, MODE>: 3 per DT    their numbers)
     GW_LS_ROLLOUT_POLICY_EP = GW_LS_ROLLOUT_PSTATS + 3 * GW_LS_NDT,      // ct_rollout_policy_ep<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_PSTATS_EP = GW_LS_ROLLOUT_POLICY_EP + 3 * GW_LS_NDT,   // ct_rollout_pstats_ep<DT, MODE>: 3 per DT
-    GW_LS_COUNT = GW_LS_ROLLOUT_PSTATS_EP + 3 * GW_LS_NDT
+    GW_LS_ROLLOUT_SYNC_EP = GW_LS_ROLLOUT_PSTATS_EP + 3 * GW_LS_NDT,     // ct_rollout_sync_ep<DT, MODE>: 3 per DT
+    GW_LS_COUNT = GW_LS_ROLLOUT_SYNC_EP + 3 * GW_LS_NDT
 };
 constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {

@@ -44,6 +44,47 @@ static PyObject* py_bind(PyObject* self, PyObject* const* args, Py_ssize_t n)
     Py_RETURN_NONE;
 }
 
+/* gw_episodes (include/gymwipe_amd.h), restated: this file includes nothing of the library's */
+typedef struct { int32_t max_steps, on_done; int32_t* state_dev; int64_t* tally_dev; } gw_episodes_rec;
+typedef int (*gw_autoreset_fn)(void*, int32_t, const int32_t*, const int32_t*, const gw_episodes_rec*, int32_t*, int32_t*, float*,
+                               uint8_t*, uint8_t*, void*);
+static gw_autoreset_fn g_autoreset = NULL;
+
+/* bind_autoreset(addr_of_gw_rollout_autoreset): a call of its own, so that bind()'s arity stays */
+static PyObject* py_bind_autoreset(PyObject* self, PyObject* const* args, Py_ssize_t n)
+{
+    void* a = NULL;
+    if (n != 1) { PyErr_SetString(PyExc_TypeError, "bind_autoreset(gw_rollout_autoreset)"); return NULL; }
+    if (as_ptr(args[0], &a)) return NULL;
+    g_autoreset = (gw_autoreset_fn)a;
+    Py_RETURN_NONE;
+}
+
+/* rollout_autoreset(env, steps, device, duration, max_steps, on_done, state, tally, obs_next, obs, reward, done, ended, stream)
+ * -> rc; addresses and three ints in, the gw_episodes record built on the C stack */
+static PyObject* py_autoreset(PyObject* self, PyObject* const* args, Py_ssize_t n)
+{
+    void* p[14];
+    long v[3];
+    if (n != 14 || !g_autoreset) {
+        PyErr_SetString(PyExc_TypeError, "rollout_autoreset(env, steps, device, duration, max_steps, on_done, state, tally, obs_next, "
+                                         "obs, reward, done, ended, stream) after bind_autoreset()");
+        return NULL;
+    }
+    for (int i = 0; i < 14; ++i) {
+        if (i == 1 || i == 4 || i == 5) {
+            long* w = &v[i == 1 ? 0 : i - 3];
+            *w = PyLong_AsLong(args[i]);
+            if (*w == -1 && PyErr_Occurred()) return NULL;
+            if (*w < INT32_MIN || *w > INT32_MAX) { PyErr_SetString(PyExc_OverflowError, "rollout_autoreset: int32 expected"); return NULL; }
+        } else if (as_ptr(args[i], &p[i])) return NULL;
+    }
+    const gw_episodes_rec ep = {(int32_t)v[1], (int32_t)v[2], (int32_t*)p[6], (int64_t*)p[7]};
+    const int rc = g_autoreset(p[0], (int32_t)v[0], (const int32_t*)p[2], (const int32_t*)p[3], &ep, (int32_t*)p[8], (int32_t*)p[9],
+                               (float*)p[10], (uint8_t*)p[11], (uint8_t*)p[12], p[13]);
+    return PyLong_FromLong(rc);
+}
+
 /* reset(env, mask, obs, stream) -> rc */
 static PyObject* py_reset(PyObject* self, PyObject* const* args, Py_ssize_t n)
 {
@@ -300,6 +341,8 @@ static PyTypeObject StepperType = {
 
 static PyMethodDef methods[] = {
     {"bind", (PyCFunction)(void (*)(void))py_bind, METH_FASTCALL, "bind(gw_step address, gw_pendulum_step address, gw_step_fb address[, gw_reset address])"},
+    {"bind_autoreset", (PyCFunction)(void (*)(void))py_bind_autoreset, METH_FASTCALL, "bind_autoreset(gw_rollout_autoreset address)"},
+    {"rollout_autoreset", (PyCFunction)(void (*)(void))py_autoreset, METH_FASTCALL, "gw_rollout_autoreset with addresses and ints"},
     {"reset", (PyCFunction)(void (*)(void))py_reset, METH_FASTCALL, "gw_reset with addresses as ints"},
     {"step", (PyCFunction)(void (*)(void))py_step, METH_FASTCALL, "gw_step with addresses as ints"},
     {"step_fb", (PyCFunction)(void (*)(void))py_step_fb, METH_FASTCALL, "gw_step_fb with addresses as ints"},

@@ -62,21 +62,23 @@ class _DeviceInterpreter(Interpreter):
 
 class StepOutputs:
     """Where one ``env.step(action, out=...)`` writes: ``obs`` int32[N], ``reward`` float32[N], ``done`` uint8[N] and, optionally,
-    ``feedback_bytes`` uint8[N] (the step's feedback in the one-byte exchange format, ``gw_step_fb``) -- preallocated,
-    contiguous tensors on the env's GPU.  Their device addresses are taken ONCE, here (a step is enqueued every few
+    ``feedback_bytes`` uint8[N] (the step's feedback in the one-byte exchange format, ``gw_step_fb``) and ``ended`` uint8[N]
+    (``step_autoreset``'s cause per env: 0, 1 done, 2 step limit) -- preallocated, contiguous tensors on the env's GPU.  Their device addresses are taken ONCE, here (a step is enqueued every few
     microseconds; four ``data_ptr()`` calls are 10 % of that), so the tensors must not be resized or re-pointed afterwards;
     the object keeps them alive."""
-    __slots__ = ("obs", "reward", "done", "feedback_bytes", "_ptrs", "_as_tuple", "_dev")
+    __slots__ = ("obs", "reward", "done", "feedback_bytes", "ended", "_ptrs", "_as_tuple", "_dev", "_ended_ptr")
 
-    def __init__(self, obs, reward, done, feedback_bytes=None):
+    def __init__(self, obs, reward, done, feedback_bytes=None, ended=None):
         torch = _torch()
         n = obs.shape[0]
-        for t, dt in ((obs, torch.int32), (reward, torch.float32), (done, torch.uint8), (feedback_bytes, torch.uint8)):
+        for t, dt in ((obs, torch.int32), (reward, torch.float32), (done, torch.uint8), (feedback_bytes, torch.uint8),
+                      (ended, torch.uint8)):
             if t is None:
                 continue
             assert (type(t) is torch.Tensor and t.dtype is dt and t.dim() == 1 and t.shape[0] == n and t.is_contiguous()
                     and t.device == obs.device and t.is_cuda), "StepOutputs: contiguous 1-D tensors of one length on one GPU"
-        self.obs, self.reward, self.done, self.feedback_bytes = obs, reward, done, feedback_bytes
+        self.obs, self.reward, self.done, self.feedback_bytes, self.ended = obs, reward, done, feedback_bytes, ended
+        self._ended_ptr = ended.data_ptr() if ended is not None else 0     # (beside _ptrs: the native stepper reads four)
         self._ptrs = (obs.data_ptr(), reward.data_ptr(), done.data_ptr(),
                       feedback_bytes.data_ptr() if feedback_bytes is not None else 0)
         self._as_tuple = (obs, reward, done)
@@ -596,9 +598,10 @@ class VecCounterTrafficEnv(BaseEnv):
         self._episode_tensors()
         return self._ep_tally
 
-    def _episodes(self, max_steps, on_done, obs_prev, who):
-        """What both episodic calls share: the env's own ``{age, ret}`` / tally / next-observation tensors (first use), the
-        gw_episodes record and the checked ``obs_prev``."""
+    def _episodes(self, max_steps, on_done, obs_prev, who, needs_obs=True):
+        """What the episodic calls share: the env's own ``{age, ret}`` / tally / next-observation tensors (first use), the
+        gw_episodes record and the checked ``obs_prev`` -- ``None`` for a caller that brings the actions (``needs_obs``
+        false: nothing in the call reads an observation)."""
         torch = _torch()
         if self._custom is not None:
             raise ValueError("%s needs the built-in interpreter" % who)
@@ -606,6 +609,8 @@ class VecCounterTrafficEnv(BaseEnv):
             raise ValueError("%s: max_steps must be >= 0" % who)
         n = self.num_envs
         self._episode_tensors()
+        if not needs_obs:
+            return nat.Episodes(int(max_steps), 1 if on_done else 0, self._ep_state.data_ptr(), self._ep_tally.data_ptr()), None
         if obs_prev is None:
             obs_prev = self._last[0]
             if obs_prev is None:
@@ -682,8 +687,92 @@ class VecCounterTrafficEnv(BaseEnv):
         self._last = (self._ep_next,) + tuple(self._last[1:])
         return table
 
+    # -- episodes for a caller that chooses the actions (gw_rollout_autoreset) ---------------------------
+    def _autoreset(self, K, dev_ptr, dur_ptr, max_steps, on_done, ptrs):
+        """gw_rollout_autoreset on the env's own episode tensors; ``ptrs``: the addresses of obs, reward, done, ended."""
+        idx = self._dev_index
+        fast = self._fast
+        if fast is not None and self._cuda_get_device() == idx:       # the per-step route: no ctypes, no context manager
+            rc = fast.rollout_autoreset(self._hv, K, dev_ptr, dur_ptr, max_steps, 1 if on_done else 0, self._ep_state.data_ptr(),
+                                        self._ep_tally.data_ptr(), self._ep_next.data_ptr(), ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                        self._cuda_raw_stream(idx))
+        else:
+            ep = nat.Episodes(max_steps, 1 if on_done else 0, self._ep_state.data_ptr(), self._ep_tally.data_ptr())
+            with _torch().cuda.device(self.device):
+                rc = self._L.gw_rollout_autoreset(self._h, K, dev_ptr, dur_ptr, C.byref(ep), self._ep_next.data_ptr(), ptrs[0],
+                                                  ptrs[1], ptrs[2], ptrs[3], self._stream())
+        if rc:
+            nat.check(rc)
+
+    def rollout_autoreset(self, device, duration, max_steps=0, on_done=True, out=None):
+        """``rollout()`` with episodes (gw_rollout_autoreset): K consecutive steps from pre-staged actions ``int32[K][N]``, in
+        which an env whose step returned ``done`` (``on_done``), or whose episode has reached ``max_steps`` steps (0: no
+        limit), is reset inside the launch exactly as ``reset(mask)`` would reset it between two steps.  Returns ``(obs, reward,
+        done, ended)``, each ``[K][N]``: row k is what step k returned (``obs[k]`` the terminal observation where ``ended[k]``
+        is 1 = done or 2 = step limit).  The episodes are the env's own -- ``episode_state``, ``episode_tally`` and the
+        observation each env acts on next are shared with ``rollout_episodes``, ``step_autoreset`` and ``reset()``, so the
+        calls continue one another.  An action outside the action space flags its env, leaves it untouched and still counts
+        as a step of its episode.  ``out``: four ``[K][N]`` tensors to write into.  May be captured into a hipGraph."""
+        torch = _torch()
+        self._episodes(max_steps, on_done, None, "rollout_autoreset", needs_obs=False)
+        dev = torch.as_tensor(device).to(device=self.device, dtype=torch.int32).contiguous()
+        dur = torch.as_tensor(duration).to(device=self.device, dtype=torch.int32).contiguous()
+        K, n = dev.shape[0], self.num_envs
+        assert dev.shape == (K, n) and dur.shape == dev.shape
+        kinds = (torch.int32, torch.float32, torch.uint8, torch.uint8)
+        if out is None:
+            out = tuple(torch.empty((K, n), dtype=dt, device=self.device) for dt in kinds)
+        for t, dt in zip(out, kinds):
+            assert t.dtype is dt and tuple(t.shape) == (K, n) and t.is_contiguous() and t.device == self.device
+        self._autoreset(K, dev.data_ptr(), dur.data_ptr(), int(max_steps), on_done, [t.data_ptr() for t in out])
+        if K:
+            self._last = (self._ep_next, out[1][-1], out[2][-1])
+        return tuple(out)
+
+    def step_autoreset(self, action, max_steps=0, on_done=True, out=None):
+        """One ``env.step()`` with autoreset -- ``rollout_autoreset`` of one step on 1-D tensors: the step, the episode
+        bookkeeping and the reset of the envs whose episode it ended, in one launch.  Returns ``(obs, reward, done, ended,
+        obs_next)``: what the step returned (``obs`` is the terminal observation where ``ended`` is not 0) and the
+        observation to act on next (``COUNTER_BOUND`` for the envs just reset; the env's own tensor, rewritten by every
+        episodic call).  ``out``: a ``StepOutputs`` with an ``ended`` tensor.  Action tensors go through ``step()``'s cache and
+        its aliasing contract.  May be captured into a hipGraph."""
+        if self._ep_state is None or self._custom is not None or max_steps < 0:
+            self._episodes(max_steps, on_done, None, "step_autoreset", needs_obs=False)
+        dev = action["device"]
+        dur = action["duration"]
+        seen = self._seen
+        hit = seen.get(id(dev))
+        if hit is None or hit[0]() is not dev:
+            dev = self._checked(dev, "device")
+            dev_ptr = dev.data_ptr()
+        else:
+            dev_ptr = hit[1]
+        hit = seen.get(id(dur))
+        if hit is None or hit[0]() is not dur:
+            dur = self._checked(dur, "duration")
+            dur_ptr = dur.data_ptr()
+        else:
+            dur_ptr = hit[1]
+        if out is None:
+            torch = _torch()
+            obs, rew, done = self._outputs()
+            ended = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
+            ptrs = (obs.data_ptr(), rew.data_ptr(), done.data_ptr(), ended.data_ptr())
+        else:
+            if out._dev != self._dev_index:
+                raise ValueError("StepOutputs on cuda:%d passed to an env on cuda:%d" % (out._dev, self._dev_index))
+            if not out._ended_ptr:
+                raise ValueError("step_autoreset: the StepOutputs needs an `ended` tensor")
+            obs, rew, done, ended = out.obs, out.reward, out.done, out.ended
+            p = out._ptrs
+            ptrs = (p[0], p[1], p[2], out._ended_ptr)
+        self._autoreset(1, dev_ptr, dur_ptr, int(max_steps), on_done, ptrs)
+        self._last = (self._ep_next, rew, done)
+        return obs, rew, done, ended, self._ep_next
+
     def episode_stats(self):
-        """The episodes ``rollout_episodes`` / ``rollout_episodes_stats`` have ended on this env so far, from the tally:
+        """The episodes the episodic calls (``rollout_episodes``, ``rollout_episodes_stats``, ``rollout_autoreset``,
+        ``step_autoreset``) have ended on this env so far, from the tally:
         ``{"episodes", "by_done", "mean_length", "mean_return", "return_stderr"}`` (the means are ``nan`` before the first
         episode ends).  Reads five numbers back: a host sync."""
         n, by_done, length, ret, sq = (int(x) for x in self._ep_tally.cpu()) if self._ep_tally is not None else (0,) * 5

@@ -35,6 +35,8 @@
  *   gw_delivered       what SimpleRrmDevice.onPacketReceived feeds a custom Interpreter     networking/devices.py:163-168
  *   gw_enqueue         SimpleNetworkDevice.send -> SimpleMac queue           networking/devices.py:84-86, simple_stack.py:463-471
  *   gw_rollout         a Python loop over step()
+ *   gw_rollout_autoreset   that loop with the caller's reset on done or after nb_max_episode_steps (keras-rl's fit, as the
+ *                      reference drives it: agents/dqn_counter_traffic.py:63-70); steps = 1 is one env.step() with autoreset
  *   gw_step_fb         gw_step + the step's feedback as one byte per env (the row a multi-GPU job gathers)
  *   gw_pack_feedback / gw_unpack_feedback   (multi-GPU exchange format; the reference is single-process)
  *   gw_pendulum_step   InvertedPendulumEnv.step              envs/inverted_pendulum.py:101-113
@@ -287,6 +289,28 @@ int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uin
 int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                               const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
                               int64_t* table_dev, void* stream);
+
+/* gw_rollout with episodes: `steps` env.step() calls from the caller's pre-staged actions (device_dev / duration_dev and the four
+ * outputs are [steps][N]), with steps 1-6 of the semantics above gw_episodes applied after every step of every env -- the caller chooses the actions, the
+ * call ends the episodes.  Row k of obs / reward / done is what step k returned; ended_dev[k][e] is its cause (0, 1 done,
+ * 2 step limit); obs_next_dev[e] (int32[N]) receives what env e acts on next: its last observation, or counter_bound where its
+ * last step ended the episode.  obs_next_dev overlaps none of the [steps][N] arrays, and the inputs none of the outputs.
+ * One step with autoreset is steps = 1.
+ * An action outside the action space (GW_FLAG_BADACT) leaves its env untouched as in gw_rollout -- the row repeats the current
+ * obs and done with reward 0 -- and still counts as a step of the episode: age += 1, ret += 0, the cause from the repeated
+ * done.  A rejected action can so end an episode by the step limit, and the env is then reset.
+ * max_steps == 0 && on_done == 0 gives exactly gw_rollout's outputs and state, ended all zero; {age, ret} still advance.
+ * Default mode: ONE launch per 64 steps (ct_rollout_sync_ep in ct_rollout_sfx.hip), the reset in registers at the step
+ * boundary.  Every other handle (explicit queues, live PHY, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0):
+ * per step a step launch, a bookkeeping launch and gw_reset's launch with a mask the handle owns -- same results;
+ * GW_ROLLOUT_STRICT turns that into GW_EUNSUPPORTED before anything is launched.  steps == 0 is GW_OK; a NULL pointer other
+ * than tally_dev / stream, steps < 0 or max_steps < 0 is GW_EINVAL before any HIP call.  Allocates nothing, stream-ordered.
+ * This call MAY be captured into a hipGraph: nothing of the call but its pointers and limits is baked into the recorded
+ * launches (there is no step0), so a replay continues the episodes from the arrays' current contents.  As for every captured
+ * launch of a handle, the recorded kernels keep the fast forms' validity-limit tests, and so does the handle from then on. */
+int gw_rollout_autoreset(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
+                         const gw_episodes* ep, int32_t* obs_next_dev,
+                         int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, void* stream);
 
 /* gw_transition_stats for rows recorded by gw_rollout_episodes: step k's observation seen is counter_bound where
  * ended_dev[k - 1] != 0; row 0 uses obs_prev_dev as it is. */
