@@ -124,6 +124,23 @@ def policy_sample_numpy(seed, env_lo, env_hi, step, cdf, obs, counter_bound, max
     return dev.astype(np.int32), (a - dev * int(max_duration)).astype(np.int32)
 
 
+def policy_sample_population_numpy(seed, env_lo, env_hi, step, cdfs, envs_per_policy, obs, counter_bound, max_duration):
+    """CPU restatement of ``gw_rollout_population``'s draw: :func:`policy_sample_numpy` for a slice of a population -- env
+    index ``i`` of the slice (0 for ``env_lo``: the env's index in its handle) draws from table ``i // envs_per_policy`` of
+    ``cdfs`` uint32[P][3][A], with the hash ids of ``[env_lo, env_hi)``: ``env_lo`` shifts the stream, not the policy index."""
+    cdfs = np.asarray(cdfs, dtype=np.uint32)
+    obs = np.asarray(obs)
+    n, M = int(env_hi) - int(env_lo), int(envs_per_policy)
+    if cdfs.ndim != 3 or cdfs.shape[1] != 3 or M < 1 or n != cdfs.shape[0] * M or obs.shape != (n,):
+        raise ValueError("cdfs must be [P][3][A] with P * envs_per_policy == env_hi - env_lo == len(obs)")
+    dev, dur = np.empty(n, np.int32), np.empty(n, np.int32)
+    for p in range(cdfs.shape[0]):
+        lo, hi = p * M, (p + 1) * M
+        dev[lo:hi], dur[lo:hi] = policy_sample_numpy(seed, env_lo + lo, env_lo + hi, step, cdfs[p], obs[lo:hi], counter_bound,
+                                                     max_duration)
+    return dev, dur
+
+
 # ---- the table of a closed loop (gw_rollout_policy_stats / gw_transition_stats, include/gymwipe_amd.h) -----------------------
 TS_COLS = 7                     # n, r_sum, r_sq, next below / at / above the bound, done
 

@@ -263,3 +263,90 @@ class TabularCounterTrafficAgent:
         n, r_sum, r_sq = (float(x) for x in t[..., :3].sum(dim=(0, 1)).cpu())
         mean = r_sum / n
         return mean, (max(r_sq / n - mean * mean, 0.0) / n) ** 0.5
+
+
+class PopulationSearchAgent:
+    """Cross-entropy search over the ``[3][A]`` logits of a tabular policy, one generation per ``env.rollout_population``
+    call: P candidate tables run on ``num_envs / P`` envs each inside one launch per 64 steps and come back as a ``[P][5]``
+    episode tally -- nothing is sized by ``steps * num_envs``, and the only host traffic per generation is the tables in and
+    the tally out.
+
+    Per generation: P logit tables ``mu + sigma * eps`` from a seeded ``numpy.random.Generator``; softmax in float64 numpy and
+    ``actions.policy_cdf`` in numpy (the torch form of ``policy_cdf`` may differ by 1 in an entry; the numpy form is the one a
+    CPU oracle can reproduce); ``evaluate(cdfs, generation)`` -> the tally; ``fitness = ret_sum / episodes`` (``-inf`` where a
+    policy ended no episode); ``mu`` and ``sigma`` become the mean and standard deviation of the elites' logits, ``sigma``
+    floored at ``SIGMA_MIN``.  ``history`` keeps ``{"generation", "fitness", "mean", "best"}`` per generation.
+
+    ``evaluate`` defaults to the env: ``env.reset()``, the episode state zeroed, ``env.rollout_population(cdfs, steps, seed,
+    max_steps=episode_steps, step0=generation * steps)``.  Pass a callable (and ``env=None`` with ``nb_actions``) to let
+    anything else that returns a ``[P][5]`` tally stand in for the GPU."""
+
+    SIGMA_MIN = 1e-3                    # the floor of sigma: a collapsed elite set must not end the search
+
+    def __init__(self, env, num_policies, steps, episode_steps, elite_frac=0.25, sigma0=1.0, seed=0, evaluate=None,
+                 nb_actions=None):
+        import numpy as np
+        self.np = np
+        self.env = env
+        if nb_actions is None:
+            if env is None:
+                raise ValueError("PopulationSearchAgent: without an env, pass nb_actions")
+            nb_actions = int(env.num_devices) * int(env.config.max_duration)
+        if env is None and evaluate is None:
+            raise ValueError("PopulationSearchAgent: without an env, pass evaluate")
+        self.nb_actions = int(nb_actions)
+        self.num_policies, self.steps, self.episode_steps = int(num_policies), int(steps), int(episode_steps)
+        self.num_elites = max(1, int(round(float(elite_frac) * self.num_policies)))
+        if self.num_policies < 1 or self.num_elites > self.num_policies:
+            raise ValueError("PopulationSearchAgent: need 1 <= elites <= num_policies")
+        self.seed = int(seed)
+        self.rng = np.random.default_rng(self.seed)
+        self.mu = np.zeros((3, self.nb_actions), np.float64)
+        self.sigma = np.full((3, self.nb_actions), float(sigma0), np.float64)
+        self.evaluate = evaluate if evaluate is not None else self._evaluate_on_env
+        self.generation = 0
+        self.history = []
+
+    def _evaluate_on_env(self, cdfs, generation):
+        env = self.env
+        env.reset()
+        env.episode_state.zero_()
+        return env.rollout_population(cdfs, self.steps, self.seed, max_steps=self.episode_steps, on_done=True,
+                                      step0=generation * self.steps)
+
+    def tables(self, logits):
+        """Logits ``[..., A]`` -> the 32-bit tables the launch reads (numpy): softmax in float64, then ``policy_cdf``."""
+        from .actions import policy_cdf
+        np = self.np
+        z = np.asarray(logits, np.float64)
+        z = np.exp(z - z.max(axis=-1, keepdims=True))
+        return policy_cdf(z / z.sum(axis=-1, keepdims=True))
+
+    def policy_cdf(self):
+        """The table of the current mean logits."""
+        return self.tables(self.mu)
+
+    def step(self):
+        """One generation; returns its ``history`` entry."""
+        np = self.np
+        logits = self.mu + self.sigma * self.rng.standard_normal((self.num_policies, 3, self.nb_actions))
+        tally = self.evaluate(self.tables(logits), self.generation)
+        tally = np.asarray(tally.cpu() if hasattr(tally, "cpu") else tally).astype(np.int64)
+        if tally.shape != (self.num_policies, 5):
+            raise ValueError("evaluate must return a [%d][5] tally, got %s" % (self.num_policies, tally.shape))
+        episodes = tally[:, 0]
+        fitness = np.where(episodes > 0, tally[:, 3] / np.maximum(episodes, 1), -np.inf)
+        elites = logits[np.argsort(-fitness, kind="stable")[:self.num_elites]]
+        self.mu = elites.mean(axis=0)
+        self.sigma = np.maximum(elites.std(axis=0), self.SIGMA_MIN)
+        ran = fitness[episodes > 0]
+        entry = {"generation": self.generation, "fitness": fitness, "mean": float(ran.mean()) if ran.size else float("-inf"),
+                 "best": float(fitness.max())}
+        self.history.append(entry)
+        self.generation += 1
+        return entry
+
+    def fit(self, generations):
+        for _ in range(int(generations)):
+            self.step()
+        return self.history

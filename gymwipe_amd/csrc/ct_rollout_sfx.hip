@@ -1126,6 +1126,100 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_ep(GwState st, GwDevConst 
     gw_ep_flush(s_ep_tally, threadIdx.x, gw_min_u32(64u, N - blockIdx.x * 64u), ea.tally);
 }
 
+// ---- a population of policies in one launch: gw_rollout_population (include/gymwipe_amd.h) ---------------------------------
+// Env e runs policy e / M.  A block is one wave of 64 consecutive envs and M is a multiple of 64 (the launcher refuses any
+// other), so a block has ONE policy, p = blockIdx.x * 64 / M: it stages that policy's [3][A] slice and flushes its episode
+// tally into that policy's row.  ct_rollout_policy_ep's source with nothing stored per step.
+struct PopulationActions {
+    const uint32_t* __restrict__ cdf;                    // the block's policy: [3][A]
+    int64_t* row;                                        // the block's policy: [GW_EP_COLS] of the caller's [P][GW_EP_COLS]
+    uint64_t seed, step0, env0;
+    uint32_t* s_cdf;
+    uint32_t A, md, inv20;
+    uint64_t env_term;
+    int d_cur, du_cur;
+    int32_t latest_next;                                 // what the env acts on next, minus counter_bound
+    EpisodeBook ep;
+    __device__ __forceinline__ void stage(unsigned long long* s_ep) const
+    {
+        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
+        if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
+    }
+    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
+    {
+        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
+        const uint32_t dv = (a * inv20) >> 20;           // (exact: PolicyActions::draw)
+        d_cur = (int)dv;
+        du_cur = (int)(a - dv * md);
+    }
+    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen, int32_t center)
+    {
+        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;   // the stream is the env's, whichever policy it runs
+        latest_next = obs_seen - center;
+        draw(gw_policy_cls(obs_seen, center), step0);
+    }
+    __device__ __forceinline__ void stepped(int k, int K, int32_t latest, uint32_t cause)
+    {
+        latest_next = cause ? 0 : latest;
+        if (k + 1 < K) draw((uint32_t)((int)(latest_next > 0) - (int)(latest_next < 0) + 1), step0 + (uint64_t)(k + 1));
+    }
+};
+
+// p.cdf is [P][3][A] here, pop_tally [P][GW_EP_COLS]; ea.tally the call-wide row (or nullptr), which gets every block's words too:
+// at most 2 * GW_EP_COLS global adds per block.
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_pop_ep(GwState st, GwDevConst c, int K, GwPolicyArgs p, GwEpisodeArgs ea, uint32_t M,
+                                                       int64_t* pop_tally)
+{
+    extern __shared__ uint32_t s_policy_cdf[];
+    __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
+    PopulationActions src;
+    src.md = (uint32_t)c.max_duration;
+    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
+    {
+        const uint32_t pol = (blockIdx.x * 64u) / M;
+        src.cdf = p.cdf + (size_t)pol * 3u * src.A;
+        src.row = pop_tally + (size_t)pol * GW_EP_COLS;
+    }
+    src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
+    src.s_cdf = s_policy_cdf;
+    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
+    src.env_term = 0; src.d_cur = 0; src.du_cur = 0; src.latest_next = 0;
+#define GW_ROLLOUT_SRC_RESETS
+#define GW_ROLLOUT_SRC_STAGE src.stage(s_ep_tally);
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.first(e, p.obs_prev[e], c.counter_bound);
+#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
+#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
+#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) (void)at;
+#define GW_ROLLOUT_SRC_STEPPED(at, latest)
+#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)                                                                                \
+    {                                                                                                                            \
+        const uint32_t cause_next = src.ep.stepped(r, dn);                                                                       \
+        if (cause_next) reset_env();                                                                                             \
+        src.stepped(k, K, latest, cause_next);                                                                                   \
+    }
+#include "ct_rollout_sync_body.h"
+#undef GW_ROLLOUT_SRC_RESETS
+#undef GW_ROLLOUT_SRC_STAGE
+#undef GW_ROLLOUT_SRC_FIRST
+#undef GW_ROLLOUT_SRC_TAKE
+#undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_OUTPUT
+#undef GW_ROLLOUT_SRC_STEPPED
+#undef GW_ROLLOUT_SRC_EPISODE
+    GW_ROLLOUT_STORE_IP
+    ea.obs_next[e] = src.latest_next + c.counter_bound;
+    {
+        GwEpisodeArgs own = ea;                          // (the book adds into LDS whenever there is a tally: here always)
+        own.tally = src.row;
+        src.ep.store(own, e, s_ep_tally);
+    }
+    const uint32_t lanes = gw_min_u32(64u, N - blockIdx.x * 64u);
+    gw_wave_lds_order();
+    gw_ep_flush(s_ep_tally, threadIdx.x, lanes, src.row);
+    gw_ep_flush(s_ep_tally, threadIdx.x, lanes, ea.tally);
+}
+
 // The per-step form's bookkeeping, for handles without the fused kernels: after a step's launch, steps 1-4 and 6 of the
 // semantics for every env -- {age, ret}, ended, the tally, the observation acted on next -- and the mask gw_reset's launch takes.
 __global__ __launch_bounds__(256) void episodes_step_kernel(uint32_t N, int32_t center, GwEpisodeArgs ea, const int32_t* obs,
@@ -1158,6 +1252,50 @@ __global__ __launch_bounds__(256) void episodes_step_kernel(uint32_t N, int32_t 
     }
     __syncthreads();
     if (ea.tally && threadIdx.x < (uint32_t)GW_EP_COLS && s_ep[threadIdx.x]) gw_ts_add(ea.tally + threadIdx.x, s_ep[threadIdx.x]);
+}
+
+// gw_rollout_population's per-step form: the same bookkeeping on the handle's own N-long rows (ended and mask among them), env
+// e's episode into row e / M of pop_tally and into the call-wide ea.tally (or nullptr).  Any M: a block whose 256 envs run one
+// policy sums in LDS and adds its words to both rows; a block that spans policies sums the call-wide words in LDS and sends
+// each ended episode's words to its policy's row directly.
+__global__ __launch_bounds__(256) void episodes_step_pop_kernel(uint32_t N, int32_t center, GwEpisodeArgs ea, uint32_t M, int64_t* pop_tally,
+                                                               const int32_t* obs, const float* reward, const uint8_t* done,
+                                                               uint8_t* ended, uint8_t* mask)
+{
+    __shared__ unsigned long long s_ep[GW_EP_COLS];
+    if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint32_t e0 = blockIdx.x * blockDim.x, e = e0 + threadIdx.x;
+    const uint32_t pol0 = e0 / M;                                               // (e0 < N: the grid is ceil(N / 256) blocks)
+    const bool one_policy = pol0 == gw_min_u32(e0 + blockDim.x - 1u, N - 1u) / M;
+    if (e < N) {
+        int2 s = *reinterpret_cast<const int2*>(ea.state + 2 * (size_t)e);
+        const int32_t r = (int32_t)reward[e];
+        s.x += 1; s.y += r;
+        const uint32_t cause = (ea.on_done != 0 && done[e] != 0) ? 1u : ((ea.max_steps > 0 && s.x >= ea.max_steps) ? 2u : 0u);
+        if (cause) {
+            const unsigned long long v[GW_EP_COLS] = {1ull, cause == 1u ? 1ull : 0ull, (unsigned long long)(int64_t)s.x,
+                                                      (unsigned long long)(int64_t)s.y,
+                                                      (unsigned long long)((int64_t)s.y * (int64_t)s.y)};
+            int64_t* row = pop_tally + (size_t)(e / M) * GW_EP_COLS;
+#pragma unroll
+            for (int j = 0; j < GW_EP_COLS; ++j) {
+                if (!v[j]) continue;
+                if (one_policy || ea.tally) __hip_atomic_fetch_add(s_ep + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (!one_policy) gw_ts_add(row + j, v[j]);
+            }
+            s.x = 0; s.y = 0;
+        }
+        *reinterpret_cast<int2*>(ea.state + 2 * (size_t)e) = s;
+        ended[e] = (uint8_t)cause;
+        mask[e] = (uint8_t)(cause != 0u);
+        ea.obs_next[e] = cause ? center : obs[e];
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)GW_EP_COLS && s_ep[threadIdx.x]) {
+        if (one_policy) gw_ts_add(pop_tally + (size_t)pol0 * GW_EP_COLS + threadIdx.x, s_ep[threadIdx.x]);
+        if (ea.tally) gw_ts_add(ea.tally + threadIdx.x, s_ep[threadIdx.x]);
+    }
 }
 
 // gw_transition_stats: the same table from recorded [K][N] transitions.  A block takes tiles of TS_EVENTS consecutive
@@ -1220,7 +1358,34 @@ __global__ __launch_bounds__(256) void policy_sample_kernel(uint32_t N, uint32_t
     duration_out[e] = (int32_t)(a - dv * md);
 }
 
+// gw_rollout_population's per-step draw: policy_sample_kernel with env e reading table e / M of p.cdf's [P][3][A].
+__global__ __launch_bounds__(256) void policy_sample_pop_kernel(uint32_t N, uint32_t A, uint32_t md, int32_t center, GwPolicyArgs p,
+                                                                uint32_t M, int32_t* __restrict__ device_out,
+                                                                int32_t* __restrict__ duration_out)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const uint32_t cls = gw_policy_cls(p.obs_prev[e], center);
+    const uint32_t* row = p.cdf + ((size_t)(e / M) * 3u + cls) * A;
+    const uint32_t a = gw_policy_count(row, A, gw_policy_u(p.seed, (p.env0 + e) * 0x9E3779B97F4A7C15ull, p.step0));
+    const uint32_t dv = a / md;
+    device_out[e] = (int32_t)dv;
+    duration_out[e] = (int32_t)(a - dv * md);
+}
+
 } // namespace
+
+// One step's draw of gw_rollout_population's per-step form: the handle's action rows from `obs_in`, env e from table e / M.
+int gw_launch_policy_sample_pop(int64_t N, int D, int max_duration, int counter_bound, const gw_population& pop, uint64_t seed,
+                                uint64_t step, uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out,
+                                void* stream)
+{
+    const GwPolicyArgs p = {pop.cdf_dev, obs_in, seed, step, env_id0};
+    hipLaunchKernelGGL(policy_sample_pop_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
+                       (uint32_t)D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound, p, (uint32_t)pop.envs_per_policy,
+                       device_out, duration_out);
+    return gw_launch_status();
+}
 
 // One step's draw of gw_rollout_policy's unfused form (every queue mode): row `step` of the action outputs from `obs_in`.
 int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const uint32_t* cdf, uint64_t seed, uint64_t step,
@@ -1351,6 +1516,41 @@ int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, in
             return gw_launch_status();
         });
     });
+}
+
+// The fused form of gw_rollout_population: gw_launch_rollout_policy_ep_sfx's availability rules, and envs_per_policy a multiple
+// of 64, so that no wave spans two policies.  (The caller has checked num_policies * envs_per_policy == N: every block's policy
+// index is below num_policies.)
+int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const gw_population& pop, uint64_t seed,
+                                 uint64_t step0, uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
+                                 void* stream, bool below_limits, uint64_t* rec)
+{
+    const int64_t A = (int64_t)st.D * cst.max_duration;
+    if (K <= 0 || K > st.rcap || st.ract != nullptr || A > GW_POLICY_A_MAX || pop.envs_per_policy % 64 != 0) return GW_EUNSUPPORTED;
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    const int mode = gw_step_mode(cst, below_limits, false);
+    const GwPolicyArgs p = {pop.cdf_dev, obs_prev, seed, step0, env_id0};
+    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
+    gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
+        gw_with_mode(mode, [&](auto m) {
+            gw_note_launch(rec, GW_LS_ROLLOUT_POP_EP + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
+            hipLaunchKernelGGL((ct_rollout_pop_ep<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64),
+                               (size_t)(3 * A) * sizeof(uint32_t), (hipStream_t)stream, st, cst, K, p, ea,
+                               (uint32_t)pop.envs_per_policy, pop.tally_dev);
+        });
+    });
+    return gw_launch_status();
+}
+
+// One step's episode bookkeeping of gw_rollout_population's per-step form, on the handle's rows.
+int gw_launch_episodes_step_pop(int64_t N, int counter_bound, const gw_episodes& ep, const gw_population& pop, int32_t* obs_next,
+                                const int32_t* obs, const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask,
+                                void* stream)
+{
+    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
+    hipLaunchKernelGGL(episodes_step_pop_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
+                       counter_bound, ea, (uint32_t)pop.envs_per_policy, pop.tally_dev, obs, reward, done, ended, mask);
+    return gw_launch_status();
 }
 
 // The fused form of gw_rollout_autoreset: gw_launch_rollout_policy_ep_sfx's availability rules without the table's (there is

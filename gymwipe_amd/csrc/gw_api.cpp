@@ -76,6 +76,8 @@ struct gw_env {
     uint64_t     launches[GW_LS_COUNT];   // kernel instantiations launched by this handle (gw_selftest_launches)
     GwSfxFns     fns;         // default mode: this handle's step / reset kernels on its device, resolved at gw_create
     uint8_t*     ep_mask;     // [N] gw_rollout_episodes' per-step form: the envs to reset after the step (scratch, not state)
+    int32_t*     pop_rows;    // gw_rollout_population's per-step form: one block of six N-long rows (device, duration, obs, reward
+                              // | done, ended), allocated by the first call that needs them (scratch, not state)
 };
 
 namespace {
@@ -848,6 +850,57 @@ int gw_rollout_autoreset(gw_env* env, int32_t steps, const int32_t* device_dev, 
     return GW_OK;
 }
 
+int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                          const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev, void* stream)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (!pop) return fail(GW_EINVAL, "gw_rollout_population: pop is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!pop->cdf_dev || !pop->tally_dev || !obs_prev_dev || !obs_next_dev)
+        return fail(GW_EINVAL, "gw_rollout_population: NULL device pointer");
+    int rc = check_episodes(ep, "gw_rollout_population");
+    if (rc) return rc;
+    if (pop->num_policies < 1 || pop->envs_per_policy < 1)
+        return fail(GW_EINVAL, "gw_rollout_population: num_policies and envs_per_policy must be >= 1");
+    if (steps == 0) return GW_OK;
+    const int64_t N = env->st.N;
+    if ((int64_t)pop->num_policies * pop->envs_per_policy != N)
+        return fail(GW_EINVAL, "gw_rollout_population: %d policies x %d envs is not the handle's %lld envs", pop->num_policies,
+                    pop->envs_per_policy, (long long)N);
+    if ((rc = select_device(env))) return rc;
+    // step s acts on what obs_next_dev holds after step s - 1 (the caller's obs_prev_dev for the call's first step)
+    auto seen_before = [&](int32_t s) { return s ? (const int32_t*)obs_next_dev : obs_prev_dev; };
+    int32_t s = 0;
+    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (A/B switch: every step through the per-step form)
+        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
+            return gw_launch_rollout_pop_ep_sfx(env->st, env->cst_host, chunk, *pop, seed, step0 + (uint64_t)s0, env_id0, *ep,
+                                                seen_before(s0), obs_next_dev, stream, below, env->launches);
+        });
+        if (rc) return rc;
+    }
+    if (s == steps) return GW_OK;
+    // (what keeps a call from the fused form does not depend on the chunk: s is 0 here, nothing was launched)
+    if (getenv("GW_ROLLOUT_STRICT"))
+        return fail(GW_EUNSUPPORTED, "no fused population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)");
+    if (!env->pop_rows && (rc = dev_alloc(env, &env->pop_rows, (size_t)(4 * N + (N + 1) / 2)))) return rc;   // 4 x 4 N + 2 x N bytes
+    int32_t *device_row = env->pop_rows, *duration_row = device_row + N, *obs_row = duration_row + N;
+    float* reward_row = reinterpret_cast<float*>(obs_row + N);
+    uint8_t *done_row = reinterpret_cast<uint8_t*>(obs_row + 2 * N), *ended_row = done_row + N;
+    for (; s < steps; ++s) {                                   // draw, step, bookkeeping, masked reset
+        if (gw_launch_policy_sample_pop(N, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, *pop, seed,
+                                        step0 + (uint64_t)s, env_id0, seen_before(s), device_row, duration_row, stream))
+            return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
+        if (launch_step(env, device_row, duration_row, obs_row, reward_row, done_row, stream))
+            return fail(GW_EHIP, "step kernel launch failed at step %d", s);
+        gw_env_add_steps(env, 1);
+        if (gw_launch_episodes_step_pop(N, env->cst_host.counter_bound, *ep, *pop, obs_next_dev, obs_row, reward_row, done_row,
+                                        ended_row, env->ep_mask, stream))
+            return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
+        if ((rc = gw_reset(env, env->ep_mask, nullptr, stream))) return rc;
+    }
+    return GW_OK;
+}
+
 int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                               const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
                               int64_t* table_dev, void* stream)
@@ -1158,7 +1211,8 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        static const char* const fam[4] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep"};
+        static const char* const fam[5] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
+                                           "ct_rollout_pop_ep"};
         const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
         snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }

@@ -333,6 +333,17 @@ int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, in
                                     uint8_t* ended, void* stream, bool below_limits, uint64_t* rec);
 int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const uint32_t* cdf, uint64_t seed, uint64_t step,
                             uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, void* stream);
+// gw_rollout_population (ct_rollout_sfx.hip): the fused form -- env e runs policy e / envs_per_policy, nothing stored per step --
+// and the per-step form's draw and bookkeeping on the handle's own rows
+int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const gw_population& pop, uint64_t seed,
+                                 uint64_t step0, uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
+                                 void* stream, bool below_limits, uint64_t* rec);
+int gw_launch_policy_sample_pop(int64_t N, int D, int max_duration, int counter_bound, const gw_population& pop, uint64_t seed,
+                                uint64_t step, uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out,
+                                void* stream);
+int gw_launch_episodes_step_pop(int64_t N, int counter_bound, const gw_episodes& ep, const gw_population& pop, int32_t* obs_next,
+                                const int32_t* obs, const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask,
+                                void* stream);
 int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream);
 int gw_launch_delivered_sfx(const GwState& st, uint32_t* out, void* stream);
 int gw_launch_clear_flags(const GwState& st, void* stream);          // ct_step_sfx.hip (both queue modes)
@@ -355,7 +366,7 @@ int gw_launch_unpack_feedback(int64_t count, int center, int pv, const uint8_t* 
 // Sender counts with a kernel instantiation of their own (template parameter DT; every other count runs DT = 0), one list
 // per kernel family.  Each family's launcher dispatches over its list (gw_dispatch.h) and nothing else restates it.
 #define GW_DTS_STEP          2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_step_sfx_kernel
-#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats, their _ep forms
+#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats, their _ep forms, ct_rollout_pop_ep
 #define GW_DTS_ROLLOUT_LOOP  2, 3, 4, 6, 8, 16, 32          // ct_rollout_sfx_kernel (event loop)
 #define GW_DTS_LIVE          2, 3, 4, 6, 8, 16, 32          // ct_step_live_kernel
 #define GW_DTS_GENERIC       2, 3, 4, 8, 16                 // ct_step_kernel on the table PHY
@@ -379,7 +390,8 @@ enum {
     GW_LS_ROLLOUT_POLICY_EP = GW_LS_ROLLOUT_PSTATS + 3 * GW_LS_NDT,      // ct_rollout_policy_ep<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_PSTATS_EP = GW_LS_ROLLOUT_POLICY_EP + 3 * GW_LS_NDT,   // ct_rollout_pstats_ep<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_SYNC_EP = GW_LS_ROLLOUT_PSTATS_EP + 3 * GW_LS_NDT,     // ct_rollout_sync_ep<DT, MODE>: 3 per DT
-    GW_LS_COUNT = GW_LS_ROLLOUT_SYNC_EP + 3 * GW_LS_NDT
+    GW_LS_ROLLOUT_POP_EP = GW_LS_ROLLOUT_SYNC_EP + 3 * GW_LS_NDT,        // ct_rollout_pop_ep<DT, MODE>: 3 per DT
+    GW_LS_COUNT = GW_LS_ROLLOUT_POP_EP + 3 * GW_LS_NDT
 };
 constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {

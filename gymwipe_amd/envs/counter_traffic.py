@@ -424,9 +424,9 @@ class VecCounterTrafficEnv(BaseEnv):
             self._last = (obs[-1], rew[-1], done[-1])
         return obs, rew, done
 
-    def _policy_table(self, cdf):
+    def _policy_table(self, cdf, population=False):
         """``cdf`` as the 32-bit words gw_rollout_policy reads: [3][A] on this env's GPU (a tensor that already is, is used in
-        place, so a caller may keep rewriting it on the same stream)."""
+        place, so a caller may keep rewriting it on the same stream).  ``population``: [P][3][A], any P >= 1."""
         torch = _torch()
         A = self.num_devices * int(self.config.max_duration)
         if isinstance(cdf, torch.Tensor):
@@ -438,7 +438,10 @@ class VecCounterTrafficEnv(BaseEnv):
                 t = torch.where(t >= (1 << 31), t - (1 << 32), t).to(torch.int32).contiguous()
         else:
             t = torch.from_numpy(np.ascontiguousarray(cdf, dtype=np.uint32).view(np.int32)).to(self.device)
-        if tuple(t.shape) != (3, A):
+        if population:
+            if t.dim() != 3 or t.shape[0] < 1 or tuple(t.shape[1:]) != (3, A):
+                raise ValueError("policy tables must have shape (P, 3, %d), got %s" % (A, tuple(t.shape)))
+        elif tuple(t.shape) != (3, A):
             raise ValueError("policy table must have shape (3, %d), got %s" % (A, tuple(t.shape)))
         return t
 
@@ -686,6 +689,60 @@ class VecCounterTrafficEnv(BaseEnv):
             nat.check(rc)
         self._last = (self._ep_next,) + tuple(self._last[1:])
         return table
+
+    # -- a population of policies in one call (gw_rollout_population) -----------------------------------
+    def rollout_population(self, cdfs, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, tally=None):
+        """``rollout_episodes`` for P policies at once, for a caller that ranks them (gw_rollout_population): ``cdfs`` is
+        ``[P][3][A]`` (``actions.policy_cdf`` of ``[P][3][A]`` probabilities), P divides ``num_envs``, and env ``e`` runs policy
+        ``e // (num_envs // P)`` -- with the draws, state changes, resets and episode bookkeeping ``rollout_episodes`` would give
+        it under that table (the stream is at ``(seed, env_id0 + e, step0 + k)``: ``env_id0`` shifts the stream, not the policy
+        index).  Nothing ``[steps][N]`` is stored.  Returns the ``int64[P][5]`` tally, one ``episode_tally`` row per policy
+        (``population_stats``): a new one of zeros, or the caller's ``tally``, ADDED into.  The episodes are the env's own --
+        ``episode_state``, ``episode_tally`` (which gets every policy's episodes too) and the observation each env acts on next
+        are shared with ``rollout_episodes``, so the calls continue one another; advance ``step0`` by ``steps``.
+        One launch per 64 steps where ``num_envs // P`` is a multiple of 64 on a handle with a fused rollout; otherwise four
+        small launches per step into six N-long rows the handle allocates at its first such call -- same results.  Not for
+        hipGraph capture (``step0`` would be baked in)."""
+        torch = _torch()
+        from ..actions import EP_COLS
+        ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_population")
+        K, n = int(steps), self.num_envs
+        table = self._policy_table(cdfs, population=True)
+        P = int(table.shape[0])
+        if n % P:
+            raise ValueError("rollout_population: %d policies do not divide %d envs" % (P, n))
+        if tally is None:
+            tally = torch.zeros((P, EP_COLS), dtype=torch.int64, device=self.device)
+        elif not (type(tally) is torch.Tensor and tally.dtype is torch.int64 and tally.device == self.device
+                  and tuple(tally.shape) == (P, EP_COLS) and tally.is_contiguous()):
+            raise ValueError("tally must be a contiguous int64 tensor of shape (%d, %d) on %s" % (P, EP_COLS, self.device))
+        pop = nat.Population(P, n // P, table.data_ptr(), tally.data_ptr())
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_rollout_population(self._h, K, C.byref(pop), int(seed) & (2 ** 64 - 1),
+                                                    int(step0) & (2 ** 64 - 1), int(env_id0) & (2 ** 64 - 1), C.byref(ep),
+                                                    prev.data_ptr(), self._ep_next.data_ptr(), self._stream()))
+        if K:
+            self._last = (self._ep_next,) + tuple(self._last[1:])
+        return tally
+
+    @staticmethod
+    def population_stats(tally):
+        """``episode_stats()`` per policy from a ``[P][5]`` tally (``rollout_population``): a dict of tensors of length P on
+        the tally's device -- ``episodes`` and ``by_done`` int64, ``mean_length``, ``mean_return`` and ``return_stderr`` float64,
+        ``nan`` where a policy ended no episode.  No host sync."""
+        torch = _torch()
+        t = torch.as_tensor(tally)
+        if t.dim() != 2 or t.shape[1] != 5:
+            raise ValueError("tally must have shape (P, 5), got %s" % (tuple(t.shape),))
+        n, by_done = t[:, 0], t[:, 1]
+        nf = n.to(torch.float64)
+        nan = torch.full_like(nf, float("nan"))
+        some = n > 0
+        safe = torch.where(some, nf, torch.ones_like(nf))
+        mean = t[:, 3].to(torch.float64) / safe
+        err = ((t[:, 4].to(torch.float64) / safe - mean * mean).clamp(min=0.0) / safe).sqrt()
+        return {"episodes": n, "by_done": by_done, "mean_length": torch.where(some, t[:, 2].to(torch.float64) / safe, nan),
+                "mean_return": torch.where(some, mean, nan), "return_stderr": torch.where(some, err, nan)}
 
     # -- episodes for a caller that chooses the actions (gw_rollout_autoreset) ---------------------------
     def _autoreset(self, K, dev_ptr, dur_ptr, max_steps, on_done, ptrs):

@@ -312,6 +312,37 @@ int gw_rollout_autoreset(gw_env* env, int32_t steps, const int32_t* device_dev, 
                          const gw_episodes* ep, int32_t* obs_next_dev,
                          int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, void* stream);
 
+/* A population of policies on one handle: P tables, M envs each -- what evolution strategies, the cross-entropy method or a
+ * comparison of checkpoints evaluate and rank by episode return. */
+typedef struct gw_population {
+    int32_t num_policies;      /* P >= 1 */
+    int32_t envs_per_policy;   /* M >= 1, P * M == num_envs; env e runs policy e / M (its index in THIS handle) */
+    const uint32_t* cdf_dev;   /* uint32[P][3][A], each [3][A] slice a table as gw_rollout_policy takes it */
+    int64_t* tally_dev;        /* int64[P][GW_EP_COLS], ADDED into (the caller zeroes it; calls accumulate), never NULL */
+} gw_population;
+
+/* gw_rollout_episodes for P policies at once, without its [steps][N] outputs.  For every env e the draws are those of
+ * gw_rollout_episodes called with cdf_dev + (e / M) * 3 * A and otherwise the same arguments -- the hash of (seed, env_id0 + e,
+ * step0 + k): env_id0 shifts the stream, not the policy index -- and so are the state changes, the resets, {age, ret} and
+ * obs_next_dev[e].  pop->tally_dev[p] receives the episode tally of policy p's envs; ep->tally_dev, where not NULL, that of all
+ * envs: the column sums of the per-policy rows.  obs_next_dev may be obs_prev_dev.  max_steps == 0 && on_done == 0 leaves every
+ * tally untouched and gives gw_rollout_policy's trajectory per policy.  Stream-ordered.  Not for hipGraph capture: step0 is
+ * baked into the recorded launch.
+ * Fused form -- a handle that has one for gw_rollout_episodes, M % 64 == 0 (a wave then never spans two policies; a policy may
+ * span many blocks) and GW_ROLLOUT_POLICY_UNFUSED unset: ONE launch per 64 steps (ct_rollout_pop_ep in ct_rollout_sfx.hip), at
+ * most 2 * GW_EP_COLS global adds per block; integer adds commute, so no result depends on their order of arrival.
+ * Per-step form -- any other M, explicit queues, live PHY, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0:
+ * per step a sampling launch, a step launch, a bookkeeping launch and gw_reset's launch with a mask the handle owns -- same
+ * results.  It steps into six N-long scratch rows that the HANDLE owns (device, duration, obs, reward, done, ended): the first
+ * call that takes this form allocates them, and so synchronises the device once; gw_destroy frees them, gw_state_bytes counts
+ * them from then on, a snapshot does not hold them (scratch, not state).  A handle that never takes this form holds nothing
+ * more.  GW_ROLLOUT_STRICT turns the per-step form into GW_EUNSUPPORTED before anything is launched or allocated.
+ * GW_EINVAL before any HIP call: env / pop / ep NULL; a NULL pointer other than ep->tally_dev / stream; steps < 0 or
+ * max_steps < 0; P < 1, M < 1 or P * M != num_envs.  steps == 0 is GW_OK.  The tables are never validated or read back: the
+ * draw's clamp keeps any content memory-safe. */
+int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                          const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev, void* stream);
+
 /* gw_transition_stats for rows recorded by gw_rollout_episodes: step k's observation seen is counter_bound where
  * ended_dev[k - 1] != 0; row 0 uses obs_prev_dev as it is. */
 int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev,
