@@ -547,6 +547,10 @@ __device__ __forceinline__ uint32_t gw_policy_u(uint64_t seed, uint64_t env_term
     z ^= z >> 31;
     return gw_min_u32((uint32_t)z, 0xfffffffeu);
 }
+__device__ __forceinline__ uint64_t gw_policy_env_term(uint64_t env0, uint32_t e)     // env env0 + e's term of the stream
+{
+    return (env0 + e) * 0x9E3779B97F4A7C15ull;
+}
 // #{ j in [0, A) : row[j] <= u } for a non-decreasing row: the upper bound by halving.  Every index read lies in [0, A),
 // whatever the row holds.  gw_policy_count: the draw's action, that count clamped to A - 1.
 template <class ROW>
@@ -574,19 +578,41 @@ __device__ __forceinline__ uint32_t gw_policy_cls(int32_t obs, int32_t center)  
 constexpr int GW_POLICY_A_MAX = GW_MAX_DEVICES * 20;     // flat actions the fused form stages (3 rows of them in LDS)
 constexpr size_t GW_LDS_PER_BLOCK = 65536;               // what one workgroup may allocate, static and dynamic together
 
-struct PolicyActions {
+// What gw_rollout_policy and its descendants pass on to the kernels below besides the outputs.
+struct GwPolicyArgs {
+    const uint32_t* cdf;          // [3][A], A = D * max_duration
+    const int32_t* obs_prev;      // [N] what each env's agent saw last
+    uint64_t seed, step0, env0;
+};
+
+// The closed loop's draw, once for every kernel that has it: the table's LDS copy, the env's stream, the action being taken.
+// A source derives from it and adds what is its own (output pointers, the histogram, the episode's book, the population's row);
+// what a kernel does not use of it (bin_cur without a histogram, latest_next without episodes) the compiler drops.
+struct PolicyDraw {
     const uint32_t* __restrict__ cdf;                    // [3][A]
-    const int32_t* __restrict__ obs_prev;                // [N], apart from every output (the C-ABI's rule: the outputs are
-                                                         // __restrict__ too; rollout_policy() copies a row of its own `out`)
-    int32_t* __restrict__ device_out;
-    int32_t* __restrict__ duration_out;
     uint64_t seed, step0, env0;
     uint32_t* s_cdf;                                     // the table in LDS (the launch's dynamic part: 3 * A words)
     uint32_t A, md, inv20;                               // inv20 = ceil(2^20 / md): a / md == (a * inv20) >> 20 for a < A <= 640
-    int32_t center;
     uint64_t env_term;
+    uint32_t bin_cur;                                    // cls * A + a of the action being taken
     int d_cur, du_cur;
-    __device__ __forceinline__ void stage() const
+    int32_t latest_next;                                 // what the env acts on next, minus counter_bound
+    // The fields every kernel sets from its arguments; D: the kernel's sender count (DT, or c.D where DT == 0).  In two parts,
+    // because a kernel that computes something of its own from A (where the table lies behind a histogram, which policy's
+    // slice a block stages) did so between them, and with inv20's division in front of that its instructions change order.
+    __device__ __forceinline__ void init(const GwPolicyArgs& p, const GwDevConst& c, int D)
+    {
+        cdf = p.cdf; seed = p.seed; step0 = p.step0; env0 = p.env0;
+        md = (uint32_t)c.max_duration;
+        A = (uint32_t)D * md;
+        env_term = 0; bin_cur = 0; d_cur = 0; du_cur = 0; latest_next = 0;
+    }
+    __device__ __forceinline__ void table_at(uint32_t* lds_cdf)
+    {
+        s_cdf = lds_cdf;
+        inv20 = ((1u << 20) + md - 1u) / md;
+    }
+    __device__ __forceinline__ void stage_cdf() const
     {
         for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
     }
@@ -595,24 +621,36 @@ struct PolicyActions {
         const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
         // exact: inv20 * md = 2^20 + r with 0 <= r < md, and a * r < 640 * 320 < 2^20 (md <= A / 2: at least two senders)
         const uint32_t dv = (a * inv20) >> 20;
+        bin_cur = cls * A + a;
         d_cur = (int)dv;
         du_cur = (int)(a - dv * md);
     }
-    __device__ __forceinline__ void first(uint32_t e)
+    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen, int32_t center)
     {
-        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;
-        draw(gw_policy_cls(obs_prev[e], center), step0);
+        env_term = gw_policy_env_term(env0, e);          // the stream is the env's, whichever policy it runs
+        latest_next = obs_seen - center;
+        draw(gw_policy_cls(obs_seen, center), step0);
     }
-    // step k is over: its action goes out with its outputs, the next one is drawn from what the agent now sees
-    __device__ __forceinline__ void stepped(size_t at, int k, int K, int32_t latest)
+    // step k is over and the env now sees `latest` (minus counter_bound; 0 behind a reset): the next action is drawn from that
+    __device__ __forceinline__ void next(int k, int K, int32_t latest)
     {
-        device_out[at] = d_cur;
-        duration_out[at] = du_cur;
-        if (k + 1 < K) draw((uint32_t)((int)(latest > 0) - (int)(latest < 0) + 1), step0 + (uint64_t)(k + 1));
+        latest_next = latest;
+        if (k + 1 < K) draw((uint32_t)((int)(latest_next > 0) - (int)(latest_next < 0) + 1), step0 + (uint64_t)(k + 1));
     }
 };
 
-// step k's three outputs as the C-ABI lays them out: what GW_ROLLOUT_SRC_OUTPUT is for a kernel with obs, reward and done arrays
+// The two ways a step gets its action, as the body's hooks (ct_rollout_sync_body.h).  Staged: the caller's [K][N] rows
+// `device` / `duration`, step k + 1's action requested while step k is walked; such an action may lie outside the action space
+// (GW_FLAG_BADACT).  Drawn: `src`, a PolicyDraw; inside the action space by construction.
+#define GW_ROLLOUT_STAGED_FIRST int d_next = device[e], du_next = duration[e];
+#define GW_ROLLOUT_STAGED_TAKE                                                                                                   \
+    const int d = d_next, du = du_next;                                                                                          \
+    if (k + 1 < K) { d_next = device[(size_t)(k + 1) * N + e]; du_next = duration[(size_t)(k + 1) * N + e]; }
+#define GW_ROLLOUT_STAGED_CHECKED(bad) (bad)
+#define GW_ROLLOUT_DRAWN_TAKE const int d = src.d_cur, du = src.du_cur;
+#define GW_ROLLOUT_DRAWN_CHECKED(bad) false
+
+// step k's three outputs as the C-ABI lays them out: GW_ROLLOUT_SRC_STEPPED's first part in a kernel with obs, reward and done arrays
 #define GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)                                                                              \
     obs[at] = latest + c.counter_bound;                                                                                          \
     reward[at] = (float)r;                                                                                                       \
@@ -624,33 +662,30 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_kernel(GwState st, GwDevCo
                                                             int32_t* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done)
 {
 #define GW_ROLLOUT_SRC_STAGE
-#define GW_ROLLOUT_SRC_FIRST int d_next = device[e], du_next = duration[e];
-#define GW_ROLLOUT_SRC_TAKE /* the next step's action is requested now */                                                        \
-    const int d = d_next, du = du_next;                                                                                          \
-    if (k + 1 < K) { d_next = device[(size_t)(k + 1) * N + e]; du_next = duration[(size_t)(k + 1) * N + e]; }
-#define GW_ROLLOUT_SRC_CHECKED(bad) (bad)                /* a staged action may lie outside the action space (GW_FLAG_BADACT) */
-#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
-#define GW_ROLLOUT_SRC_STEPPED(at, latest)
-#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)
+#define GW_ROLLOUT_SRC_FIRST GW_ROLLOUT_STAGED_FIRST
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_STAGED_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_STAGED_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
 #include "ct_rollout_sync_body.h"
-#undef GW_ROLLOUT_SRC_STAGE
-#undef GW_ROLLOUT_SRC_FIRST
-#undef GW_ROLLOUT_SRC_TAKE
-#undef GW_ROLLOUT_SRC_CHECKED
-#undef GW_ROLLOUT_SRC_OUTPUT
-#undef GW_ROLLOUT_SRC_STEPPED
-#undef GW_ROLLOUT_SRC_EPISODE
 }
 
-// What gw_rollout_policy passes on to the kernels below besides the outputs.
-struct GwPolicyArgs {
-    const uint32_t* cdf;          // [3][A], A = D * max_duration
-    const int32_t* obs_prev;      // [N] what each env's agent saw last
-    uint64_t seed, step0, env0;
+// gw_rollout_policy's source: the draw, and the action taken stored with the step's outputs.
+struct PolicyActions : PolicyDraw {
+    int32_t center;                                      // (c.counter_bound, read at the kernel's entry as it always was: read
+                                                         //  where first() runs, the kernel's argument loads change)
+    int32_t* __restrict__ device_out;
+    int32_t* __restrict__ duration_out;
+    __device__ __forceinline__ void stepped(size_t at, int k, int K, int32_t latest)
+    {
+        device_out[at] = d_cur;
+        duration_out[at] = du_cur;
+        next(k, K, latest);
+    }
 };
 
 // The closed loop in one launch: the same K steps, each env's action drawn from the table's row for the observation its own
-// previous step produced (obs_prev for step 0).  No `_kernel` suffix: the catalogue of tests/test_kernel_variants.py is about
+// previous step produced (obs_prev for step 0; apart from every output -- the C-ABI's rule: the outputs are __restrict__ too,
+// rollout_policy() copies a row of its own `out`).  No `_kernel` suffix: the catalogue of tests/test_kernel_variants.py is about
 // the families it lists; this one's cases are tests/test_rollout_policy.py's.
 template <int DT, int MODE>
 __global__ __launch_bounds__(64) void ct_rollout_policy(GwState st, GwDevConst c, int K, GwPolicyArgs p,
@@ -659,29 +694,16 @@ __global__ __launch_bounds__(64) void ct_rollout_policy(GwState st, GwDevConst c
 {
     extern __shared__ uint32_t s_policy_cdf[];
     PolicyActions src;
-    src.cdf = p.cdf; src.obs_prev = p.obs_prev; src.device_out = device_out; src.duration_out = duration_out;
-    src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
-    src.s_cdf = s_policy_cdf;
-    src.md = (uint32_t)c.max_duration;
-    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
-    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
+    src.init(p, c, DT == 0 ? c.D : DT);
+    src.table_at(s_policy_cdf);
     src.center = c.counter_bound;
-    src.env_term = 0; src.d_cur = 0; src.du_cur = 0;
-#define GW_ROLLOUT_SRC_STAGE src.stage();
-#define GW_ROLLOUT_SRC_FIRST src.first(e);
-#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
-#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
-#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
-#define GW_ROLLOUT_SRC_STEPPED(at, latest) src.stepped(at, k, K, latest);
-#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)
+    src.device_out = device_out; src.duration_out = duration_out;
+#define GW_ROLLOUT_SRC_STAGE src.stage_cdf();
+#define GW_ROLLOUT_SRC_FIRST src.first(e, p.obs_prev[e], src.center);
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_DRAWN_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_DRAWN_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn) src.stepped(at, k, K, latest);
 #include "ct_rollout_sync_body.h"
-#undef GW_ROLLOUT_SRC_STAGE
-#undef GW_ROLLOUT_SRC_FIRST
-#undef GW_ROLLOUT_SRC_TAKE
-#undef GW_ROLLOUT_SRC_CHECKED
-#undef GW_ROLLOUT_SRC_OUTPUT
-#undef GW_ROLLOUT_SRC_STEPPED
-#undef GW_ROLLOUT_SRC_EPISODE
 }
 
 // ---- the tally: gw_rollout_policy_stats and gw_transition_stats (include/gymwipe_amd.h: int64 table[3][A][GW_TS_COLS]) --------
@@ -743,9 +765,18 @@ __device__ __forceinline__ void gw_ts_flush(const uint64_t* hist, uint32_t bins,
                   (w1 >> TS_RS_BITS) & ((1ull << TS_RQ_BITS) - 1u));
     }
 }
+// The block is one wave: its LDS adds and a flush's reads are operations of the same wave, kept in order by the hardware; the
+// fences keep the compiler from moving them, and no block barrier is needed (or possible: lanes beyond N have left).
+__device__ __forceinline__ void gw_wave_lds_order()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // What gw_rollout_policy_stats passes on to ct_rollout_pstats.  obs_prev and obs_last may be one array (an env reads its own
-// element before the step loop and writes it after).
+// element before the step loop and writes it after).  (Not GwPolicyArgs plus three pointers: the kernel's signature is part
+// of its symbol, and its argument layout of its code.)
 struct GwStatsArgs {
     const uint32_t* cdf;          // [3][A]
     const int32_t* obs_prev;      // [N]
@@ -755,37 +786,29 @@ struct GwStatsArgs {
     uint64_t seed, step0, env0;
 };
 
-// PolicyActions' draw without the action stores, and the step's outcome into the histogram instead of three output arrays.
-struct StatsActions {
-    const uint32_t* __restrict__ cdf;
-    uint64_t seed, step0, env0;
-    uint64_t* s_hist;                                    // [3 * A] bins of two words (the launch's dynamic LDS, in front of
-    uint32_t* s_cdf;                                     //  the table's 3 * A words)
-    uint32_t A, md, inv20;
-    int32_t center;
-    uint64_t env_term;
-    uint32_t bin_cur;                                    // cls * A + a of the action being taken
-    int d_cur, du_cur;
-    int32_t ret, latest_last;
+// The draw of a kernel that tallies: the histogram in front of the table's copy in the launch's dynamic LDS -- [3 * A] bins of
+// two words, then 3 * A words.
+struct StatsDraw : PolicyDraw {
+    uint64_t* s_hist;
+    __device__ __forceinline__ void hist_at(uint64_t* dyn)
+    {
+        s_hist = dyn;
+        table_at(reinterpret_cast<uint32_t*>(dyn + 6u * A));
+    }
     __device__ __forceinline__ void stage() const
     {
         for (uint32_t i = threadIdx.x; i < 6u * A; i += blockDim.x) s_hist[i] = 0u;
-        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
+        stage_cdf();
     }
-    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
-    {
-        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
-        const uint32_t dv = (a * inv20) >> 20;           // (exact: PolicyActions::draw)
-        bin_cur = cls * A + a;
-        d_cur = (int)dv;
-        du_cur = (int)(a - dv * md);
-    }
-    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen)
-    {
-        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;
-        draw(gw_policy_cls(obs_seen, center), step0);
-    }
-    // step k is over: one transition of the bin its action was drawn for; the next action from what the agent now sees
+};
+
+// The draw without the action stores, and the step's outcome into the histogram instead of three output arrays.
+struct StatsActions : StatsDraw {
+    int32_t center;                                      // (as PolicyActions')
+    int32_t ret, latest_last;
+    // step k is over: one transition of the bin its action was drawn for; the next action from what the agent now sees.
+    // (Spelled out, not through next(): with latest_next in latest_last's place and the class computed a second time all 30
+    // instantiations of ct_rollout_pstats came out different.)
     __device__ __forceinline__ void stepped(int k, int K, int32_t latest, int32_t r, uint32_t dn)
     {
         const uint32_t next_cls = (uint32_t)((int)(latest > 0) - (int)(latest < 0) + 1);
@@ -796,45 +819,27 @@ struct StatsActions {
     }
 };
 
-// gw_rollout_policy_stats: ct_rollout_policy's closed loop with none of its five output streams.  A block is one wave, so the
-// histogram's adds and the flush's reads are LDS operations of the same wave, which the hardware keeps in order; the fences
-// keep the compiler from moving them, and no block barrier is needed (or possible: lanes beyond N have left).
+// gw_rollout_policy_stats: ct_rollout_policy's closed loop with none of its five output streams.
 template <int DT, int MODE>
 __global__ __launch_bounds__(64) void ct_rollout_pstats(GwState st, GwDevConst c, int K, GwStatsArgs p)
 {
     extern __shared__ uint64_t s_stats_dyn[];
     StatsActions src;
-    src.cdf = p.cdf; src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
-    src.md = (uint32_t)c.max_duration;
-    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
-    src.s_hist = s_stats_dyn;
-    src.s_cdf = reinterpret_cast<uint32_t*>(s_stats_dyn + 6u * src.A);
-    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
+    src.init({p.cdf, p.obs_prev, p.seed, p.step0, p.env0}, c, DT == 0 ? c.D : DT);
+    src.hist_at(s_stats_dyn);
     src.center = c.counter_bound;
-    src.env_term = 0; src.bin_cur = 0; src.d_cur = 0; src.du_cur = 0; src.ret = 0; src.latest_last = 0;
+    src.ret = 0; src.latest_last = 0;
 #define GW_ROLLOUT_SRC_STAGE src.stage();
-#define GW_ROLLOUT_SRC_FIRST src.first(e, p.obs_prev[e]);
-#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
-#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
-#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) (void)at; src.stepped(k, K, latest, r, dn);
-#define GW_ROLLOUT_SRC_STEPPED(at, latest)
-#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)
+#define GW_ROLLOUT_SRC_FIRST src.first(e, p.obs_prev[e], src.center);
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_DRAWN_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_DRAWN_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn) (void)at; src.stepped(k, K, latest, r, dn);
 #include "ct_rollout_sync_body.h"
-#undef GW_ROLLOUT_SRC_STAGE
-#undef GW_ROLLOUT_SRC_FIRST
-#undef GW_ROLLOUT_SRC_TAKE
-#undef GW_ROLLOUT_SRC_CHECKED
-#undef GW_ROLLOUT_SRC_OUTPUT
-#undef GW_ROLLOUT_SRC_STEPPED
-#undef GW_ROLLOUT_SRC_EPISODE
     p.obs_last[e] = src.latest_last + c.counter_bound;
     if (p.ret) p.ret[e] += src.ret;
     // the wave's lanes that have an env (all 64 but in the last block) share the bins out among themselves
-    const uint32_t lanes = gw_min_u32(64u, N - blockIdx.x * 64u);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    gw_ts_flush(src.s_hist, 3u * src.A, threadIdx.x, lanes, p.table);
+    gw_wave_lds_order();
+    gw_ts_flush(src.s_hist, 3u * src.A, threadIdx.x, gw_min_u32(64u, N - blockIdx.x * 64u), p.table);
 }
 
 // ---- episodes inside the closed loop: gw_rollout_episodes / gw_rollout_episodes_stats (include/gymwipe_amd.h) --------------
@@ -885,14 +890,11 @@ struct EpisodeBook {
             if (v[j]) __hip_atomic_fetch_add(s_ep + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 };
-// The block is one wave (as in ct_rollout_pstats): its LDS adds and the flush's reads are operations of the same wave, kept in
-// order by the hardware; the fences keep the compiler from moving them.  Then GW_EP_COLS global adds per block at most.
-__device__ __forceinline__ void gw_wave_lds_order()
+__device__ __forceinline__ void gw_ep_zero(unsigned long long* s_ep)       // the block's tally, before the block's barrier
 {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
 }
+// the block's tally into the caller's: GW_EP_COLS global adds per block at most (behind gw_wave_lds_order)
 __device__ __forceinline__ void gw_ep_flush(const unsigned long long* s_ep, uint32_t first, uint32_t stride, int64_t* tally)
 {
     if (!tally) return;
@@ -900,48 +902,46 @@ __device__ __forceinline__ void gw_ep_flush(const unsigned long long* s_ep, uint
         if (s_ep[j]) gw_ts_add(tally + j, s_ep[j]);
 }
 
-// the `ip` record of an env that may have been reset in the launch (the body's bpc / bpp), behind the body
-#define GW_ROLLOUT_STORE_IP st_plain(st.ip, o16, make_uint4(bpc.t0, bpc.c0, bpp.t0, bpp.c0));
+// What an episodic kernel does with an env behind the body, GW_ROLLOUT_EP_TAIL(own_row, row): the `ip` record of an env that may
+// have been reset in the launch (the body's bpc / bpp), the observation it acts on next, its book, the block's tally.
+// OWN_ROW (ct_rollout_pop_ep): the block's episodes go into `row`, which always exists, and into ea.tally as well where there
+// is one.  A template flag: tested at run time, all 30 instantiations of ct_rollout_pop_ep came out different.
+template <bool OWN_ROW>
+__device__ __forceinline__ void gw_ep_tail(const GwEpisodeArgs& ea, const EpisodeBook& ep, int32_t obs_next, uint32_t e, uint32_t N,
+                                           unsigned long long* s_ep, int64_t* row)
+{
+    ea.obs_next[e] = obs_next;
+    GwEpisodeArgs own = ea;                              // (the book adds into LDS whenever there is a tally)
+    if constexpr (OWN_ROW) own.tally = row;
+    ep.store(own, e, s_ep);
+    // the wave's lanes that have an env (all 64 but in the last block) share the words out among themselves
+    const uint32_t lanes = gw_min_u32(64u, N - blockIdx.x * 64u);
+    gw_wave_lds_order();
+    if constexpr (OWN_ROW) gw_ep_flush(s_ep, threadIdx.x, lanes, row);
+    gw_ep_flush(s_ep, threadIdx.x, lanes, ea.tally);
+}
+#define GW_ROLLOUT_EP_TAIL(own_row, row)                                                                                         \
+    st_plain(st.ip, o16, make_uint4(bpc.t0, bpc.c0, bpp.t0, bpp.c0));                                                            \
+    gw_ep_tail<own_row>(ea, src.ep, src.latest_next + c.counter_bound, e, N, s_ep_tally, row);
+// The head of an episodic kernel's GW_ROLLOUT_SRC_STEPPED: the book takes the step, and an env whose episode ended is reset in
+// registers (the body's reset_env).  Defines cause_next: 0, or why the episode ended.
+#define GW_ROLLOUT_EP_STEPPED(r, dn)                                                                                             \
+    const uint32_t cause_next = src.ep.stepped(r, dn);                                                                           \
+    if (cause_next) reset_env();
 
-// ct_rollout_policy's source without its __restrict__ on obs_prev (it may be obs_next), and with the episode's book: the draw
-// after a step that ended an episode is for the reset's observation, counter_bound (class 1).
-struct EpisodeActions {
-    const uint32_t* __restrict__ cdf;
+// ct_rollout_policy's source with the episode's book (obs_prev may be obs_next here): the draw after a step that ended an
+// episode is for the reset's observation, counter_bound (class 1).
+struct EpisodeActions : PolicyDraw {
     int32_t* device_out;
     int32_t* duration_out;
     uint8_t* ended;
-    uint64_t seed, step0, env0;
-    uint32_t* s_cdf;
-    uint32_t A, md, inv20;
-    uint64_t env_term;
-    int d_cur, du_cur;
-    int32_t latest_next;                                 // what the env acts on next, minus counter_bound
     EpisodeBook ep;
-    __device__ __forceinline__ void stage(unsigned long long* s_ep) const
-    {
-        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
-        if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
-    }
-    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
-    {
-        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
-        const uint32_t dv = (a * inv20) >> 20;           // (exact: PolicyActions::draw)
-        d_cur = (int)dv;
-        du_cur = (int)(a - dv * md);
-    }
-    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen, int32_t center)
-    {
-        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;
-        latest_next = obs_seen - center;
-        draw(gw_policy_cls(obs_seen, center), step0);
-    }
     __device__ __forceinline__ void stepped(size_t at, int k, int K, int32_t latest, uint32_t cause)
     {
         device_out[at] = d_cur;
         duration_out[at] = du_cur;
         ended[at] = (uint8_t)cause;
-        latest_next = cause ? 0 : latest;
-        if (k + 1 < K) draw((uint32_t)((int)(latest_next > 0) - (int)(latest_next < 0) + 1), step0 + (uint64_t)(k + 1));
+        next(k, K, cause ? 0 : latest);
     }
 };
 
@@ -953,80 +953,32 @@ __global__ __launch_bounds__(64) void ct_rollout_policy_ep(GwState st, GwDevCons
     extern __shared__ uint32_t s_policy_cdf[];
     __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
     EpisodeActions src;
-    src.cdf = p.cdf; src.device_out = device_out; src.duration_out = duration_out; src.ended = ended;
-    src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
-    src.s_cdf = s_policy_cdf;
-    src.md = (uint32_t)c.max_duration;
-    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
-    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
-    src.env_term = 0; src.d_cur = 0; src.du_cur = 0; src.latest_next = 0;
+    src.init(p, c, DT == 0 ? c.D : DT);
+    src.table_at(s_policy_cdf);
+    src.device_out = device_out; src.duration_out = duration_out; src.ended = ended;
 #define GW_ROLLOUT_SRC_RESETS
-#define GW_ROLLOUT_SRC_STAGE src.stage(s_ep_tally);
+#define GW_ROLLOUT_SRC_STAGE src.stage_cdf(); gw_ep_zero(s_ep_tally);
 #define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.first(e, p.obs_prev[e], c.counter_bound);
-#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
-#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
-#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
-#define GW_ROLLOUT_SRC_STEPPED(at, latest)
-#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)                                                                                \
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_DRAWN_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_DRAWN_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)                                                                                \
+    GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)                                                                                  \
     {                                                                                                                            \
-        const uint32_t cause_next = src.ep.stepped(r, dn);                                                                       \
-        if (cause_next) reset_env();                                                                                             \
+        GW_ROLLOUT_EP_STEPPED(r, dn)                                                                                             \
         src.stepped(at, k, K, latest, cause_next);                                                                               \
     }
 #include "ct_rollout_sync_body.h"
-#undef GW_ROLLOUT_SRC_RESETS
-#undef GW_ROLLOUT_SRC_STAGE
-#undef GW_ROLLOUT_SRC_FIRST
-#undef GW_ROLLOUT_SRC_TAKE
-#undef GW_ROLLOUT_SRC_CHECKED
-#undef GW_ROLLOUT_SRC_OUTPUT
-#undef GW_ROLLOUT_SRC_STEPPED
-#undef GW_ROLLOUT_SRC_EPISODE
-    GW_ROLLOUT_STORE_IP
-    ea.obs_next[e] = src.latest_next + c.counter_bound;
-    src.ep.store(ea, e, s_ep_tally);
-    gw_wave_lds_order();
-    gw_ep_flush(s_ep_tally, threadIdx.x, gw_min_u32(64u, N - blockIdx.x * 64u), ea.tally);
+    GW_ROLLOUT_EP_TAIL(false, nullptr)
 }
 
 // ct_rollout_pstats' source with the episode's book.  A transition is counted under the class the env acted on (the reset's
 // observation after an episode's end), with the next observation and done the step returned.
-struct EpisodeStatsActions {
-    const uint32_t* __restrict__ cdf;
-    uint64_t seed, step0, env0;
-    uint64_t* s_hist;
-    uint32_t* s_cdf;
-    uint32_t A, md, inv20;
-    uint64_t env_term;
-    uint32_t bin_cur;
-    int d_cur, du_cur;
-    int32_t latest_next;
+struct EpisodeStatsActions : StatsDraw {
     EpisodeBook ep;
-    __device__ __forceinline__ void stage(unsigned long long* s_ep) const
-    {
-        for (uint32_t i = threadIdx.x; i < 6u * A; i += blockDim.x) s_hist[i] = 0u;
-        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
-        if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
-    }
-    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
-    {
-        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
-        const uint32_t dv = (a * inv20) >> 20;           // (exact: PolicyActions::draw)
-        bin_cur = cls * A + a;
-        d_cur = (int)dv;
-        du_cur = (int)(a - dv * md);
-    }
-    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen, int32_t center)
-    {
-        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;
-        latest_next = obs_seen - center;
-        draw(gw_policy_cls(obs_seen, center), step0);
-    }
     __device__ __forceinline__ void stepped(int k, int K, int32_t latest, int32_t r, uint32_t dn, uint32_t cause)
     {
         gw_ts_count(s_hist, bin_cur, (uint32_t)((int)(latest > 0) - (int)(latest < 0) + 1), r, dn);
-        latest_next = cause ? 0 : latest;
-        if (k + 1 < K) draw((uint32_t)((int)(latest_next > 0) - (int)(latest_next < 0) + 1), step0 + (uint64_t)(k + 1));
+        next(k, K, cause ? 0 : latest);
     }
 };
 
@@ -1036,43 +988,23 @@ __global__ __launch_bounds__(64) void ct_rollout_pstats_ep(GwState st, GwDevCons
     extern __shared__ uint64_t s_stats_dyn[];
     __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
     EpisodeStatsActions src;
-    src.cdf = p.cdf; src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
-    src.md = (uint32_t)c.max_duration;
-    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
-    src.s_hist = s_stats_dyn;
-    src.s_cdf = reinterpret_cast<uint32_t*>(s_stats_dyn + 6u * src.A);
-    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
-    src.env_term = 0; src.bin_cur = 0; src.d_cur = 0; src.du_cur = 0; src.latest_next = 0;
+    src.init(p, c, DT == 0 ? c.D : DT);
+    src.hist_at(s_stats_dyn);
 #define GW_ROLLOUT_SRC_RESETS
-#define GW_ROLLOUT_SRC_STAGE src.stage(s_ep_tally);
+#define GW_ROLLOUT_SRC_STAGE src.stage(); gw_ep_zero(s_ep_tally);
 #define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.first(e, p.obs_prev[e], c.counter_bound);
-#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
-#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
-#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) (void)at;
-#define GW_ROLLOUT_SRC_STEPPED(at, latest)
-#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)                                                                                \
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_DRAWN_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_DRAWN_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)                                                                                \
+    (void)at;                                                                                                                    \
     {                                                                                                                            \
-        const uint32_t dn_step = dn, cause_next = src.ep.stepped(r, dn_step);                                                    \
-        if (cause_next) reset_env();                                                                                             \
+        const uint32_t dn_step = dn;                     /* (a reset clears the body's dn) */                                    \
+        GW_ROLLOUT_EP_STEPPED(r, dn_step)                                                                                        \
         src.stepped(k, K, latest, r, dn_step, cause_next);                                                                       \
     }
 #include "ct_rollout_sync_body.h"
-#undef GW_ROLLOUT_SRC_RESETS
-#undef GW_ROLLOUT_SRC_STAGE
-#undef GW_ROLLOUT_SRC_FIRST
-#undef GW_ROLLOUT_SRC_TAKE
-#undef GW_ROLLOUT_SRC_CHECKED
-#undef GW_ROLLOUT_SRC_OUTPUT
-#undef GW_ROLLOUT_SRC_STEPPED
-#undef GW_ROLLOUT_SRC_EPISODE
-    GW_ROLLOUT_STORE_IP
-    ea.obs_next[e] = src.latest_next + c.counter_bound;
-    src.ep.store(ea, e, s_ep_tally);
-    // the wave's lanes that have an env (all 64 but in the last block) share the bins out among themselves
-    const uint32_t lanes = gw_min_u32(64u, N - blockIdx.x * 64u);
-    gw_wave_lds_order();
-    gw_ep_flush(s_ep_tally, threadIdx.x, lanes, ea.tally);
-    gw_ts_flush(src.s_hist, 3u * src.A, threadIdx.x, lanes, table);
+    GW_ROLLOUT_EP_TAIL(false, nullptr)
+    gw_ts_flush(src.s_hist, 3u * src.A, threadIdx.x, gw_min_u32(64u, N - blockIdx.x * 64u), table);
 }
 
 // gw_rollout_autoreset: ct_rollout_sync_kernel's staged source with the episode's book -- the caller chooses the actions, the
@@ -1095,74 +1027,28 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_ep(GwState st, GwDevConst 
     src.ended = ended;
     src.latest_next = 0;
 #define GW_ROLLOUT_SRC_RESETS
-#define GW_ROLLOUT_SRC_STAGE if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep_tally[threadIdx.x] = 0ull;
-#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); int d_next = device[e], du_next = duration[e];
-#define GW_ROLLOUT_SRC_TAKE /* the next step's action is requested now */                                                        \
-    const int d = d_next, du = du_next;                                                                                          \
-    if (k + 1 < K) { d_next = device[(size_t)(k + 1) * N + e]; du_next = duration[(size_t)(k + 1) * N + e]; }
-#define GW_ROLLOUT_SRC_CHECKED(bad) (bad)                /* a staged action may lie outside the action space (GW_FLAG_BADACT) */
-#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)
-#define GW_ROLLOUT_SRC_STEPPED(at, latest)
-#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)                                                                                \
+#define GW_ROLLOUT_SRC_STAGE gw_ep_zero(s_ep_tally);
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); GW_ROLLOUT_STAGED_FIRST
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_STAGED_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_STAGED_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)                                                                                \
+    GW_ROLLOUT_STORE_OUTPUTS(at, latest, r, dn)                                                                                  \
     {                                                                                                                            \
-        const uint32_t cause_next = src.ep.stepped(r, dn);                                                                       \
-        if (cause_next) reset_env();                                                                                             \
+        GW_ROLLOUT_EP_STEPPED(r, dn)                                                                                             \
         src.ended[at] = (uint8_t)cause_next;                                                                                     \
         src.latest_next = cause_next ? 0 : latest;                                                                               \
     }
 #include "ct_rollout_sync_body.h"
-#undef GW_ROLLOUT_SRC_RESETS
-#undef GW_ROLLOUT_SRC_STAGE
-#undef GW_ROLLOUT_SRC_FIRST
-#undef GW_ROLLOUT_SRC_TAKE
-#undef GW_ROLLOUT_SRC_CHECKED
-#undef GW_ROLLOUT_SRC_OUTPUT
-#undef GW_ROLLOUT_SRC_STEPPED
-#undef GW_ROLLOUT_SRC_EPISODE
-    GW_ROLLOUT_STORE_IP
-    ea.obs_next[e] = src.latest_next + c.counter_bound;
-    src.ep.store(ea, e, s_ep_tally);
-    gw_wave_lds_order();
-    gw_ep_flush(s_ep_tally, threadIdx.x, gw_min_u32(64u, N - blockIdx.x * 64u), ea.tally);
+    GW_ROLLOUT_EP_TAIL(false, nullptr)
 }
 
 // ---- a population of policies in one launch: gw_rollout_population (include/gymwipe_amd.h) ---------------------------------
 // Env e runs policy e / M.  A block is one wave of 64 consecutive envs and M is a multiple of 64 (the launcher refuses any
 // other), so a block has ONE policy, p = blockIdx.x * 64 / M: it stages that policy's [3][A] slice and flushes its episode
 // tally into that policy's row.  ct_rollout_policy_ep's source with nothing stored per step.
-struct PopulationActions {
-    const uint32_t* __restrict__ cdf;                    // the block's policy: [3][A]
+struct PopulationActions : PolicyDraw {
     int64_t* row;                                        // the block's policy: [GW_EP_COLS] of the caller's [P][GW_EP_COLS]
-    uint64_t seed, step0, env0;
-    uint32_t* s_cdf;
-    uint32_t A, md, inv20;
-    uint64_t env_term;
-    int d_cur, du_cur;
-    int32_t latest_next;                                 // what the env acts on next, minus counter_bound
     EpisodeBook ep;
-    __device__ __forceinline__ void stage(unsigned long long* s_ep) const
-    {
-        for (uint32_t i = threadIdx.x; i < 3u * A; i += blockDim.x) s_cdf[i] = cdf[i];
-        if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
-    }
-    __device__ __forceinline__ void draw(uint32_t cls, uint64_t step)
-    {
-        const uint32_t a = gw_policy_count(s_cdf + cls * A, A, gw_policy_u(seed, env_term, step));
-        const uint32_t dv = (a * inv20) >> 20;           // (exact: PolicyActions::draw)
-        d_cur = (int)dv;
-        du_cur = (int)(a - dv * md);
-    }
-    __device__ __forceinline__ void first(uint32_t e, int32_t obs_seen, int32_t center)
-    {
-        env_term = (env0 + e) * 0x9E3779B97F4A7C15ull;   // the stream is the env's, whichever policy it runs
-        latest_next = obs_seen - center;
-        draw(gw_policy_cls(obs_seen, center), step0);
-    }
-    __device__ __forceinline__ void stepped(int k, int K, int32_t latest, uint32_t cause)
-    {
-        latest_next = cause ? 0 : latest;
-        if (k + 1 < K) draw((uint32_t)((int)(latest_next > 0) - (int)(latest_next < 0) + 1), step0 + (uint64_t)(k + 1));
-    }
 };
 
 // p.cdf is [P][3][A] here, pop_tally [P][GW_EP_COLS]; ea.tally the call-wide row (or nullptr), which gets every block's words too:
@@ -1174,50 +1060,26 @@ __global__ __launch_bounds__(64) void ct_rollout_pop_ep(GwState st, GwDevConst c
     extern __shared__ uint32_t s_policy_cdf[];
     __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
     PopulationActions src;
-    src.md = (uint32_t)c.max_duration;
-    src.A = (uint32_t)(DT == 0 ? c.D : DT) * src.md;
+    src.init(p, c, DT == 0 ? c.D : DT);
     {
         const uint32_t pol = (blockIdx.x * 64u) / M;
         src.cdf = p.cdf + (size_t)pol * 3u * src.A;
         src.row = pop_tally + (size_t)pol * GW_EP_COLS;
     }
-    src.seed = p.seed; src.step0 = p.step0; src.env0 = p.env0;
-    src.s_cdf = s_policy_cdf;
-    src.inv20 = ((1u << 20) + src.md - 1u) / src.md;
-    src.env_term = 0; src.d_cur = 0; src.du_cur = 0; src.latest_next = 0;
+    src.table_at(s_policy_cdf);
 #define GW_ROLLOUT_SRC_RESETS
-#define GW_ROLLOUT_SRC_STAGE src.stage(s_ep_tally);
+#define GW_ROLLOUT_SRC_STAGE src.stage_cdf(); gw_ep_zero(s_ep_tally);
 #define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.first(e, p.obs_prev[e], c.counter_bound);
-#define GW_ROLLOUT_SRC_TAKE const int d = src.d_cur, du = src.du_cur;
-#define GW_ROLLOUT_SRC_CHECKED(bad) false                /* a drawn action is inside the action space by construction */
-#define GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn) (void)at;
-#define GW_ROLLOUT_SRC_STEPPED(at, latest)
-#define GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)                                                                                \
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_DRAWN_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_DRAWN_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)                                                                                \
+    (void)at;                                                                                                                    \
     {                                                                                                                            \
-        const uint32_t cause_next = src.ep.stepped(r, dn);                                                                       \
-        if (cause_next) reset_env();                                                                                             \
-        src.stepped(k, K, latest, cause_next);                                                                                   \
+        GW_ROLLOUT_EP_STEPPED(r, dn)                                                                                             \
+        src.next(k, K, cause_next ? 0 : latest);                                                                                 \
     }
 #include "ct_rollout_sync_body.h"
-#undef GW_ROLLOUT_SRC_RESETS
-#undef GW_ROLLOUT_SRC_STAGE
-#undef GW_ROLLOUT_SRC_FIRST
-#undef GW_ROLLOUT_SRC_TAKE
-#undef GW_ROLLOUT_SRC_CHECKED
-#undef GW_ROLLOUT_SRC_OUTPUT
-#undef GW_ROLLOUT_SRC_STEPPED
-#undef GW_ROLLOUT_SRC_EPISODE
-    GW_ROLLOUT_STORE_IP
-    ea.obs_next[e] = src.latest_next + c.counter_bound;
-    {
-        GwEpisodeArgs own = ea;                          // (the book adds into LDS whenever there is a tally: here always)
-        own.tally = src.row;
-        src.ep.store(own, e, s_ep_tally);
-    }
-    const uint32_t lanes = gw_min_u32(64u, N - blockIdx.x * 64u);
-    gw_wave_lds_order();
-    gw_ep_flush(s_ep_tally, threadIdx.x, lanes, src.row);
-    gw_ep_flush(s_ep_tally, threadIdx.x, lanes, ea.tally);
+    GW_ROLLOUT_EP_TAIL(true, src.row)
 }
 
 // The per-step form's bookkeeping, for handles without the fused kernels: after a step's launch, steps 1-4 and 6 of the
@@ -1352,7 +1214,7 @@ __global__ __launch_bounds__(256) void policy_sample_kernel(uint32_t N, uint32_t
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     const uint32_t cls = gw_policy_cls(p.obs_prev[e], center);
-    const uint32_t a = gw_policy_count(p.cdf + (size_t)cls * A, A, gw_policy_u(p.seed, (p.env0 + e) * 0x9E3779B97F4A7C15ull, p.step0));
+    const uint32_t a = gw_policy_count(p.cdf + (size_t)cls * A, A, gw_policy_u(p.seed, gw_policy_env_term(p.env0, e), p.step0));
     const uint32_t dv = a / md;
     device_out[e] = (int32_t)dv;
     duration_out[e] = (int32_t)(a - dv * md);
@@ -1367,84 +1229,110 @@ __global__ __launch_bounds__(256) void policy_sample_pop_kernel(uint32_t N, uint
     if (e >= N) return;
     const uint32_t cls = gw_policy_cls(p.obs_prev[e], center);
     const uint32_t* row = p.cdf + ((size_t)(e / M) * 3u + cls) * A;
-    const uint32_t a = gw_policy_count(row, A, gw_policy_u(p.seed, (p.env0 + e) * 0x9E3779B97F4A7C15ull, p.step0));
+    const uint32_t a = gw_policy_count(row, A, gw_policy_u(p.seed, gw_policy_env_term(p.env0, e), p.step0));
     const uint32_t dv = a / md;
     device_out[e] = (int32_t)dv;
     duration_out[e] = (int32_t)(a - dv * md);
 }
 
-} // namespace
+// ---- launching the step-synchronous family (host side) -------------------------------------------------------------------------
+// What a family keeps in the launch's dynamic LDS decides its availability rules beyond the handle's, and that LDS's size.
+enum GwFusedLds {
+    GW_FUSED_NO_TABLE,            // staged actions: nothing
+    GW_FUSED_TABLE,               // the policy table's copy: 3 * A words, for A <= GW_POLICY_A_MAX
+    GW_FUSED_TABLE_HIST           // ... behind a histogram of 3 * A bins: at most TS_STEPS steps, where both fit beside the
+};                                //     kernel's own tables (decided by the handle alone, never by K)
 
-// One step's draw of gw_rollout_population's per-step form: the handle's action rows from `obs_in`, env e from table e / M.
-int gw_launch_policy_sample_pop(int64_t N, int D, int max_duration, int counter_bound, const gw_population& pop, uint64_t seed,
-                                uint64_t step, uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out,
-                                void* stream)
+// No fused launch of K steps on this handle: more steps than its capacity, a handle created for the event-loop form, an action
+// space larger than the table's LDS copy, more steps than the histogram's bit budget.  The caller goes on step by step.
+bool fused_unavailable(const GwState& st, const GwDevConst& cst, int K, GwFusedLds lds)
 {
-    const GwPolicyArgs p = {pop.cdf_dev, obs_in, seed, step, env_id0};
-    hipLaunchKernelGGL(policy_sample_pop_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
-                       (uint32_t)D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound, p, (uint32_t)pop.envs_per_policy,
-                       device_out, duration_out);
-    return gw_launch_status();
+    if (K <= 0 || K > st.rcap || st.ract != nullptr) return true;
+    if (lds != GW_FUSED_NO_TABLE && (int64_t)st.D * cst.max_duration > GW_POLICY_A_MAX) return true;
+    return lds == GW_FUSED_TABLE_HIST && K > (int)TS_STEPS;
 }
 
-// One step's draw of gw_rollout_policy's unfused form (every queue mode): row `step` of the action outputs from `obs_in`.
-int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const uint32_t* cdf, uint64_t seed, uint64_t step,
-                            uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, void* stream)
+// One launch of kernel_of(dt, m) -- the family's instantiation for the handle's sender count and the launch's MODE -- over a
+// grid of 64-lane blocks, recorded in the family's slots from slot_base on.  The kernel's arguments are st, cst, K, args...
+template <class KERNEL_OF, class... ARGS>
+int launch_fused(const GwState& st, const GwDevConst& cst, const GwChunk& ch, int slot_base, GwFusedLds lds, KERNEL_OF kernel_of,
+                 const ARGS&... args)
 {
-    const GwPolicyArgs p = {cdf, obs_in, seed, step, env_id0};
-    hipLaunchKernelGGL(policy_sample_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
-                       (uint32_t)D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound, p, device_out, duration_out);
-    return gw_launch_status();
-}
-
-// The fused form of gw_rollout_policy.  GW_EUNSUPPORTED where there is none -- more steps than the handle's capacity, a handle
-// created for the event-loop form, an action space larger than the table's LDS copy: the caller draws and steps per step.
-int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
-                                 uint64_t env_id0, const int32_t* obs_prev, int32_t* device_out, int32_t* duration_out, int32_t* obs,
-                                 float* reward, uint8_t* done, void* stream, bool below_limits, uint64_t* rec)
-{
-    const int64_t A = (int64_t)st.D * cst.max_duration;
-    if (K <= 0 || K > st.rcap || st.ract != nullptr || A > GW_POLICY_A_MAX) return GW_EUNSUPPORTED;
     const unsigned grid = (unsigned)((st.N + 63) / 64);
-    const int mode = gw_step_mode(cst, below_limits, false);
-    const GwPolicyArgs p = {cdf, obs_prev, seed, step0, env_id0};
-    gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
-        gw_with_mode(mode, [&](auto m) {
-            gw_note_launch(rec, GW_LS_ROLLOUT_POLICY + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
-            hipLaunchKernelGGL((ct_rollout_policy<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64),
-                               (size_t)(3 * A) * sizeof(uint32_t), (hipStream_t)stream, st, cst, K, p, device_out, duration_out, obs, reward, done);
-        });
-    });
-    return gw_launch_status();
-}
-
-// The fused form of gw_rollout_policy_stats; GW_EUNSUPPORTED as above, and where the histogram beside the kernel's own tables
-// does not fit a workgroup's LDS (decided by the handle alone, never by K: a call is refused before its first launch).
-int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
-                                 uint64_t env_id0, const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table,
-                                 void* stream, bool below_limits, uint64_t* rec)
-{
-    const int64_t A = (int64_t)st.D * cst.max_duration;
-    if (K <= 0 || K > st.rcap || K > (int)TS_STEPS || st.ract != nullptr || A > GW_POLICY_A_MAX) return GW_EUNSUPPORTED;
-    const unsigned grid = (unsigned)((st.N + 63) / 64);
-    const int mode = gw_step_mode(cst, below_limits, false);
-    const GwStatsArgs p = {cdf, obs_prev, obs_last, ret, table, seed, step0, env_id0};
-    const size_t dyn = (size_t)(3 * A) * (TS_BIN_BYTES + sizeof(uint32_t));
-    return gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
+    const int mode = gw_step_mode(cst, ch.below_limits, false);
+    const size_t A = (size_t)st.D * (size_t)cst.max_duration;
+    const size_t dyn = lds == GW_FUSED_NO_TABLE ? 0 : 3 * A * (sizeof(uint32_t) + (lds == GW_FUSED_TABLE_HIST ? TS_BIN_BYTES : 0));
+    return gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {          // (any other D: per-lane arrays in LDS)
         return gw_with_mode(mode, [&](auto m) {
             constexpr int DT = decltype(dt)::value, MODE = decltype(m)::value;
-            static const int fixed = [] {                // the instantiation's own LDS (asked once; the same on every device)
-                hipFuncAttributes fa;
-                return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&ct_rollout_pstats<DT, MODE>)) == hipSuccess
-                           ? (int)fa.sharedSizeBytes : -1;
-            }();
-            if (fixed < 0) return gw_launch_status(hipErrorInvalidDeviceFunction);
-            if ((size_t)fixed + dyn > GW_LDS_PER_BLOCK) return (int)GW_EUNSUPPORTED;
-            gw_note_launch(rec, GW_LS_ROLLOUT_PSTATS + 3 * gw_ls_dt(DT) + MODE);
-            hipLaunchKernelGGL((ct_rollout_pstats<DT, MODE>), dim3(grid), dim3(64), dyn, (hipStream_t)stream, st, cst, K, p);
+            const auto kernel = kernel_of(dt, m);
+            if (lds == GW_FUSED_TABLE_HIST) {
+                // The instantiation's own LDS, asked once (the same on every device).  One static per kernel: this generic
+                // lambda is instantiated per (KERNEL_OF, dt, m), and every GW_KERNEL_OF lambda is a type of its own, so
+                // ct_rollout_pstats and ct_rollout_pstats_ep do not share theirs.
+                static const int fixed = [&] {
+                    hipFuncAttributes fa;
+                    return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel)) == hipSuccess ? (int)fa.sharedSizeBytes : -1;
+                }();
+                if (fixed < 0) return gw_launch_status(hipErrorInvalidDeviceFunction);
+                if ((size_t)fixed + dyn > GW_LDS_PER_BLOCK) return (int)GW_EUNSUPPORTED;
+            }
+            gw_note_launch(ch.rec, slot_base + 3 * gw_ls_dt(DT) + MODE);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), dyn, (hipStream_t)ch.stream, st, cst, ch.K, args...);
             return gw_launch_status();
         });
     });
+}
+#define GW_KERNEL_OF(family) [](auto dt, auto m) { return &family<decltype(dt)::value, decltype(m)::value>; }
+
+GwPolicyArgs policy_args(const GwPolicyStream& pol, const int32_t* obs_prev)
+{
+    return {pol.cdf, obs_prev, pol.seed, pol.step0, pol.env_id0};
+}
+GwEpisodeArgs episode_args(const gw_episodes& ep, int32_t* obs_next)
+{
+    return {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
+}
+
+} // namespace
+
+// One step's draw of gw_rollout_population's per-step form: the handle's action rows from `obs_in`, env e from table e / M.
+int gw_launch_policy_sample_pop(int64_t N, int D, int max_duration, int counter_bound, const gw_population& pop,
+                                const GwPolicyStream& pol, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out,
+                                void* stream)
+{
+    hipLaunchKernelGGL(policy_sample_pop_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
+                       (uint32_t)D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound, policy_args(pol, obs_in),
+                       (uint32_t)pop.envs_per_policy, device_out, duration_out);
+    return gw_launch_status();
+}
+
+// One step's draw of gw_rollout_policy's unfused form (every queue mode): row pol.step0 of the action outputs from `obs_in`.
+int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const GwPolicyStream& pol, const int32_t* obs_in,
+                            int32_t* device_out, int32_t* duration_out, void* stream)
+{
+    hipLaunchKernelGGL(policy_sample_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
+                       (uint32_t)D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound, policy_args(pol, obs_in), device_out,
+                       duration_out);
+    return gw_launch_status();
+}
+
+// The fused forms.  Each returns GW_EUNSUPPORTED where there is none (fused_unavailable): the caller draws and steps per step,
+// or -- the two tallying forms -- refuses the call before its first launch.
+int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                 const int32_t* obs_prev, const GwRows& out)
+{
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE)) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POLICY, GW_FUSED_TABLE, GW_KERNEL_OF(ct_rollout_policy), policy_args(pol, obs_prev),
+                        out.device, out.duration, out.obs, out.reward, out.done);
+}
+
+int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                 const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table)
+{
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE_HIST)) return GW_EUNSUPPORTED;
+    const GwStatsArgs p = {pol.cdf, obs_prev, obs_last, ret, table, pol.seed, pol.step0, pol.env_id0};
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_PSTATS, GW_FUSED_TABLE_HIST, GW_KERNEL_OF(ct_rollout_pstats), p);
 }
 
 int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
@@ -1466,80 +1354,33 @@ int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int co
     return gw_launch_status();
 }
 
-// The fused forms of gw_rollout_episodes / gw_rollout_episodes_stats: their parents' launchers and availability rules, with
-// the caller's gw_episodes and obs_next passed on.
-int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
-                                    uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
-                                    int32_t* device_out, int32_t* duration_out, int32_t* obs, float* reward, uint8_t* done,
-                                    uint8_t* ended, void* stream, bool below_limits, uint64_t* rec)
+// gw_rollout_episodes / gw_rollout_episodes_stats: their parents' rules, with the caller's gw_episodes and obs_next passed on.
+int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                    const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, const GwRows& out)
 {
-    const int64_t A = (int64_t)st.D * cst.max_duration;
-    if (K <= 0 || K > st.rcap || st.ract != nullptr || A > GW_POLICY_A_MAX) return GW_EUNSUPPORTED;
-    const unsigned grid = (unsigned)((st.N + 63) / 64);
-    const int mode = gw_step_mode(cst, below_limits, false);
-    const GwPolicyArgs p = {cdf, obs_prev, seed, step0, env_id0};
-    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
-    gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
-        gw_with_mode(mode, [&](auto m) {
-            gw_note_launch(rec, GW_LS_ROLLOUT_POLICY_EP + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
-            hipLaunchKernelGGL((ct_rollout_policy_ep<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64),
-                               (size_t)(3 * A) * sizeof(uint32_t), (hipStream_t)stream, st, cst, K, p, ea, device_out, duration_out, obs,
-                               reward, done, ended);
-        });
-    });
-    return gw_launch_status();
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE)) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POLICY_EP, GW_FUSED_TABLE, GW_KERNEL_OF(ct_rollout_policy_ep),
+                        policy_args(pol, obs_prev), episode_args(ep, obs_next), out.device, out.duration, out.obs, out.reward, out.done,
+                        out.ended);
 }
 
-int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
-                                    uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
-                                    int64_t* table, void* stream, bool below_limits, uint64_t* rec)
+int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                    const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, int64_t* table)
 {
-    const int64_t A = (int64_t)st.D * cst.max_duration;
-    if (K <= 0 || K > st.rcap || K > (int)TS_STEPS || st.ract != nullptr || A > GW_POLICY_A_MAX) return GW_EUNSUPPORTED;
-    const unsigned grid = (unsigned)((st.N + 63) / 64);
-    const int mode = gw_step_mode(cst, below_limits, false);
-    const GwPolicyArgs p = {cdf, obs_prev, seed, step0, env_id0};
-    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
-    const size_t dyn = (size_t)(3 * A) * (TS_BIN_BYTES + sizeof(uint32_t));
-    return gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
-        return gw_with_mode(mode, [&](auto m) {
-            constexpr int DT = decltype(dt)::value, MODE = decltype(m)::value;
-            static const int fixed = [] {                // the instantiation's own LDS (asked once; the same on every device)
-                hipFuncAttributes fa;
-                return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&ct_rollout_pstats_ep<DT, MODE>)) == hipSuccess
-                           ? (int)fa.sharedSizeBytes : -1;
-            }();
-            if (fixed < 0) return gw_launch_status(hipErrorInvalidDeviceFunction);
-            if ((size_t)fixed + dyn > GW_LDS_PER_BLOCK) return (int)GW_EUNSUPPORTED;
-            gw_note_launch(rec, GW_LS_ROLLOUT_PSTATS_EP + 3 * gw_ls_dt(DT) + MODE);
-            hipLaunchKernelGGL((ct_rollout_pstats_ep<DT, MODE>), dim3(grid), dim3(64), dyn, (hipStream_t)stream, st, cst, K, p, ea, table);
-            return gw_launch_status();
-        });
-    });
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE_HIST)) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_PSTATS_EP, GW_FUSED_TABLE_HIST, GW_KERNEL_OF(ct_rollout_pstats_ep),
+                        policy_args(pol, obs_prev), episode_args(ep, obs_next), table);
 }
 
-// The fused form of gw_rollout_population: gw_launch_rollout_policy_ep_sfx's availability rules, and envs_per_policy a multiple
-// of 64, so that no wave spans two policies.  (The caller has checked num_policies * envs_per_policy == N: every block's policy
-// index is below num_policies.)
-int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const gw_population& pop, uint64_t seed,
-                                 uint64_t step0, uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
-                                 void* stream, bool below_limits, uint64_t* rec)
+// gw_rollout_population (pol.cdf: the population's tables): gw_rollout_episodes' rules, and envs_per_policy a multiple of 64, so
+// that no wave spans two policies.  (The caller has checked num_policies * envs_per_policy == N: every block's policy index is
+// below num_policies.)
+int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
+                                 const GwPolicyStream& pol, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next)
 {
-    const int64_t A = (int64_t)st.D * cst.max_duration;
-    if (K <= 0 || K > st.rcap || st.ract != nullptr || A > GW_POLICY_A_MAX || pop.envs_per_policy % 64 != 0) return GW_EUNSUPPORTED;
-    const unsigned grid = (unsigned)((st.N + 63) / 64);
-    const int mode = gw_step_mode(cst, below_limits, false);
-    const GwPolicyArgs p = {pop.cdf_dev, obs_prev, seed, step0, env_id0};
-    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
-    gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
-        gw_with_mode(mode, [&](auto m) {
-            gw_note_launch(rec, GW_LS_ROLLOUT_POP_EP + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
-            hipLaunchKernelGGL((ct_rollout_pop_ep<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64),
-                               (size_t)(3 * A) * sizeof(uint32_t), (hipStream_t)stream, st, cst, K, p, ea,
-                               (uint32_t)pop.envs_per_policy, pop.tally_dev);
-        });
-    });
-    return gw_launch_status();
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE) || pop.envs_per_policy % 64 != 0) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POP_EP, GW_FUSED_TABLE, GW_KERNEL_OF(ct_rollout_pop_ep), policy_args(pol, obs_prev),
+                        episode_args(ep, obs_next), (uint32_t)pop.envs_per_policy, pop.tally_dev);
 }
 
 // One step's episode bookkeeping of gw_rollout_population's per-step form, on the handle's rows.
@@ -1547,64 +1388,52 @@ int gw_launch_episodes_step_pop(int64_t N, int counter_bound, const gw_episodes&
                                 const int32_t* obs, const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask,
                                 void* stream)
 {
-    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
     hipLaunchKernelGGL(episodes_step_pop_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
-                       counter_bound, ea, (uint32_t)pop.envs_per_policy, pop.tally_dev, obs, reward, done, ended, mask);
+                       counter_bound, episode_args(ep, obs_next), (uint32_t)pop.envs_per_policy, pop.tally_dev, obs, reward, done, ended,
+                       mask);
     return gw_launch_status();
 }
 
-// The fused form of gw_rollout_autoreset: gw_launch_rollout_policy_ep_sfx's availability rules without the table's (there is
-// no table), and no dynamic LDS.
-int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
-                                    const gw_episodes& ep, int32_t* obs_next, int32_t* obs, float* reward, uint8_t* done,
-                                    uint8_t* ended, void* stream, bool below_limits, uint64_t* rec)
+// gw_rollout_autoreset: the handle's rules alone (there is no table).
+int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
+                                    const int32_t* duration, const gw_episodes& ep, int32_t* obs_next, const GwRows& out)
 {
-    if (K <= 0 || K > st.rcap || st.ract != nullptr) return GW_EUNSUPPORTED;
-    const unsigned grid = (unsigned)((st.N + 63) / 64);
-    const int mode = gw_step_mode(cst, below_limits, false);
-    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
-    gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {
-        gw_with_mode(mode, [&](auto m) {
-            gw_note_launch(rec, GW_LS_ROLLOUT_SYNC_EP + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
-            hipLaunchKernelGGL((ct_rollout_sync_ep<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64), 0,
-                               (hipStream_t)stream, st, cst, K, ea, device, duration, obs, reward, done, ended);
-        });
-    });
-    return gw_launch_status();
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_NO_TABLE)) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_SYNC_EP, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_sync_ep), episode_args(ep, obs_next),
+                        device, duration, out.obs, out.reward, out.done, out.ended);
 }
 
 // One step's episode bookkeeping of gw_rollout_episodes' per-step form (every queue mode): row `step`'s ended, the mask.
 int gw_launch_episodes_step(int64_t N, int counter_bound, const gw_episodes& ep, int32_t* obs_next, const int32_t* obs,
                             const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask, void* stream)
 {
-    const GwEpisodeArgs ea = {ep.max_steps, ep.on_done, ep.state_dev, ep.tally_dev, obs_next};
     hipLaunchKernelGGL(episodes_step_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
-                       counter_bound, ea, obs, reward, done, ended, mask);
+                       counter_bound, episode_args(ep, obs_next), obs, reward, done, ended, mask);
     return gw_launch_status();
 }
 
-// Returns GW_EUNSUPPORTED when this (D, K) has no fused kernel: the caller falls back to K step launches.
-int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
-                          int32_t* obs, float* reward, uint8_t* done, uint16_t* act_buf, uint8_t* fb_buf, int k_cap, void* stream,
-                          bool below_limits, uint64_t* rec)
+// gw_rollout's launch.  Returns GW_EUNSUPPORTED when this (D, K) has no fused kernel: the caller falls back to K step launches.
+// (Its own availability rule, not fused_unavailable: a handle created for the event-loop form runs the step-synchronous one too
+// when the switch is no longer set.)
+int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device, const int32_t* duration,
+                          const GwRows& out)
 {
-    const int Kp = (K + 15) / 16 * 16;
+    const int K = ch.K, Kp = (K + 15) / 16 * 16, k_cap = st.rcap;
+    uint16_t* const act_buf = st.ract;
+    uint8_t* const fb_buf = st.rfb;
+    int32_t* const obs = out.obs;
+    float* const reward = out.reward;
+    uint8_t* const done = out.done;
     if (K <= 0 || Kp > k_cap) return GW_EUNSUPPORTED;
-    const unsigned grid = (unsigned)((st.N + 63) / 64);
-    const int mode = gw_step_mode(cst, below_limits, false);
-    hipStream_t s = (hipStream_t)stream;
     // A/B switch: the older form -- for handles created while the switch was set (they have its scratch records)
     const bool event_loop = getenv("GW_ROLLOUT_EVENT_LOOP") != nullptr && act_buf != nullptr && fb_buf != nullptr;
-    if (!event_loop) {                                    // the step-synchronous form: the caller's step-major arrays directly
-        gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {             // (any other D: per-lane arrays in LDS)
-            gw_with_mode(mode, [&](auto m) {
-                gw_note_launch(rec, GW_LS_ROLLOUT_SYNC + 3 * gw_ls_dt(decltype(dt)::value) + decltype(m)::value);
-                hipLaunchKernelGGL((ct_rollout_sync_kernel<decltype(dt)::value, decltype(m)::value>), dim3(grid), dim3(64), 0, s,
-                                   st, cst, K, device, duration, obs, reward, done);
-            });
-        });
-        return gw_launch_status();
-    }
+    if (!event_loop)                                      // the step-synchronous form: the caller's step-major arrays directly
+        return launch_fused(st, cst, ch, GW_LS_ROLLOUT_SYNC, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_sync_kernel), device, duration,
+                            obs, reward, done);
+    const unsigned grid = (unsigned)((st.N + 63) / 64);
+    const int mode = gw_step_mode(cst, ch.below_limits, false);
+    hipStream_t s = (hipStream_t)ch.stream;
+    uint64_t* const rec = ch.rec;
     if (cst.max_duration > 0xfe) return GW_EUNSUPPORTED;  // (the event loop's packed action records hold a byte of duration)
     const uint32_t N = (uint32_t)st.N;
     const unsigned g256 = (unsigned)((st.N + TP_ENVS - 1) / TP_ENVS);      // one block per 64-env tile

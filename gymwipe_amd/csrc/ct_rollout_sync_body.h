@@ -12,17 +12,18 @@
 //   GW_ROLLOUT_SRC_FIRST            statements once per lane, before step 0
 //   GW_ROLLOUT_SRC_TAKE             statements at the start of step k that define `const int d, du`, the step's action
 //   GW_ROLLOUT_SRC_CHECKED(bad)     `bad` if an action can lie outside the action space, else false
-//   GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn)   statements that put step k's outcome (index `at` of [K][N] outputs) where the
-//                                   kernel wants it: GW_ROLLOUT_STORE_OUTPUTS, the three stores into the kernel's obs, reward
-//                                   and done, or a tally
-//   GW_ROLLOUT_SRC_STEPPED(at, latest)   statements when step k is over (outputs at index `at`; k not yet advanced)
-//   GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)   the last statements of step k: empty, or the episodic kernels' bookkeeping
-//                                   (ended[at], the next draw).  An includer that defines GW_ROLLOUT_SRC_RESETS may call
-//                                   reset_env() here: gw_reset for this one env, in registers (see there).  Such a kernel
-//                                   stores the env's `ip` record behind the body (GW_ROLLOUT_STORE_IP), which no other does.
+//                                   (ct_rollout_sfx.hip spells both pairs once: GW_ROLLOUT_STAGED_* and GW_ROLLOUT_DRAWN_*)
+//   GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)   the last statements of step k (index `at` of [K][N] outputs; k not yet
+//                                   advanced): its outcome where the kernel wants it -- GW_ROLLOUT_STORE_OUTPUTS, the three
+//                                   stores into the kernel's obs, reward and done, or a tally -- then the action taken, the
+//                                   next draw, the episodic kernels' bookkeeping (ended[at]).  An includer that defines
+//                                   GW_ROLLOUT_SRC_RESETS may call reset_env() here: gw_reset for this one env, in registers
+//                                   (see there).  Such a kernel stores the env's `ip` record behind the body
+//                                   (GW_ROLLOUT_EP_TAIL), which no other does.
 // The hooks share the body's scope.  Of its names they read only e, N, k, K and c, and they define only d and du; whatever else a
 // source keeps lives in names the body leaves free: `src` and anything ending in `_next`.  A new local of the body takes
-// neither form.
+// neither form.  The hooks are one include's: the body's last lines undefine all of them, so an includer defines and never
+// undefines.
     // Actions and outputs in the C-ABI's own step-major layout ([K][N]: a step's row is coalesced across the wave's lanes), read
     // and written by this kernel itself: step k + 1's action is loaded while step k is walked, a step's three outputs are
     // stores nothing waits for.  (The event loop reads packed per-env action records and writes feedback bytes, with a
@@ -144,9 +145,7 @@
 #endif
     auto put_feedback = [&](int32_t latest, int32_t r) {
         const size_t at = (size_t)k * N + e;
-        GW_ROLLOUT_SRC_OUTPUT(at, latest, r, dn)
-        GW_ROLLOUT_SRC_STEPPED(at, latest)
-        GW_ROLLOUT_SRC_EPISODE(at, latest, r, dn)
+        GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)
         k++;
     };
 
@@ -397,3 +396,9 @@
     st_plain(st.tw, o16, make_double2(now, wake));
     st_plain(st.tk, o16, make_uint4(tau, nbp, rvm, (uint32_t)last_abs | (dn << 31)));
     publish_env_counters(st.sa, N, e, kt.pop, kt.deliv, k_bad, fl, (uint32_t)K);
+#undef GW_ROLLOUT_SRC_RESETS
+#undef GW_ROLLOUT_SRC_STAGE
+#undef GW_ROLLOUT_SRC_FIRST
+#undef GW_ROLLOUT_SRC_TAKE
+#undef GW_ROLLOUT_SRC_CHECKED
+#undef GW_ROLLOUT_SRC_STEPPED

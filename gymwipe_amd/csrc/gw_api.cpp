@@ -331,18 +331,17 @@ bool gw_env_below_limits(gw_env* env, void* stream)
     return env->t_bound + env->step_max < env->t_limit;
 }
 
-// The fused part of a rollout (ct_rollout_sfx.hip), shared by gw_rollout and gw_rollout_policy: chunks of up to rcap steps
-// through launch(first step, steps in the chunk, below_limits) while the handle has a fused form; *s = the steps done.  A
-// launcher's GW_EUNSUPPORTED ends it (steps > rollout capacity 0, max_duration > 254, ...): the caller goes on step by step,
-// or, under GW_ROLLOUT_STRICT, fails.
+// The fused part of a rollout (ct_rollout_sfx.hip): chunks of up to rcap steps through launch(first step, the chunk) while the
+// handle has a fused form; *s = the steps done.  A launcher's GW_EUNSUPPORTED ends it (steps > rollout capacity 0,
+// max_duration > 254, ...): the caller goes on step by step, or, under GW_ROLLOUT_STRICT, fails.
 template <class F>
-static int fused_chunks(gw_env* env, int32_t steps, void* stream, int32_t* s, F&& launch, int32_t longest = INT32_MAX)
+static int fused_chunks(gw_env* env, int32_t steps, void* stream, int32_t* s, F&& launch, int32_t longest)
 {
     const int32_t cap = env->st.rcap < longest ? env->st.rcap : longest;       // (a launcher may take fewer steps than rcap)
     while (env->st.tk && !env->dyn && cap > 0 && *s < steps) {
         const int32_t chunk = steps - *s < cap ? steps - *s : cap;
-        const int rc = launch(*s, chunk,
-                              gw_env_below_limits(env, stream) && env->t_bound + (double)(chunk + 1) * env->step_max < env->t_limit);
+        const bool below = gw_env_below_limits(env, stream) && env->t_bound + (double)(chunk + 1) * env->step_max < env->t_limit;
+        const int rc = launch(*s, GwChunk{chunk, stream, below, env->launches});
         if (rc == GW_EUNSUPPORTED) {
             if (getenv("GW_ROLLOUT_STRICT")) return fail(GW_EUNSUPPORTED, "no fused rollout for this handle (GW_ROLLOUT_STRICT is set)");
             break;
@@ -512,6 +511,87 @@ int create_init(gw_env* env)
 
 } // namespace
 
+// ---- the rollout entry points: one set of checks, one skeleton ------------------------------------------------------------------
+static int check_episodes(const gw_episodes* ep, const char* who)
+{
+    if (!ep || !ep->state_dev) return fail(GW_EINVAL, "%s: NULL device pointer", who);
+    if (ep->max_steps < 0) return fail(GW_EINVAL, "%s: max_steps < 0", who);
+    return GW_OK;
+}
+
+// What every one of them checks first, in this order; `who` names the call in its messages.  episodic: the call takes a
+// gw_episodes, ep (which the caller may have left NULL).
+static int rollout_checks(gw_env* env, int32_t steps, bool pointers, const char* who, bool episodic = false,
+                          const gw_episodes* ep = nullptr)
+{
+    if (!env) return fail(GW_EINVAL, "env is NULL");
+    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
+    if (!pointers) return fail(GW_EINVAL, "%s: NULL device pointer", who);
+    return episodic ? check_episodes(ep, who) : GW_OK;
+}
+
+// Behind the checks: the fused form in chunks while the handle has one (fused(first step, GwChunk); `fusable` false: an A/B
+// switch has turned it off), then per_step(s) for every step left -- unless GW_ROLLOUT_STRICT is set and the call has a
+// refusal of its own for that (strict_refusal, the message; nullptr: none).
+template <class FUSED, class STEP>
+static int rollout_drive(gw_env* env, int32_t steps, void* stream, bool fusable, int32_t longest, const char* strict_refusal,
+                         FUSED&& fused, STEP&& per_step)
+{
+    int rc;
+    int32_t s = 0;
+    if (fusable && (rc = fused_chunks(env, steps, stream, &s, fused, longest))) return rc;
+    if (s < steps && strict_refusal && getenv("GW_ROLLOUT_STRICT")) return fail(GW_EUNSUPPORTED, "%s", strict_refusal);
+    for (; s < steps; ++s)
+        if ((rc = per_step(s))) return rc;
+    return GW_OK;
+}
+// The tallying calls have a fused form or none: what that leaves is refused, whatever the environment says.  (What keeps a
+// handle from the fused form does not depend on the chunk: nothing was launched then.)
+template <class FUSED>
+static int rollout_drive_tally(gw_env* env, int32_t steps, void* stream, const char* refusal, FUSED&& fused)
+{
+    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), GW_TS_STEPS, nullptr, fused,
+                         [&](int32_t) { return fail(GW_EUNSUPPORTED, "%s", refusal); });
+}
+
+// One step of the per-step forms: the step's launch on one row of outputs ...
+static int plain_step(gw_env* env, int32_t s, const int32_t* device_row, const int32_t* duration_row, const GwRows& row, void* stream)
+{
+    if (launch_step(env, device_row, duration_row, row.obs, row.reward, row.done, stream))
+        return fail(GW_EHIP, "step kernel launch failed at step %d", s);
+    gw_env_add_steps(env, 1);
+    return GW_OK;
+}
+// ... in front of it the draw of the closed loops, from the observations `seen` (pop: the population's, or nullptr) ...
+static int draw_step(gw_env* env, int32_t s, const GwPolicyStream& pol, const gw_population* pop, const int32_t* seen, const GwRows& row,
+                     void* stream)
+{
+    const int64_t N = env->st.N;
+    const GwDevConst& c = env->cst_host;
+    if (pop ? gw_launch_policy_sample_pop(N, env->st.D, c.max_duration, c.counter_bound, *pop, pol.at(s), seen, row.device, row.duration, stream)
+            : gw_launch_policy_sample(N, env->st.D, c.max_duration, c.counter_bound, pol.at(s), seen, row.device, row.duration, stream))
+        return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
+    return GW_OK;
+}
+// ... and behind it the episodic forms' bookkeeping launch (ended, obs_next, the tally or tallies, the handle's reset mask) and
+// gw_reset's launch with that mask.
+static int episode_step(gw_env* env, int32_t s, const int32_t* device_row, const int32_t* duration_row, const gw_episodes* ep,
+                        const gw_population* pop, int32_t* obs_next_dev, const GwRows& row, void* stream)
+{
+    if (const int rc = plain_step(env, s, device_row, duration_row, row, stream)) return rc;
+    const int64_t N = env->st.N;
+    const int center = env->cst_host.counter_bound;
+    if (pop ? gw_launch_episodes_step_pop(N, center, *ep, *pop, obs_next_dev, row.obs, row.reward, row.done, row.ended, env->ep_mask, stream)
+            : gw_launch_episodes_step(N, center, *ep, obs_next_dev, row.obs, row.reward, row.done, row.ended, env->ep_mask, stream))
+        return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
+    return gw_reset(env, env->ep_mask, nullptr, stream);
+}
+// an episodic call's step s acts on what obs_next_dev holds after step s - 1 (the caller's obs_prev_dev for the call's first step)
+static const int32_t* seen_before(int32_t s, const int32_t* obs_prev_dev, const int32_t* obs_next_dev)
+{
+    return s ? obs_next_dev : obs_prev_dev;
+}
+
 extern "C" {
 
 int gw_abi_version(void) { return GW_ABI_VERSION; }
@@ -651,129 +731,83 @@ int gw_step_fb(gw_env* env, const int32_t* device_dev, const int32_t* duration_d
 int gw_rollout(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
                int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream)
 {
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!device_dev || !duration_dev || !obs_dev || !reward_dev || !done_dev)
-        return fail(GW_EINVAL, "gw_rollout: NULL device pointer");
-    int rc = select_device(env);
-    if (rc) return rc;
+    int rc = rollout_checks(env, steps, device_dev && duration_dev && obs_dev && reward_dev && done_dev, "gw_rollout");
+    if (rc || (rc = select_device(env))) return rc;
     const int64_t N = env->st.N;
-    int32_t s = 0;
-    // fused persistent rollout (ct_rollout_sfx.hip) in chunks of up to rcap steps, when this D has one
-    rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
-        const int64_t o = (int64_t)s0 * N;
-        return gw_launch_rollout_sfx(env->st, env->cst_host, chunk, device_dev + o, duration_dev + o, obs_dev + o,
-                                     reward_dev + o, done_dev + o, env->st.ract, env->st.rfb, env->st.rcap, stream, below,
-                                     env->launches);
-    });
-    if (rc) return rc;
-    for (; s < steps; ++s) {                                   // generic path: one step launch per step
-        const int64_t o = (int64_t)s * N;
-        if (launch_step(env, device_dev + o, duration_dev + o, obs_dev + o, reward_dev + o, done_dev + o, stream))
-            return fail(GW_EHIP, "step kernel launch failed at step %d", s);
-        gw_env_add_steps(env, 1);
-    }
-    return GW_OK;
+    const GwRows out = {nullptr, nullptr, obs_dev, reward_dev, done_dev, nullptr};
+    return rollout_drive(env, steps, stream, true, INT32_MAX, nullptr,
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_sfx(env->st, env->cst_host, ch, device_dev + s0 * N, duration_dev + s0 * N, out.at(s0 * N));
+        },
+        [&](int32_t s) { return plain_step(env, s, device_dev + s * N, duration_dev + s * N, out.at(s * N), stream); });
 }
 
 int gw_rollout_policy(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                       const int32_t* obs_prev_dev, int32_t* device_out_dev, int32_t* duration_out_dev,
                       int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream)
 {
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!cdf_dev || !obs_prev_dev || !device_out_dev || !duration_out_dev || !obs_dev || !reward_dev || !done_dev)
-        return fail(GW_EINVAL, "gw_rollout_policy: NULL device pointer");
-    if (steps == 0) return GW_OK;
-    int rc = select_device(env);
-    if (rc) return rc;
+    int rc = rollout_checks(env, steps, cdf_dev && obs_prev_dev && device_out_dev && duration_out_dev && obs_dev && reward_dev && done_dev,
+                            "gw_rollout_policy");
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
     const int64_t N = env->st.N;
+    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
+    const GwRows out = {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, nullptr};
     // step s acts on the observations of step s - 1: the caller's for the call's first step, this call's own rows afterwards
-    auto seen_before = [&](int32_t s) { return s ? obs_dev + (int64_t)(s - 1) * N : obs_prev_dev; };
-    int32_t s = 0;
-    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (A/B switch: every step through the unfused form)
-        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
-            const int64_t o = (int64_t)s0 * N;
-            return gw_launch_rollout_policy_sfx(env->st, env->cst_host, chunk, cdf_dev, seed, step0 + (uint64_t)s0, env_id0,
-                                                seen_before(s0), device_out_dev + o, duration_out_dev + o, obs_dev + o,
-                                                reward_dev + o, done_dev + o, stream, below, env->launches);
+    auto seen = [&](int32_t s) { return s ? obs_dev + (s - 1) * N : obs_prev_dev; };
+    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        "no fused policy rollout for this handle (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_policy_sfx(env->st, env->cst_host, ch, pol.at(s0), seen(s0), out.at(s0 * N));
+        },
+        [&](int32_t s) {                                       // every other handle: draw, then one step launch, per step
+            const GwRows row = out.at(s * N);
+            if (const int e = draw_step(env, s, pol, nullptr, seen(s), row, stream)) return e;
+            return plain_step(env, s, row.device, row.duration, row, stream);
         });
-        if (rc) return rc;
-    }
-    if (s < steps && getenv("GW_ROLLOUT_STRICT"))
-        return fail(GW_EUNSUPPORTED, "no fused policy rollout for this handle (GW_ROLLOUT_STRICT is set)");
-    for (; s < steps; ++s) {                                   // every other handle: draw, then one step launch, per step
-        const int64_t o = (int64_t)s * N;
-        if (gw_launch_policy_sample(N, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, cdf_dev, seed,
-                                    step0 + (uint64_t)s, env_id0, seen_before(s), device_out_dev + o, duration_out_dev + o, stream))
-            return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
-        if (launch_step(env, device_out_dev + o, duration_out_dev + o, obs_dev + o, reward_dev + o, done_dev + o, stream))
-            return fail(GW_EHIP, "step kernel launch failed at step %d", s);
-        gw_env_add_steps(env, 1);
-    }
-    return GW_OK;
 }
 
 int gw_rollout_policy_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                             const int32_t* obs_prev_dev, int32_t* obs_last_dev, int32_t* return_dev, int64_t* table_dev, void* stream)
 {
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!cdf_dev || !obs_prev_dev || !obs_last_dev || !table_dev)
-        return fail(GW_EINVAL, "gw_rollout_policy_stats: NULL device pointer");
-    if (steps == 0) return GW_OK;
-    int rc = select_device(env);
-    if (rc) return rc;
-    int32_t s = 0;
-    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (the A/B switch leaves no fused form: the caller composes)
-        // a chunk acts on what the one before it left in obs_last_dev
-        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
-            return gw_launch_rollout_pstats_sfx(env->st, env->cst_host, chunk, cdf_dev, seed, step0 + (uint64_t)s0, env_id0,
-                                                s0 ? obs_last_dev : obs_prev_dev, obs_last_dev, return_dev, table_dev, stream,
-                                                below, env->launches);
-        }, GW_TS_STEPS);
-        if (rc) return rc;
-    }
-    // (what keeps a handle from the fused form does not depend on the chunk: s is 0 here, nothing was launched)
-    if (s < steps) return fail(GW_EUNSUPPORTED, "no fused policy rollout for this handle: gw_rollout_policy, then gw_transition_stats");
+    int rc = rollout_checks(env, steps, cdf_dev && obs_prev_dev && obs_last_dev && table_dev, "gw_rollout_policy_stats");
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
+    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
+    return rollout_drive_tally(env, steps, stream, "no fused policy rollout for this handle: gw_rollout_policy, then gw_transition_stats",
+        [&](int32_t s0, const GwChunk& ch) {                   // a chunk acts on what the one before it left in obs_last_dev
+            return gw_launch_rollout_pstats_sfx(env->st, env->cst_host, ch, pol.at(s0), seen_before(s0, obs_prev_dev, obs_last_dev),
+                                                obs_last_dev, return_dev, table_dev);
+        });
+}
+
+// gw_transition_stats and gw_transition_stats_ep (ended_dev: the latter's rows, else nullptr)
+static int transition_stats(gw_env* env, int32_t steps, bool pointers, const char* who, const int32_t* obs_prev_dev,
+                            const int32_t* device_dev, const int32_t* duration_dev, const int32_t* obs_dev, const float* reward_dev,
+                            const uint8_t* done_dev, const uint8_t* ended_dev, int64_t* table_dev, void* stream)
+{
+    int rc = rollout_checks(env, steps, pointers, who);
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
+    if (gw_launch_transition_stats(env->st.N, steps, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, obs_prev_dev,
+                                   device_dev, duration_dev, obs_dev, reward_dev, done_dev, ended_dev, table_dev, stream))
+        return fail(GW_EHIP, "transition statistics kernel launch failed");
     return GW_OK;
 }
 
 int gw_transition_stats(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev, const int32_t* duration_dev,
                         const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev, int64_t* table_dev, void* stream)
 {
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!obs_prev_dev || !device_dev || !duration_dev || !obs_dev || !reward_dev || !done_dev || !table_dev)
-        return fail(GW_EINVAL, "gw_transition_stats: NULL device pointer");
-    if (steps == 0) return GW_OK;
-    int rc = select_device(env);
-    if (rc) return rc;
-    if (gw_launch_transition_stats(env->st.N, steps, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, obs_prev_dev,
-                                   device_dev, duration_dev, obs_dev, reward_dev, done_dev, nullptr, table_dev, stream))
-        return fail(GW_EHIP, "transition statistics kernel launch failed");
-    return GW_OK;
+    return transition_stats(env, steps, obs_prev_dev && device_dev && duration_dev && obs_dev && reward_dev && done_dev && table_dev,
+                            "gw_transition_stats", obs_prev_dev, device_dev, duration_dev, obs_dev, reward_dev, done_dev, nullptr, table_dev,
+                            stream);
 }
 
-static int check_episodes(const gw_episodes* ep, const char* who)
+int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev,
+                           const int32_t* duration_dev, const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                           const uint8_t* ended_dev, int64_t* table_dev, void* stream)
 {
-    if (!ep || !ep->state_dev) return fail(GW_EINVAL, "%s: NULL device pointer", who);
-    if (ep->max_steps < 0) return fail(GW_EINVAL, "%s: max_steps < 0", who);
-    return GW_OK;
-}
-
-// Step s of the per-step episodic forms, behind its action: the step's launch on one row of the outputs, the bookkeeping
-// launch (ended, obs_next, the tally, the handle's reset mask) and gw_reset's launch with that mask.
-static int episode_step(gw_env* env, int32_t s, const int32_t* device_row, const int32_t* duration_row, const gw_episodes* ep,
-                        int32_t* obs_next_dev, int32_t* obs_row, float* reward_row, uint8_t* done_row, uint8_t* ended_row, void* stream)
-{
-    if (launch_step(env, device_row, duration_row, obs_row, reward_row, done_row, stream))
-        return fail(GW_EHIP, "step kernel launch failed at step %d", s);
-    gw_env_add_steps(env, 1);
-    if (gw_launch_episodes_step(env->st.N, env->cst_host.counter_bound, *ep, obs_next_dev, obs_row, reward_row, done_row, ended_row,
-                                env->ep_mask, stream))
-        return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
-    return gw_reset(env, env->ep_mask, nullptr, stream);
+    return transition_stats(env, steps,
+                            obs_prev_dev && device_dev && duration_dev && obs_dev && reward_dev && done_dev && ended_dev && table_dev,
+                            "gw_transition_stats_ep", obs_prev_dev, device_dev, duration_dev, obs_dev, reward_dev, done_dev, ended_dev,
+                            table_dev, stream);
 }
 
 int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
@@ -781,84 +815,51 @@ int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uin
                         int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
                         uint8_t* done_dev, uint8_t* ended_dev, void* stream)
 {
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!cdf_dev || !obs_prev_dev || !obs_next_dev || !device_out_dev || !duration_out_dev || !obs_dev || !reward_dev || !done_dev ||
-        !ended_dev)
-        return fail(GW_EINVAL, "gw_rollout_episodes: NULL device pointer");
-    int rc = check_episodes(ep, "gw_rollout_episodes");
-    if (rc) return rc;
-    if (steps == 0) return GW_OK;
-    if ((rc = select_device(env))) return rc;
+    int rc = rollout_checks(env, steps,
+                            cdf_dev && obs_prev_dev && obs_next_dev && device_out_dev && duration_out_dev && obs_dev && reward_dev &&
+                                done_dev && ended_dev,
+                            "gw_rollout_episodes", true, ep);
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
     const int64_t N = env->st.N;
-    // step s acts on what obs_next_dev holds after step s - 1 (the caller's obs_prev_dev for the call's first step)
-    auto seen_before = [&](int32_t s) { return s ? (const int32_t*)obs_next_dev : obs_prev_dev; };
-    int32_t s = 0;
-    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (A/B switch: every step through the per-step form)
-        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
-            const int64_t o = (int64_t)s0 * N;
-            return gw_launch_rollout_policy_ep_sfx(env->st, env->cst_host, chunk, cdf_dev, seed, step0 + (uint64_t)s0, env_id0, *ep,
-                                                   seen_before(s0), obs_next_dev, device_out_dev + o, duration_out_dev + o,
-                                                   obs_dev + o, reward_dev + o, done_dev + o, ended_dev + o, stream, below,
-                                                   env->launches);
+    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
+    const GwRows out = {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, ended_dev};
+    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        "no fused episodic rollout for this handle (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_policy_ep_sfx(env->st, env->cst_host, ch, pol.at(s0), *ep, seen_before(s0, obs_prev_dev, obs_next_dev),
+                                                   obs_next_dev, out.at(s0 * N));
+        },
+        [&](int32_t s) {                                       // every other handle: draw, step, bookkeeping, masked reset
+            const GwRows row = out.at(s * N);
+            if (const int e = draw_step(env, s, pol, nullptr, seen_before(s, obs_prev_dev, obs_next_dev), row, stream)) return e;
+            return episode_step(env, s, row.device, row.duration, ep, nullptr, obs_next_dev, row, stream);
         });
-        if (rc) return rc;
-    }
-    if (s < steps && getenv("GW_ROLLOUT_STRICT"))
-        return fail(GW_EUNSUPPORTED, "no fused episodic rollout for this handle (GW_ROLLOUT_STRICT is set)");
-    for (; s < steps; ++s) {                                   // every other handle: draw, step, bookkeeping, masked reset
-        const int64_t o = (int64_t)s * N;
-        if (gw_launch_policy_sample(N, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, cdf_dev, seed,
-                                    step0 + (uint64_t)s, env_id0, seen_before(s), device_out_dev + o, duration_out_dev + o, stream))
-            return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
-        if ((rc = episode_step(env, s, device_out_dev + o, duration_out_dev + o, ep, obs_next_dev, obs_dev + o, reward_dev + o,
-                               done_dev + o, ended_dev + o, stream)))
-            return rc;
-    }
-    return GW_OK;
 }
 
 int gw_rollout_autoreset(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
                          const gw_episodes* ep, int32_t* obs_next_dev,
                          int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, void* stream)
 {
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!device_dev || !duration_dev || !obs_next_dev || !obs_dev || !reward_dev || !done_dev || !ended_dev)
-        return fail(GW_EINVAL, "gw_rollout_autoreset: NULL device pointer");
-    int rc = check_episodes(ep, "gw_rollout_autoreset");
-    if (rc) return rc;
-    if (steps == 0) return GW_OK;
-    if ((rc = select_device(env))) return rc;
+    int rc = rollout_checks(env, steps, device_dev && duration_dev && obs_next_dev && obs_dev && reward_dev && done_dev && ended_dev,
+                            "gw_rollout_autoreset", true, ep);
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
     const int64_t N = env->st.N;
-    int32_t s = 0;
-    rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
-        const int64_t o = (int64_t)s0 * N;
-        return gw_launch_rollout_autoreset_sfx(env->st, env->cst_host, chunk, device_dev + o, duration_dev + o, *ep, obs_next_dev,
-                                               obs_dev + o, reward_dev + o, done_dev + o, ended_dev + o, stream, below,
-                                               env->launches);
-    });
-    if (rc) return rc;
-    if (s < steps && getenv("GW_ROLLOUT_STRICT"))
-        return fail(GW_EUNSUPPORTED, "no fused autoreset rollout for this handle (GW_ROLLOUT_STRICT is set)");
-    for (; s < steps; ++s) {                                   // every other handle: step, bookkeeping, masked reset
-        const int64_t o = (int64_t)s * N;
-        if ((rc = episode_step(env, s, device_dev + o, duration_dev + o, ep, obs_next_dev, obs_dev + o, reward_dev + o, done_dev + o,
-                               ended_dev + o, stream)))
-            return rc;
-    }
-    return GW_OK;
+    const GwRows out = {nullptr, nullptr, obs_dev, reward_dev, done_dev, ended_dev};
+    return rollout_drive(env, steps, stream, true, INT32_MAX, "no fused autoreset rollout for this handle (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_autoreset_sfx(env->st, env->cst_host, ch, device_dev + s0 * N, duration_dev + s0 * N, *ep, obs_next_dev,
+                                                   out.at(s0 * N));
+        },
+        [&](int32_t s) {                                       // every other handle: step, bookkeeping, masked reset
+            return episode_step(env, s, device_dev + s * N, duration_dev + s * N, ep, nullptr, obs_next_dev, out.at(s * N), stream);
+        });
 }
 
 int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
                           const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev, void* stream)
 {
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (!pop) return fail(GW_EINVAL, "gw_rollout_population: pop is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!pop->cdf_dev || !pop->tally_dev || !obs_prev_dev || !obs_next_dev)
-        return fail(GW_EINVAL, "gw_rollout_population: NULL device pointer");
-    int rc = check_episodes(ep, "gw_rollout_population");
+    if (env && !pop) return fail(GW_EINVAL, "gw_rollout_population: pop is NULL");
+    int rc = rollout_checks(env, steps, pop && pop->cdf_dev && pop->tally_dev && obs_prev_dev && obs_next_dev, "gw_rollout_population", true, ep);
     if (rc) return rc;
     if (pop->num_policies < 1 || pop->envs_per_policy < 1)
         return fail(GW_EINVAL, "gw_rollout_population: num_policies and envs_per_policy must be >= 1");
@@ -868,81 +869,39 @@ int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, 
         return fail(GW_EINVAL, "gw_rollout_population: %d policies x %d envs is not the handle's %lld envs", pop->num_policies,
                     pop->envs_per_policy, (long long)N);
     if ((rc = select_device(env))) return rc;
-    // step s acts on what obs_next_dev holds after step s - 1 (the caller's obs_prev_dev for the call's first step)
-    auto seen_before = [&](int32_t s) { return s ? (const int32_t*)obs_next_dev : obs_prev_dev; };
-    int32_t s = 0;
-    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (A/B switch: every step through the per-step form)
-        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
-            return gw_launch_rollout_pop_ep_sfx(env->st, env->cst_host, chunk, *pop, seed, step0 + (uint64_t)s0, env_id0, *ep,
-                                                seen_before(s0), obs_next_dev, stream, below, env->launches);
+    const GwPolicyStream pol = {pop->cdf_dev, seed, step0, env_id0};
+    GwRows row = {};                                           // the per-step form's own N-long rows, allocated when it first runs
+    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        "no fused population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_pop_ep_sfx(env->st, env->cst_host, ch, *pop, pol.at(s0), *ep, seen_before(s0, obs_prev_dev, obs_next_dev),
+                                                obs_next_dev);
+        },
+        [&](int32_t s) {                                       // draw, step, bookkeeping, masked reset
+            if (!row.obs) {
+                if (!env->pop_rows)                              // 4 x 4 N + 2 x N bytes
+                    if (const int e = dev_alloc(env, &env->pop_rows, (size_t)(4 * N + (N + 1) / 2))) return e;
+                int32_t* const r = env->pop_rows;
+                row = {r, r + N, r + 2 * N, reinterpret_cast<float*>(r + 3 * N), reinterpret_cast<uint8_t*>(r + 4 * N),
+                       reinterpret_cast<uint8_t*>(r + 4 * N) + N};
+            }
+            if (const int e = draw_step(env, s, pol, pop, seen_before(s, obs_prev_dev, obs_next_dev), row, stream)) return e;
+            return episode_step(env, s, row.device, row.duration, ep, pop, obs_next_dev, row, stream);
         });
-        if (rc) return rc;
-    }
-    if (s == steps) return GW_OK;
-    // (what keeps a call from the fused form does not depend on the chunk: s is 0 here, nothing was launched)
-    if (getenv("GW_ROLLOUT_STRICT"))
-        return fail(GW_EUNSUPPORTED, "no fused population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)");
-    if (!env->pop_rows && (rc = dev_alloc(env, &env->pop_rows, (size_t)(4 * N + (N + 1) / 2)))) return rc;   // 4 x 4 N + 2 x N bytes
-    int32_t *device_row = env->pop_rows, *duration_row = device_row + N, *obs_row = duration_row + N;
-    float* reward_row = reinterpret_cast<float*>(obs_row + N);
-    uint8_t *done_row = reinterpret_cast<uint8_t*>(obs_row + 2 * N), *ended_row = done_row + N;
-    for (; s < steps; ++s) {                                   // draw, step, bookkeeping, masked reset
-        if (gw_launch_policy_sample_pop(N, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, *pop, seed,
-                                        step0 + (uint64_t)s, env_id0, seen_before(s), device_row, duration_row, stream))
-            return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
-        if (launch_step(env, device_row, duration_row, obs_row, reward_row, done_row, stream))
-            return fail(GW_EHIP, "step kernel launch failed at step %d", s);
-        gw_env_add_steps(env, 1);
-        if (gw_launch_episodes_step_pop(N, env->cst_host.counter_bound, *ep, *pop, obs_next_dev, obs_row, reward_row, done_row,
-                                        ended_row, env->ep_mask, stream))
-            return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
-        if ((rc = gw_reset(env, env->ep_mask, nullptr, stream))) return rc;
-    }
-    return GW_OK;
 }
 
 int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                               const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
                               int64_t* table_dev, void* stream)
 {
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!cdf_dev || !obs_prev_dev || !obs_next_dev || !table_dev)
-        return fail(GW_EINVAL, "gw_rollout_episodes_stats: NULL device pointer");
-    int rc = check_episodes(ep, "gw_rollout_episodes_stats");
-    if (rc) return rc;
-    if (steps == 0) return GW_OK;
-    if ((rc = select_device(env))) return rc;
-    int32_t s = 0;
-    if (!getenv("GW_ROLLOUT_POLICY_UNFUSED")) {                // (the A/B switch leaves no fused form: the caller composes)
-        rc = fused_chunks(env, steps, stream, &s, [&](int32_t s0, int32_t chunk, bool below) {
-            return gw_launch_rollout_pstats_ep_sfx(env->st, env->cst_host, chunk, cdf_dev, seed, step0 + (uint64_t)s0, env_id0, *ep,
-                                                   s0 ? (const int32_t*)obs_next_dev : obs_prev_dev, obs_next_dev, table_dev, stream,
-                                                   below, env->launches);
-        }, GW_TS_STEPS);
-        if (rc) return rc;
-    }
-    // (what keeps a handle from the fused form does not depend on the chunk: s is 0 here, nothing was launched)
-    if (s < steps)
-        return fail(GW_EUNSUPPORTED, "no fused episodic rollout for this handle: gw_rollout_episodes, then gw_transition_stats_ep");
-    return GW_OK;
-}
-
-int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev,
-                           const int32_t* duration_dev, const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev,
-                           const uint8_t* ended_dev, int64_t* table_dev, void* stream)
-{
-    if (!env) return fail(GW_EINVAL, "env is NULL");
-    if (steps < 0) return fail(GW_EINVAL, "steps < 0");
-    if (!obs_prev_dev || !device_dev || !duration_dev || !obs_dev || !reward_dev || !done_dev || !ended_dev || !table_dev)
-        return fail(GW_EINVAL, "gw_transition_stats_ep: NULL device pointer");
-    if (steps == 0) return GW_OK;
-    int rc = select_device(env);
-    if (rc) return rc;
-    if (gw_launch_transition_stats(env->st.N, steps, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, obs_prev_dev,
-                                   device_dev, duration_dev, obs_dev, reward_dev, done_dev, ended_dev, table_dev, stream))
-        return fail(GW_EHIP, "transition statistics kernel launch failed");
-    return GW_OK;
+    int rc = rollout_checks(env, steps, cdf_dev && obs_prev_dev && obs_next_dev && table_dev, "gw_rollout_episodes_stats", true, ep);
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
+    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
+    return rollout_drive_tally(env, steps, stream, "no fused episodic rollout for this handle: gw_rollout_episodes, then gw_transition_stats_ep",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_pstats_ep_sfx(env->st, env->cst_host, ch, pol.at(s0), *ep, seen_before(s0, obs_prev_dev, obs_next_dev),
+                                                   obs_next_dev, table_dev);
+        });
 }
 
 int gw_delivered(gw_env* env, uint32_t* out_dev, void* stream)

@@ -300,47 +300,57 @@ int gw_launch_step_sfx(const GwState& st, const GwDevConst& cst, const int32_t* 
                        uint64_t* rec, const GwSfxFns* fns);
 int gw_launch_reset_sfx(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream, const GwSfxFns* fns);
 int gw_launch_init_sfx(const GwState& st, void* stream);
-int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
-                          int32_t* obs, float* reward, uint8_t* done, uint16_t* act_buf, uint8_t* fb_buf, int k_cap, void* stream,
-                          bool below_limits, uint64_t* rec);
-// gw_rollout_policy (ct_rollout_sfx.hip): the fused form, and one step's draw of the unfused one
-int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
-                                 uint64_t env_id0, const int32_t* obs_prev, int32_t* device_out, int32_t* duration_out, int32_t* obs,
-                                 float* reward, uint8_t* done, void* stream, bool below_limits, uint64_t* rec);
-// gw_rollout_policy_stats / gw_transition_stats (ct_rollout_sfx.hip): the fused form, and the table from recorded transitions
+// The rollout launchers (ct_rollout_sfx.hip).  What a call passes to every one of its launches travels as three small values:
+struct GwChunk {                        // one launch of a call: its steps, where it goes, what the host knows about it
+    int K;
+    void* stream;
+    bool below_limits;                  // (gw_env_below_limits, for all K steps)
+    uint64_t* rec;                      // the handle's launch record, or nullptr
+};
+struct GwPolicyStream {                 // the policy a closed loop draws from, and the identity of its action stream
+    const uint32_t* cdf;                // [3][A] (gw_rollout_population: [P][3][A])
+    uint64_t seed, step0, env_id0;      // step0: of the launch's (or the per-step draw's) first step
+    GwPolicyStream at(int32_t s) const { return {cdf, seed, step0 + (uint64_t)s, env_id0}; }
+};
+struct GwRows {                         // a call's [K][N] outputs; a member a call does not have is nullptr
+    int32_t *device, *duration;         // the actions drawn (the closed loops)
+    int32_t* obs; float* reward; uint8_t* done;
+    uint8_t* ended;                     // the episodic calls
+    GwRows at(int64_t o) const          // the rows from element o on
+    {
+        return {device ? device + o : nullptr, duration ? duration + o : nullptr, obs + o, reward + o, done + o, ended ? ended + o : nullptr};
+    }
+};
+// Each fused form returns GW_EUNSUPPORTED where the handle (or the call) has none; the per-step forms' launches follow.
+int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device, const int32_t* duration,
+                          const GwRows& out);                                                       // gw_rollout
+int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                 const int32_t* obs_prev, const GwRows& out);                       // gw_rollout_policy
 #define GW_TS_STEPS 64                  // steps per ct_rollout_pstats launch at most: its LDS histogram's bit budget (ct_rollout_sfx.hip)
-int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
-                                 uint64_t env_id0, const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table,
-                                 void* stream, bool below_limits, uint64_t* rec);
+int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                 const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table);   // gw_rollout_policy_stats
+int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                    const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, const GwRows& out);   // gw_rollout_episodes
+int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                    const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, int64_t* table);   // gw_rollout_episodes_stats
+int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
+                                    const int32_t* duration, const gw_episodes& ep, int32_t* obs_next, const GwRows& out);   // gw_rollout_autoreset
+// gw_rollout_population: env e runs policy e / envs_per_policy (pol.cdf: the population's tables), nothing stored per step
+int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
+                                 const GwPolicyStream& pol, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next);
+// the table from recorded transitions (ended: nullptr, or gw_transition_stats_ep's rows)
 int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
                                const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
-                               const uint8_t* done, const uint8_t* ended, int64_t* table, void* stream);   // ended: nullptr, or
-                                                                                    // gw_transition_stats_ep's rows
-// gw_rollout_episodes / gw_rollout_episodes_stats (ct_rollout_sfx.hip): the fused forms, and one step's bookkeeping of the
-// per-step form (ended, the handle's reset mask, obs_next)
-int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
-                                    uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
-                                    int32_t* device_out, int32_t* duration_out, int32_t* obs, float* reward, uint8_t* done,
-                                    uint8_t* ended, void* stream, bool below_limits, uint64_t* rec);
-int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const uint32_t* cdf, uint64_t seed, uint64_t step0,
-                                    uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
-                                    int64_t* table, void* stream, bool below_limits, uint64_t* rec);
+                               const uint8_t* done, const uint8_t* ended, int64_t* table, void* stream);
+// one step of the per-step forms: the draw for step pol.step0 from `obs_in`, and the episodes' bookkeeping behind the step's
+// launch (ended, the handle's reset mask, obs_next); _pop: on the handle's own rows, env e from table / into row e / envs_per_policy
+int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const GwPolicyStream& pol, const int32_t* obs_in,
+                            int32_t* device_out, int32_t* duration_out, void* stream);
+int gw_launch_policy_sample_pop(int64_t N, int D, int max_duration, int counter_bound, const gw_population& pop,
+                                const GwPolicyStream& pol, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out,
+                                void* stream);
 int gw_launch_episodes_step(int64_t N, int counter_bound, const gw_episodes& ep, int32_t* obs_next, const int32_t* obs,
                             const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask, void* stream);
-// gw_rollout_autoreset (ct_rollout_sfx.hip): the fused form -- staged actions, episodes inside the launch
-int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, int K, const int32_t* device, const int32_t* duration,
-                                    const gw_episodes& ep, int32_t* obs_next, int32_t* obs, float* reward, uint8_t* done,
-                                    uint8_t* ended, void* stream, bool below_limits, uint64_t* rec);
-int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const uint32_t* cdf, uint64_t seed, uint64_t step,
-                            uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, void* stream);
-// gw_rollout_population (ct_rollout_sfx.hip): the fused form -- env e runs policy e / envs_per_policy, nothing stored per step --
-// and the per-step form's draw and bookkeeping on the handle's own rows
-int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, int K, const gw_population& pop, uint64_t seed,
-                                 uint64_t step0, uint64_t env_id0, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next,
-                                 void* stream, bool below_limits, uint64_t* rec);
-int gw_launch_policy_sample_pop(int64_t N, int D, int max_duration, int counter_bound, const gw_population& pop, uint64_t seed,
-                                uint64_t step, uint64_t env_id0, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out,
-                                void* stream);
 int gw_launch_episodes_step_pop(int64_t N, int counter_bound, const gw_episodes& ep, const gw_population& pop, int32_t* obs_next,
                                 const int32_t* obs, const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask,
                                 void* stream);

@@ -413,9 +413,7 @@ class VecCounterTrafficEnv(BaseEnv):
         K = dev.shape[0]
         assert dev.shape == (K, self.num_envs) and dur.shape == dev.shape
         if out is None:
-            out = (torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device),
-                   torch.empty((K, self.num_envs), dtype=torch.float32, device=self.device),
-                   torch.empty((K, self.num_envs), dtype=torch.uint8, device=self.device))
+            out = self._rows(K, (torch.int32, torch.float32, torch.uint8), None)
         obs, rew, done = out
         with torch.cuda.device(self.device):
             nat.check(self._L.gw_rollout(self._h, K, dev.data_ptr(), dur.data_ptr(), obs.data_ptr(),
@@ -445,6 +443,62 @@ class VecCounterTrafficEnv(BaseEnv):
             raise ValueError("policy table must have shape (3, %d), got %s" % (A, tuple(t.shape)))
         return t
 
+    # -- what the closed-loop calls share ------------------------------------------------------------
+    def _obs_prev(self, obs_prev, who):
+        """The checked ``obs_prev`` int32[N] on this env's GPU (default: what the env returned last)."""
+        if obs_prev is None:
+            obs_prev = self._last[0]
+            if obs_prev is None:
+                raise ValueError("%s: no observation yet -- reset() or step() first, or pass obs_prev" % who)
+        n = self.num_envs
+        prev = _torch().as_tensor(obs_prev).to(device=self.device, dtype=_torch().int32).contiguous()
+        if prev.shape != (n,):
+            raise ValueError("obs_prev must have shape (%d,), got %s" % (n, tuple(prev.shape)))
+        return prev
+
+    def _rows(self, K, kinds, out):
+        """A call's ``[K][N]`` outputs, one per dtype of ``kinds``: the caller's ``out``, checked, or new tensors."""
+        n = self.num_envs
+        if out is None:
+            out = tuple(_torch().empty((K, n), dtype=dt, device=self.device) for dt in kinds)
+        for t, dt in zip(out, kinds):
+            assert t.dtype is dt and tuple(t.shape) == (K, n) and t.is_contiguous() and t.device == self.device
+        return tuple(out)
+
+    @staticmethod
+    def _apart(prev, out):
+        """``prev``, or a copy of it where it lies inside one of the tensors ``out`` (the native calls want them apart)."""
+        lo, hi = prev.data_ptr(), prev.data_ptr() + prev.numel() * prev.element_size()
+        if any(lo < t.data_ptr() + t.numel() * t.element_size() and t.data_ptr() < hi for t in out):
+            return prev.clone()
+        return prev
+
+    @staticmethod
+    def _stream_id(seed, step0, env_id0):
+        """The action stream's identity as the three 64-bit words of the C-ABI."""
+        return int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), int(env_id0) & (2 ** 64 - 1)
+
+    def _compose_stats(self, K, table, seen, episodic, record):
+        """A tallying call on a handle without its fused form, composed from the two other calls in chunks of at most 64 steps
+        into buffers the env keeps: ``record(s, k, out)`` runs steps ``s .. s + k`` from the observations ``seen`` into the
+        rows ``out`` and returns what each env acts on next; ``transition_stats`` adds the rows into ``table``."""
+        torch = _torch()
+        n = self.num_envs
+        if self._stats_buf is None:
+            self._stats_buf = tuple(torch.empty((64, n), dtype=t, device=self.device)
+                                    for t in (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8))
+        bufs = self._stats_buf
+        if episodic:
+            if self._ep_buf is None:
+                self._ep_buf = torch.empty((64, n), dtype=torch.uint8, device=self.device)
+            bufs = bufs + (self._ep_buf,)
+        for s in range(0, K, 64):
+            k = min(64, K - s)
+            out = tuple(b[:k] for b in bufs)
+            nxt = record(s, k, out)
+            self.transition_stats(seen, *out[:5], table=table, ended=out[5] if episodic else None)
+            seen.copy_(nxt)
+
     def rollout_policy(self, cdf, steps, seed, step0=0, env_id0=0, obs_prev=None, out=None):
         """``steps`` consecutive steps with the policy inside the launch (gw_rollout_policy): every env draws its action from
         row ``sign(obs - COUNTER_BOUND) + 1`` of ``cdf`` (``actions.policy_cdf``, [3][num_devices * max_duration]) for the
@@ -459,33 +513,16 @@ class VecCounterTrafficEnv(BaseEnv):
         if self._custom is not None:
             raise ValueError("rollout_policy needs the built-in interpreter: a custom interpreter's observations are not "
                              "the ones the kernel draws from")
-        K, n = int(steps), self.num_envs
-        if obs_prev is None:
-            obs_prev = self._last[0]
-            if obs_prev is None:
-                raise ValueError("rollout_policy: no observation yet -- reset() or step() first, or pass obs_prev")
-        prev = torch.as_tensor(obs_prev).to(device=self.device, dtype=torch.int32).contiguous()
-        if prev.shape != (n,):
-            raise ValueError("obs_prev must have shape (%d,), got %s" % (n, tuple(prev.shape)))
+        K = int(steps)
+        prev = self._obs_prev(obs_prev, "rollout_policy")
         table = self._policy_table(cdf)
-        if out is None:
-            out = (torch.empty((K, n), dtype=torch.int32, device=self.device),
-                   torch.empty((K, n), dtype=torch.int32, device=self.device),
-                   torch.empty((K, n), dtype=torch.int32, device=self.device),
-                   torch.empty((K, n), dtype=torch.float32, device=self.device),
-                   torch.empty((K, n), dtype=torch.uint8, device=self.device))
+        out = self._rows(K, (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8), out)
         dev, dur, obs, rew, done = out
-        for t, dt in ((dev, torch.int32), (dur, torch.int32), (obs, torch.int32), (rew, torch.float32), (done, torch.uint8)):
-            assert t.dtype is dt and tuple(t.shape) == (K, n) and t.is_contiguous() and t.device == self.device
         if K:
-            lo, hi = prev.data_ptr(), prev.data_ptr() + 4 * n
-            if any(lo < t.data_ptr() + t.numel() * t.element_size() and t.data_ptr() < hi for t in out):
-                prev = prev.clone()
+            prev = self._apart(prev, out)
         with torch.cuda.device(self.device):
-            nat.check(self._L.gw_rollout_policy(self._h, K, table.data_ptr(), int(seed) & (2 ** 64 - 1),
-                                                int(step0) & (2 ** 64 - 1), int(env_id0) & (2 ** 64 - 1), prev.data_ptr(),
-                                                dev.data_ptr(), dur.data_ptr(), obs.data_ptr(), rew.data_ptr(),
-                                                done.data_ptr(), self._stream()))
+            nat.check(self._L.gw_rollout_policy(self._h, K, table.data_ptr(), *self._stream_id(seed, step0, env_id0), prev.data_ptr(),
+                                                *[t.data_ptr() for t in out], self._stream()))
         if K:
             self._last = (obs[-1], rew[-1], done[-1])
         return dev, dur, obs, rew, done
@@ -538,13 +575,7 @@ class VecCounterTrafficEnv(BaseEnv):
         if self._custom is not None:
             raise ValueError("rollout_policy_stats needs the built-in interpreter")
         K, n = int(steps), self.num_envs
-        if obs_prev is None:
-            obs_prev = self._last[0]
-            if obs_prev is None:
-                raise ValueError("rollout_policy_stats: no observation yet -- reset() or step() first, or pass obs_prev")
-        prev = torch.as_tensor(obs_prev).to(device=self.device, dtype=torch.int32).contiguous()
-        if prev.shape != (n,):
-            raise ValueError("obs_prev must have shape (%d,), got %s" % (n, tuple(prev.shape)))
+        prev = self._obs_prev(obs_prev, "rollout_policy_stats")
         cdf_t = self._policy_table(cdf)
         table = self._stats_table(table)
         if returns is not None and not (type(returns) is torch.Tensor and returns.dtype is torch.int32 and returns.device == self.device
@@ -555,24 +586,19 @@ class VecCounterTrafficEnv(BaseEnv):
         last = self._stats_last
         if last is None:
             last = self._stats_last = torch.empty(n, dtype=torch.int32, device=self.device)
-        seed, step0, env_id0 = int(seed) & (2 ** 64 - 1), int(step0), int(env_id0) & (2 ** 64 - 1)
+        seed, step0, env_id0 = self._stream_id(seed, step0, env_id0)
         with torch.cuda.device(self.device):
-            rc = self._L.gw_rollout_policy_stats(self._h, K, cdf_t.data_ptr(), seed, step0 & (2 ** 64 - 1), env_id0, prev.data_ptr(),
+            rc = self._L.gw_rollout_policy_stats(self._h, K, cdf_t.data_ptr(), seed, step0, env_id0, prev.data_ptr(),
                                                  last.data_ptr(), returns.data_ptr() if returns is not None else None,
                                                  table.data_ptr(), self._stream())
         if rc == nat.EUNSUPPORTED and not os.environ.get("GW_ROLLOUT_STRICT"):
-            last.copy_(prev)
-            for s in range(0, K, 64):                      # refused before anything ran: compose it from the two other calls
-                k = min(64, K - s)
-                if self._stats_buf is None:
-                    self._stats_buf = tuple(torch.empty((64, n), dtype=t, device=self.device)
-                                            for t in (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8))
-                out = tuple(b[:k] for b in self._stats_buf)
+            def record(s, k, out):                         # refused before anything ran: compose it from the two other calls
                 self.rollout_policy(cdf_t, k, seed, step0=step0 + s, env_id0=env_id0, obs_prev=last, out=out)
-                self.transition_stats(last, *out, table=table)
                 if returns is not None:
-                    returns += out[3].sum(dim=0).to(torch.int32)
-                last.copy_(out[2][k - 1])
+                    returns.add_(out[3].sum(dim=0).to(torch.int32))
+                return out[2][k - 1]
+            last.copy_(prev)
+            self._compose_stats(K, table, last, False, record)
         else:
             nat.check(rc)
         self._last = (last,) + tuple(self._last[1:])
@@ -605,24 +631,13 @@ class VecCounterTrafficEnv(BaseEnv):
         """What the episodic calls share: the env's own ``{age, ret}`` / tally / next-observation tensors (first use), the
         gw_episodes record and the checked ``obs_prev`` -- ``None`` for a caller that brings the actions (``needs_obs``
         false: nothing in the call reads an observation)."""
-        torch = _torch()
         if self._custom is not None:
             raise ValueError("%s needs the built-in interpreter" % who)
         if int(max_steps) < 0:
             raise ValueError("%s: max_steps must be >= 0" % who)
-        n = self.num_envs
         self._episode_tensors()
-        if not needs_obs:
-            return nat.Episodes(int(max_steps), 1 if on_done else 0, self._ep_state.data_ptr(), self._ep_tally.data_ptr()), None
-        if obs_prev is None:
-            obs_prev = self._last[0]
-            if obs_prev is None:
-                raise ValueError("%s: no observation yet -- reset() or step() first, or pass obs_prev" % who)
-        prev = torch.as_tensor(obs_prev).to(device=self.device, dtype=torch.int32).contiguous()
-        if prev.shape != (n,):
-            raise ValueError("obs_prev must have shape (%d,), got %s" % (n, tuple(prev.shape)))
         ep = nat.Episodes(int(max_steps), 1 if on_done else 0, self._ep_state.data_ptr(), self._ep_tally.data_ptr())
-        return ep, prev
+        return ep, (self._obs_prev(obs_prev, who) if needs_obs else None)
 
     def rollout_episodes(self, cdf, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, out=None):
         """``rollout_policy`` with episodes (gw_rollout_episodes): an env whose step returned ``done`` (``on_done``), or whose
@@ -635,25 +650,18 @@ class VecCounterTrafficEnv(BaseEnv):
         stream.  ``out``: six ``[steps][N]`` tensors to write into.  Not for hipGraph capture (``step0`` would be baked in)."""
         torch = _torch()
         ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_episodes")
-        K, n = int(steps), self.num_envs
+        K = int(steps)
         table = self._policy_table(cdf)
-        kinds = (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8, torch.uint8)
-        if out is None:
-            out = tuple(torch.empty((K, n), dtype=dt, device=self.device) for dt in kinds)
-        for t, dt in zip(out, kinds):
-            assert t.dtype is dt and tuple(t.shape) == (K, n) and t.is_contiguous() and t.device == self.device
+        out = self._rows(K, (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8, torch.uint8), out)
         if K:
-            lo, hi = prev.data_ptr(), prev.data_ptr() + 4 * n
-            if any(lo < t.data_ptr() + t.numel() * t.element_size() and t.data_ptr() < hi for t in out):
-                prev = prev.clone()
+            prev = self._apart(prev, out)
         with torch.cuda.device(self.device):
-            nat.check(self._L.gw_rollout_episodes(self._h, K, table.data_ptr(), int(seed) & (2 ** 64 - 1),
-                                                  int(step0) & (2 ** 64 - 1), int(env_id0) & (2 ** 64 - 1), C.byref(ep),
+            nat.check(self._L.gw_rollout_episodes(self._h, K, table.data_ptr(), *self._stream_id(seed, step0, env_id0), C.byref(ep),
                                                   prev.data_ptr(), self._ep_next.data_ptr(), *[t.data_ptr() for t in out],
                                                   self._stream()))
         if K:
             self._last = (self._ep_next, out[3][-1], out[4][-1])
-        return tuple(out)
+        return out
 
     def rollout_episodes_stats(self, cdf, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, table=None):
         """``rollout_episodes`` for a caller that wants the tally, not the transitions (gw_rollout_episodes_stats): the same
@@ -668,23 +676,17 @@ class VecCounterTrafficEnv(BaseEnv):
         table = self._stats_table(table)
         if K == 0:
             return table
-        seed, step0, env_id0 = int(seed) & (2 ** 64 - 1), int(step0), int(env_id0) & (2 ** 64 - 1)
+        seed, step0, env_id0 = self._stream_id(seed, step0, env_id0)
         with torch.cuda.device(self.device):
-            rc = self._L.gw_rollout_episodes_stats(self._h, K, cdf_t.data_ptr(), seed, step0 & (2 ** 64 - 1), env_id0, C.byref(ep),
+            rc = self._L.gw_rollout_episodes_stats(self._h, K, cdf_t.data_ptr(), seed, step0, env_id0, C.byref(ep),
                                                    prev.data_ptr(), self._ep_next.data_ptr(), table.data_ptr(), self._stream())
         if rc == nat.EUNSUPPORTED and not os.environ.get("GW_ROLLOUT_STRICT"):
-            if self._stats_buf is None:
-                self._stats_buf = tuple(torch.empty((64, n), dtype=t, device=self.device)
-                                        for t in (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8))
-            if self._ep_buf is None:
-                self._ep_buf = torch.empty((64, n), dtype=torch.uint8, device=self.device)
             seen = prev.clone()
-            for s in range(0, K, 64):                      # refused before anything ran: compose it from the two other calls
-                k = min(64, K - s)
-                out = tuple(b[:k] for b in self._stats_buf + (self._ep_buf,))
+
+            def record(s, k, out):                         # refused before anything ran: compose it from the two other calls
                 self.rollout_episodes(cdf_t, k, seed, max_steps, on_done, step0=step0 + s, env_id0=env_id0, obs_prev=seen, out=out)
-                self.transition_stats(seen, *out[:5], table=table, ended=out[5])
-                seen.copy_(self._ep_next)
+                return self._ep_next
+            self._compose_stats(K, table, seen, True, record)
         else:
             nat.check(rc)
         self._last = (self._ep_next,) + tuple(self._last[1:])
@@ -718,8 +720,7 @@ class VecCounterTrafficEnv(BaseEnv):
             raise ValueError("tally must be a contiguous int64 tensor of shape (%d, %d) on %s" % (P, EP_COLS, self.device))
         pop = nat.Population(P, n // P, table.data_ptr(), tally.data_ptr())
         with torch.cuda.device(self.device):
-            nat.check(self._L.gw_rollout_population(self._h, K, C.byref(pop), int(seed) & (2 ** 64 - 1),
-                                                    int(step0) & (2 ** 64 - 1), int(env_id0) & (2 ** 64 - 1), C.byref(ep),
+            nat.check(self._L.gw_rollout_population(self._h, K, C.byref(pop), *self._stream_id(seed, step0, env_id0), C.byref(ep),
                                                     prev.data_ptr(), self._ep_next.data_ptr(), self._stream()))
         if K:
             self._last = (self._ep_next,) + tuple(self._last[1:])
@@ -776,11 +777,7 @@ class VecCounterTrafficEnv(BaseEnv):
         dur = torch.as_tensor(duration).to(device=self.device, dtype=torch.int32).contiguous()
         K, n = dev.shape[0], self.num_envs
         assert dev.shape == (K, n) and dur.shape == dev.shape
-        kinds = (torch.int32, torch.float32, torch.uint8, torch.uint8)
-        if out is None:
-            out = tuple(torch.empty((K, n), dtype=dt, device=self.device) for dt in kinds)
-        for t, dt in zip(out, kinds):
-            assert t.dtype is dt and tuple(t.shape) == (K, n) and t.is_contiguous() and t.device == self.device
+        out = self._rows(K, (torch.int32, torch.float32, torch.uint8, torch.uint8), out)
         self._autoreset(K, dev.data_ptr(), dur.data_ptr(), int(max_steps), on_done, [t.data_ptr() for t in out])
         if K:
             self._last = (self._ep_next, out[1][-1], out[2][-1])

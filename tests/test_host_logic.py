@@ -433,21 +433,6 @@ KERNEL_FAMILIES = ("ct_step_sfx_kernel", "ct_rollout_sync_kernel", "ct_rollout_s
 KERNELS_OUT_OF_SCOPE = ("grid_run_kernel",)
 
 
-def _library_kernel_instantiations(path):
-    """Every `<name>_kernel<...>` template instantiation in the library's symbol table, as c++filt spells it (no namespace,
-    no parameter list)."""
-    nm = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
-    dem = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True, check=True).stdout
-    names = set()
-    for line in dem.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"(?:^|[\s:])(\w+_kernel<[^()]*>)\(", line)
-        if m:
-            names.add(m.group(1))
-    return names
-
-
 def test_every_kernel_instantiation_has_a_gpu_recipe(native_lib):
     """tests/test_kernel_variants.py runs one oracle-parity case per instantiation.  An instantiation added to the library
     (a new `case 12:` in a launcher), or a new templated kernel family, fails here until a recipe -- or an explicit,
@@ -455,7 +440,8 @@ def test_every_kernel_instantiation_has_a_gpu_recipe(native_lib):
     from gymwipe_amd import _native
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import test_kernel_variants as kv
-    names = _library_kernel_instantiations(_native.LIB_PATH)
+    from util import kernel_instantiations
+    names = kernel_instantiations(_native.LIB_PATH, r"\w+_kernel")
     families = {n.split("<")[0] for n in names}
     assert families - set(KERNEL_FAMILIES) - set(KERNELS_OUT_OF_SCOPE) == set(), "templated kernel family without recipes"
     lib_set = {n for n in names if n.split("<")[0] in KERNEL_FAMILIES}

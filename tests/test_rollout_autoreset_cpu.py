@@ -9,7 +9,7 @@ import sys
 
 import pytest
 
-from test_rollout_episodes_cpu import _instantiations
+from util import kernel_instantiations
 
 
 def test_argument_validation_without_a_gpu(native_lib):
@@ -74,7 +74,7 @@ def test_every_autoreset_rollout_instantiation_has_a_gpu_case(native_lib):
     from gymwipe_amd import _native
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import test_rollout_autoreset as ra
-    lib_set = _instantiations(_native.LIB_PATH, "ct_rollout_sync_ep")
+    lib_set = kernel_instantiations(_native.LIB_PATH, "ct_rollout_sync_ep")
     assert len(lib_set) == 30, sorted(lib_set)
     assert sorted(lib_set - set(ra.INSTANTIATIONS)) == [], "instantiations without a case"
     assert sorted(set(ra.INSTANTIATIONS) - lib_set) == [], "cases for instantiations the library does not have"

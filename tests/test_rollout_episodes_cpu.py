@@ -6,8 +6,6 @@ ct_rollout_pstats_ep<DT, MODE> instantiations are exactly the cases tests/test_r
 """
 import ctypes as C
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -111,27 +109,13 @@ def test_argument_validation_without_a_gpu(native_lib):
     assert L.gw_transition_stats_ep(fake, 0, *[one] * 8, None) == nat.OK
 
 
-def _instantiations(path, family):
-    """Every <family><...> instantiation in the library's symbol table, as c++filt spells it (the reading of
-    tests/test_rollout_policy_cpu.py, with this family's name)."""
-    nm = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
-    dem = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True, check=True).stdout
-    names = set()
-    for line in dem.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"(?:^|[\s:])(" + family + r"<[^()]*>)\(", line)
-        if m:
-            names.add(m.group(1))
-    return names
-
-
 def test_every_episodic_rollout_instantiation_has_a_gpu_case(native_lib):
     from gymwipe_amd import _native
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import test_rollout_episodes as re_
+    from util import kernel_instantiations
     for family, cases in (("ct_rollout_policy_ep", re_.INSTANTIATIONS), ("ct_rollout_pstats_ep", re_.STATS_INSTANTIATIONS)):
-        lib_set = _instantiations(_native.LIB_PATH, family)
+        lib_set = kernel_instantiations(_native.LIB_PATH, family)
         assert len(lib_set) == 30, sorted(lib_set)
         assert sorted(lib_set - set(cases)) == [], "instantiations without a case"
         assert sorted(set(cases) - lib_set) == [], "cases for instantiations the library does not have"

@@ -5,8 +5,6 @@ the library's ct_rollout_policy<DT, MODE> instantiations are exactly the cases t
 """
 import ctypes as C
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -101,26 +99,12 @@ def test_argument_validation_without_a_gpu(native_lib):
     assert L.gw_rollout_policy(fake, 0, one, 1, 0, 0, one, one, one, one, one, one, None) == nat.OK
 
 
-def _policy_instantiations(path):
-    """Every ct_rollout_policy<...> instantiation in the library's symbol table, as c++filt spells it (the reading of
-    tests/test_host_logic.py's catalogue, with this family's name)."""
-    nm = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
-    dem = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True, check=True).stdout
-    names = set()
-    for line in dem.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"(?:^|[\s:])(ct_rollout_policy<[^()]*>)\(", line)
-        if m:
-            names.add(m.group(1))
-    return names
-
-
 def test_every_policy_rollout_instantiation_has_a_gpu_case(native_lib):
     from gymwipe_amd import _native
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import test_rollout_policy as rp
-    lib_set = _policy_instantiations(_native.LIB_PATH)
+    from util import kernel_instantiations
+    lib_set = kernel_instantiations(_native.LIB_PATH, "ct_rollout_policy")
     assert len(lib_set) == 30, sorted(lib_set)
     assert sorted(lib_set - set(rp.INSTANTIATIONS)) == [], "instantiations without a case"
     assert sorted(set(rp.INSTANTIATIONS) - lib_set) == [], "cases for instantiations the library does not have"

@@ -114,8 +114,8 @@ def test_every_population_rollout_instantiation_has_a_gpu_case(native_lib):
     from gymwipe_amd import _native
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import test_rollout_population as rp
-    from test_rollout_episodes_cpu import _instantiations
-    lib_set = _instantiations(_native.LIB_PATH, "ct_rollout_pop_ep")
+    from util import kernel_instantiations
+    lib_set = kernel_instantiations(_native.LIB_PATH, "ct_rollout_pop_ep")
     assert len(lib_set) == 30, sorted(lib_set)
     assert sorted(lib_set - set(rp.INSTANTIATIONS)) == [], "instantiations without a case"
     assert sorted(set(rp.INSTANTIATIONS) - lib_set) == [], "cases for instantiations the library does not have"

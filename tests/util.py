@@ -1,4 +1,7 @@
 """Shared helpers for the parity tests."""
+import re
+import subprocess
+
 import numpy as np
 
 
@@ -28,3 +31,18 @@ def assert_state_equal(gpu_env, oracle, fields=STATE_FIELDS, where=""):
             bad = np.argwhere(~same)[:5]
             raise AssertionError("state field %r differs %s at %s: gpu=%r oracle=%r"
                                  % (f, where, bad.tolist(), a[tuple(bad[0])], b[tuple(bad[0])]))
+
+
+def kernel_instantiations(path, family):
+    """Every ``<family><...>`` template instantiation in the symbol table of the library at ``path``, as c++filt spells it (no
+    namespace, no parameter list).  ``family``: a kernel's name, or a regular expression for several (``r"\\w+_kernel"``)."""
+    nm = subprocess.run(["nm", path], capture_output=True, text=True, check=True).stdout
+    dem = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True, check=True).stdout
+    names = set()
+    for line in dem.splitlines():
+        if "__device_stub__" in line:
+            continue
+        m = re.search(r"(?:^|[\s:])(" + family + r"<[^()]*>)\(", line)
+        if m:
+            names.add(m.group(1))
+    return names
