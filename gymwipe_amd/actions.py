@@ -204,3 +204,44 @@ def episodes_numpy(state, reward, done, max_steps, on_done):
     tally = np.array([over.sum(), (ended == 1).sum(), age.sum(), ret.sum(), (ret * ret).sum()], np.int64)
     state[over] = 0
     return ended, tally
+
+
+# ---- episodes scored by what they delivered (gw_rollout_episodes_scored, include/gymwipe_amd.h) ---------------------------------
+MAX_DEVICES = 32                # GW_MAX_DEVICES
+SCORE_W_MAX = 1024              # GW_SCORE_W_MAX
+
+
+def make_score(num_devices, reward=1, delivered=0):
+    """The ``int32[1 + MAX_DEVICES]`` image of ``gw_score``: ``[0]`` the weight of a step's built-in reward, ``[1 + d]`` the
+    weight of ONE data packet of sender ``d`` that the RRM decoded in the step (0 from ``num_devices`` on).  ``delivered``: one
+    weight for every sender, or a sequence of ``num_devices``.  Every weight is an integer in ``[-SCORE_W_MAX, SCORE_W_MAX]``.
+    ``make_score(D)`` is the neutral score: the scored calls then give their parents' results."""
+    D = int(num_devices)
+    if not 2 <= D <= MAX_DEVICES:
+        raise ValueError("make_score: num_devices must be in [2, %d]" % MAX_DEVICES)
+    w = np.asarray(delivered)
+    if w.ndim == 0:
+        w = np.full(D, w)
+    if w.shape != (D,):
+        raise ValueError("make_score: delivered must be a scalar or a sequence of %d weights, got shape %s" % (D, w.shape))
+    vals = np.concatenate([np.asarray(reward).reshape(1), w])
+    if vals.dtype.kind not in "iu" and not (np.isfinite(vals.astype(np.float64)).all() and (vals == np.rint(vals.astype(np.float64))).all()):
+        raise ValueError("make_score: weights must be integers")
+    vals = vals.astype(np.int64)
+    if (np.abs(vals) > SCORE_W_MAX).any():
+        raise ValueError("make_score: a weight lies outside [-%d, %d]" % (SCORE_W_MAX, SCORE_W_MAX))
+    out = np.zeros(1 + MAX_DEVICES, np.int32)
+    out[:1 + D] = vals
+    return out
+
+
+def score_numpy(score, reward, device, delivered):
+    """CPU restatement of a step's score: ``score[0] * reward + score[1 + device] * delivered`` per env, int32 (``reward``: the
+    built-in interpreter's, an integer in [-10, 10] in any dtype; ``device``: the sender each step assigned; ``delivered``: the
+    data packets of that sender the RRM decoded in the step)."""
+    score = np.asarray(score)
+    if score.shape != (1 + MAX_DEVICES,):
+        raise ValueError("score must be make_score()'s int32[%d]" % (1 + MAX_DEVICES))
+    w = score.astype(np.int64)
+    r = np.rint(np.asarray(reward, dtype=np.float64)).astype(np.int64)
+    return (w[0] * r + w[1 + np.asarray(device).astype(np.int64)] * np.asarray(delivered).astype(np.int64)).astype(np.int32)

@@ -279,12 +279,17 @@ class PopulationSearchAgent:
 
     ``evaluate`` defaults to the env: ``env.reset()``, the episode state zeroed, ``env.rollout_population(cdfs, steps, seed,
     max_steps=episode_steps, step0=generation * steps)``.  Pass a callable (and ``env=None`` with ``nb_actions``) to let
-    anything else that returns a ``[P][5]`` tally stand in for the GPU."""
+    anything else that returns a ``[P][5]`` tally stand in for the GPU.
+
+    ``score`` (``actions.make_score``) is passed on to ``rollout_population``: the fitness is then the mean episode SCORE --
+    with ``make_score(D, reward=0, delivered=1)`` the packets delivered per episode, where the built-in reward's return is 0
+    or ``-payload_value`` whatever the policy does and is highest for the policy that assigns nothing.  A caller's own
+    ``evaluate`` reads it from ``self.score``."""
 
     SIGMA_MIN = 1e-3                    # the floor of sigma: a collapsed elite set must not end the search
 
     def __init__(self, env, num_policies, steps, episode_steps, elite_frac=0.25, sigma0=1.0, seed=0, evaluate=None,
-                 nb_actions=None):
+                 nb_actions=None, score=None):
         import numpy as np
         self.np = np
         self.env = env
@@ -303,6 +308,7 @@ class PopulationSearchAgent:
         self.rng = np.random.default_rng(self.seed)
         self.mu = np.zeros((3, self.nb_actions), np.float64)
         self.sigma = np.full((3, self.nb_actions), float(sigma0), np.float64)
+        self.score = score
         self.evaluate = evaluate if evaluate is not None else self._evaluate_on_env
         self.generation = 0
         self.history = []
@@ -311,8 +317,9 @@ class PopulationSearchAgent:
         env = self.env
         env.reset()
         env.episode_state.zero_()
+        kw = {} if self.score is None else {"score": self.score}
         return env.rollout_population(cdfs, self.steps, self.seed, max_steps=self.episode_steps, on_done=True,
-                                      step0=generation * self.steps)
+                                      step0=generation * self.steps, **kw)
 
     def tables(self, logits):
         """Logits ``[..., A]`` -> the 32-bit tables the launch reads (numpy): softmax in float64, then ``policy_cdf``."""

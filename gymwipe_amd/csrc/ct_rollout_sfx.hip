@@ -536,6 +536,9 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
 //                           action from the reset's observation; gw_rollout_episodes_stats: the same with ct_rollout_pstats' tally.
 //   ct_rollout_sync_ep      gw_rollout_autoreset: ct_rollout_sync_kernel's staged rows with the same episodes -- the caller's
 //                           actions, the launch's resets.
+//   ct_rollout_pop_ep       gw_rollout_population: ct_rollout_policy_ep with one table per block and nothing stored per step.
+//   ct_rollout_policy_eps   gw_rollout_episodes_scored / gw_rollout_population_scored: the two before with the step's score --
+//   ct_rollout_pop_eps      the reward and the packets the step delivered, weighted -- where they have the reward.
 // The policy's draw (include/gymwipe_amd.h, gw_rollout_policy): the first 32 bits of the action stream's hash
 // (gymwipe_amd/actions.py) against the observation class's row of the table.
 __device__ __forceinline__ uint32_t gw_policy_u(uint64_t seed, uint64_t env_term, uint64_t step)
@@ -1082,6 +1085,106 @@ __global__ __launch_bounds__(64) void ct_rollout_pop_ep(GwState st, GwDevConst c
     GW_ROLLOUT_EP_TAIL(true, src.row)
 }
 
+// ---- episodes scored by what they delivered: gw_rollout_episodes_scored / gw_rollout_population_scored ------------------------
+// score_k = w_reward * reward_k + w_delivered[d_k] * delivered_k (include/gymwipe_amd.h).  delivered_k is the step's share of
+// the body's running kt.deliv, which restarts at 0 in every launch -- and the baseline with it (first()).  The D weights lie
+// behind the policy table's copy in the launch's dynamic LDS: one LDS read per step, indexed by the sender the step assigned.
+struct StepScore {
+    int32_t* s_w;                                        // [D] in LDS
+    int32_t w_reward;
+    uint32_t deliv_next;                                 // kt.deliv when the step that is being walked began
+    __device__ __forceinline__ void weights_at(uint32_t* lds_w, const gw_score& w)
+    {
+        s_w = reinterpret_cast<int32_t*>(lds_w);
+        w_reward = w.w_reward;
+    }
+    __device__ __forceinline__ void stage(const gw_score& w, int D) const
+    {
+        for (int i = threadIdx.x; i < D; i += blockDim.x) s_w[i] = w.w_delivered[i];
+    }
+    __device__ __forceinline__ void first() { deliv_next = 0u; }
+    // the packets step k delivered, given the running count behind it
+    __device__ __forceinline__ uint32_t delivered(uint32_t deliv_now)
+    {
+        const uint32_t dl = deliv_now - deliv_next;
+        deliv_next = deliv_now;
+        return dl;
+    }
+    __device__ __forceinline__ int32_t of(int32_t r, int d, uint32_t dl) const { return w_reward * r + s_w[d] * (int32_t)dl; }
+};
+
+struct ScoredEpisodeActions : EpisodeActions {
+    StepScore sc;
+    int32_t* delivered_out;
+};
+
+// ct_rollout_policy_ep with the score where it has the reward: the reward row, the book's return -- and the packets per step.
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_policy_eps(GwState st, GwDevConst c, int K, GwPolicyArgs p, GwEpisodeArgs ea, gw_score w,
+                                                           int32_t* device_out, int32_t* duration_out, int32_t* obs, float* reward,
+                                                           uint8_t* done, uint8_t* ended, int32_t* delivered)
+{
+    extern __shared__ uint32_t s_policy_cdf[];
+    __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
+    ScoredEpisodeActions src;
+    src.init(p, c, DT == 0 ? c.D : DT);
+    src.table_at(s_policy_cdf);
+    src.sc.weights_at(s_policy_cdf + 3u * src.A, w);
+    src.device_out = device_out; src.duration_out = duration_out; src.ended = ended; src.delivered_out = delivered;
+#define GW_ROLLOUT_SRC_RESETS
+#define GW_ROLLOUT_SRC_STAGE src.stage_cdf(); src.sc.stage(w, DT == 0 ? c.D : DT); gw_ep_zero(s_ep_tally);
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.sc.first(); src.first(e, p.obs_prev[e], c.counter_bound);
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_DRAWN_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_DRAWN_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)                                                                                \
+    {                                                                                                                            \
+        const uint32_t dl_next = src.sc.delivered(kt.deliv);                                                                     \
+        const int32_t score_next = src.sc.of(r, src.d_cur, dl_next);                                                             \
+        GW_ROLLOUT_STORE_OUTPUTS(at, latest, score_next, dn)                                                                     \
+        src.delivered_out[at] = (int32_t)dl_next;                                                                                \
+        GW_ROLLOUT_EP_STEPPED(score_next, dn)                                                                                    \
+        src.stepped(at, k, K, latest, cause_next);                                                                               \
+    }
+#include "ct_rollout_sync_body.h"
+    GW_ROLLOUT_EP_TAIL(false, nullptr)
+}
+
+struct ScoredPopulationActions : PopulationActions {
+    StepScore sc;
+};
+
+// ct_rollout_pop_ep with the book's return the score.
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_pop_eps(GwState st, GwDevConst c, int K, GwPolicyArgs p, GwEpisodeArgs ea, gw_score w,
+                                                        uint32_t M, int64_t* pop_tally)
+{
+    extern __shared__ uint32_t s_policy_cdf[];
+    __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
+    ScoredPopulationActions src;
+    src.init(p, c, DT == 0 ? c.D : DT);
+    {
+        const uint32_t pol = (blockIdx.x * 64u) / M;
+        src.cdf = p.cdf + (size_t)pol * 3u * src.A;
+        src.row = pop_tally + (size_t)pol * GW_EP_COLS;
+    }
+    src.table_at(s_policy_cdf);
+    src.sc.weights_at(s_policy_cdf + 3u * src.A, w);
+#define GW_ROLLOUT_SRC_RESETS
+#define GW_ROLLOUT_SRC_STAGE src.stage_cdf(); src.sc.stage(w, DT == 0 ? c.D : DT); gw_ep_zero(s_ep_tally);
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.sc.first(); src.first(e, p.obs_prev[e], c.counter_bound);
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_DRAWN_TAKE
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_DRAWN_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)                                                                                \
+    (void)at;                                                                                                                    \
+    {                                                                                                                            \
+        const int32_t score_next = src.sc.of(r, src.d_cur, src.sc.delivered(kt.deliv));                                          \
+        GW_ROLLOUT_EP_STEPPED(score_next, dn)                                                                                    \
+        src.next(k, K, cause_next ? 0 : latest);                                                                                 \
+    }
+#include "ct_rollout_sync_body.h"
+    GW_ROLLOUT_EP_TAIL(true, src.row)
+}
+
 // The per-step form's bookkeeping, for handles without the fused kernels: after a step's launch, steps 1-4 and 6 of the
 // semantics for every env -- {age, ret}, ended, the tally, the observation acted on next -- and the mask gw_reset's launch takes.
 __global__ __launch_bounds__(256) void episodes_step_kernel(uint32_t N, int32_t center, GwEpisodeArgs ea, const int32_t* obs,
@@ -1235,11 +1338,78 @@ __global__ __launch_bounds__(256) void policy_sample_pop_kernel(uint32_t N, uint
     duration_out[e] = (int32_t)(a - dv * md);
 }
 
+// The scored calls' per-step form, in front of the step: policy_sample_pop_kernel's draw (one table: M = N), and each env's
+// delivered counter (GwState::sa, word 2 e + 1: what gw_delivered reads) into the handle's scratch row.
+__global__ __launch_bounds__(256) void policy_sample_scored_kernel(uint32_t N, uint32_t A, uint32_t md, int32_t center, GwPolicyArgs p,
+                                                                   uint32_t M, const uint32_t* __restrict__ sa,
+                                                                   int32_t* __restrict__ device_out, int32_t* __restrict__ duration_out,
+                                                                   uint32_t* __restrict__ deliv_before)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const uint32_t cls = gw_policy_cls(p.obs_prev[e], center);
+    const uint32_t* row = p.cdf + ((size_t)(e / M) * 3u + cls) * A;
+    const uint32_t a = gw_policy_count(row, A, gw_policy_u(p.seed, gw_policy_env_term(p.env0, e), p.step0));
+    const uint32_t dv = a / md;
+    device_out[e] = (int32_t)dv;
+    duration_out[e] = (int32_t)(a - dv * md);
+    deliv_before[e] = sa[(size_t)2 * e + 1];
+}
+
+// ... and behind it: the counter differenced, the step scored (`reward` comes in as the step's reward and goes out as its
+// score), and episodes_step_pop_kernel's bookkeeping with the score.  pop_tally == nullptr: no per-policy rows (the records
+// form); delivered_out == nullptr: the packets per step are not kept (the population's form).
+__global__ __launch_bounds__(256) void episodes_step_scored_kernel(uint32_t N, uint32_t D, int32_t center, GwEpisodeArgs ea, gw_score w,
+                                                                  uint32_t M, int64_t* pop_tally, const uint32_t* sa,
+                                                                  const uint32_t* deliv_before, const int32_t* device,
+                                                                  const int32_t* obs, float* reward, const uint8_t* done,
+                                                                  uint8_t* ended, uint8_t* mask, int32_t* delivered_out)
+{
+    __shared__ unsigned long long s_ep[GW_EP_COLS];
+    if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint32_t e0 = blockIdx.x * blockDim.x, e = e0 + threadIdx.x;
+    const uint32_t pol0 = e0 / M;                                               // (e0 < N: the grid is ceil(N / 256) blocks)
+    const bool one_policy = !pop_tally || pol0 == gw_min_u32(e0 + blockDim.x - 1u, N - 1u) / M;
+    if (e < N) {
+        int2 s = *reinterpret_cast<const int2*>(ea.state + 2 * (size_t)e);
+        const uint32_t dl = sa[(size_t)2 * e + 1] - deliv_before[e];
+        const uint32_t dv = gw_min_u32((uint32_t)device[e], D - 1u);            // (a drawn action: inside the action space)
+        const int32_t r = w.w_reward * (int32_t)reward[e] + w.w_delivered[dv] * (int32_t)dl;
+        reward[e] = (float)r;
+        if (delivered_out) delivered_out[e] = (int32_t)dl;
+        s.x += 1; s.y += r;
+        const uint32_t cause = (ea.on_done != 0 && done[e] != 0) ? 1u : ((ea.max_steps > 0 && s.x >= ea.max_steps) ? 2u : 0u);
+        if (cause) {
+            const unsigned long long v[GW_EP_COLS] = {1ull, cause == 1u ? 1ull : 0ull, (unsigned long long)(int64_t)s.x,
+                                                      (unsigned long long)(int64_t)s.y,
+                                                      (unsigned long long)((int64_t)s.y * (int64_t)s.y)};
+#pragma unroll
+            for (int j = 0; j < GW_EP_COLS; ++j) {
+                if (!v[j]) continue;
+                if (one_policy || ea.tally) __hip_atomic_fetch_add(s_ep + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (!one_policy) gw_ts_add(pop_tally + (size_t)(e / M) * GW_EP_COLS + j, v[j]);
+            }
+            s.x = 0; s.y = 0;
+        }
+        *reinterpret_cast<int2*>(ea.state + 2 * (size_t)e) = s;
+        ended[e] = (uint8_t)cause;
+        mask[e] = (uint8_t)(cause != 0u);
+        ea.obs_next[e] = cause ? center : obs[e];
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)GW_EP_COLS && s_ep[threadIdx.x]) {
+        if (pop_tally && one_policy) gw_ts_add(pop_tally + (size_t)pol0 * GW_EP_COLS + threadIdx.x, s_ep[threadIdx.x]);
+        if (ea.tally) gw_ts_add(ea.tally + threadIdx.x, s_ep[threadIdx.x]);
+    }
+}
+
 // ---- launching the step-synchronous family (host side) -------------------------------------------------------------------------
 // What a family keeps in the launch's dynamic LDS decides its availability rules beyond the handle's, and that LDS's size.
 enum GwFusedLds {
     GW_FUSED_NO_TABLE,            // staged actions: nothing
     GW_FUSED_TABLE,               // the policy table's copy: 3 * A words, for A <= GW_POLICY_A_MAX
+    GW_FUSED_TABLE_SCORE,         // ... and the score's D weights behind it (checked against the block's LDS as the next one is)
     GW_FUSED_TABLE_HIST           // ... behind a histogram of 3 * A bins: at most TS_STEPS steps, where both fit beside the
 };                                //     kernel's own tables (decided by the handle alone, never by K)
 
@@ -1261,12 +1431,13 @@ int launch_fused(const GwState& st, const GwDevConst& cst, const GwChunk& ch, in
     const unsigned grid = (unsigned)((st.N + 63) / 64);
     const int mode = gw_step_mode(cst, ch.below_limits, false);
     const size_t A = (size_t)st.D * (size_t)cst.max_duration;
-    const size_t dyn = lds == GW_FUSED_NO_TABLE ? 0 : 3 * A * (sizeof(uint32_t) + (lds == GW_FUSED_TABLE_HIST ? TS_BIN_BYTES : 0));
+    const size_t dyn = lds == GW_FUSED_NO_TABLE ? 0 : 3 * A * (sizeof(uint32_t) + (lds == GW_FUSED_TABLE_HIST ? TS_BIN_BYTES : 0)) +
+                                                      (lds == GW_FUSED_TABLE_SCORE ? (size_t)st.D * sizeof(int32_t) : 0);
     return gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {          // (any other D: per-lane arrays in LDS)
         return gw_with_mode(mode, [&](auto m) {
             constexpr int DT = decltype(dt)::value, MODE = decltype(m)::value;
             const auto kernel = kernel_of(dt, m);
-            if (lds == GW_FUSED_TABLE_HIST) {
+            if (lds == GW_FUSED_TABLE_HIST || lds == GW_FUSED_TABLE_SCORE) {
                 // The instantiation's own LDS, asked once (the same on every device).  One static per kernel: this generic
                 // lambda is instantiated per (KERNEL_OF, dt, m), and every GW_KERNEL_OF lambda is a type of its own, so
                 // ct_rollout_pstats and ct_rollout_pstats_ep do not share theirs.
@@ -1381,6 +1552,48 @@ int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, const
     if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE) || pop.envs_per_policy % 64 != 0) return GW_EUNSUPPORTED;
     return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POP_EP, GW_FUSED_TABLE, GW_KERNEL_OF(ct_rollout_pop_ep), policy_args(pol, obs_prev),
                         episode_args(ep, obs_next), (uint32_t)pop.envs_per_policy, pop.tally_dev);
+}
+
+// gw_rollout_episodes_scored / gw_rollout_population_scored: their parents' rules, the D weights counted into the launch's LDS.
+int gw_launch_rollout_policy_eps_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                     const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev, int32_t* obs_next,
+                                     const GwRows& out, int32_t* delivered)
+{
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE_SCORE)) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POLICY_EPS, GW_FUSED_TABLE_SCORE, GW_KERNEL_OF(ct_rollout_policy_eps),
+                        policy_args(pol, obs_prev), episode_args(ep, obs_next), score, out.device, out.duration, out.obs, out.reward,
+                        out.done, out.ended, delivered);
+}
+
+int gw_launch_rollout_pop_eps_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
+                                  const GwPolicyStream& pol, const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev,
+                                  int32_t* obs_next)
+{
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE_SCORE) || pop.envs_per_policy % 64 != 0) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POP_EPS, GW_FUSED_TABLE_SCORE, GW_KERNEL_OF(ct_rollout_pop_eps),
+                        policy_args(pol, obs_prev), episode_args(ep, obs_next), score, (uint32_t)pop.envs_per_policy, pop.tally_dev);
+}
+
+// One step of the scored calls' per-step form: the draw with the delivered counters' copy (M: envs per table; one table: N) ...
+int gw_launch_policy_sample_scored(const GwState& st, int max_duration, int counter_bound, int64_t M, const GwPolicyStream& pol,
+                                   const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, uint32_t* deliv_before,
+                                   void* stream)
+{
+    hipLaunchKernelGGL(policy_sample_scored_kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (uint32_t)st.N, (uint32_t)st.D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound,
+                       policy_args(pol, obs_in), (uint32_t)M, (const uint32_t*)st.sa, device_out, duration_out, deliv_before);
+    return gw_launch_status();
+}
+// ... and the scoring and the episodes' bookkeeping behind the step (pop_tally: the population's rows, or nullptr).
+int gw_launch_episodes_step_scored(const GwState& st, int counter_bound, const gw_episodes& ep, const gw_score& score, int64_t M,
+                                   int64_t* pop_tally, const uint32_t* deliv_before, int32_t* obs_next, const GwRows& row,
+                                   uint8_t* mask, int32_t* delivered_out, void* stream)
+{
+    hipLaunchKernelGGL(episodes_step_scored_kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (uint32_t)st.N, (uint32_t)st.D, counter_bound, episode_args(ep, obs_next), score, (uint32_t)M, pop_tally,
+                       (const uint32_t*)st.sa, deliv_before, (const int32_t*)row.device, (const int32_t*)row.obs, row.reward,
+                       (const uint8_t*)row.done, row.ended, mask, delivered_out);
+    return gw_launch_status();
 }
 
 // One step's episode bookkeeping of gw_rollout_population's per-step form, on the handle's rows.

@@ -1,7 +1,8 @@
 // ct_rollout_sync_body.h -- the body of the step-synchronous rollout kernels (ct_rollout_sfx.hip), included once per kernel:
 // ct_rollout_sync_kernel (actions staged by the caller), ct_rollout_policy (actions drawn in the kernel), ct_rollout_pstats
 // (drawn in the kernel, the transitions tallied instead of stored) and their episodic forms ct_rollout_policy_ep /
-// ct_rollout_pstats_ep / ct_rollout_sync_ep (an env that ends an episode is reset inside the launch).  It is text
+// ct_rollout_pstats_ep / ct_rollout_sync_ep (an env that ends an episode is reset inside the launch), ct_rollout_pop_ep, and the
+// scored ct_rollout_policy_eps / ct_rollout_pop_eps.  It is text
 // with macro hooks, not a function, on purpose.  As a __forceinline__ template over an action-source type the compiler
 // optimised the callee on its own before inlining it, and all 30 instantiations of ct_rollout_sync_kernel came out different
 // (up to 31 more VGPRs at D = 16 and 32, SGPRs parked in VGPR lanes at D = 4); with the source as an object whose members hold
@@ -20,7 +21,8 @@
 //                                   GW_ROLLOUT_SRC_RESETS may call reset_env() here: gw_reset for this one env, in registers
 //                                   (see there).  Such a kernel stores the env's `ip` record behind the body
 //                                   (GW_ROLLOUT_EP_TAIL), which no other does.
-// The hooks share the body's scope.  Of its names they read only e, N, k, K and c, and they define only d and du; whatever else a
+// The hooks share the body's scope.  Of its names they read only e, N, k, K, c and -- the scored kernels' STEPPED, for the
+// packets a step delivered -- the running kt.deliv, which restarts at 0 in every launch; they define only d and du; whatever else a
 // source keeps lives in names the body leaves free: `src` and anything ending in `_next`.  A new local of the body takes
 // neither form.  The hooks are one include's: the body's last lines undefine all of them, so an includer defines and never
 // undefines.

@@ -78,6 +78,7 @@ struct gw_env {
     uint8_t*     ep_mask;     // [N] gw_rollout_episodes' per-step form: the envs to reset after the step (scratch, not state)
     int32_t*     pop_rows;    // gw_rollout_population's per-step form: one block of six N-long rows (device, duration, obs, reward
                               // | done, ended), allocated by the first call that needs them (scratch, not state)
+    uint32_t*    score_base;  // [N] the scored calls' per-step form: each env's delivered counter before the step (the same rules)
 };
 
 namespace {
@@ -890,6 +891,103 @@ int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, 
         });
 }
 
+// ---- the scored calls (include/gymwipe_amd.h, gw_score) --------------------------------------------------------------------------
+// What both check behind rollout_checks and before any HIP call: the weights' bounds.
+static int check_score(const gw_score* score, const char* who)
+{
+    bool ok = score->w_reward >= -GW_SCORE_W_MAX && score->w_reward <= GW_SCORE_W_MAX;
+    for (int i = 0; i < GW_MAX_DEVICES; ++i) ok = ok && score->w_delivered[i] >= -GW_SCORE_W_MAX && score->w_delivered[i] <= GW_SCORE_W_MAX;
+    return ok ? GW_OK : fail(GW_EINVAL, "%s: a score weight lies outside [-%d, %d]", who, GW_SCORE_W_MAX, GW_SCORE_W_MAX);
+}
+// ... and behind steps == 0: the handle keeps a delivered counter per env (what gw_delivered asks too)
+static int check_scored_handle(gw_env* env, const char* who)
+{
+    if (!env->st.sa) return fail(GW_EUNSUPPORTED, "%s needs the default queue mode: an explicit-queue handle has no per-env delivered counter", who);
+    return GW_OK;
+}
+// One step of their per-step form: the draw with the counters' copy, the step, the scored bookkeeping, the masked reset.  M:
+// envs per table; pop_tally: the population's rows, or nullptr; delivered_row: row s of the caller's, or nullptr.
+static int scored_step(gw_env* env, int32_t s, const GwPolicyStream& pol, int64_t M, int64_t* pop_tally, const gw_episodes* ep,
+                       const gw_score* score, const int32_t* seen, int32_t* obs_next_dev, const GwRows& row, int32_t* delivered_row,
+                       void* stream)
+{
+    const GwDevConst& c = env->cst_host;
+    if (!env->score_base)
+        if (const int e = dev_alloc(env, &env->score_base, (size_t)env->st.N)) return e;
+    if (gw_launch_policy_sample_scored(env->st, c.max_duration, c.counter_bound, M, pol.at(s), seen, row.device, row.duration,
+                                       env->score_base, stream))
+        return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
+    if (const int rc = plain_step(env, s, row.device, row.duration, row, stream)) return rc;
+    if (gw_launch_episodes_step_scored(env->st, c.counter_bound, *ep, *score, M, pop_tally, env->score_base, obs_next_dev, row,
+                                       env->ep_mask, delivered_row, stream))
+        return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
+    return gw_reset(env, env->ep_mask, nullptr, stream);
+}
+
+int gw_rollout_episodes_scored(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                               const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                               int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
+                               uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev, void* stream)
+{
+    int rc = rollout_checks(env, steps,
+                            cdf_dev && score && obs_prev_dev && obs_next_dev && device_out_dev && duration_out_dev && obs_dev &&
+                                reward_dev && done_dev && ended_dev && delivered_dev,
+                            "gw_rollout_episodes_scored", true, ep);
+    if (rc || (rc = check_score(score, "gw_rollout_episodes_scored")) || steps == 0) return rc;
+    if ((rc = check_scored_handle(env, "gw_rollout_episodes_scored")) || (rc = select_device(env))) return rc;
+    const int64_t N = env->st.N;
+    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
+    const GwRows out = {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, ended_dev};
+    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        "no fused scored rollout for this handle (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_policy_eps_sfx(env->st, env->cst_host, ch, pol.at(s0), *ep, *score,
+                                                    seen_before(s0, obs_prev_dev, obs_next_dev), obs_next_dev, out.at(s0 * N),
+                                                    delivered_dev + s0 * N);
+        },
+        [&](int32_t s) {
+            return scored_step(env, s, pol, N, nullptr, ep, score, seen_before(s, obs_prev_dev, obs_next_dev), obs_next_dev,
+                               out.at(s * N), delivered_dev + s * N, stream);
+        });
+}
+
+int gw_rollout_population_scored(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                                 const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                                 void* stream)
+{
+    if (env && !pop) return fail(GW_EINVAL, "gw_rollout_population_scored: pop is NULL");
+    int rc = rollout_checks(env, steps, pop && pop->cdf_dev && pop->tally_dev && score && obs_prev_dev && obs_next_dev,
+                            "gw_rollout_population_scored", true, ep);
+    if (rc || (rc = check_score(score, "gw_rollout_population_scored"))) return rc;
+    if (pop->num_policies < 1 || pop->envs_per_policy < 1)
+        return fail(GW_EINVAL, "gw_rollout_population_scored: num_policies and envs_per_policy must be >= 1");
+    if (steps == 0) return GW_OK;
+    const int64_t N = env->st.N;
+    if ((int64_t)pop->num_policies * pop->envs_per_policy != N)
+        return fail(GW_EINVAL, "gw_rollout_population_scored: %d policies x %d envs is not the handle's %lld envs", pop->num_policies,
+                    pop->envs_per_policy, (long long)N);
+    if ((rc = check_scored_handle(env, "gw_rollout_population_scored")) || (rc = select_device(env))) return rc;
+    const GwPolicyStream pol = {pop->cdf_dev, seed, step0, env_id0};
+    GwRows row = {};                                           // the per-step form's own N-long rows (gw_rollout_population's)
+    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        "no fused scored population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_pop_eps_sfx(env->st, env->cst_host, ch, *pop, pol.at(s0), *ep, *score,
+                                                 seen_before(s0, obs_prev_dev, obs_next_dev), obs_next_dev);
+        },
+        [&](int32_t s) {
+            if (!row.obs) {
+                if (!env->pop_rows)                              // 4 x 4 N + 2 x N bytes
+                    if (const int e = dev_alloc(env, &env->pop_rows, (size_t)(4 * N + (N + 1) / 2))) return e;
+                int32_t* const r = env->pop_rows;
+                row = {r, r + N, r + 2 * N, reinterpret_cast<float*>(r + 3 * N), reinterpret_cast<uint8_t*>(r + 4 * N),
+                       reinterpret_cast<uint8_t*>(r + 4 * N) + N};
+            }
+            return scored_step(env, s, pol, pop->envs_per_policy, pop->tally_dev, ep, score, seen_before(s, obs_prev_dev, obs_next_dev),
+                               obs_next_dev, row, nullptr, stream);
+        });
+}
+
 int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                               const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
                               int64_t* table_dev, void* stream)
@@ -1170,8 +1268,8 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        static const char* const fam[5] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
-                                           "ct_rollout_pop_ep"};
+        static const char* const fam[7] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
+                                           "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps"};
         const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
         snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }

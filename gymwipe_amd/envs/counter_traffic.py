@@ -639,7 +639,16 @@ class VecCounterTrafficEnv(BaseEnv):
         ep = nat.Episodes(int(max_steps), 1 if on_done else 0, self._ep_state.data_ptr(), self._ep_tally.data_ptr())
         return ep, (self._obs_prev(obs_prev, who) if needs_obs else None)
 
-    def rollout_episodes(self, cdf, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, out=None):
+    def _score(self, score):
+        """``actions.make_score``'s image as the gw_score record the scored calls read (by value, before they return)."""
+        w = np.asarray(score)
+        if w.shape != (1 + nat.MAX_DEVICES,) or w.dtype.kind not in "iu":
+            raise ValueError("score must be actions.make_score()'s int32[%d]" % (1 + nat.MAX_DEVICES))
+        if (np.abs(w.astype(np.int64)) > nat.SCORE_W_MAX).any():
+            raise ValueError("score: a weight lies outside [-%d, %d]" % (nat.SCORE_W_MAX, nat.SCORE_W_MAX))
+        return nat.Score.from_buffer_copy(np.ascontiguousarray(w, dtype=np.int32).tobytes())
+
+    def rollout_episodes(self, cdf, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, out=None, score=None):
         """``rollout_policy`` with episodes (gw_rollout_episodes): an env whose step returned ``done`` (``on_done``), or whose
         episode has reached ``max_steps`` steps (0: no limit), is reset inside the launch exactly as ``reset(mask)`` would reset
         it between two steps, and draws its next action from the reset's observation.  Returns ``(device, duration, obs,
@@ -647,18 +656,29 @@ class VecCounterTrafficEnv(BaseEnv):
         ``ended[k]`` is 1 = done or 2 = step limit).  The env keeps each env's ``{age, ret}`` since its last reset, adds every
         ended episode into its tally (``episode_stats()``) and remembers the observation each env acts on next, so calls
         continue one another; advance ``step0`` by ``steps``.  The draws are ``rollout_policy``'s: resets do not shift the
-        stream.  ``out``: six ``[steps][N]`` tensors to write into.  Not for hipGraph capture (``step0`` would be baked in)."""
+        stream.  ``out``: six ``[steps][N]`` tensors to write into.  Not for hipGraph capture (``step0`` would be baked in).
+        ``score`` (``actions.make_score``; gw_rollout_episodes_scored): ``reward``, each env's ``ret`` and the tally's return
+        columns carry the step's score -- ``score[0] * reward + score[1 + device] * delivered`` -- and a seventh output,
+        ``delivered`` int32[steps][N], the data packets of the assigned sender the RRM decoded in the step (``out``: seven
+        tensors).  Everything else is as without; ``None`` is the call above, unchanged."""
         torch = _torch()
         ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_episodes")
         K = int(steps)
         table = self._policy_table(cdf)
-        out = self._rows(K, (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8, torch.uint8), out)
+        kinds = (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8, torch.uint8)
+        out = self._rows(K, kinds + ((torch.int32,) if score is not None else ()), out)
         if K:
             prev = self._apart(prev, out)
         with torch.cuda.device(self.device):
-            nat.check(self._L.gw_rollout_episodes(self._h, K, table.data_ptr(), *self._stream_id(seed, step0, env_id0), C.byref(ep),
-                                                  prev.data_ptr(), self._ep_next.data_ptr(), *[t.data_ptr() for t in out],
-                                                  self._stream()))
+            if score is not None:
+                sc = self._score(score)
+                nat.check(self._L.gw_rollout_episodes_scored(self._h, K, table.data_ptr(), *self._stream_id(seed, step0, env_id0),
+                                                             C.byref(ep), C.byref(sc), prev.data_ptr(), self._ep_next.data_ptr(),
+                                                             *[t.data_ptr() for t in out], self._stream()))
+            else:
+                nat.check(self._L.gw_rollout_episodes(self._h, K, table.data_ptr(), *self._stream_id(seed, step0, env_id0),
+                                                      C.byref(ep), prev.data_ptr(), self._ep_next.data_ptr(),
+                                                      *[t.data_ptr() for t in out], self._stream()))
         if K:
             self._last = (self._ep_next, out[3][-1], out[4][-1])
         return out
@@ -693,7 +713,8 @@ class VecCounterTrafficEnv(BaseEnv):
         return table
 
     # -- a population of policies in one call (gw_rollout_population) -----------------------------------
-    def rollout_population(self, cdfs, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, tally=None):
+    def rollout_population(self, cdfs, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, tally=None,
+                           score=None):
         """``rollout_episodes`` for P policies at once, for a caller that ranks them (gw_rollout_population): ``cdfs`` is
         ``[P][3][A]`` (``actions.policy_cdf`` of ``[P][3][A]`` probabilities), P divides ``num_envs``, and env ``e`` runs policy
         ``e // (num_envs // P)`` -- with the draws, state changes, resets and episode bookkeeping ``rollout_episodes`` would give
@@ -704,7 +725,10 @@ class VecCounterTrafficEnv(BaseEnv):
         are shared with ``rollout_episodes``, so the calls continue one another; advance ``step0`` by ``steps``.
         One launch per 64 steps where ``num_envs // P`` is a multiple of 64 on a handle with a fused rollout; otherwise four
         small launches per step into six N-long rows the handle allocates at its first such call -- same results.  Not for
-        hipGraph capture (``step0`` would be baked in)."""
+        hipGraph capture (``step0`` would be baked in).
+        ``score`` (``actions.make_score``; gw_rollout_population_scored): the tally's return columns, and each env's ``ret``,
+        are sums of step scores -- ``score[0] * reward + score[1 + device] * delivered`` -- so a caller can rank policies by the
+        packets they delivered.  ``None`` is the call above, unchanged."""
         torch = _torch()
         from ..actions import EP_COLS
         ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_population")
@@ -720,8 +744,14 @@ class VecCounterTrafficEnv(BaseEnv):
             raise ValueError("tally must be a contiguous int64 tensor of shape (%d, %d) on %s" % (P, EP_COLS, self.device))
         pop = nat.Population(P, n // P, table.data_ptr(), tally.data_ptr())
         with torch.cuda.device(self.device):
-            nat.check(self._L.gw_rollout_population(self._h, K, C.byref(pop), *self._stream_id(seed, step0, env_id0), C.byref(ep),
-                                                    prev.data_ptr(), self._ep_next.data_ptr(), self._stream()))
+            if score is not None:
+                sc = self._score(score)
+                nat.check(self._L.gw_rollout_population_scored(self._h, K, C.byref(pop), *self._stream_id(seed, step0, env_id0),
+                                                               C.byref(ep), C.byref(sc), prev.data_ptr(), self._ep_next.data_ptr(),
+                                                               self._stream()))
+            else:
+                nat.check(self._L.gw_rollout_population(self._h, K, C.byref(pop), *self._stream_id(seed, step0, env_id0), C.byref(ep),
+                                                        prev.data_ptr(), self._ep_next.data_ptr(), self._stream()))
         if K:
             self._last = (self._ep_next,) + tuple(self._last[1:])
         return tally

@@ -37,6 +37,9 @@
  *   gw_rollout         a Python loop over step()
  *   gw_rollout_autoreset   that loop with the caller's reset on done or after nb_max_episode_steps (keras-rl's fit, as the
  *                      reference drives it: agents/dqn_counter_traffic.py:63-70); steps = 1 is one env.step() with autoreset
+ *   gw_rollout_episodes_scored / gw_rollout_population_scored   the closed loops with a custom Interpreter's getReward in
+ *                      place of the built-in one: a weighted sum of the step's reward and of the packets the RRM sniffed
+ *                      (envs/core.py:59-159, networking/devices.py:163-168)
  *   gw_step_fb         gw_step + the step's feedback as one byte per env (the row a multi-GPU job gathers)
  *   gw_pack_feedback / gw_unpack_feedback   (multi-GPU exchange format; the reference is single-process)
  *   gw_pendulum_step   InvertedPendulumEnv.step              envs/inverted_pendulum.py:101-113
@@ -342,6 +345,49 @@ typedef struct gw_population {
  * draw's clamp keeps any content memory-safe. */
 int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
                           const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev, void* stream);
+
+/* Episodes scored by what they delivered.  The built-in reward is lastAbs - abs of received[0] - received[1]
+ * (envs/counter_traffic.py:85-101): over an episode it telescopes to -|final difference|, so an episode's return is 0 or
+ * -payload_value whatever the policy does, and the policy that assigns nothing attains the maximum.  What a band-assignment
+ * scheduler exists for is delivered packets, so the two calls below score a step as
+ *     score_k = w_reward * reward_k + w_delivered[d_k] * delivered_k
+ * d_k: the sender the step assigned; delivered_k: the data packets of d_k that the RRM decoded in step k
+ * (SimpleRrmDevice.onPacketReceived, networking/devices.py:163-168) -- the increase of gw_delivered's counter over the step; a
+ * reset does not touch that counter.  All integer arithmetic; every weight lies in [-GW_SCORE_W_MAX, GW_SCORE_W_MAX] (all
+ * GW_MAX_DEVICES entries of w_delivered are checked, those from num_devices on are not otherwise read), so (float)score_k is
+ * exact.  w_reward = 1 with every w_delivered = 0 gives the parents' results bit for bit. */
+#define GW_SCORE_W_MAX 1024
+typedef struct gw_score {
+    int32_t w_reward;                      /* weight of the built-in reward of the step */
+    int32_t w_delivered[GW_MAX_DEVICES];   /* weight of ONE data packet of sender d decoded by the RRM in the step */
+} gw_score;
+
+/* gw_rollout_episodes with {age, ret}, the tally's return columns and reward_dev carrying the SCORE where the parent carries
+ * the reward: reward_dev[k][e] = (float)score_k, ret += score_k; delivered_dev (int32[steps][N], never NULL) receives
+ * delivered_k.  The draws, the episode causes, the resets, obs_next_dev, device_out_dev / duration_out_dev, obs_dev, done_dev
+ * and ended_dev are exactly the parent's.  The score is read by value before the call returns.
+ * Default mode: ONE launch per 64 steps (ct_rollout_policy_eps in ct_rollout_sfx.hip), the weights staged beside the table.
+ * Per-step form -- live PHY with default queues, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0, or any
+ * handle while GW_ROLLOUT_POLICY_UNFUSED is set: per step a sampling launch that also copies each env's delivered counter
+ * into a uint32[N] scratch row the HANDLE owns, a step launch, a bookkeeping launch that differences the counter and scores,
+ * and gw_reset's launch -- same results.  The first call that takes this form allocates the row (and so synchronises the
+ * device once); gw_destroy frees it, gw_state_bytes counts it from then on, a snapshot does not hold it.  GW_ROLLOUT_STRICT
+ * turns the per-step form into GW_EUNSUPPORTED before anything is launched or allocated.  An explicit-queue handle has no
+ * per-env delivered counter (gw_delivered refuses it too): GW_EUNSUPPORTED before any launch.
+ * GW_EINVAL before any HIP call: score NULL (call the parent), a weight outside the bounds, delivered_dev NULL, and the
+ * parent's cases.  steps == 0 is GW_OK.  Stream-ordered; not for hipGraph capture (step0 is baked into the launch). */
+int gw_rollout_episodes_scored(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                               const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                               int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
+                               uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev, void* stream);
+
+/* gw_rollout_population with columns 3 and 4 of pop->tally_dev[p] and of ep->tally_dev the sums of episode SCORES and of their
+ * squares ({age, ret} carries the score too); everything else is the parent's.  Fused form where the parent has one
+ * (ct_rollout_pop_eps); the per-step form, its scratch (the parent's six rows and the uint32[N] row above), GW_ROLLOUT_STRICT,
+ * explicit-queue handles and the argument rules as for gw_rollout_episodes_scored. */
+int gw_rollout_population_scored(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                                 const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                                 void* stream);
 
 /* gw_transition_stats for rows recorded by gw_rollout_episodes: step k's observation seen is counter_bound where
  * ended_dev[k - 1] != 0; row 0 uses obs_prev_dev as it is. */

@@ -24,6 +24,16 @@ p/e and q/f walk the same steps (checked once, before the timing: the same rewar
 share of its env-steps with a non-zero reward beside its rate: what the steps are worth.
 Each of t, r and s must count every transition (checked once, before the timing; that they produce the same table from the
 same steps is tests/test_rollout_stats.py's business).
+The scored legs (--scored; profiles/rollout_scored/README.md) -- episodes of T steps (--episodes, default 8) ranked by what they
+delivered, score = packets of the assigned sender the RRM decoded; the legs alternate in one process, --repeats rounds each,
+median wall time per step over --windows calls of K steps:
+  P1 env.rollout_population(score=...)       the fused scored form, P = --policies tables
+  P0 env.rollout_population()                unscored on the same box: the cost of scoring
+  P2 P1 under GW_ROLLOUT_POLICY_UNFUSED      its own per-step form
+  P3 the composition available without it    per step: rollout_episodes(1 step), gw_delivered, the difference, the score and
+                                             the per-env return in torch (one table for all envs: rollout_episodes has no
+                                             population; the per-policy tally is left out, which favours this leg)
+  R1 / R0 / R2 / R3                          the same four for the records form, env.rollout_episodes(score=...)
 Each form is timed `--repeats` times over `--windows` windows (wall clock around a device synchronize); one JSON line with the
 best, the median and the spread.  GW_TREE names the checkout whose gymwipe_amd package (and built library) is measured --
 default: this file's own -- so one job can run a and b on the parent commit's build and c on this one's; a form the measured
@@ -40,6 +50,98 @@ import numpy as np
 sys.path.insert(0, os.environ.get("GW_TREE") or os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
+def scored_legs(args):
+    import ctypes as C
+    import torch
+    from gymwipe_amd import VecCounterTrafficEnv, actions
+    from gymwipe_amd import _native as nat
+
+    N, D, K, T, P, W = args.envs, args.devices, args.steps, args.episodes or 8, args.policies, args.windows
+    dev = torch.device("cuda:0")
+    md = 20
+    A = D * md
+    rng = np.random.default_rng(7)
+    cdf = actions.policy_cdf(rng.dirichlet(np.full(A, 0.3), size=3))
+    cdfs = actions.policy_cdf(rng.dirichlet(np.full(A, 0.3), size=(P, 3)))
+    score = actions.make_score(D, reward=0, delivered=1)
+    w = torch.from_numpy(score.astype(np.int64)).to(dev)
+    kinds = (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8, torch.uint8, torch.int32)
+    envs, step0 = {}, {}
+
+    def env_of(leg):                                           # a handle per leg: each continues its own episodes and stream
+        if leg not in envs:
+            e = envs[leg] = VecCounterTrafficEnv(N, num_devices=D, device=dev)
+            e.reset()
+            e.bench = {"table": e._policy_table(cdf), "tables": e._policy_table(cdfs, population=True),
+                       "tally": torch.zeros((P, 5), dtype=torch.int64, device=dev),
+                       "rows": tuple(torch.empty((K, N), dtype=t, device=dev) for t in kinds),
+                       "deliv": torch.zeros((2, N), dtype=torch.int32, device=dev),
+                       "ret": torch.zeros(N, dtype=torch.int64, device=dev)}
+            step0[leg] = 0
+        return envs[leg]
+
+    def population(leg, scored):
+        e = env_of(leg)
+        e.rollout_population(e.bench["tables"], K, 5, max_steps=T, step0=step0[leg], tally=e.bench["tally"],
+                             **({"score": score} if scored else {}))
+
+    def records(leg, scored):
+        e = env_of(leg)
+        e.rollout_episodes(e.bench["table"], K, 5, max_steps=T, step0=step0[leg],
+                           out=e.bench["rows"][:7 if scored else 6], **({"score": score} if scored else {}))
+
+    def composed(leg, keep_rows):
+        e = env_of(leg)
+        b = e.bench
+        L, h = nat.lib(), e._h
+        for k in range(K):
+            nat.check(L.gw_delivered(h, b["deliv"][0].data_ptr(), e._stream()))
+            out = tuple(r[k:k + 1] for r in b["rows"][:6])
+            e.rollout_episodes(b["table"], 1, 5, max_steps=T, step0=step0[leg] + k, out=out)
+            nat.check(L.gw_delivered(h, b["deliv"][1].data_ptr(), e._stream()))
+            dl = b["deliv"][1] - b["deliv"][0]
+            sc = w[0] * out[3][0].to(torch.int64) + w[1 + out[0][0].to(torch.int64)] * dl
+            b["ret"] = torch.where(out[5][0] != 0, torch.zeros_like(sc), b["ret"] + sc)
+            if keep_rows:
+                b["rows"][6][k] = dl
+                out[3][0].copy_(sc)
+
+    def unfused(fn):
+        def run():
+            os.environ["GW_ROLLOUT_POLICY_UNFUSED"] = "1"
+            try:
+                fn()
+            finally:
+                del os.environ["GW_ROLLOUT_POLICY_UNFUSED"]
+        return run
+
+    legs = {"P1": lambda: population("P1", True), "P0": lambda: population("P0", False), "P2": unfused(lambda: population("P2", True)),
+            "P3": lambda: composed("P3", False),
+            "R1": lambda: records("R1", True), "R0": lambda: records("R0", False), "R2": unfused(lambda: records("R2", True)),
+            "R3": lambda: composed("R3", True)}
+    times = {name: [] for name in legs}
+    for rnd in range(args.repeats + 1):                        # round 0: warm-up (first launches, allocator)
+        for name, fn in legs.items():
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(W):                                 # W calls of K steps per timing
+                fn()
+                step0[name] += K
+            torch.cuda.synchronize(dev)
+            if rnd:
+                times[name].append((time.perf_counter() - t0) / (K * W) * 1e6)
+    for e in envs.values():
+        e.check()
+    res = {"label": args.label, "envs": N, "devices": D, "steps": K, "windows": W, "episodes": T, "policies": P, "rounds": args.repeats,
+           "device": torch.cuda.get_device_name(0)}
+    for name, t in times.items():
+        res[name] = {"us_per_step_median": round(float(np.median(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
+    med = {k: v["us_per_step_median"] for k, v in res.items() if isinstance(v, dict)}
+    res["ratios"] = {"P1/P0": round(med["P1"] / med["P0"], 3), "P2/P1": round(med["P2"] / med["P1"], 3), "P3/P1": round(med["P3"] / med["P1"], 3),
+                     "R1/R0": round(med["R1"] / med["R0"], 3), "R2/R1": round(med["R2"] / med["R1"], 3), "R3/R1": round(med["R3"] / med["R1"], 3)}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
@@ -50,7 +152,11 @@ def main():
     ap.add_argument("--forms", default="a,b,c")
     ap.add_argument("--label", default="")
     ap.add_argument("--episodes", type=int, default=0, help="episode length T of the forms p, e, q, f (must divide --steps)")
+    ap.add_argument("--scored", action="store_true", help="run the scored legs instead of --forms")
+    ap.add_argument("--policies", type=int, default=64, help="P of the scored population legs")
     args = ap.parse_args()
+    if args.scored:
+        return scored_legs(args)
 
     import torch
     from gymwipe_amd import VecCounterTrafficEnv, actions
