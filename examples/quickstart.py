@@ -60,6 +60,10 @@ print("rollout_episodes:", int((ended != 0).sum()), "episodes ended,", venv.epis
 o, r, d, ended, nxt = venv.step_autoreset(action, max_steps=8)
 print("step_autoreset:", int((ended != 0).sum()), "episodes ended,", int((nxt != o).sum()), "envs act on the reset's observation")
 
+# 3f. ... scored by what the step delivered instead of the built-in reward: `r` is 1 point per packet of the sender you chose
+from gymwipe_amd.actions import make_score
+o, r, d, ended, nxt, delivered = venv.step_autoreset(action, max_steps=8, score=make_score(4, reward=0, delivered=1))
+print("step_autoreset(score=):", int(delivered.sum()), "packets decoded in the step,", float(r.sum()), "points")
 
 # 4. your own Interpreter (envs/core.py:59-159), fed with what the RRM sniffed each step
 class CountDeliveries(VecInterpreter):

@@ -96,16 +96,20 @@ class DqnCounterTrafficAgent:
             qv = self.q(self._features(obs))
             return policy_cdf(torch.softmax(torch.clamp(qv / self.tau, -500.0, 500.0), dim=-1))
 
-    def collect(self, steps, episode_steps=None):
+    def collect(self, steps, episode_steps=None, score=None):
         """``steps`` env steps of all N envs under the current policy in ONE ``env.rollout_policy`` call -- observation ->
         policy -> step inside the launch -- and their transitions into the replay memory.  Returns the rollout's
         ``(device, duration, obs, reward, done)``.
         ``episode_steps``: episodes of at most that many steps, ended by ``done`` too, through ``env.rollout_episodes`` (the
         reference's caller: keras-rl resets on done and after nb_max_episode_steps).  The memory then holds the observation
         each step acted on -- the reset's after an episode's end -- as ``m_obs`` and the terminal observation as ``m_next``;
-        the return value gains ``ended``."""
+        the return value gains ``ended``.
+        ``score`` (``actions.make_score``; needs ``episode_steps``): passed on to ``rollout_episodes`` -- the memory's reward
+        is the step's score, the return value gains ``delivered``."""
         torch = self.torch
         steps = int(steps)
+        if score is not None and episode_steps is None:
+            raise ValueError("collect(score=) needs episode_steps: only the episodic rollout has a scored form")
         if self.env._last[0] is None:
             self.env.reset()
         first = self.env._last[0].clone()
@@ -114,7 +118,7 @@ class DqnCounterTrafficAgent:
             after = rows[2][:-1]
         else:
             rows = self.env.rollout_episodes(self.policy_cdf(), steps, self.seed, max_steps=int(episode_steps), on_done=True,
-                                             step0=self.stream_pos)
+                                             step0=self.stream_pos, score=score)
             after = torch.where(rows[5][:-1] != 0, torch.full_like(rows[2][:-1], int(self.center)), rows[2][:-1])
         dev, dur, obs, rew, done = rows[:5]
         self.stream_pos += steps
@@ -159,19 +163,24 @@ class DqnCounterTrafficAgent:
                 pt.mul_(1.0 - self.target_update).add_(p, alpha=self.target_update)
         return loss
 
-    def fit(self, nb_steps, reset_every=64, episode_steps=None):
+    def fit(self, nb_steps, reset_every=64, episode_steps=None, score=None):
         """Vectorised dqn.fit(): nb_steps env.step() calls of all N envs; returns the last loss (tensor).
         ``episode_steps``: per-env episodes of at most that many steps, ended by ``done`` too, through
         ``env.step_autoreset`` (keras-rl's reset on done and nb_max_episode_steps) instead of the global reset every
         ``reset_every`` steps: the memory gets the terminal observation as ``m_next``, and the next action is for the
-        observation the env acts on next -- the reset's where the step ended an episode."""
+        observation the env acts on next -- the reset's where the step ended an episode.
+        ``score`` (``actions.make_score``; needs ``episode_steps``, there is no scored plain ``step()``): the steps go through
+        ``env.step_autoreset(score=)`` and the memory's reward is the step's score -- ``make_score(D, reward=0, delivered=1)``
+        trains on the packets the RRM decoded -- as are the returns of ``env.episode_stats()``."""
+        if score is not None and episode_steps is None:
+            raise ValueError("fit(score=) needs episode_steps: only step_autoreset has a scored form")
         obs = self.env.reset().clone()
         loss = None
         if episode_steps is not None:
             for k in range(nb_steps):
                 flat = self.act(obs)
                 o, r, d, _, nxt = self.env.step_autoreset(self.processor.process_action(flat), max_steps=int(episode_steps),
-                                                          on_done=True)
+                                                          on_done=True, score=score)[:5]
                 self.remember(obs, flat, r, o, d)
                 obs = nxt.clone()
                 self.steps += 1

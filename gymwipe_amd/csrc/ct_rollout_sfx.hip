@@ -539,6 +539,7 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
 //   ct_rollout_pop_ep       gw_rollout_population: ct_rollout_policy_ep with one table per block and nothing stored per step.
 //   ct_rollout_policy_eps   gw_rollout_episodes_scored / gw_rollout_population_scored: the two before with the step's score --
 //   ct_rollout_pop_eps      the reward and the packets the step delivered, weighted -- where they have the reward.
+//   ct_rollout_sync_eps     gw_rollout_autoreset_scored: ct_rollout_sync_ep with the same score, the sender the caller's.
 // The policy's draw (include/gymwipe_amd.h, gw_rollout_policy): the first 32 bits of the action stream's hash
 // (gymwipe_amd/actions.py) against the observation class's row of the table.
 __device__ __forceinline__ uint32_t gw_policy_u(uint64_t seed, uint64_t env_term, uint64_t step)
@@ -1111,6 +1112,12 @@ struct StepScore {
         return dl;
     }
     __device__ __forceinline__ int32_t of(int32_t r, int d, uint32_t dl) const { return w_reward * r + s_w[d] * (int32_t)dl; }
+    // ... for a sender the caller staged, which may lie outside [0, D): the index is clamped, and a rejected step has r == 0 and
+    // dl == 0 (the env was left alone), so whichever weight is read its score is exactly 0
+    __device__ __forceinline__ int32_t of_staged(int32_t r, int d, uint32_t dl, int D) const
+    {
+        return w_reward * r + s_w[gw_min_u32((uint32_t)d, (uint32_t)D - 1u)] * (int32_t)dl;
+    }
 };
 
 struct ScoredEpisodeActions : EpisodeActions {
@@ -1183,6 +1190,49 @@ __global__ __launch_bounds__(64) void ct_rollout_pop_eps(GwState st, GwDevConst 
     }
 #include "ct_rollout_sync_body.h"
     GW_ROLLOUT_EP_TAIL(true, src.row)
+}
+
+// gw_rollout_autoreset_scored: ct_rollout_sync_ep with the score where it has the reward, and the packets per step.  The hook
+// that scores (GW_ROLLOUT_SRC_STEPPED) expands in the body's put_feedback, in front of the step loop's `d`, so the source keeps
+// the step's sender itself (d_cur, as the drawn sources do).  There is no table here, so the weights' LDS copy is static: D
+// words beside the body's own tables, their sum checked when the kernel is compiled.  Nothing of the call but its pointers,
+// limits and weights is baked into the launch: it may be recorded into a hipGraph as its parent may.
+struct ScoredStagedEpisodes : StagedEpisodes {
+    StepScore sc;
+    int32_t* delivered_out;
+    int d_cur;                                           // the sender step k was staged with, inside the action space or not
+};
+
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_sync_eps(GwState st, GwDevConst c, int K, GwEpisodeArgs ea, gw_score w,
+                                                         const int32_t* __restrict__ device, const int32_t* __restrict__ duration,
+                                                         int32_t* obs, float* reward, uint8_t* done, uint8_t* ended, int32_t* delivered)
+{
+    __shared__ uint32_t s_score_w[DT == 0 ? GW_MAX_DEVICES : DT];
+    __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
+    ScoredStagedEpisodes src;
+    src.ended = ended;
+    src.latest_next = 0;
+    src.sc.weights_at(s_score_w, w);
+    src.delivered_out = delivered;
+    src.d_cur = 0;
+#define GW_ROLLOUT_SRC_RESETS
+#define GW_ROLLOUT_SRC_STAGE src.sc.stage(w, DT == 0 ? c.D : DT); gw_ep_zero(s_ep_tally);
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.sc.first(); GW_ROLLOUT_STAGED_FIRST
+#define GW_ROLLOUT_SRC_TAKE GW_ROLLOUT_STAGED_TAKE src.d_cur = d;
+#define GW_ROLLOUT_SRC_CHECKED(bad) GW_ROLLOUT_STAGED_CHECKED(bad)
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)                                                                                \
+    {                                                                                                                            \
+        const uint32_t dl_next = src.sc.delivered(kt.deliv);                                                                     \
+        const int32_t score_next = src.sc.of_staged(r, src.d_cur, dl_next, DT == 0 ? c.D : DT);                                  \
+        GW_ROLLOUT_STORE_OUTPUTS(at, latest, score_next, dn)                                                                     \
+        src.delivered_out[at] = (int32_t)dl_next;                                                                                \
+        GW_ROLLOUT_EP_STEPPED(score_next, dn)                                                                                    \
+        src.ended[at] = (uint8_t)cause_next;                                                                                     \
+        src.latest_next = cause_next ? 0 : latest;                                                                               \
+    }
+#include "ct_rollout_sync_body.h"
+    GW_ROLLOUT_EP_TAIL(false, nullptr)
 }
 
 // The per-step form's bookkeeping, for handles without the fused kernels: after a step's launch, steps 1-4 and 6 of the
@@ -1614,6 +1664,16 @@ int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, co
     if (fused_unavailable(st, cst, ch.K, GW_FUSED_NO_TABLE)) return GW_EUNSUPPORTED;
     return launch_fused(st, cst, ch, GW_LS_ROLLOUT_SYNC_EP, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_sync_ep), episode_args(ep, obs_next),
                         device, duration, out.obs, out.reward, out.done, out.ended);
+}
+
+// gw_rollout_autoreset_scored: the same rules (the weights' LDS copy is static, part of the kernel's own figure).
+int gw_launch_rollout_autoreset_scored_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
+                                           const int32_t* duration, const gw_episodes& ep, const gw_score& score, int32_t* obs_next,
+                                           const GwRows& out, int32_t* delivered)
+{
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_NO_TABLE)) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_SYNC_EPS, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_sync_eps), episode_args(ep, obs_next),
+                        score, device, duration, out.obs, out.reward, out.done, out.ended, delivered);
 }
 
 // One step's episode bookkeeping of gw_rollout_episodes' per-step form (every queue mode): row `step`'s ended, the mask.

@@ -924,6 +924,24 @@ static int scored_step(gw_env* env, int32_t s, const GwPolicyStream& pol, int64_
     return gw_reset(env, env->ep_mask, nullptr, stream);
 }
 
+// ... and of gw_rollout_autoreset_scored's, where the caller brings the actions: the counters' copy is gw_delivered's launch into
+// the same scratch row, and the bookkeeping takes one table's worth of envs (it clamps the staged sender; a rejected action
+// moved neither the counter nor the reward, so it scores 0).
+static int scored_staged_step(gw_env* env, int32_t s, const int32_t* device_row, const int32_t* duration_row, const gw_episodes* ep,
+                              const gw_score* score, int32_t* obs_next_dev, const GwRows& out_row, int32_t* delivered_row, void* stream)
+{
+    if (!env->score_base)
+        if (const int e = dev_alloc(env, &env->score_base, (size_t)env->st.N)) return e;
+    if (gw_launch_delivered_sfx(env->st, env->score_base, stream)) return fail(GW_EHIP, "delivered kernel launch failed at step %d", s);
+    if (const int rc = plain_step(env, s, device_row, duration_row, out_row, stream)) return rc;
+    GwRows row = out_row;
+    row.device = const_cast<int32_t*>(device_row);             // (only read behind the step)
+    if (gw_launch_episodes_step_scored(env->st, env->cst_host.counter_bound, *ep, *score, env->st.N, nullptr, env->score_base,
+                                       obs_next_dev, row, env->ep_mask, delivered_row, stream))
+        return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
+    return gw_reset(env, env->ep_mask, nullptr, stream);
+}
+
 int gw_rollout_episodes_scored(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                                const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
                                int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
@@ -985,6 +1003,29 @@ int gw_rollout_population_scored(gw_env* env, int32_t steps, const gw_population
             }
             return scored_step(env, s, pol, pop->envs_per_policy, pop->tally_dev, ep, score, seen_before(s, obs_prev_dev, obs_next_dev),
                                obs_next_dev, row, nullptr, stream);
+        });
+}
+
+int gw_rollout_autoreset_scored(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
+                                const gw_episodes* ep, const gw_score* score, int32_t* obs_next_dev, int32_t* obs_dev,
+                                float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev, void* stream)
+{
+    int rc = rollout_checks(env, steps,
+                            device_dev && duration_dev && score && obs_next_dev && obs_dev && reward_dev && done_dev && ended_dev &&
+                                delivered_dev,
+                            "gw_rollout_autoreset_scored", true, ep);
+    if (rc || (rc = check_score(score, "gw_rollout_autoreset_scored")) || steps == 0) return rc;
+    if ((rc = check_scored_handle(env, "gw_rollout_autoreset_scored")) || (rc = select_device(env))) return rc;
+    const int64_t N = env->st.N;
+    const GwRows out = {nullptr, nullptr, obs_dev, reward_dev, done_dev, ended_dev};
+    return rollout_drive(env, steps, stream, true, INT32_MAX, "no fused scored autoreset rollout for this handle (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_autoreset_scored_sfx(env->st, env->cst_host, ch, device_dev + s0 * N, duration_dev + s0 * N, *ep,
+                                                          *score, obs_next_dev, out.at(s0 * N), delivered_dev + s0 * N);
+        },
+        [&](int32_t s) {
+            return scored_staged_step(env, s, device_dev + s * N, duration_dev + s * N, ep, score, obs_next_dev, out.at(s * N),
+                                      delivered_dev + s * N, stream);
         });
 }
 
@@ -1268,8 +1309,8 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        static const char* const fam[7] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
-                                           "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps"};
+        static const char* const fam[8] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
+                                           "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps", "ct_rollout_sync_eps"};
         const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
         snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }

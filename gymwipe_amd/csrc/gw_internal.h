@@ -345,6 +345,10 @@ int gw_launch_rollout_policy_eps_sfx(const GwState& st, const GwDevConst& cst, c
 int gw_launch_rollout_pop_eps_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
                                   const GwPolicyStream& pol, const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev,
                                   int32_t* obs_next);
+// gw_rollout_autoreset_scored: gw_rollout_autoreset's launch with the score, and the packets per step
+int gw_launch_rollout_autoreset_scored_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
+                                           const int32_t* duration, const gw_episodes& ep, const gw_score& score, int32_t* obs_next,
+                                           const GwRows& out, int32_t* delivered);
 // their per-step form: the draw that also copies the delivered counters (M envs per table), and the scored bookkeeping
 int gw_launch_policy_sample_scored(const GwState& st, int max_duration, int counter_bound, int64_t M, const GwPolicyStream& pol,
                                    const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, uint32_t* deliv_before,
@@ -390,7 +394,7 @@ int gw_launch_unpack_feedback(int64_t count, int center, int pv, const uint8_t* 
 // Sender counts with a kernel instantiation of their own (template parameter DT; every other count runs DT = 0), one list
 // per kernel family.  Each family's launcher dispatches over its list (gw_dispatch.h) and nothing else restates it.
 #define GW_DTS_STEP          2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_step_sfx_kernel
-#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats, their _ep forms, ct_rollout_pop_ep, the two _eps forms
+#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats, their _ep forms, ct_rollout_pop_ep, the three _eps forms
 #define GW_DTS_ROLLOUT_LOOP  2, 3, 4, 6, 8, 16, 32          // ct_rollout_sfx_kernel (event loop)
 #define GW_DTS_LIVE          2, 3, 4, 6, 8, 16, 32          // ct_step_live_kernel
 #define GW_DTS_GENERIC       2, 3, 4, 8, 16                 // ct_step_kernel on the table PHY
@@ -417,7 +421,8 @@ enum {
     GW_LS_ROLLOUT_POP_EP = GW_LS_ROLLOUT_SYNC_EP + 3 * GW_LS_NDT,        // ct_rollout_pop_ep<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_POLICY_EPS = GW_LS_ROLLOUT_POP_EP + 3 * GW_LS_NDT,     // ct_rollout_policy_eps<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_POP_EPS = GW_LS_ROLLOUT_POLICY_EPS + 3 * GW_LS_NDT,    // ct_rollout_pop_eps<DT, MODE>: 3 per DT
-    GW_LS_COUNT = GW_LS_ROLLOUT_POP_EPS + 3 * GW_LS_NDT
+    GW_LS_ROLLOUT_SYNC_EPS = GW_LS_ROLLOUT_POP_EPS + 3 * GW_LS_NDT,      // ct_rollout_sync_eps<DT, MODE>: 3 per DT
+    GW_LS_COUNT = GW_LS_ROLLOUT_SYNC_EPS + 3 * GW_LS_NDT
 };
 constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {

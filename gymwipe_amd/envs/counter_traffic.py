@@ -62,23 +62,27 @@ class _DeviceInterpreter(Interpreter):
 
 class StepOutputs:
     """Where one ``env.step(action, out=...)`` writes: ``obs`` int32[N], ``reward`` float32[N], ``done`` uint8[N] and, optionally,
-    ``feedback_bytes`` uint8[N] (the step's feedback in the one-byte exchange format, ``gw_step_fb``) and ``ended`` uint8[N]
-    (``step_autoreset``'s cause per env: 0, 1 done, 2 step limit) -- preallocated, contiguous tensors on the env's GPU.  Their device addresses are taken ONCE, here (a step is enqueued every few
+    ``feedback_bytes`` uint8[N] (the step's feedback in the one-byte exchange format, ``gw_step_fb``), ``ended`` uint8[N]
+    (``step_autoreset``'s cause per env: 0, 1 done, 2 step limit) and ``delivered`` int32[N] (``step_autoreset(score=)``'s
+    packets per env) -- preallocated, contiguous tensors on the env's GPU.  Their device addresses are taken ONCE, here (a step is enqueued every few
     microseconds; four ``data_ptr()`` calls are 10 % of that), so the tensors must not be resized or re-pointed afterwards;
     the object keeps them alive."""
-    __slots__ = ("obs", "reward", "done", "feedback_bytes", "ended", "_ptrs", "_as_tuple", "_dev", "_ended_ptr")
+    __slots__ = ("obs", "reward", "done", "feedback_bytes", "ended", "delivered", "_ptrs", "_as_tuple", "_dev", "_ended_ptr",
+                 "_delivered_ptr")
 
-    def __init__(self, obs, reward, done, feedback_bytes=None, ended=None):
+    def __init__(self, obs, reward, done, feedback_bytes=None, ended=None, delivered=None):
         torch = _torch()
         n = obs.shape[0]
         for t, dt in ((obs, torch.int32), (reward, torch.float32), (done, torch.uint8), (feedback_bytes, torch.uint8),
-                      (ended, torch.uint8)):
+                      (ended, torch.uint8), (delivered, torch.int32)):
             if t is None:
                 continue
             assert (type(t) is torch.Tensor and t.dtype is dt and t.dim() == 1 and t.shape[0] == n and t.is_contiguous()
                     and t.device == obs.device and t.is_cuda), "StepOutputs: contiguous 1-D tensors of one length on one GPU"
         self.obs, self.reward, self.done, self.feedback_bytes, self.ended = obs, reward, done, feedback_bytes, ended
         self._ended_ptr = ended.data_ptr() if ended is not None else 0     # (beside _ptrs: the native stepper reads four)
+        self.delivered = delivered
+        self._delivered_ptr = delivered.data_ptr() if delivered is not None else 0
         self._ptrs = (obs.data_ptr(), reward.data_ptr(), done.data_ptr(),
                       feedback_bytes.data_ptr() if feedback_bytes is not None else 0)
         self._as_tuple = (obs, reward, done)
@@ -199,6 +203,7 @@ class VecCounterTrafficEnv(BaseEnv):
         self._seen = {}                                   # action tensor objects already validated (step())
         self._dev_index = self.device.index or 0
         self._last = (None, None, None)
+        self._scored_records = None                       # _autoreset(score=): the last gw_episodes / gw_score records passed
         self._stats_last = None                           # rollout_policy_stats: the last observations, and the fallback's
         self._stats_buf = None                            # 64-step transition buffers (both allocated on first use)
         self._ep_state = self._ep_tally = self._ep_next = None   # rollout_episodes: {age, ret}[N], the episode tally, the
@@ -776,11 +781,27 @@ class VecCounterTrafficEnv(BaseEnv):
                 "mean_return": torch.where(some, mean, nan), "return_stderr": torch.where(some, err, nan)}
 
     # -- episodes for a caller that chooses the actions (gw_rollout_autoreset) ---------------------------
-    def _autoreset(self, K, dev_ptr, dur_ptr, max_steps, on_done, ptrs):
-        """gw_rollout_autoreset on the env's own episode tensors; ``ptrs``: the addresses of obs, reward, done, ended."""
+    def _autoreset(self, K, dev_ptr, dur_ptr, max_steps, on_done, ptrs, score=None):
+        """gw_rollout_autoreset on the env's own episode tensors; ``ptrs``: the addresses of obs, reward, done, ended -- and, with
+        a ``score`` (gw_rollout_autoreset_scored, through ctypes), of delivered."""
         idx = self._dev_index
         fast = self._fast
-        if fast is not None and self._cuda_get_device() == idx:       # the per-step route: no ctypes, no context manager
+        if score is not None:
+            # a step-by-step caller passes the same weights and limits every time: the two records are rebuilt only when the
+            # score's bytes or the limits change (the episode tensors are allocated once, so their addresses hold)
+            key = (score.tobytes() if type(score) is np.ndarray and score.dtype == np.int32 else None, max_steps, on_done)
+            hit = self._scored_records
+            if key[0] is None or hit is None or hit[0] != key:
+                ep = nat.Episodes(max_steps, 1 if on_done else 0, self._ep_state.data_ptr(), self._ep_tally.data_ptr())
+                hit = self._scored_records = (key, C.byref(ep), C.byref(self._score(score)), self._ep_next.data_ptr())
+            if self._cuda_get_device() == idx:                        # the one-process-per-GPU case: no context manager
+                rc = self._L.gw_rollout_autoreset_scored(self._h, K, dev_ptr, dur_ptr, hit[1], hit[2], hit[3], ptrs[0], ptrs[1],
+                                                         ptrs[2], ptrs[3], ptrs[4], self._cuda_raw_stream(idx))
+            else:
+                with _torch().cuda.device(self.device):
+                    rc = self._L.gw_rollout_autoreset_scored(self._h, K, dev_ptr, dur_ptr, hit[1], hit[2], hit[3], ptrs[0],
+                                                             ptrs[1], ptrs[2], ptrs[3], ptrs[4], self._stream())
+        elif fast is not None and self._cuda_get_device() == idx:     # the per-step route: no ctypes, no context manager
             rc = fast.rollout_autoreset(self._hv, K, dev_ptr, dur_ptr, max_steps, 1 if on_done else 0, self._ep_state.data_ptr(),
                                         self._ep_tally.data_ptr(), self._ep_next.data_ptr(), ptrs[0], ptrs[1], ptrs[2], ptrs[3],
                                         self._cuda_raw_stream(idx))
@@ -792,7 +813,7 @@ class VecCounterTrafficEnv(BaseEnv):
         if rc:
             nat.check(rc)
 
-    def rollout_autoreset(self, device, duration, max_steps=0, on_done=True, out=None):
+    def rollout_autoreset(self, device, duration, max_steps=0, on_done=True, out=None, score=None):
         """``rollout()`` with episodes (gw_rollout_autoreset): K consecutive steps from pre-staged actions ``int32[K][N]``, in
         which an env whose step returned ``done`` (``on_done``), or whose episode has reached ``max_steps`` steps (0: no
         limit), is reset inside the launch exactly as ``reset(mask)`` would reset it between two steps.  Returns ``(obs, reward,
@@ -800,26 +821,33 @@ class VecCounterTrafficEnv(BaseEnv):
         is 1 = done or 2 = step limit).  The episodes are the env's own -- ``episode_state``, ``episode_tally`` and the
         observation each env acts on next are shared with ``rollout_episodes``, ``step_autoreset`` and ``reset()``, so the
         calls continue one another.  An action outside the action space flags its env, leaves it untouched and still counts
-        as a step of its episode.  ``out``: four ``[K][N]`` tensors to write into.  May be captured into a hipGraph."""
+        as a step of its episode.  ``out``: four ``[K][N]`` tensors to write into.  May be captured into a hipGraph.
+        ``score`` (``actions.make_score``; gw_rollout_autoreset_scored): ``reward``, each env's ``ret`` and the tally's return
+        columns carry the step's score -- ``score[0] * reward + score[1 + device] * delivered`` -- and a fifth output,
+        ``delivered`` int32[K][N], the data packets of the staged sender the RRM decoded in the step (``out``: five tensors).
+        A rejected action delivers 0 and scores 0.  Everything else is as without; ``None`` is the call above, unchanged."""
         torch = _torch()
         self._episodes(max_steps, on_done, None, "rollout_autoreset", needs_obs=False)
         dev = torch.as_tensor(device).to(device=self.device, dtype=torch.int32).contiguous()
         dur = torch.as_tensor(duration).to(device=self.device, dtype=torch.int32).contiguous()
         K, n = dev.shape[0], self.num_envs
         assert dev.shape == (K, n) and dur.shape == dev.shape
-        out = self._rows(K, (torch.int32, torch.float32, torch.uint8, torch.uint8), out)
-        self._autoreset(K, dev.data_ptr(), dur.data_ptr(), int(max_steps), on_done, [t.data_ptr() for t in out])
+        out = self._rows(K, (torch.int32, torch.float32, torch.uint8, torch.uint8) + ((torch.int32,) if score is not None else ()), out)
+        self._autoreset(K, dev.data_ptr(), dur.data_ptr(), int(max_steps), on_done, [t.data_ptr() for t in out], score)
         if K:
             self._last = (self._ep_next, out[1][-1], out[2][-1])
         return tuple(out)
 
-    def step_autoreset(self, action, max_steps=0, on_done=True, out=None):
+    def step_autoreset(self, action, max_steps=0, on_done=True, out=None, score=None):
         """One ``env.step()`` with autoreset -- ``rollout_autoreset`` of one step on 1-D tensors: the step, the episode
         bookkeeping and the reset of the envs whose episode it ended, in one launch.  Returns ``(obs, reward, done, ended,
         obs_next)``: what the step returned (``obs`` is the terminal observation where ``ended`` is not 0) and the
         observation to act on next (``COUNTER_BOUND`` for the envs just reset; the env's own tensor, rewritten by every
         episodic call).  ``out``: a ``StepOutputs`` with an ``ended`` tensor.  Action tensors go through ``step()``'s cache and
-        its aliasing contract.  May be captured into a hipGraph."""
+        its aliasing contract.  May be captured into a hipGraph.
+        ``score`` (``actions.make_score``; gw_rollout_autoreset_scored): ``reward`` is the step's score and the return value
+        gains ``delivered`` int32[N] -- ``(obs, reward, done, ended, obs_next, delivered)``; ``out`` then needs a ``delivered``
+        tensor too.  A recorded graph keeps the weights it was recorded with."""
         if self._ep_state is None or self._custom is not None or max_steps < 0:
             self._episodes(max_steps, on_done, None, "step_autoreset", needs_obs=False)
         dev = action["device"]
@@ -842,6 +870,9 @@ class VecCounterTrafficEnv(BaseEnv):
             obs, rew, done = self._outputs()
             ended = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
             ptrs = (obs.data_ptr(), rew.data_ptr(), done.data_ptr(), ended.data_ptr())
+            if score is not None:
+                delivered = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+                ptrs += (delivered.data_ptr(),)
         else:
             if out._dev != self._dev_index:
                 raise ValueError("StepOutputs on cuda:%d passed to an env on cuda:%d" % (out._dev, self._dev_index))
@@ -850,8 +881,15 @@ class VecCounterTrafficEnv(BaseEnv):
             obs, rew, done, ended = out.obs, out.reward, out.done, out.ended
             p = out._ptrs
             ptrs = (p[0], p[1], p[2], out._ended_ptr)
-        self._autoreset(1, dev_ptr, dur_ptr, int(max_steps), on_done, ptrs)
+            if score is not None:
+                if not out._delivered_ptr:
+                    raise ValueError("step_autoreset(score=): the StepOutputs needs a `delivered` tensor")
+                delivered = out.delivered
+                ptrs += (out._delivered_ptr,)
+        self._autoreset(1, dev_ptr, dur_ptr, int(max_steps), on_done, ptrs, score)
         self._last = (self._ep_next, rew, done)
+        if score is not None:
+            return obs, rew, done, ended, self._ep_next, delivered
         return obs, rew, done, ended, self._ep_next
 
     def episode_stats(self):

@@ -40,6 +40,8 @@
  *   gw_rollout_episodes_scored / gw_rollout_population_scored   the closed loops with a custom Interpreter's getReward in
  *                      place of the built-in one: a weighted sum of the step's reward and of the packets the RRM sniffed
  *                      (envs/core.py:59-159, networking/devices.py:163-168)
+ *   gw_rollout_autoreset_scored   keras-rl's fit loop (gw_rollout_autoreset) around an env with such a custom Interpreter: the
+ *                      caller's actions, the launch's resets, the score as the reward the agent remembers
  *   gw_step_fb         gw_step + the step's feedback as one byte per env (the row a multi-GPU job gathers)
  *   gw_pack_feedback / gw_unpack_feedback   (multi-GPU exchange format; the reference is single-process)
  *   gw_pendulum_step   InvertedPendulumEnv.step              envs/inverted_pendulum.py:101-113
@@ -388,6 +390,32 @@ int gw_rollout_episodes_scored(gw_env* env, int32_t steps, const uint32_t* cdf_d
 int gw_rollout_population_scored(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
                                  const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
                                  void* stream);
+
+/* gw_rollout_autoreset with the SCORE where the parent carries the reward, as gw_rollout_episodes_scored relates to
+ * gw_rollout_episodes: reward_dev[k][e] = (float)score_k, ret += score_k, the tally's return columns are sums of episode scores
+ * and of their squares; delivered_dev (int32[steps][N], never NULL) receives delivered_k.  d_k is the sender the caller staged
+ * for the step.  The episode causes, the resets, obs_dev, done_dev, ended_dev, obs_next_dev and every state change are exactly
+ * the parent's; w_reward = 1 with every w_delivered = 0 gives the parent's outputs, {age, ret}, tally and state bit for bit.
+ * An action outside the action space (GW_FLAG_BADACT) delivers nothing and scores exactly 0: its row repeats the current obs
+ * and done, delivered 0, reward 0, and it is still a step of the episode.  No weight is read at an unchecked sender: the
+ * index is clamped to [0, num_devices).
+ * Default mode: ONE launch per 64 steps (ct_rollout_sync_eps in ct_rollout_sfx.hip), the weights in LDS.  Per-step form -- live
+ * PHY with default queues, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0: per step gw_delivered's launch
+ * into the uint32[N] scratch row above, a step launch, the scored bookkeeping launch and gw_reset's launch -- same results.
+ * The row's rules are as above: the first call that takes this form allocates it (and so synchronises the device once),
+ * gw_destroy frees it, gw_state_bytes counts it from then on, a snapshot does not hold it.  GW_ROLLOUT_STRICT turns the
+ * per-step form into GW_EUNSUPPORTED before anything is launched or allocated.  An explicit-queue handle, which the parent
+ * accepts, has no per-env delivered counter: GW_EUNSUPPORTED before any launch.
+ * GW_EINVAL before any HIP call: env / ep / score NULL, a NULL pointer other than ep->tally_dev / stream, steps < 0,
+ * max_steps < 0, a weight outside the bounds (all GW_MAX_DEVICES entries, also when steps == 0).  steps == 0 with valid
+ * arguments is GW_OK.  Stream-ordered.
+ * This call MAY be captured into a hipGraph, as the parent may: there is no step0.  The score is read by value before the
+ * call returns, so a recorded launch keeps the weights it was recorded with -- record again to change them.  Because of the
+ * scratch row's allocation, a capture of the PER-STEP form needs one eager call on the handle first. */
+int gw_rollout_autoreset_scored(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
+                                const gw_episodes* ep, const gw_score* score, int32_t* obs_next_dev,
+                                int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev,
+                                int32_t* delivered_dev, void* stream);
 
 /* gw_transition_stats for rows recorded by gw_rollout_episodes: step k's observation seen is counter_bound where
  * ended_dev[k - 1] != 0; row 0 uses obs_prev_dev as it is. */

@@ -12,6 +12,15 @@ Five legs, each on a handle of its own, in ONE process, alternated block by bloc
   c  env.step_autoreset(action, T, out=...)         the feature, one launch
   d  env.rollout() of 64 steps                      context
   e  env.rollout_autoreset() of 64 steps            the feature
+Scored legs (profiles/autoreset_scored/README.md), behind names of their own -- `--legs s1,s0,s2,s3,r1,r0,r2,r3`; the score is one
+point per delivered packet, make_score(D, reward=0, delivered=1):
+  s1  env.step_autoreset(action, T, out=..., score=)   the scored one-step form, fused
+  s0  env.step_autoreset(action, T, out=...)           the unscored parent call on the same box (leg c on a handle of its own)
+  s2  s1 on a handle created with GW_ROLLOUT_CAP=0     the scored call's own per-step form
+  s3  the composition available before                 gw_delivered, step_autoreset, gw_delivered, the difference and the score in
+                                                       torch (it cannot reach {age, ret} or the tally: written inside the launch)
+  r1 / r0 / r2 / r3                                    the same four for a rollout of 64: env.rollout_autoreset(score=); r3 is s3
+                                                       per step with the packets and the score written into [64][N] rows
 A block is `--block` steps (a multiple of 64) of one leg between two HIP events and two wall-clock reads (the second after a
 synchronize); blocks are repeated until every leg has at least `--seconds` of stream time.  Reported per leg: the median and
 the spread over blocks of the wall-clock and of the event microseconds per step.  b and c walk the same trajectory (checked
@@ -60,7 +69,7 @@ def main():
                            torch.empty(N, dtype=torch.uint8, device=dev),
                            ended=torch.empty(N, dtype=torch.uint8, device=dev) if ended else None)
 
-    envs = {leg: new_env() for leg in "abcde"}
+    envs = {leg: new_env() for leg in "abcde"}                          # (the scored legs' handles: below, where they are named)
     center = int(envs["a"].config.counter_bound)
     out_a, out_b, out_c = outputs(), outputs(), outputs(ended=True)
     out3 = (torch.empty((K, N), dtype=torch.int32, device=dev), torch.empty((K, N), dtype=torch.float32, device=dev),
@@ -108,6 +117,86 @@ def main():
 
     legs = {"a": leg_a, "b": leg_b, "c": leg_c, "d": leg_d, "e": leg_e}
     names = [x for x in args.legs.split(",") if x]
+
+    # ---- the scored legs: handles and buffers only for the legs asked for ----
+    scored = [n for n in names if n in ("s0", "s1", "s2", "s3", "r0", "r1", "r2", "r3")]
+    if scored:
+        from gymwipe_amd import _native as nat
+        score = actions.make_score(D, reward=0, delivered=1)
+        w = torch.from_numpy(score.astype(np.int64)).to(dev)
+
+        def outputs_scored():
+            o = outputs(ended=True)
+            return StepOutputs(o.obs, o.reward, o.done, ended=o.ended, delivered=torch.empty(N, dtype=torch.int32, device=dev))
+
+        for n in scored:
+            if n.endswith("2"):
+                os.environ["GW_ROLLOUT_CAP"] = "0"                     # read when the handle is created: no fused rollout
+            envs[n] = new_env()
+            os.environ.pop("GW_ROLLOUT_CAP", None)
+        so = {n: (outputs_scored() if n in ("s1", "s2") else outputs(ended=True)) for n in scored if n[0] == "s" or n == "r3"}
+        rows5 = {n: out4 + (torch.empty((K, N), dtype=torch.int32, device=dev),) for n in scored if n in ("r1", "r2", "r3")}
+        rows5 = {n: tuple(torch.empty_like(t) for t in r) for n, r in rows5.items()}
+        deliv = {n: (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev))
+                 for n in scored if n.endswith("3")}
+
+        def one_step(n, with_score):
+            env, out = envs[n], so[n]
+            kw = {"score": score} if with_score else {}
+
+            def run(steps):
+                for s in range(steps):
+                    env.step_autoreset(acts[s % K], T, True, out, **kw)
+            return run
+
+        def rollout64(n, with_score):
+            env = envs[n]
+            kw = {"score": score, "out": rows5[n]} if with_score else {"out": out4}
+
+            def run(steps):
+                for _ in range(steps // K):
+                    env.rollout_autoreset(a_dev, a_dur, T, True, **kw)
+            return run
+
+        def composition(n, keep_rows):
+            env, out, (before, after) = envs[n], so[n], deliv[n]
+            L, h = env._L, env._h
+
+            def run(steps):
+                for s in range(steps):
+                    k = s % K
+                    nat.check(L.gw_delivered(h, before.data_ptr(), env._stream()))
+                    obs, rew, done, ended, nxt = env.step_autoreset(acts[k], T, True, out)
+                    nat.check(L.gw_delivered(h, after.data_ptr(), env._stream()))
+                    dl = after - before
+                    sc = w[0] * rew.to(torch.int64) + w[1 + a_dev[k].to(torch.int64)] * dl
+                    if keep_rows:
+                        r = rows5[n]
+                        r[0][k].copy_(obs); r[1][k].copy_(sc); r[2][k].copy_(done); r[3][k].copy_(ended); r[4][k].copy_(dl)
+                    else:
+                        rew.copy_(sc)
+            return run
+
+        legs.update({"s1": lambda: one_step("s1", True), "s0": lambda: one_step("s0", False), "s2": lambda: one_step("s2", True),
+                     "s3": lambda: composition("s3", False), "r1": lambda: rollout64("r1", True), "r0": lambda: rollout64("r0", False),
+                     "r2": lambda: rollout64("r2", True), "r3": lambda: composition("r3", True)})
+        for n in scored:
+            legs[n] = legs[n]()
+        # the fused, the per-step and the composed form score the same steps: one round of the stream from fresh handles
+        sums = {}
+        for n in [x for x in ("s1", "s2", "s3") if x in scored]:
+            total_sc = 0.0
+            for s in range(K):
+                if n == "s3":                                           # (one point per packet: the score is the difference)
+                    nat.check(envs[n]._L.gw_delivered(envs[n]._h, deliv[n][0].data_ptr(), envs[n]._stream()))
+                    envs[n].step_autoreset(acts[s], T, True, so[n])
+                    nat.check(envs[n]._L.gw_delivered(envs[n]._h, deliv[n][1].data_ptr(), envs[n]._stream()))
+                    total_sc += float((deliv[n][1] - deliv[n][0]).double().sum())
+                else:
+                    total_sc += float(envs[n].step_autoreset(acts[s], T, True, so[n], score=score)[1].double().sum())
+            sums[n] = total_sc
+            envs[n].reset()
+        assert len(set(sums.values())) <= 1 and all(v > 0 for v in sums.values()), "the scored legs walk different steps: %r" % sums
 
     # b and c walk the same steps: rewards and episode count over one round of the stream, from fresh handles
     if "b" in names and "c" in names:
