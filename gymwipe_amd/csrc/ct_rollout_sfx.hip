@@ -1236,79 +1236,64 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_eps(GwState st, GwDevConst
 }
 
 // The per-step form's bookkeeping, for handles without the fused kernels: after a step's launch, steps 1-4 and 6 of the
-// semantics for every env -- {age, ret}, ended, the tally, the observation acted on next -- and the mask gw_reset's launch takes.
-__global__ __launch_bounds__(256) void episodes_step_kernel(uint32_t N, int32_t center, GwEpisodeArgs ea, const int32_t* obs,
-                                                           const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask)
+// semantics for every env -- {age, ret} (EpisodeBook: the fused kernels' rule, one step of it), ended, the tally, the observation
+// acted on next -- and the mask gw_reset's launch takes.
+//   SCORED                   a scored call: the delivered counter (GwState::sa, word 2 e + 1) differenced against the copy the
+//                            draw took (deliv_before), the step scored with the sender in `device` (clamped: a staged one may
+//                            lie outside the action space, and such a step moved neither counter nor reward) -- `reward` comes
+//                            in as the step's reward and goes out as its score.  Otherwise the reward is the return's term, and
+//                            w, D, sa, deliv_before and `device` are not read.  A template flag (two instantiations): tested
+//                            at run time, the score's loads wait behind the branch for the reward's and the kernel takes one
+//                            memory round trip more (profiles/per_step_fold/README.md).  (Not a family of
+//                            tests/test_kernel_variants.py's catalogue: tests/test_host_logic.py lists it as out of scope and
+//                            checks that these two instantiations are the library's.)
+//   delivered_out            the packets per step, or nullptr (the population's form keeps none).
+//   pop_tally                gw_rollout_population's [P][GW_EP_COLS], env e's episodes into row e / M as well as into the
+//                            call-wide ea.tally (either may be nullptr).  Any M: a block whose 256 envs run one policy sums in
+//                            LDS and adds its words to both rows; a block that spans policies sums the call-wide words in LDS
+//                            and sends each ended episode's words to its policy's row directly.  nullptr: M = N.
+template <bool SCORED>
+__global__ __launch_bounds__(256) void episodes_step_kernel(uint32_t N, uint32_t D, int32_t center, GwEpisodeArgs ea, gw_score w,
+                                                           uint32_t M, int64_t* pop_tally, const uint32_t* sa,
+                                                           const uint32_t* deliv_before, const int32_t* device, const int32_t* obs,
+                                                           float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask,
+                                                           int32_t* delivered_out)
 {
     __shared__ unsigned long long s_ep[GW_EP_COLS];
-    if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
-    __syncthreads();
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < N) {
-        int2 s = *reinterpret_cast<const int2*>(ea.state + 2 * (size_t)e);
-        const int32_t r = (int32_t)reward[e];
-        s.x += 1; s.y += r;
-        const uint32_t cause = (ea.on_done != 0 && done[e] != 0) ? 1u : ((ea.max_steps > 0 && s.x >= ea.max_steps) ? 2u : 0u);
-        if (cause) {
-            if (ea.tally) {
-                const unsigned long long v[GW_EP_COLS] = {1ull, cause == 1u ? 1ull : 0ull, (unsigned long long)(int64_t)s.x,
-                                                          (unsigned long long)(int64_t)s.y,
-                                                          (unsigned long long)((int64_t)s.y * (int64_t)s.y)};
-#pragma unroll
-                for (int j = 0; j < GW_EP_COLS; ++j)
-                    if (v[j]) __hip_atomic_fetch_add(s_ep + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            s.x = 0; s.y = 0;
-        }
-        *reinterpret_cast<int2*>(ea.state + 2 * (size_t)e) = s;
-        ended[e] = (uint8_t)cause;
-        mask[e] = (uint8_t)(cause != 0u);
-        ea.obs_next[e] = cause ? center : obs[e];
-    }
-    __syncthreads();
-    if (ea.tally && threadIdx.x < (uint32_t)GW_EP_COLS && s_ep[threadIdx.x]) gw_ts_add(ea.tally + threadIdx.x, s_ep[threadIdx.x]);
-}
-
-// gw_rollout_population's per-step form: the same bookkeeping on the handle's own N-long rows (ended and mask among them), env
-// e's episode into row e / M of pop_tally and into the call-wide ea.tally (or nullptr).  Any M: a block whose 256 envs run one
-// policy sums in LDS and adds its words to both rows; a block that spans policies sums the call-wide words in LDS and sends
-// each ended episode's words to its policy's row directly.
-__global__ __launch_bounds__(256) void episodes_step_pop_kernel(uint32_t N, int32_t center, GwEpisodeArgs ea, uint32_t M, int64_t* pop_tally,
-                                                               const int32_t* obs, const float* reward, const uint8_t* done,
-                                                               uint8_t* ended, uint8_t* mask)
-{
-    __shared__ unsigned long long s_ep[GW_EP_COLS];
-    if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
+    gw_ep_zero(s_ep);
     __syncthreads();
     const uint32_t e0 = blockIdx.x * blockDim.x, e = e0 + threadIdx.x;
     const uint32_t pol0 = e0 / M;                                               // (e0 < N: the grid is ceil(N / 256) blocks)
-    const bool one_policy = pol0 == gw_min_u32(e0 + blockDim.x - 1u, N - 1u) / M;
+    const bool block_row = pop_tally && pol0 == gw_min_u32(e0 + blockDim.x - 1u, N - 1u) / M;
     if (e < N) {
-        int2 s = *reinterpret_cast<const int2*>(ea.state + 2 * (size_t)e);
-        const int32_t r = (int32_t)reward[e];
-        s.x += 1; s.y += r;
-        const uint32_t cause = (ea.on_done != 0 && done[e] != 0) ? 1u : ((ea.max_steps > 0 && s.x >= ea.max_steps) ? 2u : 0u);
-        if (cause) {
-            const unsigned long long v[GW_EP_COLS] = {1ull, cause == 1u ? 1ull : 0ull, (unsigned long long)(int64_t)s.x,
-                                                      (unsigned long long)(int64_t)s.y,
-                                                      (unsigned long long)((int64_t)s.y * (int64_t)s.y)};
-            int64_t* row = pop_tally + (size_t)(e / M) * GW_EP_COLS;
-#pragma unroll
-            for (int j = 0; j < GW_EP_COLS; ++j) {
-                if (!v[j]) continue;
-                if (one_policy || ea.tally) __hip_atomic_fetch_add(s_ep + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (!one_policy) gw_ts_add(row + j, v[j]);
-            }
-            s.x = 0; s.y = 0;
+        EpisodeBook ep;
+        ep.load(ea, e);
+        int32_t r = (int32_t)reward[e];
+        if constexpr (SCORED) {
+            const uint32_t dl = sa[(size_t)2 * e + 1] - deliv_before[e];
+            r = w.w_reward * r + w.w_delivered[gw_min_u32((uint32_t)device[e], D - 1u)] * (int32_t)dl;
+            reward[e] = (float)r;
+            if (delivered_out) delivered_out[e] = (int32_t)dl;
         }
-        *reinterpret_cast<int2*>(ea.state + 2 * (size_t)e) = s;
+        const uint32_t cause = ep.stepped(r, done[e]);
+        GwEpisodeArgs own = ea;                          // (the book adds into LDS whenever there is a tally)
+        if (block_row) own.tally = pop_tally;
+        ep.store(own, e, s_ep);
+        if (cause && pop_tally && !block_row) {
+            int64_t* row = pop_tally + (size_t)(e / M) * GW_EP_COLS;
+            const unsigned long long v[GW_EP_COLS] = {ep.n, ep.n_done, (unsigned long long)ep.len_sum, (unsigned long long)ep.ret_sum,
+                                                      (unsigned long long)ep.ret_sq};
+#pragma unroll
+            for (int j = 0; j < GW_EP_COLS; ++j)
+                if (v[j]) gw_ts_add(row + j, v[j]);
+        }
         ended[e] = (uint8_t)cause;
         mask[e] = (uint8_t)(cause != 0u);
         ea.obs_next[e] = cause ? center : obs[e];
     }
     __syncthreads();
     if (threadIdx.x < (uint32_t)GW_EP_COLS && s_ep[threadIdx.x]) {
-        if (one_policy) gw_ts_add(pop_tally + (size_t)pol0 * GW_EP_COLS + threadIdx.x, s_ep[threadIdx.x]);
+        if (block_row) gw_ts_add(pop_tally + (size_t)pol0 * GW_EP_COLS + threadIdx.x, s_ep[threadIdx.x]);
         if (ea.tally) gw_ts_add(ea.tally + threadIdx.x, s_ep[threadIdx.x]);
     }
 }
@@ -1360,23 +1345,13 @@ __global__ __launch_bounds__(256) void transition_stats_rows(uint64_t total, uin
     }
 }
 
-// The unfused form's draw, for handles without a fused rollout: one step's actions for every env from the observations `obs_in`.
+// The per-step form's draw, for handles without a fused rollout: one step's actions for every env from the observations
+// p.obs_prev, env e from table e / M of p.cdf's [P][3][A] (one table: M = N).  deliv_before != nullptr (the scored calls): each
+// env's delivered counter (GwState::sa, word 2 e + 1: what gw_delivered reads) into that row as well, in front of the step.
 __global__ __launch_bounds__(256) void policy_sample_kernel(uint32_t N, uint32_t A, uint32_t md, int32_t center, GwPolicyArgs p,
-                                                            int32_t* __restrict__ device_out, int32_t* __restrict__ duration_out)
-{
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    const uint32_t cls = gw_policy_cls(p.obs_prev[e], center);
-    const uint32_t a = gw_policy_count(p.cdf + (size_t)cls * A, A, gw_policy_u(p.seed, gw_policy_env_term(p.env0, e), p.step0));
-    const uint32_t dv = a / md;
-    device_out[e] = (int32_t)dv;
-    duration_out[e] = (int32_t)(a - dv * md);
-}
-
-// gw_rollout_population's per-step draw: policy_sample_kernel with env e reading table e / M of p.cdf's [P][3][A].
-__global__ __launch_bounds__(256) void policy_sample_pop_kernel(uint32_t N, uint32_t A, uint32_t md, int32_t center, GwPolicyArgs p,
-                                                                uint32_t M, int32_t* __restrict__ device_out,
-                                                                int32_t* __restrict__ duration_out)
+                                                            uint32_t M, const uint32_t* __restrict__ sa,
+                                                            int32_t* __restrict__ device_out, int32_t* __restrict__ duration_out,
+                                                            uint32_t* __restrict__ deliv_before)
 {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
@@ -1386,72 +1361,7 @@ __global__ __launch_bounds__(256) void policy_sample_pop_kernel(uint32_t N, uint
     const uint32_t dv = a / md;
     device_out[e] = (int32_t)dv;
     duration_out[e] = (int32_t)(a - dv * md);
-}
-
-// The scored calls' per-step form, in front of the step: policy_sample_pop_kernel's draw (one table: M = N), and each env's
-// delivered counter (GwState::sa, word 2 e + 1: what gw_delivered reads) into the handle's scratch row.
-__global__ __launch_bounds__(256) void policy_sample_scored_kernel(uint32_t N, uint32_t A, uint32_t md, int32_t center, GwPolicyArgs p,
-                                                                   uint32_t M, const uint32_t* __restrict__ sa,
-                                                                   int32_t* __restrict__ device_out, int32_t* __restrict__ duration_out,
-                                                                   uint32_t* __restrict__ deliv_before)
-{
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    const uint32_t cls = gw_policy_cls(p.obs_prev[e], center);
-    const uint32_t* row = p.cdf + ((size_t)(e / M) * 3u + cls) * A;
-    const uint32_t a = gw_policy_count(row, A, gw_policy_u(p.seed, gw_policy_env_term(p.env0, e), p.step0));
-    const uint32_t dv = a / md;
-    device_out[e] = (int32_t)dv;
-    duration_out[e] = (int32_t)(a - dv * md);
-    deliv_before[e] = sa[(size_t)2 * e + 1];
-}
-
-// ... and behind it: the counter differenced, the step scored (`reward` comes in as the step's reward and goes out as its
-// score), and episodes_step_pop_kernel's bookkeeping with the score.  pop_tally == nullptr: no per-policy rows (the records
-// form); delivered_out == nullptr: the packets per step are not kept (the population's form).
-__global__ __launch_bounds__(256) void episodes_step_scored_kernel(uint32_t N, uint32_t D, int32_t center, GwEpisodeArgs ea, gw_score w,
-                                                                  uint32_t M, int64_t* pop_tally, const uint32_t* sa,
-                                                                  const uint32_t* deliv_before, const int32_t* device,
-                                                                  const int32_t* obs, float* reward, const uint8_t* done,
-                                                                  uint8_t* ended, uint8_t* mask, int32_t* delivered_out)
-{
-    __shared__ unsigned long long s_ep[GW_EP_COLS];
-    if (threadIdx.x < (uint32_t)GW_EP_COLS) s_ep[threadIdx.x] = 0ull;
-    __syncthreads();
-    const uint32_t e0 = blockIdx.x * blockDim.x, e = e0 + threadIdx.x;
-    const uint32_t pol0 = e0 / M;                                               // (e0 < N: the grid is ceil(N / 256) blocks)
-    const bool one_policy = !pop_tally || pol0 == gw_min_u32(e0 + blockDim.x - 1u, N - 1u) / M;
-    if (e < N) {
-        int2 s = *reinterpret_cast<const int2*>(ea.state + 2 * (size_t)e);
-        const uint32_t dl = sa[(size_t)2 * e + 1] - deliv_before[e];
-        const uint32_t dv = gw_min_u32((uint32_t)device[e], D - 1u);            // (a drawn action: inside the action space)
-        const int32_t r = w.w_reward * (int32_t)reward[e] + w.w_delivered[dv] * (int32_t)dl;
-        reward[e] = (float)r;
-        if (delivered_out) delivered_out[e] = (int32_t)dl;
-        s.x += 1; s.y += r;
-        const uint32_t cause = (ea.on_done != 0 && done[e] != 0) ? 1u : ((ea.max_steps > 0 && s.x >= ea.max_steps) ? 2u : 0u);
-        if (cause) {
-            const unsigned long long v[GW_EP_COLS] = {1ull, cause == 1u ? 1ull : 0ull, (unsigned long long)(int64_t)s.x,
-                                                      (unsigned long long)(int64_t)s.y,
-                                                      (unsigned long long)((int64_t)s.y * (int64_t)s.y)};
-#pragma unroll
-            for (int j = 0; j < GW_EP_COLS; ++j) {
-                if (!v[j]) continue;
-                if (one_policy || ea.tally) __hip_atomic_fetch_add(s_ep + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (!one_policy) gw_ts_add(pop_tally + (size_t)(e / M) * GW_EP_COLS + j, v[j]);
-            }
-            s.x = 0; s.y = 0;
-        }
-        *reinterpret_cast<int2*>(ea.state + 2 * (size_t)e) = s;
-        ended[e] = (uint8_t)cause;
-        mask[e] = (uint8_t)(cause != 0u);
-        ea.obs_next[e] = cause ? center : obs[e];
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)GW_EP_COLS && s_ep[threadIdx.x]) {
-        if (pop_tally && one_policy) gw_ts_add(pop_tally + (size_t)pol0 * GW_EP_COLS + threadIdx.x, s_ep[threadIdx.x]);
-        if (ea.tally) gw_ts_add(ea.tally + threadIdx.x, s_ep[threadIdx.x]);
-    }
+    if (deliv_before) deliv_before[e] = sa[(size_t)2 * e + 1];
 }
 
 // ---- launching the step-synchronous family (host side) -------------------------------------------------------------------------
@@ -1517,24 +1427,31 @@ GwEpisodeArgs episode_args(const gw_episodes& ep, int32_t* obs_next)
 
 } // namespace
 
-// One step's draw of gw_rollout_population's per-step form: the handle's action rows from `obs_in`, env e from table e / M.
-int gw_launch_policy_sample_pop(int64_t N, int D, int max_duration, int counter_bound, const gw_population& pop,
-                                const GwPolicyStream& pol, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out,
-                                void* stream)
+// One step of the per-step forms (every queue mode), around the step's launch.  In front of it, the closed loops' draw for step
+// pol.step0 from `obs_in` into row's action rows, env e from table e / M (one table: M = st.N); deliv_before: where a scored
+// call's copy of the delivered counters goes, or nullptr ...
+int gw_launch_policy_sample(const GwState& st, const GwDevConst& cst, const GwPolicyStream& pol, int64_t M, const int32_t* obs_in,
+                            const GwRows& row, uint32_t* deliv_before, void* stream)
 {
-    hipLaunchKernelGGL(policy_sample_pop_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
-                       (uint32_t)D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound, policy_args(pol, obs_in),
-                       (uint32_t)pop.envs_per_policy, device_out, duration_out);
+    hipLaunchKernelGGL(policy_sample_kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)st.N,
+                       (uint32_t)st.D * (uint32_t)cst.max_duration, (uint32_t)cst.max_duration, cst.counter_bound,
+                       policy_args(pol, obs_in), (uint32_t)M, (const uint32_t*)st.sa, row.device, row.duration, deliv_before);
     return gw_launch_status();
 }
-
-// One step's draw of gw_rollout_policy's unfused form (every queue mode): row pol.step0 of the action outputs from `obs_in`.
-int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const GwPolicyStream& pol, const int32_t* obs_in,
-                            int32_t* device_out, int32_t* duration_out, void* stream)
+// ... and behind it the episodes' bookkeeping on that row (row.device: the senders the step took), with the handle's reset
+// mask.  score: the weights and deliv_before's copy to score the step with, or nullptr; pop_tally: the population's rows for M
+// envs each, or nullptr; delivered_out: the packets per step, or nullptr.
+int gw_launch_episodes_step(const GwState& st, const GwDevConst& cst, const gw_episodes& ep, const gw_score* score, int64_t M,
+                            int64_t* pop_tally, const uint32_t* deliv_before, int32_t* obs_next, const GwRows& row, uint8_t* mask,
+                            int32_t* delivered_out, void* stream)
 {
-    hipLaunchKernelGGL(policy_sample_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
-                       (uint32_t)D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound, policy_args(pol, obs_in), device_out,
-                       duration_out);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)st.N,
+                           (uint32_t)st.D, cst.counter_bound, episode_args(ep, obs_next), score ? *score : gw_score{}, (uint32_t)M,
+                           pop_tally, (const uint32_t*)st.sa, deliv_before, (const int32_t*)row.device, (const int32_t*)row.obs,
+                           row.reward, (const uint8_t*)row.done, row.ended, mask, delivered_out);
+    };
+    if (score) launch(episodes_step_kernel<true>); else launch(episodes_step_kernel<false>);
     return gw_launch_status();
 }
 
@@ -1576,10 +1493,17 @@ int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int co
 }
 
 // gw_rollout_episodes / gw_rollout_episodes_stats: their parents' rules, with the caller's gw_episodes and obs_next passed on.
+// score (here and below): nullptr, or the _scored call's weights -- the same rules with the D weights counted into the launch's
+// LDS, the family with the score, and `delivered` where the call keeps the packets per step.
 int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
-                                    const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, const GwRows& out)
+                                    const gw_episodes& ep, const gw_score* score, const int32_t* obs_prev, int32_t* obs_next,
+                                    const GwRows& out, int32_t* delivered)
 {
-    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE)) return GW_EUNSUPPORTED;
+    if (fused_unavailable(st, cst, ch.K, score ? GW_FUSED_TABLE_SCORE : GW_FUSED_TABLE)) return GW_EUNSUPPORTED;
+    if (score)
+        return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POLICY_EPS, GW_FUSED_TABLE_SCORE, GW_KERNEL_OF(ct_rollout_policy_eps),
+                            policy_args(pol, obs_prev), episode_args(ep, obs_next), *score, out.device, out.duration, out.obs, out.reward,
+                            out.done, out.ended, delivered);
     return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POLICY_EP, GW_FUSED_TABLE, GW_KERNEL_OF(ct_rollout_policy_ep),
                         policy_args(pol, obs_prev), episode_args(ep, obs_next), out.device, out.duration, out.obs, out.reward, out.done,
                         out.ended);
@@ -1597,92 +1521,30 @@ int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, co
 // that no wave spans two policies.  (The caller has checked num_policies * envs_per_policy == N: every block's policy index is
 // below num_policies.)
 int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
-                                 const GwPolicyStream& pol, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next)
+                                 const GwPolicyStream& pol, const gw_episodes& ep, const gw_score* score, const int32_t* obs_prev,
+                                 int32_t* obs_next)
 {
-    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE) || pop.envs_per_policy % 64 != 0) return GW_EUNSUPPORTED;
+    if (fused_unavailable(st, cst, ch.K, score ? GW_FUSED_TABLE_SCORE : GW_FUSED_TABLE) || pop.envs_per_policy % 64 != 0)
+        return GW_EUNSUPPORTED;
+    if (score)
+        return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POP_EPS, GW_FUSED_TABLE_SCORE, GW_KERNEL_OF(ct_rollout_pop_eps),
+                            policy_args(pol, obs_prev), episode_args(ep, obs_next), *score, (uint32_t)pop.envs_per_policy, pop.tally_dev);
     return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POP_EP, GW_FUSED_TABLE, GW_KERNEL_OF(ct_rollout_pop_ep), policy_args(pol, obs_prev),
                         episode_args(ep, obs_next), (uint32_t)pop.envs_per_policy, pop.tally_dev);
 }
 
-// gw_rollout_episodes_scored / gw_rollout_population_scored: their parents' rules, the D weights counted into the launch's LDS.
-int gw_launch_rollout_policy_eps_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
-                                     const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev, int32_t* obs_next,
-                                     const GwRows& out, int32_t* delivered)
-{
-    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE_SCORE)) return GW_EUNSUPPORTED;
-    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POLICY_EPS, GW_FUSED_TABLE_SCORE, GW_KERNEL_OF(ct_rollout_policy_eps),
-                        policy_args(pol, obs_prev), episode_args(ep, obs_next), score, out.device, out.duration, out.obs, out.reward,
-                        out.done, out.ended, delivered);
-}
-
-int gw_launch_rollout_pop_eps_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
-                                  const GwPolicyStream& pol, const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev,
-                                  int32_t* obs_next)
-{
-    if (fused_unavailable(st, cst, ch.K, GW_FUSED_TABLE_SCORE) || pop.envs_per_policy % 64 != 0) return GW_EUNSUPPORTED;
-    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_POP_EPS, GW_FUSED_TABLE_SCORE, GW_KERNEL_OF(ct_rollout_pop_eps),
-                        policy_args(pol, obs_prev), episode_args(ep, obs_next), score, (uint32_t)pop.envs_per_policy, pop.tally_dev);
-}
-
-// One step of the scored calls' per-step form: the draw with the delivered counters' copy (M: envs per table; one table: N) ...
-int gw_launch_policy_sample_scored(const GwState& st, int max_duration, int counter_bound, int64_t M, const GwPolicyStream& pol,
-                                   const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, uint32_t* deliv_before,
-                                   void* stream)
-{
-    hipLaunchKernelGGL(policy_sample_scored_kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (uint32_t)st.N, (uint32_t)st.D * (uint32_t)max_duration, (uint32_t)max_duration, counter_bound,
-                       policy_args(pol, obs_in), (uint32_t)M, (const uint32_t*)st.sa, device_out, duration_out, deliv_before);
-    return gw_launch_status();
-}
-// ... and the scoring and the episodes' bookkeeping behind the step (pop_tally: the population's rows, or nullptr).
-int gw_launch_episodes_step_scored(const GwState& st, int counter_bound, const gw_episodes& ep, const gw_score& score, int64_t M,
-                                   int64_t* pop_tally, const uint32_t* deliv_before, int32_t* obs_next, const GwRows& row,
-                                   uint8_t* mask, int32_t* delivered_out, void* stream)
-{
-    hipLaunchKernelGGL(episodes_step_scored_kernel, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (uint32_t)st.N, (uint32_t)st.D, counter_bound, episode_args(ep, obs_next), score, (uint32_t)M, pop_tally,
-                       (const uint32_t*)st.sa, deliv_before, (const int32_t*)row.device, (const int32_t*)row.obs, row.reward,
-                       (const uint8_t*)row.done, row.ended, mask, delivered_out);
-    return gw_launch_status();
-}
-
-// One step's episode bookkeeping of gw_rollout_population's per-step form, on the handle's rows.
-int gw_launch_episodes_step_pop(int64_t N, int counter_bound, const gw_episodes& ep, const gw_population& pop, int32_t* obs_next,
-                                const int32_t* obs, const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask,
-                                void* stream)
-{
-    hipLaunchKernelGGL(episodes_step_pop_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
-                       counter_bound, episode_args(ep, obs_next), (uint32_t)pop.envs_per_policy, pop.tally_dev, obs, reward, done, ended,
-                       mask);
-    return gw_launch_status();
-}
-
-// gw_rollout_autoreset: the handle's rules alone (there is no table).
+// gw_rollout_autoreset: the handle's rules alone (there is no table; the weights' LDS copy is static, part of the kernel's own
+// figure).
 int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
-                                    const int32_t* duration, const gw_episodes& ep, int32_t* obs_next, const GwRows& out)
+                                    const int32_t* duration, const gw_episodes& ep, const gw_score* score, int32_t* obs_next,
+                                    const GwRows& out, int32_t* delivered)
 {
     if (fused_unavailable(st, cst, ch.K, GW_FUSED_NO_TABLE)) return GW_EUNSUPPORTED;
+    if (score)
+        return launch_fused(st, cst, ch, GW_LS_ROLLOUT_SYNC_EPS, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_sync_eps),
+                            episode_args(ep, obs_next), *score, device, duration, out.obs, out.reward, out.done, out.ended, delivered);
     return launch_fused(st, cst, ch, GW_LS_ROLLOUT_SYNC_EP, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_sync_ep), episode_args(ep, obs_next),
                         device, duration, out.obs, out.reward, out.done, out.ended);
-}
-
-// gw_rollout_autoreset_scored: the same rules (the weights' LDS copy is static, part of the kernel's own figure).
-int gw_launch_rollout_autoreset_scored_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
-                                           const int32_t* duration, const gw_episodes& ep, const gw_score& score, int32_t* obs_next,
-                                           const GwRows& out, int32_t* delivered)
-{
-    if (fused_unavailable(st, cst, ch.K, GW_FUSED_NO_TABLE)) return GW_EUNSUPPORTED;
-    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_SYNC_EPS, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_sync_eps), episode_args(ep, obs_next),
-                        score, device, duration, out.obs, out.reward, out.done, out.ended, delivered);
-}
-
-// One step's episode bookkeeping of gw_rollout_episodes' per-step form (every queue mode): row `step`'s ended, the mask.
-int gw_launch_episodes_step(int64_t N, int counter_bound, const gw_episodes& ep, int32_t* obs_next, const int32_t* obs,
-                            const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask, void* stream)
-{
-    hipLaunchKernelGGL(episodes_step_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)N,
-                       counter_bound, episode_args(ep, obs_next), obs, reward, done, ended, mask);
-    return gw_launch_status();
 }
 
 // gw_rollout's launch.  Returns GW_EUNSUPPORTED when this (D, K) has no fused kernel: the caller falls back to K step launches.

@@ -76,9 +76,10 @@ struct gw_env {
     uint64_t     launches[GW_LS_COUNT];   // kernel instantiations launched by this handle (gw_selftest_launches)
     GwSfxFns     fns;         // default mode: this handle's step / reset kernels on its device, resolved at gw_create
     uint8_t*     ep_mask;     // [N] gw_rollout_episodes' per-step form: the envs to reset after the step (scratch, not state)
-    int32_t*     pop_rows;    // gw_rollout_population's per-step form: one block of six N-long rows (device, duration, obs, reward
-                              // | done, ended), allocated by the first call that needs them (scratch, not state)
-    uint32_t*    score_base;  // [N] the scored calls' per-step form: each env's delivered counter before the step (the same rules)
+    int32_t*     pop_rows;    // the population calls' per-step form: one block of six N-long rows (device, duration, obs, reward |
+                              // done, ended), allocated by the first call that runs per step (pop_rows_of; scratch, not state)
+    uint32_t*    score_base;  // [N] the scored calls' per-step form: each env's delivered counter before the step, allocated by
+                              // the first scored call that runs per step (score_base_of; scratch, not state)
 };
 
 namespace {
@@ -563,27 +564,52 @@ static int plain_step(gw_env* env, int32_t s, const int32_t* device_row, const i
     gw_env_add_steps(env, 1);
     return GW_OK;
 }
-// ... in front of it the draw of the closed loops, from the observations `seen` (pop: the population's, or nullptr) ...
-static int draw_step(gw_env* env, int32_t s, const GwPolicyStream& pol, const gw_population* pop, const int32_t* seen, const GwRows& row,
-                     void* stream)
+// The per-step forms' scratch, which the handle allocates when a call first runs that way (gw_state_bytes counts it from then
+// on; a call GW_ROLLOUT_STRICT refuses never gets here): the population calls' six N-long rows ...
+static int pop_rows_of(gw_env* env, GwRows* row)
 {
     const int64_t N = env->st.N;
-    const GwDevConst& c = env->cst_host;
-    if (pop ? gw_launch_policy_sample_pop(N, env->st.D, c.max_duration, c.counter_bound, *pop, pol.at(s), seen, row.device, row.duration, stream)
-            : gw_launch_policy_sample(N, env->st.D, c.max_duration, c.counter_bound, pol.at(s), seen, row.device, row.duration, stream))
+    if (!env->pop_rows)                                        // 4 x 4 N + 2 x N bytes
+        if (const int e = dev_alloc(env, &env->pop_rows, (size_t)(4 * N + (N + 1) / 2))) return e;
+    int32_t* const r = env->pop_rows;
+    *row = {r, r + N, r + 2 * N, reinterpret_cast<float*>(r + 3 * N), reinterpret_cast<uint8_t*>(r + 4 * N),
+            reinterpret_cast<uint8_t*>(r + 4 * N) + N};
+    return GW_OK;
+}
+// ... and the scored calls' row of delivered counters as they stood in front of the step.
+static int score_base_of(gw_env* env, uint32_t** base)
+{
+    if (!env->score_base)
+        if (const int e = dev_alloc(env, &env->score_base, (size_t)env->st.N)) return e;
+    *base = env->score_base;
+    return GW_OK;
+}
+// ... in front of it the draw of the closed loops, from the observations `seen`, env e from table e / M (one table: M = N);
+// score != nullptr: with the delivered counters' copy a scored call's bookkeeping differences against ...
+static int draw_step(gw_env* env, int32_t s, const GwPolicyStream& pol, int64_t M, const gw_score* score, const int32_t* seen,
+                     const GwRows& row, void* stream)
+{
+    uint32_t* base = nullptr;
+    if (score)
+        if (const int e = score_base_of(env, &base)) return e;
+    if (gw_launch_policy_sample(env->st, env->cst_host, pol.at(s), M, seen, row, base, stream))
         return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
     return GW_OK;
 }
-// ... and behind it the episodic forms' bookkeeping launch (ended, obs_next, the tally or tallies, the handle's reset mask) and
-// gw_reset's launch with that mask.
+// ... and the episodic forms' step: the step's launch, behind it the bookkeeping launch (ended, obs_next, the tally or tallies,
+// the handle's reset mask) and gw_reset's launch with that mask.  score: the step's reward becomes its score (the counters'
+// copy was taken in front of this: the draw's, or gw_delivered's launch where the caller brought the actions -- the
+// bookkeeping clamps a staged sender; a rejected action moved neither the counter nor the reward, so it scores 0).  pop_tally:
+// the population's rows for M envs each, or nullptr (M = N); delivered_row: row s of the caller's, or nullptr.
 static int episode_step(gw_env* env, int32_t s, const int32_t* device_row, const int32_t* duration_row, const gw_episodes* ep,
-                        const gw_population* pop, int32_t* obs_next_dev, const GwRows& row, void* stream)
+                        const gw_score* score, int64_t M, int64_t* pop_tally, int32_t* obs_next_dev, const GwRows& out_row,
+                        int32_t* delivered_row, void* stream)
 {
-    if (const int rc = plain_step(env, s, device_row, duration_row, row, stream)) return rc;
-    const int64_t N = env->st.N;
-    const int center = env->cst_host.counter_bound;
-    if (pop ? gw_launch_episodes_step_pop(N, center, *ep, *pop, obs_next_dev, row.obs, row.reward, row.done, row.ended, env->ep_mask, stream)
-            : gw_launch_episodes_step(N, center, *ep, obs_next_dev, row.obs, row.reward, row.done, row.ended, env->ep_mask, stream))
+    if (const int rc = plain_step(env, s, device_row, duration_row, out_row, stream)) return rc;
+    GwRows row = out_row;
+    row.device = const_cast<int32_t*>(device_row);             // (only read behind the step)
+    if (gw_launch_episodes_step(env->st, env->cst_host, *ep, score, M, pop_tally, env->score_base, obs_next_dev, row, env->ep_mask,
+                                delivered_row, stream))
         return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
     return gw_reset(env, env->ep_mask, nullptr, stream);
 }
@@ -762,7 +788,7 @@ int gw_rollout_policy(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint6
         },
         [&](int32_t s) {                                       // every other handle: draw, then one step launch, per step
             const GwRows row = out.at(s * N);
-            if (const int e = draw_step(env, s, pol, nullptr, seen(s), row, stream)) return e;
+            if (const int e = draw_step(env, s, pol, N, nullptr, seen(s), row, stream)) return e;
             return plain_step(env, s, row.device, row.duration, row, stream);
         });
 }
@@ -811,88 +837,10 @@ int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_d
                             table_dev, stream);
 }
 
-int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
-                        const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
-                        int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
-                        uint8_t* done_dev, uint8_t* ended_dev, void* stream)
-{
-    int rc = rollout_checks(env, steps,
-                            cdf_dev && obs_prev_dev && obs_next_dev && device_out_dev && duration_out_dev && obs_dev && reward_dev &&
-                                done_dev && ended_dev,
-                            "gw_rollout_episodes", true, ep);
-    if (rc || steps == 0 || (rc = select_device(env))) return rc;
-    const int64_t N = env->st.N;
-    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
-    const GwRows out = {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, ended_dev};
-    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
-        "no fused episodic rollout for this handle (GW_ROLLOUT_STRICT is set)",
-        [&](int32_t s0, const GwChunk& ch) {
-            return gw_launch_rollout_policy_ep_sfx(env->st, env->cst_host, ch, pol.at(s0), *ep, seen_before(s0, obs_prev_dev, obs_next_dev),
-                                                   obs_next_dev, out.at(s0 * N));
-        },
-        [&](int32_t s) {                                       // every other handle: draw, step, bookkeeping, masked reset
-            const GwRows row = out.at(s * N);
-            if (const int e = draw_step(env, s, pol, nullptr, seen_before(s, obs_prev_dev, obs_next_dev), row, stream)) return e;
-            return episode_step(env, s, row.device, row.duration, ep, nullptr, obs_next_dev, row, stream);
-        });
-}
-
-int gw_rollout_autoreset(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
-                         const gw_episodes* ep, int32_t* obs_next_dev,
-                         int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, void* stream)
-{
-    int rc = rollout_checks(env, steps, device_dev && duration_dev && obs_next_dev && obs_dev && reward_dev && done_dev && ended_dev,
-                            "gw_rollout_autoreset", true, ep);
-    if (rc || steps == 0 || (rc = select_device(env))) return rc;
-    const int64_t N = env->st.N;
-    const GwRows out = {nullptr, nullptr, obs_dev, reward_dev, done_dev, ended_dev};
-    return rollout_drive(env, steps, stream, true, INT32_MAX, "no fused autoreset rollout for this handle (GW_ROLLOUT_STRICT is set)",
-        [&](int32_t s0, const GwChunk& ch) {
-            return gw_launch_rollout_autoreset_sfx(env->st, env->cst_host, ch, device_dev + s0 * N, duration_dev + s0 * N, *ep, obs_next_dev,
-                                                   out.at(s0 * N));
-        },
-        [&](int32_t s) {                                       // every other handle: step, bookkeeping, masked reset
-            return episode_step(env, s, device_dev + s * N, duration_dev + s * N, ep, nullptr, obs_next_dev, out.at(s * N), stream);
-        });
-}
-
-int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
-                          const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev, void* stream)
-{
-    if (env && !pop) return fail(GW_EINVAL, "gw_rollout_population: pop is NULL");
-    int rc = rollout_checks(env, steps, pop && pop->cdf_dev && pop->tally_dev && obs_prev_dev && obs_next_dev, "gw_rollout_population", true, ep);
-    if (rc) return rc;
-    if (pop->num_policies < 1 || pop->envs_per_policy < 1)
-        return fail(GW_EINVAL, "gw_rollout_population: num_policies and envs_per_policy must be >= 1");
-    if (steps == 0) return GW_OK;
-    const int64_t N = env->st.N;
-    if ((int64_t)pop->num_policies * pop->envs_per_policy != N)
-        return fail(GW_EINVAL, "gw_rollout_population: %d policies x %d envs is not the handle's %lld envs", pop->num_policies,
-                    pop->envs_per_policy, (long long)N);
-    if ((rc = select_device(env))) return rc;
-    const GwPolicyStream pol = {pop->cdf_dev, seed, step0, env_id0};
-    GwRows row = {};                                           // the per-step form's own N-long rows, allocated when it first runs
-    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
-        "no fused population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)",
-        [&](int32_t s0, const GwChunk& ch) {
-            return gw_launch_rollout_pop_ep_sfx(env->st, env->cst_host, ch, *pop, pol.at(s0), *ep, seen_before(s0, obs_prev_dev, obs_next_dev),
-                                                obs_next_dev);
-        },
-        [&](int32_t s) {                                       // draw, step, bookkeeping, masked reset
-            if (!row.obs) {
-                if (!env->pop_rows)                              // 4 x 4 N + 2 x N bytes
-                    if (const int e = dev_alloc(env, &env->pop_rows, (size_t)(4 * N + (N + 1) / 2))) return e;
-                int32_t* const r = env->pop_rows;
-                row = {r, r + N, r + 2 * N, reinterpret_cast<float*>(r + 3 * N), reinterpret_cast<uint8_t*>(r + 4 * N),
-                       reinterpret_cast<uint8_t*>(r + 4 * N) + N};
-            }
-            if (const int e = draw_step(env, s, pol, pop, seen_before(s, obs_prev_dev, obs_next_dev), row, stream)) return e;
-            return episode_step(env, s, row.device, row.duration, ep, pop, obs_next_dev, row, stream);
-        });
-}
-
-// ---- the scored calls (include/gymwipe_amd.h, gw_score) --------------------------------------------------------------------------
-// What both check behind rollout_checks and before any HIP call: the weights' bounds.
+// ---- the episodic calls and their scored forms (include/gymwipe_amd.h, gw_score) ------------------------------------------------
+// Each pair of entry points is one body: `who` names the call in its messages; `scored` says which of the two it is, and then
+// `score` and delivered_dev (where the call has one) are among the pointers rollout_checks wants -- behind it `score` is nullptr
+// exactly for the parent.  What a scored call checks behind rollout_checks and before any HIP call: the weights' bounds ...
 static int check_score(const gw_score* score, const char* who)
 {
     bool ok = score->w_reward >= -GW_SCORE_W_MAX && score->w_reward <= GW_SCORE_W_MAX;
@@ -905,41 +853,103 @@ static int check_scored_handle(gw_env* env, const char* who)
     if (!env->st.sa) return fail(GW_EUNSUPPORTED, "%s needs the default queue mode: an explicit-queue handle has no per-env delivered counter", who);
     return GW_OK;
 }
-// One step of their per-step form: the draw with the counters' copy, the step, the scored bookkeeping, the masked reset.  M:
-// envs per table; pop_tally: the population's rows, or nullptr; delivered_row: row s of the caller's, or nullptr.
-static int scored_step(gw_env* env, int32_t s, const GwPolicyStream& pol, int64_t M, int64_t* pop_tally, const gw_episodes* ep,
-                       const gw_score* score, const int32_t* seen, int32_t* obs_next_dev, const GwRows& row, int32_t* delivered_row,
-                       void* stream)
+
+static int rollout_episodes(gw_env* env, const char* who, int32_t steps, const GwPolicyStream& pol, const gw_episodes* ep,
+                            const gw_score* score, bool scored, const int32_t* obs_prev_dev, int32_t* obs_next_dev, const GwRows& out,
+                            int32_t* delivered_dev, void* stream)
 {
-    const GwDevConst& c = env->cst_host;
-    if (!env->score_base)
-        if (const int e = dev_alloc(env, &env->score_base, (size_t)env->st.N)) return e;
-    if (gw_launch_policy_sample_scored(env->st, c.max_duration, c.counter_bound, M, pol.at(s), seen, row.device, row.duration,
-                                       env->score_base, stream))
-        return fail(GW_EHIP, "policy sampling kernel launch failed at step %d", s);
-    if (const int rc = plain_step(env, s, row.device, row.duration, row, stream)) return rc;
-    if (gw_launch_episodes_step_scored(env->st, c.counter_bound, *ep, *score, M, pop_tally, env->score_base, obs_next_dev, row,
-                                       env->ep_mask, delivered_row, stream))
-        return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
-    return gw_reset(env, env->ep_mask, nullptr, stream);
+    int rc = rollout_checks(env, steps,
+                            (!scored || (score && delivered_dev)) && pol.cdf && obs_prev_dev && obs_next_dev && out.device &&
+                                out.duration && out.obs && out.reward && out.done && out.ended,
+                            who, true, ep);
+    if (rc || (score && (rc = check_score(score, who))) || steps == 0) return rc;
+    if ((score && (rc = check_scored_handle(env, who))) || (rc = select_device(env))) return rc;
+    const int64_t N = env->st.N;
+    auto delivered = [&](int32_t s) { return score ? delivered_dev + s * N : nullptr; };
+    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        score ? "no fused scored rollout for this handle (GW_ROLLOUT_STRICT is set)"
+              : "no fused episodic rollout for this handle (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_policy_ep_sfx(env->st, env->cst_host, ch, pol.at(s0), *ep, score,
+                                                   seen_before(s0, obs_prev_dev, obs_next_dev), obs_next_dev, out.at(s0 * N), delivered(s0));
+        },
+        [&](int32_t s) {                                       // every other handle: draw, step, bookkeeping, masked reset
+            const GwRows row = out.at(s * N);
+            if (const int e = draw_step(env, s, pol, N, score, seen_before(s, obs_prev_dev, obs_next_dev), row, stream)) return e;
+            return episode_step(env, s, row.device, row.duration, ep, score, N, nullptr, obs_next_dev, row, delivered(s), stream);
+        });
 }
 
-// ... and of gw_rollout_autoreset_scored's, where the caller brings the actions: the counters' copy is gw_delivered's launch into
-// the same scratch row, and the bookkeeping takes one table's worth of envs (it clamps the staged sender; a rejected action
-// moved neither the counter nor the reward, so it scores 0).
-static int scored_staged_step(gw_env* env, int32_t s, const int32_t* device_row, const int32_t* duration_row, const gw_episodes* ep,
-                              const gw_score* score, int32_t* obs_next_dev, const GwRows& out_row, int32_t* delivered_row, void* stream)
+static int rollout_autoreset(gw_env* env, const char* who, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
+                             const gw_episodes* ep, const gw_score* score, bool scored, int32_t* obs_next_dev, const GwRows& out,
+                             int32_t* delivered_dev, void* stream)
 {
-    if (!env->score_base)
-        if (const int e = dev_alloc(env, &env->score_base, (size_t)env->st.N)) return e;
-    if (gw_launch_delivered_sfx(env->st, env->score_base, stream)) return fail(GW_EHIP, "delivered kernel launch failed at step %d", s);
-    if (const int rc = plain_step(env, s, device_row, duration_row, out_row, stream)) return rc;
-    GwRows row = out_row;
-    row.device = const_cast<int32_t*>(device_row);             // (only read behind the step)
-    if (gw_launch_episodes_step_scored(env->st, env->cst_host.counter_bound, *ep, *score, env->st.N, nullptr, env->score_base,
-                                       obs_next_dev, row, env->ep_mask, delivered_row, stream))
-        return fail(GW_EHIP, "episode bookkeeping kernel launch failed at step %d", s);
-    return gw_reset(env, env->ep_mask, nullptr, stream);
+    int rc = rollout_checks(env, steps,
+                            (!scored || (score && delivered_dev)) && device_dev && duration_dev && obs_next_dev && out.obs &&
+                                out.reward && out.done && out.ended,
+                            who, true, ep);
+    if (rc || (score && (rc = check_score(score, who))) || steps == 0) return rc;
+    if ((score && (rc = check_scored_handle(env, who))) || (rc = select_device(env))) return rc;
+    const int64_t N = env->st.N;
+    auto delivered = [&](int32_t s) { return score ? delivered_dev + s * N : nullptr; };
+    return rollout_drive(env, steps, stream, true, INT32_MAX,
+        score ? "no fused scored autoreset rollout for this handle (GW_ROLLOUT_STRICT is set)"
+              : "no fused autoreset rollout for this handle (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_autoreset_sfx(env->st, env->cst_host, ch, device_dev + s0 * N, duration_dev + s0 * N, *ep, score,
+                                                   obs_next_dev, out.at(s0 * N), delivered(s0));
+        },
+        [&](int32_t s) {                                       // every other handle: step, bookkeeping, masked reset
+            if (score) {                                       // (the counters' copy: gw_delivered's launch into the scratch row)
+                uint32_t* base;
+                if (const int e = score_base_of(env, &base)) return e;
+                if (gw_launch_delivered_sfx(env->st, base, stream)) return fail(GW_EHIP, "delivered kernel launch failed at step %d", s);
+            }
+            return episode_step(env, s, device_dev + s * N, duration_dev + s * N, ep, score, N, nullptr, obs_next_dev, out.at(s * N),
+                                delivered(s), stream);
+        });
+}
+
+static int rollout_population(gw_env* env, const char* who, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0,
+                              uint64_t env_id0, const gw_episodes* ep, const gw_score* score, bool scored, const int32_t* obs_prev_dev,
+                              int32_t* obs_next_dev, void* stream)
+{
+    if (env && !pop) return fail(GW_EINVAL, "%s: pop is NULL", who);
+    int rc = rollout_checks(env, steps, (!scored || score) && pop && pop->cdf_dev && pop->tally_dev && obs_prev_dev && obs_next_dev, who,
+                            true, ep);
+    if (rc || (score && (rc = check_score(score, who)))) return rc;
+    if (pop->num_policies < 1 || pop->envs_per_policy < 1)
+        return fail(GW_EINVAL, "%s: num_policies and envs_per_policy must be >= 1", who);
+    if (steps == 0) return GW_OK;
+    const int64_t N = env->st.N, M = pop->envs_per_policy;
+    if ((int64_t)pop->num_policies * M != N)
+        return fail(GW_EINVAL, "%s: %d policies x %d envs is not the handle's %lld envs", who, pop->num_policies, pop->envs_per_policy,
+                    (long long)N);
+    if ((score && (rc = check_scored_handle(env, who))) || (rc = select_device(env))) return rc;
+    const GwPolicyStream pol = {pop->cdf_dev, seed, step0, env_id0};
+    GwRows row = {};                                           // the per-step form's own N-long rows, allocated when it first runs
+    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        score ? "no fused scored population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)"
+              : "no fused population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_pop_ep_sfx(env->st, env->cst_host, ch, *pop, pol.at(s0), *ep, score,
+                                                seen_before(s0, obs_prev_dev, obs_next_dev), obs_next_dev);
+        },
+        [&](int32_t s) {                                       // draw, step, bookkeeping, masked reset
+            if (!row.obs)
+                if (const int e = pop_rows_of(env, &row)) return e;
+            if (const int e = draw_step(env, s, pol, M, score, seen_before(s, obs_prev_dev, obs_next_dev), row, stream)) return e;
+            return episode_step(env, s, row.device, row.duration, ep, score, M, pop->tally_dev, obs_next_dev, row, nullptr, stream);
+        });
+}
+
+int gw_rollout_episodes(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                        const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                        int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
+                        uint8_t* done_dev, uint8_t* ended_dev, void* stream)
+{
+    return rollout_episodes(env, "gw_rollout_episodes", steps, {cdf_dev, seed, step0, env_id0}, ep, nullptr, false, obs_prev_dev,
+                            obs_next_dev, {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, ended_dev}, nullptr, stream);
 }
 
 int gw_rollout_episodes_scored(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
@@ -947,86 +957,40 @@ int gw_rollout_episodes_scored(gw_env* env, int32_t steps, const uint32_t* cdf_d
                                int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
                                uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev, void* stream)
 {
-    int rc = rollout_checks(env, steps,
-                            cdf_dev && score && obs_prev_dev && obs_next_dev && device_out_dev && duration_out_dev && obs_dev &&
-                                reward_dev && done_dev && ended_dev && delivered_dev,
-                            "gw_rollout_episodes_scored", true, ep);
-    if (rc || (rc = check_score(score, "gw_rollout_episodes_scored")) || steps == 0) return rc;
-    if ((rc = check_scored_handle(env, "gw_rollout_episodes_scored")) || (rc = select_device(env))) return rc;
-    const int64_t N = env->st.N;
-    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
-    const GwRows out = {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, ended_dev};
-    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
-        "no fused scored rollout for this handle (GW_ROLLOUT_STRICT is set)",
-        [&](int32_t s0, const GwChunk& ch) {
-            return gw_launch_rollout_policy_eps_sfx(env->st, env->cst_host, ch, pol.at(s0), *ep, *score,
-                                                    seen_before(s0, obs_prev_dev, obs_next_dev), obs_next_dev, out.at(s0 * N),
-                                                    delivered_dev + s0 * N);
-        },
-        [&](int32_t s) {
-            return scored_step(env, s, pol, N, nullptr, ep, score, seen_before(s, obs_prev_dev, obs_next_dev), obs_next_dev,
-                               out.at(s * N), delivered_dev + s * N, stream);
-        });
+    return rollout_episodes(env, "gw_rollout_episodes_scored", steps, {cdf_dev, seed, step0, env_id0}, ep, score, true,
+                            obs_prev_dev, obs_next_dev, {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, ended_dev},
+                            delivered_dev, stream);
 }
 
-int gw_rollout_population_scored(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
-                                 const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
-                                 void* stream)
+int gw_rollout_autoreset(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
+                         const gw_episodes* ep, int32_t* obs_next_dev,
+                         int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, void* stream)
 {
-    if (env && !pop) return fail(GW_EINVAL, "gw_rollout_population_scored: pop is NULL");
-    int rc = rollout_checks(env, steps, pop && pop->cdf_dev && pop->tally_dev && score && obs_prev_dev && obs_next_dev,
-                            "gw_rollout_population_scored", true, ep);
-    if (rc || (rc = check_score(score, "gw_rollout_population_scored"))) return rc;
-    if (pop->num_policies < 1 || pop->envs_per_policy < 1)
-        return fail(GW_EINVAL, "gw_rollout_population_scored: num_policies and envs_per_policy must be >= 1");
-    if (steps == 0) return GW_OK;
-    const int64_t N = env->st.N;
-    if ((int64_t)pop->num_policies * pop->envs_per_policy != N)
-        return fail(GW_EINVAL, "gw_rollout_population_scored: %d policies x %d envs is not the handle's %lld envs", pop->num_policies,
-                    pop->envs_per_policy, (long long)N);
-    if ((rc = check_scored_handle(env, "gw_rollout_population_scored")) || (rc = select_device(env))) return rc;
-    const GwPolicyStream pol = {pop->cdf_dev, seed, step0, env_id0};
-    GwRows row = {};                                           // the per-step form's own N-long rows (gw_rollout_population's)
-    return rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
-        "no fused scored population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)",
-        [&](int32_t s0, const GwChunk& ch) {
-            return gw_launch_rollout_pop_eps_sfx(env->st, env->cst_host, ch, *pop, pol.at(s0), *ep, *score,
-                                                 seen_before(s0, obs_prev_dev, obs_next_dev), obs_next_dev);
-        },
-        [&](int32_t s) {
-            if (!row.obs) {
-                if (!env->pop_rows)                              // 4 x 4 N + 2 x N bytes
-                    if (const int e = dev_alloc(env, &env->pop_rows, (size_t)(4 * N + (N + 1) / 2))) return e;
-                int32_t* const r = env->pop_rows;
-                row = {r, r + N, r + 2 * N, reinterpret_cast<float*>(r + 3 * N), reinterpret_cast<uint8_t*>(r + 4 * N),
-                       reinterpret_cast<uint8_t*>(r + 4 * N) + N};
-            }
-            return scored_step(env, s, pol, pop->envs_per_policy, pop->tally_dev, ep, score, seen_before(s, obs_prev_dev, obs_next_dev),
-                               obs_next_dev, row, nullptr, stream);
-        });
+    return rollout_autoreset(env, "gw_rollout_autoreset", steps, device_dev, duration_dev, ep, nullptr, false, obs_next_dev,
+                             {nullptr, nullptr, obs_dev, reward_dev, done_dev, ended_dev}, nullptr, stream);
 }
 
 int gw_rollout_autoreset_scored(gw_env* env, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev,
                                 const gw_episodes* ep, const gw_score* score, int32_t* obs_next_dev, int32_t* obs_dev,
                                 float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev, void* stream)
 {
-    int rc = rollout_checks(env, steps,
-                            device_dev && duration_dev && score && obs_next_dev && obs_dev && reward_dev && done_dev && ended_dev &&
-                                delivered_dev,
-                            "gw_rollout_autoreset_scored", true, ep);
-    if (rc || (rc = check_score(score, "gw_rollout_autoreset_scored")) || steps == 0) return rc;
-    if ((rc = check_scored_handle(env, "gw_rollout_autoreset_scored")) || (rc = select_device(env))) return rc;
-    const int64_t N = env->st.N;
-    const GwRows out = {nullptr, nullptr, obs_dev, reward_dev, done_dev, ended_dev};
-    return rollout_drive(env, steps, stream, true, INT32_MAX, "no fused scored autoreset rollout for this handle (GW_ROLLOUT_STRICT is set)",
-        [&](int32_t s0, const GwChunk& ch) {
-            return gw_launch_rollout_autoreset_scored_sfx(env->st, env->cst_host, ch, device_dev + s0 * N, duration_dev + s0 * N, *ep,
-                                                          *score, obs_next_dev, out.at(s0 * N), delivered_dev + s0 * N);
-        },
-        [&](int32_t s) {
-            return scored_staged_step(env, s, device_dev + s * N, duration_dev + s * N, ep, score, obs_next_dev, out.at(s * N),
-                                      delivered_dev + s * N, stream);
-        });
+    return rollout_autoreset(env, "gw_rollout_autoreset_scored", steps, device_dev, duration_dev, ep, score, true,
+                             obs_next_dev, {nullptr, nullptr, obs_dev, reward_dev, done_dev, ended_dev}, delivered_dev, stream);
+}
+
+int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                          const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev, void* stream)
+{
+    return rollout_population(env, "gw_rollout_population", steps, pop, seed, step0, env_id0, ep, nullptr, false, obs_prev_dev,
+                              obs_next_dev, stream);
+}
+
+int gw_rollout_population_scored(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                                 const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                                 void* stream)
+{
+    return rollout_population(env, "gw_rollout_population_scored", steps, pop, seed, step0, env_id0, ep, score, true,
+                              obs_prev_dev, obs_next_dev, stream);
 }
 
 int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,

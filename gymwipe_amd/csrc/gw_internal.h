@@ -329,49 +329,33 @@ int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, const
 #define GW_TS_STEPS 64                  // steps per ct_rollout_pstats launch at most: its LDS histogram's bit budget (ct_rollout_sfx.hip)
 int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
                                  const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table);   // gw_rollout_policy_stats
+// score (the three episodic forms that take one): nullptr, or the _scored call's weights -- the family with the step's score
+// where it has the reward; delivered: that call's packets per step
 int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
-                                    const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, const GwRows& out);   // gw_rollout_episodes
+                                    const gw_episodes& ep, const gw_score* score, const int32_t* obs_prev, int32_t* obs_next,
+                                    const GwRows& out, int32_t* delivered);                         // gw_rollout_episodes[_scored]
 int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
                                     const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, int64_t* table);   // gw_rollout_episodes_stats
 int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
-                                    const int32_t* duration, const gw_episodes& ep, int32_t* obs_next, const GwRows& out);   // gw_rollout_autoreset
-// gw_rollout_population: env e runs policy e / envs_per_policy (pol.cdf: the population's tables), nothing stored per step
+                                    const int32_t* duration, const gw_episodes& ep, const gw_score* score, int32_t* obs_next,
+                                    const GwRows& out, int32_t* delivered);                         // gw_rollout_autoreset[_scored]
+// gw_rollout_population[_scored]: env e runs policy e / envs_per_policy (pol.cdf: the population's tables), nothing stored per step
 int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
-                                 const GwPolicyStream& pol, const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next);
-// gw_rollout_episodes_scored / gw_rollout_population_scored: the two above with the step's score where they have the reward
-int gw_launch_rollout_policy_eps_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
-                                     const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev, int32_t* obs_next,
-                                     const GwRows& out, int32_t* delivered);
-int gw_launch_rollout_pop_eps_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
-                                  const GwPolicyStream& pol, const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev,
-                                  int32_t* obs_next);
-// gw_rollout_autoreset_scored: gw_rollout_autoreset's launch with the score, and the packets per step
-int gw_launch_rollout_autoreset_scored_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
-                                           const int32_t* duration, const gw_episodes& ep, const gw_score& score, int32_t* obs_next,
-                                           const GwRows& out, int32_t* delivered);
-// their per-step form: the draw that also copies the delivered counters (M envs per table), and the scored bookkeeping
-int gw_launch_policy_sample_scored(const GwState& st, int max_duration, int counter_bound, int64_t M, const GwPolicyStream& pol,
-                                   const int32_t* obs_in, int32_t* device_out, int32_t* duration_out, uint32_t* deliv_before,
-                                   void* stream);
-int gw_launch_episodes_step_scored(const GwState& st, int counter_bound, const gw_episodes& ep, const gw_score& score, int64_t M,
-                                   int64_t* pop_tally, const uint32_t* deliv_before, int32_t* obs_next, const GwRows& row,
-                                   uint8_t* mask, int32_t* delivered_out, void* stream);
+                                 const GwPolicyStream& pol, const gw_episodes& ep, const gw_score* score, const int32_t* obs_prev,
+                                 int32_t* obs_next);
 // the table from recorded transitions (ended: nullptr, or gw_transition_stats_ep's rows)
 int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
                                const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
                                const uint8_t* done, const uint8_t* ended, int64_t* table, void* stream);
-// one step of the per-step forms: the draw for step pol.step0 from `obs_in`, and the episodes' bookkeeping behind the step's
-// launch (ended, the handle's reset mask, obs_next); _pop: on the handle's own rows, env e from table / into row e / envs_per_policy
-int gw_launch_policy_sample(int64_t N, int D, int max_duration, int counter_bound, const GwPolicyStream& pol, const int32_t* obs_in,
-                            int32_t* device_out, int32_t* duration_out, void* stream);
-int gw_launch_policy_sample_pop(int64_t N, int D, int max_duration, int counter_bound, const gw_population& pop,
-                                const GwPolicyStream& pol, const int32_t* obs_in, int32_t* device_out, int32_t* duration_out,
-                                void* stream);
-int gw_launch_episodes_step(int64_t N, int counter_bound, const gw_episodes& ep, int32_t* obs_next, const int32_t* obs,
-                            const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask, void* stream);
-int gw_launch_episodes_step_pop(int64_t N, int counter_bound, const gw_episodes& ep, const gw_population& pop, int32_t* obs_next,
-                                const int32_t* obs, const float* reward, const uint8_t* done, uint8_t* ended, uint8_t* mask,
-                                void* stream);
+// One step of the per-step forms.  The draw for step pol.step0 from `obs_in` into row.device / row.duration, env e from table
+// e / M (one table: M = st.N), with a scored call's copy of the delivered counters into deliv_before (or nullptr); and, behind
+// the step's launch, the episodes' bookkeeping on that row (ended, the handle's reset mask, obs_next): scored with deliv_before
+// where there is a score, into row e / M of pop_tally where there is one, the packets per step into delivered_out where kept.
+int gw_launch_policy_sample(const GwState& st, const GwDevConst& cst, const GwPolicyStream& pol, int64_t M, const int32_t* obs_in,
+                            const GwRows& row, uint32_t* deliv_before, void* stream);
+int gw_launch_episodes_step(const GwState& st, const GwDevConst& cst, const gw_episodes& ep, const gw_score* score, int64_t M,
+                            int64_t* pop_tally, const uint32_t* deliv_before, int32_t* obs_next, const GwRows& row, uint8_t* mask,
+                            int32_t* delivered_out, void* stream);
 int gw_launch_received_sfx(const GwState& st, int32_t* out, void* stream);
 int gw_launch_delivered_sfx(const GwState& st, uint32_t* out, void* stream);
 int gw_launch_clear_flags(const GwState& st, void* stream);          // ct_step_sfx.hip (both queue modes)

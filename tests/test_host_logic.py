@@ -429,8 +429,12 @@ def test_bench_self_launch_happens_before_torch_is_imported():
 # ---- the kernel catalogue: every instantiation of the step / rollout families has a GPU parity recipe ----------------------
 KERNEL_FAMILIES = ("ct_step_sfx_kernel", "ct_rollout_sync_kernel", "ct_rollout_sfx_kernel", "pend_step_kernel",
                    "ct_step_kernel", "ct_step_live_kernel")
-# templated kernels outside this catalogue, with checkers of their own (tests/test_grid.py, tests/test_control_loop.py)
-KERNELS_OUT_OF_SCOPE = ("grid_run_kernel",)
+# templated kernels outside this catalogue, with checkers of their own (tests/test_grid.py, tests/test_control_loop.py);
+# episodes_step_kernel<SCORED>: the per-step forms' bookkeeping, no DT x MODE family and not in the launch record -- <false> is
+# what the per-step sections of tests/test_rollout_episodes.py, test_rollout_autoreset.py and test_rollout_population.py run,
+# <true> what those of tests/test_rollout_scored.py and test_rollout_autoreset_scored.py run, each against the oracle
+KERNELS_OUT_OF_SCOPE = ("grid_run_kernel", "episodes_step_kernel")
+PER_STEP_KERNELS = {"episodes_step_kernel<false>", "episodes_step_kernel<true>"}
 
 
 def test_every_kernel_instantiation_has_a_gpu_recipe(native_lib):
@@ -452,6 +456,7 @@ def test_every_kernel_instantiation_has_a_gpu_recipe(native_lib):
     assert sorted(covered - lib_set) == [], "recipes for instantiations the library does not have"
     for name, r in kv.RECIPES.items():
         assert r["target"] == name and name in r["declared"] and r["declared"] <= lib_set, name
+    assert {n for n in names if n.startswith("episodes_step")} == PER_STEP_KERNELS, "the per-step bookkeeping has two instantiations"
 
 
 def test_recorded_open_layouts_are_still_open(native_lib):

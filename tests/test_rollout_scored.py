@@ -263,10 +263,13 @@ def test_records_form_per_step(kind, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["m96", "unfused_switch"])
+@pytest.mark.parametrize("kind", ["m96", "unfused_switch", "m50"])
 def test_population_per_step(kind, monkeypatch):
+    """The bookkeeping kernel's blocks are 256 envs.  unfused_switch, 3 x 128: the first block spans two policies (each ended
+    episode's words go to its policy's row directly), the second lies in one (summed in LDS, added to the row once).  m50,
+    4 x 50: one block, not full, over four policies.  m96, 2 x 96: one block over two."""
     D = 4
-    P, M = (2, 96) if kind == "m96" else POPS[0]
+    P, M = {"m96": (2, 96), "unfused_switch": POPS[0], "m50": (4, 50)}[kind]
     if kind == "unfused_switch":
         monkeypatch.setenv("GW_ROLLOUT_POLICY_UNFUSED", "1")
     ref = population_reference(D, P, M)
