@@ -145,7 +145,8 @@ class VecControlLoopEnv(BaseEnv):
     "duration": int32[N]}) -> (obs, reward, done, {"Sensor angle": deg})``."""
     SENSOR, CONTROLLER, ACTUATOR = 0, 1, 2
 
-    def __init__(self, num_envs, device="cuda:0", ctrl_start_tick=None, ctrl_period_ticks=None, positions=None, x0=None):
+    def __init__(self, num_envs, device="cuda:0", ctrl_start_tick=None, ctrl_period_ticks=None, positions=None, x0=None,
+                 A=None, B=None, u0=None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gymwipe_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -168,6 +169,15 @@ class VecControlLoopEnv(BaseEnv):
         if x0 is not None:
             for i, v in enumerate(x0):
                 cfg.x0[i] = float(v)
+        if A is not None:                                  # the plant x <- A x + B u: 4x4 row-major, 4, and the input before
+            for i, row in enumerate(A):                    # the first command arrives
+                for j, v in enumerate(row):
+                    cfg.A[i * 4 + j] = float(v)
+        if B is not None:
+            for i, v in enumerate(B):
+                cfg.B[i] = float(v)
+        if u0 is not None:
+            cfg.u0 = float(u0)
         self.config = cfg
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):

@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from util import action_stream, assert_state_equal, STATE_FIELDS, STAT_FIELDS
+from util import (action_stream, assert_state_equal, STATE_FIELDS, STAT_FIELDS, PLANT_MODELS, PLANT_KMAX, PlantEmulation,
+                  plant_err, plant_error_bound, plant_reference_ld)
 
 # sender counts with an instantiation of their own, per family (ct_step_sfx.hip, ct_rollout_sfx.hip, ct_step.hip,
 # ct_step_dyn.hip); any other D takes DT = 0
@@ -265,25 +266,45 @@ def drive(env, orc, D, N, K, per_env_stats, rollout_k=0, seed=0):
         assert st[name] == int(orc.get(f).sum()), name
 
 
-def _run_pendulum(recipe):
+def _run_pendulum(recipe, plant=None):
     """pend_step_kernel against the network's oracle (bit-exact) and the plant's oracle advanced to the oracle's clocks
-    (<= 1e-5 relative), as tests/test_plant.py does."""
-    from gymwipe_amd import VecInvertedPendulumEnv
+    (<= 1e-5 relative), as tests/test_plant.py does.  ``plant``: (model of tests/util.py, dt) in place of the default plant,
+    with a different input per env; the plant state is then also held to the long-double reference within
+    util.plant_error_bound after every step, as tests/test_plant_models.py does, and the run must hold three-pass counts."""
+    import torch
+    from gymwipe_amd import VecInvertedPendulumEnv, VecLinearPlant
     from gymwipe_amd.actions import actions_torch
     from oracle.ct_oracle import CtOracle, default_config
     from oracle.plant_oracle import PlantOracle
     N, K = recipe["N"], 24
-    env = VecInvertedPendulumEnv(N)
+    emu = None
+    if plant is None:
+        env = VecInvertedPendulumEnv(N)
+    else:
+        m, dt = PLANT_MODELS[plant[0]], plant[1]
+        u = np.random.default_rng(13).normal(0.0, 0.3, N)
+        env = VecInvertedPendulumEnv(N, plant=VecLinearPlant(N, A=m["A"], B=m["B"], dt=dt, x0=m["x0"], u0=m["u0"]))
+        env.plant.setMotorVelocity(torch.from_numpy(u))
+        emu = PlantEmulation(m["A"], m["B"], dt, m["x0"], u, N)
     cfg = default_config(2, positions=[(0.0, 0.0), (0.0, -1.0)], rrm_pos=(0.0, 1.0), mult=[1, 0], dest=[1, 0])
     net = CtOracle(N, 2, config=cfg, nthreads=8)
     pc = env.plant.config
     porc = PlantOracle(N, list(pc.A), list(pc.B), pc.dt, list(pc.x0), pc.u0)
+    if plant is not None:
+        porc.set_input(u)
     a_dev, a_dur = actions_torch(31, 0, N, 0, K, 2, device="cuda")
     h_dev, h_dur = a_dev.cpu().numpy(), a_dur.cpu().numpy()
+    nows, xs = [], []
     for k in range(K):
         env.step({"device": a_dev[k], "duration": a_dur[k]})
         net.step(h_dev[k], h_dur[k])
         porc.update(net.get("now"))
+        if emu is not None:
+            emu.update(net.get("now"))
+            nows.append(net.get("now").copy())
+            xs.append((env.plant.state(), porc.x.copy(), emu.x.copy()))
+            assert (env.plant.get_state("substeps") == porc.substeps).all(), k
+            assert (env.plant.get_state("t_last") == porc.t_last).all(), k
         if k % 8 == 7:
             for f in ("now", "wake", "counter", "qlen", "queue", "rx_power"):
                 a, b = env.network.get_state(f), net.get(f)
@@ -293,6 +314,12 @@ def _run_pendulum(recipe):
             assert (env.plant.get_state("t_last") == porc.t_last).all()
             err = np.abs(x - porc.x) / np.maximum(np.abs(porc.x), 1e-6)
             assert err.max() < 1e-5, err.max()
+    if emu is not None:
+        ref = plant_reference_ld(m["A"], m["B"], dt, m["x0"], u, np.array(nows))
+        assert (ref["substeps"][-1] == porc.substeps).all() and (ref["n"] > 2 * PLANT_KMAX).any()
+        e_gpu, e_orc, e_emu = (max(plant_err(v[i], ref["x"][k]) for k, v in enumerate(xs)) for i in range(3))
+        print("PLANT_ERR %s %s err_gpu=%.3g err_orc=%.3g err_emu=%.3g" % (recipe["target"], plant[0], e_gpu, e_orc, e_emu))
+        assert e_gpu <= plant_error_bound(e_orc, e_emu) and e_gpu < 1e-9, (e_gpu, e_orc, e_emu)
     return env.network
 
 
@@ -319,3 +346,16 @@ def test_kernel_instantiation_matches_oracle(name, monkeypatch):
     got = launches(env)
     assert got.get(name, 0) > 0, (name, got)
     assert set(got) <= recipe["declared"], (name, got)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", sorted(MODE_SWITCHES))
+def test_pendulum_dense_plant_in_every_mode(mode, monkeypatch):
+    """The plant half of pend_step_kernel is compiled once per MODE: each of the three with a dense plant at dt = 2.5e-4, where
+    an env takes up to ~88 substeps in a step (three passes of the kernel's loop; the default plant never needs a second)."""
+    for k, v in MODE_SWITCHES[mode].items():
+        monkeypatch.setenv(k, v)
+    name = "pend_step_kernel<%d, true>" % mode
+    env = _run_pendulum(RECIPES[name], plant=("dense0", 2.5e-4))
+    got = launches(env)
+    assert got.get(name, 0) > 0 and set(got) <= RECIPES[name]["declared"], (name, got)
