@@ -7,7 +7,7 @@ episode's return is 0 or -payload_value whatever the policy does -- and the poli
 maximum.  env.rollout_population(score=...) ranks the candidates by a score of the caller's instead: here one point per data
 packet of the assigned sender that the RRM decoded (actions.make_score(D, reward=0, delivered=1)).
 
-    python examples/throughput_search.py [--envs 65536] [--policies 256] [--generations 10]
+    python examples/throughput_search.py [--envs 65536] [--policies 256] [--generations 10] [--baseline]
 """
 import argparse
 import os
@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--episode-steps", type=int, default=8)
     ap.add_argument("--generations", type=int, default=10)
+    ap.add_argument("--baseline", action="store_true", help="also run the queue-aware backlog scheduler (env.rollout_backlog)")
     args = ap.parse_args()
 
     from gymwipe_amd import VecCounterTrafficEnv, actions
@@ -51,9 +52,20 @@ def main():
 
     # 2. cross-entropy search ranked by delivered packets: each generation is one rollout_population call
     agent = PopulationSearchAgent(env, P, args.steps, args.episode_steps, seed=0, score=packets)
+    e = {"best": float("nan")}
     for _ in range(args.generations):
         e = agent.step()
         print("generation %2d  mean packets per episode %.3f  best %.3f" % (e["generation"], e["mean"], e["best"]))
+
+    # 3. the yardstick: a scheduler that sees the queues (the longest queue, for as long as its backlog needs), on the same
+    #    handle -- what the three-valued observation leaves undelivered
+    if args.baseline:
+        env.reset()
+        env.episode_state.zero_()
+        out = env.rollout_backlog(args.steps, max_steps=args.episode_steps, score=packets)
+        per_step = float(out[4].sum()) / (args.steps * args.envs)
+        print("backlog scheduler      %.4f packets per env-step; the search's best policy %.4f"
+              % (per_step, e["best"] / args.episode_steps))
     env.check()
 
 

@@ -245,3 +245,61 @@ def score_numpy(score, reward, device, delivered):
     w = score.astype(np.int64)
     r = np.rint(np.asarray(reward, dtype=np.float64)).astype(np.int64)
     return (w[0] * r + w[1 + np.asarray(device).astype(np.int64)] * np.asarray(delivered).astype(np.int64)).astype(np.int32)
+
+
+# ---- a queue-aware scheduler inside the rollout (gw_rollout_backlog, include/gymwipe_amd.h) --------------------------------------
+QUEUE_CAP = 100                 # GW_QUEUE_CAP
+BACKLOG_BYTES = 4 * MAX_DEVICES + QUEUE_CAP + 1
+
+
+def make_backlog_policy(num_devices, weights=1, duration_of_len=None, max_duration=20):
+    """The ``uint8[BACKLOG_BYTES]`` image of ``gw_backlog_policy``: ``MAX_DEVICES`` little-endian int32 weights -- sender i's
+    priority is ``weights[i] * qlen_i``, each weight an integer in ``[0, SCORE_W_MAX]``, 0 from ``num_devices`` on -- then the
+    duration for a chosen sender whose queue holds ``L`` packets, ``L`` in ``[0, QUEUE_CAP]``, one byte each (the call clamps
+    it to ``max_duration - 1``).  ``weights``: one for every sender, or a sequence of ``num_devices``.  ``duration_of_len``:
+    ``QUEUE_CAP + 1`` values in ``[0, 255]``; the default is ``min(max_duration - 1, 4 * L)``.  With the defaults: the band
+    goes to the longest queue for as long as its backlog needs."""
+    D = int(num_devices)
+    if not 2 <= D <= MAX_DEVICES:
+        raise ValueError("make_backlog_policy: num_devices must be in [2, %d]" % MAX_DEVICES)
+    w = np.asarray(weights)
+    if w.ndim == 0:
+        w = np.full(D, w)
+    if w.shape != (D,):
+        raise ValueError("make_backlog_policy: weights must be a scalar or a sequence of %d, got shape %s" % (D, w.shape))
+    if w.dtype.kind not in "iu" and not (np.isfinite(w.astype(np.float64)).all() and (w == np.rint(w.astype(np.float64))).all()):
+        raise ValueError("make_backlog_policy: weights must be integers")
+    w = w.astype(np.int64)
+    if (w < 0).any() or (w > SCORE_W_MAX).any():
+        raise ValueError("make_backlog_policy: a weight lies outside [0, %d]" % SCORE_W_MAX)
+    if duration_of_len is None:
+        t = np.minimum(int(max_duration) - 1, 4 * np.arange(QUEUE_CAP + 1))
+    else:
+        t = np.asarray(duration_of_len)
+        if t.shape != (QUEUE_CAP + 1,) or t.dtype.kind not in "iu":
+            raise ValueError("make_backlog_policy: duration_of_len must be %d integers" % (QUEUE_CAP + 1))
+    t = t.astype(np.int64)
+    if (t < 0).any() or (t > 255).any():
+        raise ValueError("make_backlog_policy: a duration lies outside [0, 255]")
+    wl = np.zeros(MAX_DEVICES, "<i4")
+    wl[:D] = w
+    return np.concatenate([wl.view(np.uint8), t.astype(np.uint8)])
+
+
+def backlog_sample_numpy(policy, qlen, max_duration):
+    """CPU restatement of gw_rollout_backlog's choice for one step: ``qlen`` int[N][D], each sender's queue length at the env's
+    current time (``get_state("qlen")``) -> ``(device, duration, seen_len)``, int32[N] each: the lowest index attaining the
+    largest ``w_len[i] * qlen[i]`` (sender 0 where every priority is 0), ``min(duration_of_len[its length], max_duration - 1)``
+    and that length."""
+    policy = np.asarray(policy)
+    if policy.shape != (BACKLOG_BYTES,) or policy.dtype != np.uint8:
+        raise ValueError("policy must be make_backlog_policy()'s uint8[%d]" % BACKLOG_BYTES)
+    q = np.asarray(qlen).astype(np.int64)
+    if q.ndim != 2 or not 1 <= q.shape[1] <= MAX_DEVICES or (q < 0).any() or (q > QUEUE_CAP).any():
+        raise ValueError("qlen must be [N][D] with lengths in [0, %d]" % QUEUE_CAP)
+    w = policy[:4 * MAX_DEVICES].view("<i4").astype(np.int64)[:q.shape[1]]
+    table = policy[4 * MAX_DEVICES:].astype(np.int64)
+    dev = np.argmax(w[None, :] * q, axis=1)              # (the first index of the maximum)
+    seen = q[np.arange(len(q)), dev]
+    dur = np.minimum(table[seen], int(max_duration) - 1)
+    return dev.astype(np.int32), dur.astype(np.int32), seen.astype(np.int32)

@@ -540,6 +540,8 @@ __global__ __launch_bounds__(256) void ct_rollout_sfx_kernel(GwState st, GwDevCo
 //   ct_rollout_policy_eps   gw_rollout_episodes_scored / gw_rollout_population_scored: the two before with the step's score --
 //   ct_rollout_pop_eps      the reward and the packets the step delivered, weighted -- where they have the reward.
 //   ct_rollout_sync_eps     gw_rollout_autoreset_scored: ct_rollout_sync_ep with the same score, the sender the caller's.
+//   ct_rollout_backlog      gw_rollout_backlog: ct_rollout_sync_eps with the action chosen at the step boundary from the queue
+//                           lengths, which the body brings to the current tick there (BacklogEpisodes).
 // The policy's draw (include/gymwipe_amd.h, gw_rollout_policy): the first 32 bits of the action stream's hash
 // (gymwipe_amd/actions.py) against the observation class's row of the table.
 __device__ __forceinline__ uint32_t gw_policy_u(uint64_t seed, uint64_t env_term, uint64_t step)
@@ -1235,6 +1237,112 @@ __global__ __launch_bounds__(64) void ct_rollout_sync_eps(GwState st, GwDevConst
     GW_ROLLOUT_EP_TAIL(false, nullptr)
 }
 
+// gw_rollout_backlog: ct_rollout_sync_eps with the action not loaded from rows but chosen at the step boundary from the body's
+// own queue lengths (queues_now(), ct_rollout_sync_body.h): the lowest sender attaining the largest w_len[i] * len[i], for
+// duration_of_len[its length] clamped into the action space.  The policy's 128 + 101 bytes lie in static LDS beside the score's
+// weights: one LDS read per sender and one per step, all at wave-uniform or per-lane byte addresses.  DT != 0: the scan is
+// unrolled over the length registers; DT == 0: it walks the lane's LDS column.  What was chosen and the length it was chosen
+// for are stored with the step's outputs.  No draws and no step0: it may be recorded into a hipGraph as its parent may.
+struct BacklogEpisodes : ScoredStagedEpisodes {
+    const uint32_t* s_w;                                 // [D] in LDS
+    const uint8_t* s_dur;                                // [GW_QUEUE_CAP + 1] in LDS
+    int32_t* device_out;
+    int32_t* duration_out;
+    int32_t* seen_len;
+    int du_cur;
+    uint32_t q_cur;                                      // the chosen sender's length when it was chosen
+    __device__ __forceinline__ void stage(const gw_backlog_policy& pol, int D, uint32_t* lds_w, uint8_t* lds_dur) const
+    {
+        for (int i = threadIdx.x; i < D; i += blockDim.x) lds_w[i] = (uint32_t)pol.w_len[i];
+        for (int i = threadIdx.x; i <= GW_QUEUE_CAP; i += blockDim.x) lds_dur[i] = pol.duration_of_len[i];
+    }
+    // the step's action from the lengths `len` (all at the env's current time); a strict > keeps the lowest index of a tie,
+    // and sender 0 where every priority is 0
+    template <int DT, class ARR>
+    __device__ __forceinline__ int pick(ARR& len, int D, int max_duration)
+    {
+        const int n = DT ? DT : D;
+        uint32_t q = len[0], p = s_w[0] * q;
+        int d = 0;
+#pragma unroll
+        for (int i = 1; i < n; ++i) {
+            const uint32_t qi = len[i], pi = s_w[i] * qi;
+            const bool more = pi > p;
+            p = more ? pi : p; q = more ? qi : q; d = more ? i : d;
+        }
+        d_cur = d;
+        q_cur = q;
+        du_cur = (int)gw_min_u32((uint32_t)s_dur[gw_min_u32(q, (uint32_t)GW_QUEUE_CAP)], (uint32_t)max_duration - 1u);
+        return d;
+    }
+};
+
+template <int DT, int MODE>
+__global__ __launch_bounds__(64) void ct_rollout_backlog(GwState st, GwDevConst c, int K, GwEpisodeArgs ea, gw_score w, gw_backlog_policy pol,
+                                                        int32_t* device_out, int32_t* duration_out, int32_t* seen_len, int32_t* obs,
+                                                        float* reward, uint8_t* done, uint8_t* ended, int32_t* delivered)
+{
+    __shared__ uint32_t s_score_w[DT == 0 ? GW_MAX_DEVICES : DT];
+    __shared__ uint32_t s_backlog_w[DT == 0 ? GW_MAX_DEVICES : DT];
+    __shared__ uint8_t s_backlog_dur[(GW_QUEUE_CAP + 1 + 3) / 4 * 4];
+    __shared__ unsigned long long s_ep_tally[GW_EP_COLS];
+    BacklogEpisodes src;
+    src.ended = ended;
+    src.latest_next = 0;
+    src.sc.weights_at(s_score_w, w);
+    src.delivered_out = delivered;
+    src.d_cur = 0; src.du_cur = 0; src.q_cur = 0;
+    src.s_w = s_backlog_w; src.s_dur = s_backlog_dur;
+    src.device_out = device_out; src.duration_out = duration_out; src.seen_len = seen_len;
+#define GW_ROLLOUT_SRC_RESETS
+#define GW_ROLLOUT_SRC_QUEUES
+#define GW_ROLLOUT_SRC_STAGE                                                                                                     \
+    src.sc.stage(w, DT == 0 ? c.D : DT);                                                                                         \
+    src.stage(pol, DT == 0 ? c.D : DT, s_backlog_w, s_backlog_dur);                                                              \
+    gw_ep_zero(s_ep_tally);
+#define GW_ROLLOUT_SRC_FIRST src.ep.load(ea, e); src.sc.first();
+#define GW_ROLLOUT_SRC_TAKE                                                                                                      \
+    queues_now();                                                                                                                \
+    const int d = src.pick<DT>(len, D, c.max_duration), du = src.du_cur;
+#define GW_ROLLOUT_SRC_CHECKED(bad) false
+#define GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)                                                                                \
+    {                                                                                                                            \
+        const uint32_t dl_next = src.sc.delivered(kt.deliv);                                                                     \
+        const int32_t score_next = src.sc.of(r, src.d_cur, dl_next);                                                             \
+        GW_ROLLOUT_STORE_OUTPUTS(at, latest, score_next, dn)                                                                     \
+        src.delivered_out[at] = (int32_t)dl_next;                                                                                \
+        src.device_out[at] = src.d_cur;                                                                                          \
+        src.duration_out[at] = src.du_cur;                                                                                       \
+        src.seen_len[at] = (int32_t)src.q_cur;                                                                                   \
+        GW_ROLLOUT_EP_STEPPED(score_next, dn)                                                                                    \
+        src.ended[at] = (uint8_t)cause_next;                                                                                     \
+        src.latest_next = cause_next ? 0 : latest;                                                                               \
+    }
+#include "ct_rollout_sync_body.h"
+    GW_ROLLOUT_EP_TAIL(false, nullptr)
+}
+
+// The per-step form's choice, for handles without the fused kernel: one step's (d, du, q_d) for every env from the queue-length
+// bytes in the env's qb record -- where gw_get_state "qlen" reads them; every step and reset kernel leaves them at the env's
+// current time -- by BacklogEpisodes::pick's rule.
+__global__ __launch_bounds__(256) void backlog_select_rows(uint32_t N, uint32_t D, uint32_t RB, uint32_t md, gw_backlog_policy pol,
+                                                           const uint8_t* __restrict__ qb, int32_t* __restrict__ device_out,
+                                                           int32_t* __restrict__ duration_out, int32_t* __restrict__ seen_len)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    const uint8_t* row = qb + (size_t)e * RB;
+    uint32_t q = row[0], p = (uint32_t)pol.w_len[0] * q, d = 0;
+    for (uint32_t i = 1; i < D; ++i) {
+        const uint32_t qi = row[i], pi = (uint32_t)pol.w_len[i] * qi;
+        const bool more = pi > p;
+        p = more ? pi : p; q = more ? qi : q; d = more ? i : d;
+    }
+    device_out[e] = (int32_t)d;
+    duration_out[e] = (int32_t)gw_min_u32((uint32_t)pol.duration_of_len[gw_min_u32(q, (uint32_t)GW_QUEUE_CAP)], md - 1u);
+    seen_len[e] = (int32_t)q;
+}
+
 // The per-step form's bookkeeping, for handles without the fused kernels: after a step's launch, steps 1-4 and 6 of the
 // semantics for every env -- {age, ret} (EpisodeBook: the fused kernels' rule, one step of it), ended, the tally, the observation
 // acted on next -- and the mask gw_reset's launch takes.
@@ -1545,6 +1653,26 @@ int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, co
                             episode_args(ep, obs_next), *score, device, duration, out.obs, out.reward, out.done, out.ended, delivered);
     return launch_fused(st, cst, ch, GW_LS_ROLLOUT_SYNC_EP, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_sync_ep), episode_args(ep, obs_next),
                         device, duration, out.obs, out.reward, out.done, out.ended);
+}
+
+// gw_rollout_backlog: gw_rollout_autoreset_scored's rules (the policy's LDS copy is static too).  out.device / out.duration:
+// where the chosen actions go.
+int gw_launch_rollout_backlog_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_backlog_policy& pol,
+                                  const gw_episodes& ep, const gw_score& score, int32_t* obs_next, const GwRows& out, int32_t* seen_len,
+                                  int32_t* delivered)
+{
+    if (fused_unavailable(st, cst, ch.K, GW_FUSED_NO_TABLE)) return GW_EUNSUPPORTED;
+    return launch_fused(st, cst, ch, GW_LS_ROLLOUT_BACKLOG, GW_FUSED_NO_TABLE, GW_KERNEL_OF(ct_rollout_backlog), episode_args(ep, obs_next),
+                        score, pol, out.device, out.duration, seen_len, out.obs, out.reward, out.done, out.ended, delivered);
+}
+// ... and its per-step form's choice for one step, into row.device / row.duration / seen_len (default queue mode: st.qb)
+int gw_launch_backlog_select(const GwState& st, const GwDevConst& cst, const gw_backlog_policy& pol, const GwRows& row, int32_t* seen_len,
+                             void* stream)
+{
+    hipLaunchKernelGGL(backlog_select_rows, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)st.N,
+                       (uint32_t)st.D, (uint32_t)st.RB, (uint32_t)cst.max_duration, pol, (const uint8_t*)st.qb, row.device, row.duration,
+                       seen_len);
+    return gw_launch_status();
 }
 
 // gw_rollout's launch.  Returns GW_EUNSUPPORTED when this (D, K) has no fused kernel: the caller falls back to K step launches.

@@ -2,7 +2,7 @@
 // ct_rollout_sync_kernel (actions staged by the caller), ct_rollout_policy (actions drawn in the kernel), ct_rollout_pstats
 // (drawn in the kernel, the transitions tallied instead of stored) and their episodic forms ct_rollout_policy_ep /
 // ct_rollout_pstats_ep / ct_rollout_sync_ep (an env that ends an episode is reset inside the launch), ct_rollout_pop_ep, and the
-// scored ct_rollout_policy_eps / ct_rollout_pop_eps / ct_rollout_sync_eps.  It is text
+// scored ct_rollout_policy_eps / ct_rollout_pop_eps / ct_rollout_sync_eps, and ct_rollout_backlog.  It is text
 // with macro hooks, not a function, on purpose.  As a __forceinline__ template over an action-source type the compiler
 // optimised the callee on its own before inlining it, and all 30 instantiations of ct_rollout_sync_kernel came out different
 // (up to 31 more VGPRs at D = 16 and 32, SGPRs parked in VGPR lanes at D = 4); with the source as an object whose members hold
@@ -20,7 +20,9 @@
 //                                   next draw, the episodic kernels' bookkeeping (ended[at]).  An includer that defines
 //                                   GW_ROLLOUT_SRC_RESETS may call reset_env() here: gw_reset for this one env, in registers
 //                                   (see there).  Such a kernel stores the env's `ip` record behind the body
-//                                   (GW_ROLLOUT_EP_TAIL), which no other does.
+//                                   (GW_ROLLOUT_EP_TAIL), which no other does.  An includer that defines
+//                                   GW_ROLLOUT_SRC_QUEUES may call queues_now() in GW_ROLLOUT_SRC_TAKE and then read the body's
+//                                   len[0 .. D): every queue's length at the env's current time (ct_rollout_backlog).
 // The hooks share the body's scope.  Of its names they read only e, N, k, K, c and -- the scored kernels' STEPPED, for the
 // packets a step delivered -- the running kt.deliv, which restarts at 0 in every launch; they define only d and du; whatever else a
 // source keeps lives in names the body leaves free: `src` and anything ending in `_next`.  A new local of the body takes
@@ -143,6 +145,19 @@
         }
         bpc = cur;
         rvm = 0u; last_abs = 0; dn = 0u;                        // interpreter.reset(): receivedValues, lastAbs, done
+    };
+#endif
+#ifdef GW_ROLLOUT_SRC_QUEUES
+    // Every queue at the env's current time, for a source that chooses the action from the lengths (GW_ROLLOUT_SRC_TAKE may
+    // call it): the ticks up to `now` counted as reset_env and the tail count them (GW_FLAG_TIE rule included), then every
+    // length brought to that tick.  gw_len_after_ticks is additive over a split of the ticks, in the length and in both
+    // tallied terms, so what the lazy form derives from them stays what it was.
+    auto queues_now = [&]() {
+        uint32_t kk = 0;
+        while (wake <= now) { if (wake == now) fl |= GW_FLAG_TIE; wake = wake + interval; kk++; }
+        tau += kk;
+#pragma unroll
+        for (int i = 0; i < D; ++i) { len[i] = gw_len_after_ticks(len[i], tau - tb[i], mult[i], kt); tb[i] = tau; }
     };
 #endif
     auto put_feedback = [&](int32_t latest, int32_t r) {
@@ -399,6 +414,7 @@
     st_plain(st.tk, o16, make_uint4(tau, nbp, rvm, (uint32_t)last_abs | (dn << 31)));
     publish_env_counters(st.sa, N, e, kt.pop, kt.deliv, k_bad, fl, (uint32_t)K);
 #undef GW_ROLLOUT_SRC_RESETS
+#undef GW_ROLLOUT_SRC_QUEUES
 #undef GW_ROLLOUT_SRC_STAGE
 #undef GW_ROLLOUT_SRC_FIRST
 #undef GW_ROLLOUT_SRC_TAKE

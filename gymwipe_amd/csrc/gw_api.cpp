@@ -978,6 +978,56 @@ int gw_rollout_autoreset_scored(gw_env* env, int32_t steps, const int32_t* devic
                              obs_next_dev, {nullptr, nullptr, obs_dev, reward_dev, done_dev, ended_dev}, delivered_dev, stream);
 }
 
+// The scored autoreset call with the actions chosen from the queue lengths: its checks, then the policy's; the fused form, or per
+// step the choice's launch into row s of the caller's action rows and rollout_autoreset's per-step sequence on that row.
+int gw_rollout_backlog(gw_env* env, int32_t steps, const gw_backlog_policy* pol, const gw_episodes* ep, const gw_score* score,
+                       int32_t* obs_next_dev, int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* seen_len_dev,
+                       int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev, void* stream)
+{
+    const char* const who = "gw_rollout_backlog";
+    int rc = rollout_checks(env, steps,
+                            pol && obs_next_dev && device_out_dev && duration_out_dev && seen_len_dev && obs_dev && reward_dev &&
+                                done_dev && ended_dev && delivered_dev,
+                            who, true, ep);
+    if (rc || (score && (rc = check_score(score, who)))) return rc;
+    for (int i = 0; i < GW_MAX_DEVICES; ++i)
+        if (pol->w_len[i] < 0 || pol->w_len[i] > GW_SCORE_W_MAX)
+            return fail(GW_EINVAL, "%s: a w_len weight lies outside [0, %d]", who, GW_SCORE_W_MAX);
+    if (steps == 0) return GW_OK;
+    if ((rc = check_scored_handle(env, who)) || (rc = select_device(env))) return rc;
+    gw_score w = {};                                           // NULL: the built-in reward
+    w.w_reward = 1;
+    if (score) w = *score;
+    const int64_t N = env->st.N;
+    const GwRows out = {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, ended_dev};
+    int32_t n_per_step = 0;
+    double t_bound_before = 0.0;
+    rc = rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        "no fused backlog rollout for this handle (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_backlog_sfx(env->st, env->cst_host, ch, *pol, *ep, w, obs_next_dev, out.at(s0 * N),
+                                                 seen_len_dev + s0 * N, delivered_dev + s0 * N);
+        },
+        [&](int32_t s) {                                       // choice, counters' copy, step, bookkeeping, masked reset
+            const GwRows row = out.at(s * N);
+            uint32_t* base;
+            if (const int e = score_base_of(env, &base)) return e;
+            if (!n_per_step++) t_bound_before = env->t_bound;
+            if (gw_launch_backlog_select(env->st, env->cst_host, *pol, row, seen_len_dev + s * N, stream))
+                return fail(GW_EHIP, "backlog selection kernel launch failed at step %d", s);
+            if (gw_launch_delivered_sfx(env->st, base, stream)) return fail(GW_EHIP, "delivered kernel launch failed at step %d", s);
+            return episode_step(env, s, row.device, row.duration, ep, &w, N, nullptr, obs_next_dev, row, delivered_dev + s * N, stream);
+        });
+    // The host's bound on the clocks is a float sum, so it depends on how the steps were added: the per-step form leaves what the
+    // fused form would have left (one term per chunk), and a snapshot's header then does not tell which of the two forms ran.
+    if (!rc && n_per_step) {
+        const int32_t chunk = env->st.rcap > 0 ? env->st.rcap : 64;
+        env->t_bound = t_bound_before;
+        for (int32_t left = n_per_step; left > 0; left -= chunk) gw_env_add_steps(env, (uint64_t)(left < chunk ? left : chunk));
+    }
+    return rc;
+}
+
 int gw_rollout_population(gw_env* env, int32_t steps, const gw_population* pop, uint64_t seed, uint64_t step0, uint64_t env_id0,
                           const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev, void* stream)
 {
@@ -1273,8 +1323,9 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        static const char* const fam[8] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
-                                           "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps", "ct_rollout_sync_eps"};
+        static const char* const fam[9] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
+                                           "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps", "ct_rollout_sync_eps",
+                                           "ct_rollout_backlog"};
         const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
         snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }

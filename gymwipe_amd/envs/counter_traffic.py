@@ -838,6 +838,43 @@ class VecCounterTrafficEnv(BaseEnv):
             self._last = (self._ep_next, out[1][-1], out[2][-1])
         return tuple(out)
 
+    def rollout_backlog(self, steps, policy=None, max_steps=0, on_done=True, score=None, out=None):
+        """``rollout_autoreset(score=)`` with a queue-aware scheduler choosing the actions inside the call (gw_rollout_backlog):
+        at every step the band goes to the sender with the largest ``w_len[i] * qlen_i`` (the lowest index of a tie), for
+        ``duration_of_len[its length]`` clamped to ``MAX_ASSIGN_DURATION - 1`` -- ``policy`` is ``actions.make_backlog_policy``'s
+        image, ``None`` its default: the longest queue, for ``min(19, 4 * length)``.  The reference's RRM cannot see the
+        senders' queues: this is a genie baseline to measure observation-bound policies against, not a reference path.
+        Returns ``(obs, reward, done, ended, delivered, device, duration, seen_len)``, each ``[steps][N]``: the first five are
+        ``rollout_autoreset(score=)``'s for the chosen actions (``score=None`` is ``actions.make_score(D)``: ``reward`` is the
+        built-in reward), ``device`` / ``duration`` the actions chosen and ``seen_len`` the chosen sender's queue length when it
+        was chosen.  Replaying ``device`` / ``duration`` through ``rollout_autoreset(score=)`` from the same state gives the
+        same rows and state.  ``episode_state``, ``episode_tally`` and the observation acted on next are kept as that call
+        keeps them.  ``out``: eight ``[steps][N]`` tensors to write into.  May be captured into a hipGraph."""
+        torch = _torch()
+        from ..actions import make_backlog_policy, BACKLOG_BYTES
+        ep, _ = self._episodes(max_steps, on_done, None, "rollout_backlog", needs_obs=False)
+        K = int(steps)
+        if K < 0:
+            raise ValueError("rollout_backlog: steps must be >= 0")
+        if policy is None:
+            policy = make_backlog_policy(self.num_devices, max_duration=self.MAX_ASSIGN_DURATION)
+        image = np.asarray(policy)
+        if image.shape != (BACKLOG_BYTES,) or image.dtype != np.uint8:
+            raise ValueError("policy must be actions.make_backlog_policy()'s uint8[%d]" % BACKLOG_BYTES)
+        pol = nat.BacklogPolicy.from_buffer_copy(image.tobytes() + b"\0" * (C.sizeof(nat.BacklogPolicy) - BACKLOG_BYTES))
+        sc = self._score(score) if score is not None else None
+        kinds = (torch.int32, torch.float32, torch.uint8, torch.uint8, torch.int32, torch.int32, torch.int32, torch.int32)
+        out = self._rows(K, kinds, out)
+        if K == 0:
+            return out
+        p = [t.data_ptr() for t in out]
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_rollout_backlog(self._h, K, C.byref(pol), C.byref(ep), C.byref(sc) if sc is not None else None,
+                                                 self._ep_next.data_ptr(), p[5], p[6], p[7], p[0], p[1], p[2], p[3], p[4],
+                                                 self._stream()))
+        self._last = (self._ep_next, out[1][-1], out[2][-1])
+        return out
+
     def step_autoreset(self, action, max_steps=0, on_done=True, out=None, score=None):
         """One ``env.step()`` with autoreset -- ``rollout_autoreset`` of one step on 1-D tensors: the step, the episode
         bookkeeping and the reset of the envs whose episode it ended, in one launch.  Returns ``(obs, reward, done, ended,

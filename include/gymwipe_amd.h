@@ -42,6 +42,8 @@
  *                      (envs/core.py:59-159, networking/devices.py:163-168)
  *   gw_rollout_autoreset_scored   keras-rl's fit loop (gw_rollout_autoreset) around an env with such a custom Interpreter: the
  *                      caller's actions, the launch's resets, the score as the reward the agent remembers
+ *   gw_rollout_backlog (builder-defined: the reference's RRM cannot read sender._mac._packetQueue) that loop with a genie
+ *                      scheduler in the RRM's place, which assigns the band to the longest queue -- a baseline, not a reference path
  *   gw_step_fb         gw_step + the step's feedback as one byte per env (the row a multi-GPU job gathers)
  *   gw_pack_feedback / gw_unpack_feedback   (multi-GPU exchange format; the reference is single-process)
  *   gw_pendulum_step   InvertedPendulumEnv.step              envs/inverted_pendulum.py:101-113
@@ -416,6 +418,46 @@ int gw_rollout_autoreset_scored(gw_env* env, int32_t steps, const int32_t* devic
                                 const gw_episodes* ep, const gw_score* score, int32_t* obs_next_dev,
                                 int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev,
                                 int32_t* delivered_dev, void* stream);
+
+/* A queue-aware scheduler inside the rollout: assign the band to the sender with the largest weighted backlog, for as long as
+ * a table says its backlog needs.  The reference's RRM cannot see sender._mac._packetQueue, so this is a builder-defined genie
+ * baseline -- the yardstick for what a policy that acts on the three-valued observation leaves undelivered -- and not a
+ * reference path. */
+typedef struct gw_backlog_policy {
+    int32_t w_len[GW_MAX_DEVICES];              /* priority of sender i = w_len[i] * qlen_i; each in [0, GW_SCORE_W_MAX] */
+    uint8_t duration_of_len[GW_QUEUE_CAP + 1];  /* duration for a chosen sender whose queue holds L packets */
+} gw_backlog_policy;
+
+/* gw_rollout_autoreset_scored with the actions chosen in the call from the queue lengths.  Step k of env e:
+ *   1. q_i is the length of sender i's MAC queue at the env's current time -- exactly what gw_get_state "qlen" would return
+ *      had the call ended before step k: every counter tick with wake <= now has been counted, a reset at the previous step
+ *      boundary is already applied (a reset leaves the queues alone);
+ *   2. d is the lowest index attaining max_i w_len[i] * q_i over i in [0, num_devices) -- 0 where every priority is 0;
+ *   3. du = min(duration_of_len[q_d], max_duration - 1);
+ *   4. seen_len_dev[k][e] = q_d, device_out_dev[k][e] = d, duration_out_dev[k][e] = du (each int32[steps][N]);
+ *   5. the step, its score, delivered_dev and steps 1-6 of the gw_episodes bookkeeping run exactly as
+ *      gw_rollout_autoreset_scored runs them for the staged action (d, du).
+ * So an action is always inside the action space (no GW_FLAG_BADACT), any byte in duration_of_len is valid, and replaying
+ * device_out_dev / duration_out_dev through gw_rollout_autoreset_scored from the same state gives every other output,
+ * {age, ret}, the tally and the state bit for bit.  score == NULL is {1, 0...}: the built-in reward.
+ * Default mode: ONE launch per 64 steps (ct_rollout_backlog in ct_rollout_sfx.hip) on the handles that have
+ * ct_rollout_sync_eps; the queues are brought to the current tick in registers at every step boundary, the policy lies in
+ * LDS.  Per-step form -- live PHY with default queues, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0, or
+ * any handle while GW_ROLLOUT_POLICY_UNFUSED is set (read per call): per step one small launch that reads each env's
+ * queue-length bytes where gw_get_state "qlen" reads them and writes (d, du, q_d) into row k, then
+ * gw_rollout_autoreset_scored's per-step sequence on that row -- same results.  The uint32[N] scratch row's rules are that
+ * call's: allocated by the first call that takes this form, counted by gw_state_bytes from then on, freed by gw_destroy, not
+ * in snapshots.  GW_ROLLOUT_STRICT turns the per-step form into GW_EUNSUPPORTED before anything is launched or allocated.
+ * An explicit-queue handle has no per-env delivered counter: GW_EUNSUPPORTED before any launch.
+ * GW_EINVAL before any HIP call: env / pol / ep NULL, a NULL pointer other than score / ep->tally_dev / stream, steps < 0,
+ * max_steps < 0, a w_len entry outside [0, GW_SCORE_W_MAX] (all GW_MAX_DEVICES entries, also when steps == 0), a score weight
+ * outside its bounds.  steps == 0 with valid arguments is GW_OK.  Stream-ordered.
+ * There are no draws and no step0, so this call MAY be captured into a hipGraph under gw_rollout_autoreset_scored's rules;
+ * the policy and the score are read by value before the call returns. */
+int gw_rollout_backlog(gw_env* env, int32_t steps, const gw_backlog_policy* pol, const gw_episodes* ep, const gw_score* score,
+                       int32_t* obs_next_dev, int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* seen_len_dev,
+                       int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev,
+                       void* stream);
 
 /* gw_transition_stats for rows recorded by gw_rollout_episodes: step k's observation seen is counter_bound where
  * ended_dev[k - 1] != 0; row 0 uses obs_prev_dev as it is. */
