@@ -8,6 +8,7 @@ maximum.  env.rollout_population(score=...) ranks the candidates by a score of t
 packet of the assigned sender that the RRM decoded (actions.make_score(D, reward=0, delivered=1)).
 
     python examples/throughput_search.py [--envs 65536] [--policies 256] [--generations 10] [--baseline]
+                                          [--tune-baseline [--counter-interval 0.03] [--tune-policies 64] [--tune-generations 8]]
 """
 import argparse
 import os
@@ -27,12 +28,17 @@ def main():
     ap.add_argument("--episode-steps", type=int, default=8)
     ap.add_argument("--generations", type=int, default=10)
     ap.add_argument("--baseline", action="store_true", help="also run the queue-aware backlog scheduler (env.rollout_backlog)")
+    ap.add_argument("--tune-baseline", action="store_true",
+                    help="tune the scheduler's policy for this configuration first (BacklogSearchAgent) and use the tuned policy as the baseline")
+    ap.add_argument("--counter-interval", type=float, default=None, help="the senders' counter_interval (default: the reference's 1 ms)")
+    ap.add_argument("--tune-policies", type=int, default=64)
+    ap.add_argument("--tune-generations", type=int, default=8)
     args = ap.parse_args()
 
     from gymwipe_amd import VecCounterTrafficEnv, actions
-    from gymwipe_amd.agents import PopulationSearchAgent
+    from gymwipe_amd.agents import BacklogSearchAgent, PopulationSearchAgent
 
-    env = VecCounterTrafficEnv(args.envs, num_devices=args.devices)
+    env = VecCounterTrafficEnv(args.envs, num_devices=args.devices, counter_interval=args.counter_interval)
     D, md = args.devices, int(env.config.max_duration)
     packets = actions.make_score(D, reward=0, delivered=1)
 
@@ -58,14 +64,26 @@ def main():
         print("generation %2d  mean packets per episode %.3f  best %.3f" % (e["generation"], e["mean"], e["best"]))
 
     # 3. the yardstick: a scheduler that sees the queues (the longest queue, for as long as its backlog needs), on the same
-    #    handle -- what the three-valued observation leaves undelivered
-    if args.baseline:
+    #    handle -- what the three-valued observation leaves undelivered.  Its default table is a guess; --tune-baseline searches
+    #    weights and table for this configuration, every generation one rollout_backlog_population call from the same state.
+    policy = None
+    if args.tune_baseline:
+        tuner = BacklogSearchAgent(env, args.tune_policies, args.steps, args.episode_steps, seed=0, score=packets)
+        for _ in range(args.tune_generations):
+            t = tuner.step()
+            print("tuning generation %2d  packets per episode: the mean policy %.3f  best %.3f" % (t["generation"], t["of_mu"], t["best"]))
+        policy = tuner.policy()
+        both = actions.make_backlog_population([actions.make_backlog_policy(D, max_duration=md), policy] * (args.tune_policies // 2))
+        tally = tuner.evaluate(both, 0).cpu().numpy()
+        print("scheduler's default policy %.3f packets per episode, tuned %.3f"
+              % (tally[0::2, 3].sum() / tally[0::2, 0].sum(), tally[1::2, 3].sum() / tally[1::2, 0].sum()))
+    if args.baseline or args.tune_baseline:
         env.reset()
         env.episode_state.zero_()
-        out = env.rollout_backlog(args.steps, max_steps=args.episode_steps, score=packets)
+        out = env.rollout_backlog(args.steps, policy, max_steps=args.episode_steps, score=packets)
         per_step = float(out[4].sum()) / (args.steps * args.envs)
-        print("backlog scheduler      %.4f packets per env-step; the search's best policy %.4f"
-              % (per_step, e["best"] / args.episode_steps))
+        print("backlog scheduler%s %.4f packets per env-step; the search's best policy %.4f"
+              % (" (tuned)" if policy is not None else "      ", per_step, e["best"] / args.episode_steps))
     env.check()
 
 

@@ -27,7 +27,7 @@ CFG_PER_ENV_GEOMETRY = 32
 
 EXPORTS = (
     "gw_abi_version", "gw_last_error", "gw_device_count", "gw_config_default", "gw_create",
-    "gw_destroy", "gw_reset", "gw_step", "gw_step_fb", "gw_rollout", "gw_rollout_policy", "gw_rollout_policy_stats", "gw_transition_stats", "gw_rollout_episodes", "gw_rollout_episodes_stats", "gw_transition_stats_ep", "gw_rollout_autoreset", "gw_rollout_population", "gw_rollout_episodes_scored", "gw_rollout_population_scored", "gw_rollout_autoreset_scored", "gw_rollout_backlog", "gw_set_position", "gw_set_positions", "gw_received", "gw_delivered", "gw_enqueue", "gw_pack_feedback", "gw_unpack_feedback", "gw_get_state",
+    "gw_destroy", "gw_reset", "gw_step", "gw_step_fb", "gw_rollout", "gw_rollout_policy", "gw_rollout_policy_stats", "gw_transition_stats", "gw_rollout_episodes", "gw_rollout_episodes_stats", "gw_transition_stats_ep", "gw_rollout_autoreset", "gw_rollout_population", "gw_rollout_episodes_scored", "gw_rollout_population_scored", "gw_rollout_autoreset_scored", "gw_rollout_backlog", "gw_rollout_backlog_population", "gw_set_position", "gw_set_positions", "gw_received", "gw_delivered", "gw_enqueue", "gw_pack_feedback", "gw_unpack_feedback", "gw_get_state",
     "gw_stats_read", "gw_clear_flags", "gw_state_bytes", "gw_snapshot_bytes", "gw_get_snapshot", "gw_set_state", "gw_link_info", "gw_noise_states", "gw_selftest_queue", "gw_selftest_runq",
     "gw_selftest_fastmath", "gw_selftest_launches",
     "gw_plant_config_default", "gw_plant_create", "gw_plant_destroy", "gw_plant_update", "gw_plant_set_input",
@@ -137,6 +137,12 @@ class BacklogPolicy(C.Structure):
     _fields_ = [("w_len", C.c_int32 * MAX_DEVICES), ("duration_of_len", C.c_uint8 * (QUEUE_CAP + 1))]
 
 
+class BacklogPopulation(C.Structure):
+    """gw_backlog_population: P scheduler policies in device memory (``actions.make_backlog_population``'s rows), M envs each,
+    and the ``int64[P][5]`` tally their episodes are added into."""
+    _fields_ = [("num_policies", C.c_int32), ("envs_per_policy", C.c_int32), ("policies_dev", C.c_void_p), ("tally_dev", C.c_void_p)]
+
+
 class NativeError(RuntimeError):
     def __init__(self, code, message):
         RuntimeError.__init__(self, "gymwipe_amd native error %d: %s" % (code, message))
@@ -239,6 +245,8 @@ def lib():
     L.gw_rollout_backlog.argtypes = [vp, i32, C.POINTER(BacklogPolicy), C.POINTER(Episodes), C.POINTER(Score), vp, vp, vp, vp, vp, vp, vp,
                                      vp, vp, vp]
     L.gw_rollout_backlog.restype = C.c_int
+    L.gw_rollout_backlog_population.argtypes = [vp, i32, C.POINTER(BacklogPopulation), C.POINTER(Episodes), C.POINTER(Score), vp, vp]
+    L.gw_rollout_backlog_population.restype = C.c_int
     L.gw_received.argtypes, L.gw_received.restype = [vp, vp, vp], C.c_int
     L.gw_enqueue.argtypes, L.gw_enqueue.restype = [vp, i32, vp, vp], C.c_int
     L.gw_pack_feedback.argtypes, L.gw_pack_feedback.restype = [vp, C.c_int64, vp, vp, vp, vp, i32, vp], C.c_int

@@ -303,3 +303,47 @@ def backlog_sample_numpy(policy, qlen, max_duration):
     seen = q[np.arange(len(q)), dev]
     dur = np.minimum(table[seen], int(max_duration) - 1)
     return dev.astype(np.int32), dur.astype(np.int32), seen.astype(np.int32)
+
+
+# ---- a population of scheduler policies (gw_rollout_backlog_population) ----------------------------------------------------------
+BACKLOG_STRIDE = (BACKLOG_BYTES + 3) // 4 * 4       # sizeof(gw_backlog_policy): the image padded to the int32's alignment
+
+
+def make_backlog_population(policies):
+    """``uint8[P][BACKLOG_STRIDE]``: the ``gw_backlog_policy[P]`` array ``env.rollout_backlog_population`` uploads, from a
+    sequence of ``make_backlog_policy`` images (``uint8[BACKLOG_BYTES]`` each), every row padded with zeros to the record's
+    size."""
+    rows = list(policies)
+    if not rows:
+        raise ValueError("make_backlog_population: at least one policy")
+    out = np.zeros((len(rows), BACKLOG_STRIDE), np.uint8)
+    for p, image in enumerate(rows):
+        image = np.asarray(image)
+        if image.shape != (BACKLOG_BYTES,) or image.dtype != np.uint8:
+            raise ValueError("make_backlog_population: policy %d is not make_backlog_policy()'s uint8[%d]" % (p, BACKLOG_BYTES))
+        out[p, :BACKLOG_BYTES] = image
+    return out
+
+
+def backlog_sample_population_numpy(population, envs_per_policy, qlen, max_duration):
+    """CPU restatement of gw_rollout_backlog_population's choice for one step: env ``e`` of ``qlen`` int[N][D] chooses by row
+    ``e // envs_per_policy`` of ``population`` (``uint8[P][BACKLOG_STRIDE]``, ``P * envs_per_policy == N``) as
+    ``backlog_sample_numpy`` would -- with each weight clamped into ``[0, SCORE_W_MAX]`` first, since the call cannot validate
+    an array it never reads on the host.  Returns ``(device, duration, seen_len)``, int32[N] each."""
+    pop = np.asarray(population)
+    if pop.ndim != 2 or pop.shape[1] != BACKLOG_STRIDE or pop.dtype != np.uint8:
+        raise ValueError("population must be make_backlog_population()'s uint8[P][%d]" % BACKLOG_STRIDE)
+    q = np.asarray(qlen).astype(np.int64)
+    M = int(envs_per_policy)
+    if q.ndim != 2 or not 1 <= q.shape[1] <= MAX_DEVICES or (q < 0).any() or (q > QUEUE_CAP).any():
+        raise ValueError("qlen must be [N][D] with lengths in [0, %d]" % QUEUE_CAP)
+    if M < 1 or len(pop) * M != len(q):
+        raise ValueError("%d policies x %d envs is not qlen's %d envs" % (len(pop), M, len(q)))
+    pop = np.ascontiguousarray(pop)
+    w = np.clip(pop[:, :4 * MAX_DEVICES].view("<i4").astype(np.int64), 0, SCORE_W_MAX)[:, :q.shape[1]]
+    table = pop[:, 4 * MAX_DEVICES:BACKLOG_BYTES].astype(np.int64)
+    of = np.arange(len(q)) // M
+    dev = np.argmax(w[of] * q, axis=1)                   # (the first index of the maximum)
+    seen = q[np.arange(len(q)), dev]
+    dur = np.minimum(table[of, seen], int(max_duration) - 1)
+    return dev.astype(np.int32), dur.astype(np.int32), seen.astype(np.int32)

@@ -366,3 +366,107 @@ class PopulationSearchAgent:
         for _ in range(int(generations)):
             self.step()
         return self.history
+
+
+class BacklogSearchAgent:
+    """Cross-entropy search over the queue-aware scheduler's policy (``actions.make_backlog_policy``), one generation per
+    ``env.rollout_backlog_population`` call: P candidate policies run on ``num_envs / P`` envs each inside one launch per 64
+    steps and come back as a ``[P][5]`` episode tally.  The default table, ``min(19, 4 * length)`` with unit weights, is a
+    guess; which table delivers most depends on the load, so the baseline is tuned per configuration.
+
+    The genome is real-valued: D weight genes, then one duration gene per knot ``L`` in ``KNOTS``.  A genome's policy: the
+    weights rounded and clipped to ``[0, W_MAX]``; the knots interpolated piecewise-linearly over ``L = 0 .. QUEUE_CAP``,
+    rounded and clipped to ``[0, max_duration - 1]``.  ``mu`` starts at the default policy (the knots at ``min(4 L,
+    max_duration + 4)``, which interpolates and clips to exactly the default table).  Per generation: candidate 0 is ``mu``
+    itself, the others ``mu + sigma * eps`` from a seeded ``numpy.random.Generator``; ``evaluate(population, generation)`` ->
+    the tally (``population``: ``actions.make_backlog_population``'s image); ``fitness = ret_sum / episodes`` (``-inf`` where
+    a policy ended no episode); ``mu`` and ``sigma`` become the mean and standard deviation of the elites' genomes, ``sigma``
+    floored at ``SIGMA_MIN``.  ``history`` keeps ``{"generation", "fitness", "mean", "best", "of_mu"}`` per generation.
+
+    ``evaluate`` defaults to the env: a ``snapshot()`` is taken at construction, after ``env.reset()``, and before every
+    generation it is ``restore()``d and the episode state zeroed -- a reset leaves the queues alone, so without the restore a
+    candidate would inherit the queues its slot's predecessor left, and generations would not be comparable.  Pass a callable
+    (and ``env=None`` with ``num_devices``) to let anything else that returns a ``[P][5]`` tally stand in for the GPU.
+    ``score`` (``actions.make_score``) is passed on; a caller's own ``evaluate`` reads it from ``self.score``."""
+
+    KNOTS = (0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 100)
+    W_MAX = 16
+    SIGMA_MIN = 0.25                    # the floor of sigma: genes are rounded, a collapsed elite set must not end the search
+
+    def __init__(self, env, num_policies, steps, episode_steps, elite_frac=0.25, sigma_weight=1.0, sigma_duration=4.0, seed=0,
+                 evaluate=None, num_devices=None, max_duration=None, score=None):
+        import numpy as np
+        self.np = np
+        self.env = env
+        if env is None and (evaluate is None or num_devices is None):
+            raise ValueError("BacklogSearchAgent: without an env, pass evaluate and num_devices")
+        self.num_devices = int(env.num_devices if num_devices is None else num_devices)
+        if max_duration is None:
+            max_duration = env.MAX_ASSIGN_DURATION if env is not None else 20
+        self.max_duration = int(max_duration)
+        self.num_policies, self.steps, self.episode_steps = int(num_policies), int(steps), int(episode_steps)
+        self.num_elites = max(1, int(round(float(elite_frac) * self.num_policies)))
+        if self.num_policies < 1 or self.num_elites > self.num_policies:
+            raise ValueError("BacklogSearchAgent: need 1 <= elites <= num_policies")
+        self.seed = int(seed)
+        self.rng = np.random.default_rng(self.seed)
+        D, knots = self.num_devices, np.asarray(self.KNOTS, np.float64)
+        self.mu = np.concatenate([np.ones(D), np.minimum(4.0 * knots, self.max_duration + 4.0)])
+        self.sigma = np.concatenate([np.full(D, float(sigma_weight)), np.full(len(knots), float(sigma_duration))])
+        self.score = score
+        self.evaluate = evaluate if evaluate is not None else self._evaluate_on_env
+        self._start = None
+        if evaluate is None:
+            env.reset()
+            self._start = env.snapshot()
+        self.generation = 0
+        self.history = []
+
+    def _evaluate_on_env(self, population, generation):
+        env = self.env
+        env.restore(self._start)
+        env.episode_state.zero_()
+        kw = {} if self.score is None else {"score": self.score}
+        return env.rollout_backlog_population(population, self.steps, max_steps=self.episode_steps, on_done=True, **kw)
+
+    def image(self, genome):
+        """A genome -> ``make_backlog_policy``'s image."""
+        from .actions import make_backlog_policy, QUEUE_CAP
+        np = self.np
+        g = np.asarray(genome, np.float64)
+        D = self.num_devices
+        w = np.clip(np.rint(g[:D]), 0, self.W_MAX).astype(np.int64)
+        t = np.interp(np.arange(QUEUE_CAP + 1), self.KNOTS, g[D:])
+        t = np.clip(np.rint(t), 0, self.max_duration - 1).astype(np.int64)
+        return make_backlog_policy(D, w, t, self.max_duration)
+
+    def policy(self):
+        """The image of the current mean genome."""
+        return self.image(self.mu)
+
+    def step(self):
+        """One generation; returns its ``history`` entry."""
+        from .actions import make_backlog_population
+        np = self.np
+        genomes = self.mu + self.sigma * self.rng.standard_normal((self.num_policies, self.mu.size))
+        genomes[0] = self.mu
+        tally = self.evaluate(make_backlog_population([self.image(g) for g in genomes]), self.generation)
+        tally = np.asarray(tally.cpu() if hasattr(tally, "cpu") else tally).astype(np.int64)
+        if tally.shape != (self.num_policies, 5):
+            raise ValueError("evaluate must return a [%d][5] tally, got %s" % (self.num_policies, tally.shape))
+        episodes = tally[:, 0]
+        fitness = np.where(episodes > 0, tally[:, 3] / np.maximum(episodes, 1), -np.inf)
+        elites = genomes[np.argsort(-fitness, kind="stable")[:self.num_elites]]
+        self.mu = elites.mean(axis=0)
+        self.sigma = np.maximum(elites.std(axis=0), self.SIGMA_MIN)
+        ran = fitness[episodes > 0]
+        entry = {"generation": self.generation, "fitness": fitness, "mean": float(ran.mean()) if ran.size else float("-inf"),
+                 "best": float(fitness.max()), "of_mu": float(fitness[0])}
+        self.history.append(entry)
+        self.generation += 1
+        return entry
+
+    def fit(self, generations):
+        for _ in range(int(generations)):
+            self.step()
+        return self.history

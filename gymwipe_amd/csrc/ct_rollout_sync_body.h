@@ -2,7 +2,7 @@
 // ct_rollout_sync_kernel (actions staged by the caller), ct_rollout_policy (actions drawn in the kernel), ct_rollout_pstats
 // (drawn in the kernel, the transitions tallied instead of stored) and their episodic forms ct_rollout_policy_ep /
 // ct_rollout_pstats_ep / ct_rollout_sync_ep (an env that ends an episode is reset inside the launch), ct_rollout_pop_ep, and the
-// scored ct_rollout_policy_eps / ct_rollout_pop_eps / ct_rollout_sync_eps, and ct_rollout_backlog.  It is text
+// scored ct_rollout_policy_eps / ct_rollout_pop_eps / ct_rollout_sync_eps, ct_rollout_backlog and ct_rollout_backlog_pop.  It is text
 // with macro hooks, not a function, on purpose.  As a __forceinline__ template over an action-source type the compiler
 // optimised the callee on its own before inlining it, and all 30 instantiations of ct_rollout_sync_kernel came out different
 // (up to 31 more VGPRs at D = 16 and 32, SGPRs parked in VGPR lanes at D = 4); with the source as an object whose members hold

@@ -978,6 +978,17 @@ int gw_rollout_autoreset_scored(gw_env* env, int32_t steps, const int32_t* devic
                              obs_next_dev, {nullptr, nullptr, obs_dev, reward_dev, done_dev, ended_dev}, delivered_dev, stream);
 }
 
+// The host's bound on the clocks is a float sum, so it depends on how the steps were added: a per-step form that ran n steps from
+// the bound t_bound_before leaves what the fused form would have left (one term per chunk), and a snapshot's header then does not
+// tell which of the two forms ran.
+static void bound_as_fused(gw_env* env, int32_t n, double t_bound_before)
+{
+    if (!n) return;
+    const int32_t chunk = env->st.rcap > 0 ? env->st.rcap : 64;
+    env->t_bound = t_bound_before;
+    for (int32_t left = n; left > 0; left -= chunk) gw_env_add_steps(env, (uint64_t)(left < chunk ? left : chunk));
+}
+
 // The scored autoreset call with the actions chosen from the queue lengths: its checks, then the policy's; the fused form, or per
 // step the choice's launch into row s of the caller's action rows and rollout_autoreset's per-step sequence on that row.
 int gw_rollout_backlog(gw_env* env, int32_t steps, const gw_backlog_policy* pol, const gw_episodes* ep, const gw_score* score,
@@ -1018,13 +1029,50 @@ int gw_rollout_backlog(gw_env* env, int32_t steps, const gw_backlog_policy* pol,
             if (gw_launch_delivered_sfx(env->st, base, stream)) return fail(GW_EHIP, "delivered kernel launch failed at step %d", s);
             return episode_step(env, s, row.device, row.duration, ep, &w, N, nullptr, obs_next_dev, row, delivered_dev + s * N, stream);
         });
-    // The host's bound on the clocks is a float sum, so it depends on how the steps were added: the per-step form leaves what the
-    // fused form would have left (one term per chunk), and a snapshot's header then does not tell which of the two forms ran.
-    if (!rc && n_per_step) {
-        const int32_t chunk = env->st.rcap > 0 ? env->st.rcap : 64;
-        env->t_bound = t_bound_before;
-        for (int32_t left = n_per_step; left > 0; left -= chunk) gw_env_add_steps(env, (uint64_t)(left < chunk ? left : chunk));
-    }
+    if (!rc) bound_as_fused(env, n_per_step, t_bound_before);
+    return rc;
+}
+
+// gw_rollout_backlog with one policy per M envs, read from device memory, and the tally instead of the rows: the population
+// call's checks in its order, then the fused form, or per step the choice's launch into the handle's scratch rows and the scored
+// population's per-step sequence on them.
+int gw_rollout_backlog_population(gw_env* env, int32_t steps, const gw_backlog_population* pop, const gw_episodes* ep, const gw_score* score,
+                                  int32_t* obs_next_dev, void* stream)
+{
+    const char* const who = "gw_rollout_backlog_population";
+    if (env && !pop) return fail(GW_EINVAL, "%s: pop is NULL", who);
+    int rc = rollout_checks(env, steps, pop && pop->policies_dev && pop->tally_dev && obs_next_dev, who, true, ep);
+    if (rc || (score && (rc = check_score(score, who)))) return rc;
+    if ((uintptr_t)pop->policies_dev % 4u) return fail(GW_EINVAL, "%s: policies_dev is not 4-byte aligned", who);
+    if (pop->num_policies < 1 || pop->envs_per_policy < 1)
+        return fail(GW_EINVAL, "%s: num_policies and envs_per_policy must be >= 1", who);
+    if (steps == 0) return GW_OK;
+    const int64_t N = env->st.N, M = pop->envs_per_policy;
+    if ((int64_t)pop->num_policies * M != N)
+        return fail(GW_EINVAL, "%s: %d policies x %d envs is not the handle's %lld envs", who, pop->num_policies, pop->envs_per_policy,
+                    (long long)N);
+    if ((rc = check_scored_handle(env, who)) || (rc = select_device(env))) return rc;
+    gw_score w = {};                                           // NULL: the built-in reward
+    w.w_reward = 1;
+    if (score) w = *score;
+    GwRows row = {};                                           // the per-step form's own N-long rows, allocated when it first runs
+    int32_t n_per_step = 0;
+    double t_bound_before = 0.0;
+    rc = rollout_drive(env, steps, stream, !getenv("GW_ROLLOUT_POLICY_UNFUSED"), INT32_MAX,
+        "no fused backlog population rollout for this handle and envs_per_policy (GW_ROLLOUT_STRICT is set)",
+        [&](int32_t, const GwChunk& ch) { return gw_launch_rollout_backlog_pop_sfx(env->st, env->cst_host, ch, *pop, *ep, w, obs_next_dev); },
+        [&](int32_t s) {                                       // choice, counters' copy, step, bookkeeping, masked reset
+            uint32_t* base;
+            if (!row.obs)
+                if (const int e = pop_rows_of(env, &row)) return e;
+            if (const int e = score_base_of(env, &base)) return e;
+            if (!n_per_step++) t_bound_before = env->t_bound;
+            if (gw_launch_backlog_select_pop(env->st, env->cst_host, *pop, row, stream))
+                return fail(GW_EHIP, "backlog selection kernel launch failed at step %d", s);
+            if (gw_launch_delivered_sfx(env->st, base, stream)) return fail(GW_EHIP, "delivered kernel launch failed at step %d", s);
+            return episode_step(env, s, row.device, row.duration, ep, &w, M, pop->tally_dev, obs_next_dev, row, nullptr, stream);
+        });
+    if (!rc) bound_as_fused(env, n_per_step, t_bound_before);
     return rc;
 }
 
@@ -1323,9 +1371,9 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        static const char* const fam[9] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
-                                           "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps", "ct_rollout_sync_eps",
-                                           "ct_rollout_backlog"};
+        static const char* const fam[10] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
+                                            "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps", "ct_rollout_sync_eps",
+                                            "ct_rollout_backlog", "ct_rollout_backlog_pop"};
         const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
         snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }

@@ -347,6 +347,11 @@ int gw_launch_rollout_backlog_sfx(const GwState& st, const GwDevConst& cst, cons
 // ... and one step's choice for its per-step form, from the queue-length bytes of the default queue mode
 int gw_launch_backlog_select(const GwState& st, const GwDevConst& cst, const gw_backlog_policy& pol, const GwRows& row, int32_t* seen_len,
                              void* stream);
+// gw_rollout_backlog_population: env e under scheduler policy e / envs_per_policy of pop.policies_dev, nothing stored per step ...
+int gw_launch_rollout_backlog_pop_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_backlog_population& pop,
+                                      const gw_episodes& ep, const gw_score& score, int32_t* obs_next);
+// ... and one step's choice for its per-step form, into row.device / row.duration
+int gw_launch_backlog_select_pop(const GwState& st, const GwDevConst& cst, const gw_backlog_population& pop, const GwRows& row, void* stream);
 // gw_rollout_population[_scored]: env e runs policy e / envs_per_policy (pol.cdf: the population's tables), nothing stored per step
 int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
                                  const GwPolicyStream& pol, const gw_episodes& ep, const gw_score* score, const int32_t* obs_prev,
@@ -386,7 +391,7 @@ int gw_launch_unpack_feedback(int64_t count, int center, int pv, const uint8_t* 
 // Sender counts with a kernel instantiation of their own (template parameter DT; every other count runs DT = 0), one list
 // per kernel family.  Each family's launcher dispatches over its list (gw_dispatch.h) and nothing else restates it.
 #define GW_DTS_STEP          2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_step_sfx_kernel
-#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats, their _ep forms, ct_rollout_pop_ep, the three _eps forms, ct_rollout_backlog
+#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats, their _ep forms, ct_rollout_pop_ep, the three _eps forms, ct_rollout_backlog, ct_rollout_backlog_pop
 #define GW_DTS_ROLLOUT_LOOP  2, 3, 4, 6, 8, 16, 32          // ct_rollout_sfx_kernel (event loop)
 #define GW_DTS_LIVE          2, 3, 4, 6, 8, 16, 32          // ct_step_live_kernel
 #define GW_DTS_GENERIC       2, 3, 4, 8, 16                 // ct_step_kernel on the table PHY
@@ -415,7 +420,8 @@ enum {
     GW_LS_ROLLOUT_POP_EPS = GW_LS_ROLLOUT_POLICY_EPS + 3 * GW_LS_NDT,    // ct_rollout_pop_eps<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_SYNC_EPS = GW_LS_ROLLOUT_POP_EPS + 3 * GW_LS_NDT,      // ct_rollout_sync_eps<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_BACKLOG = GW_LS_ROLLOUT_SYNC_EPS + 3 * GW_LS_NDT,      // ct_rollout_backlog<DT, MODE>: 3 per DT
-    GW_LS_COUNT = GW_LS_ROLLOUT_BACKLOG + 3 * GW_LS_NDT
+    GW_LS_ROLLOUT_BACKLOG_POP = GW_LS_ROLLOUT_BACKLOG + 3 * GW_LS_NDT,   // ct_rollout_backlog_pop<DT, MODE>: 3 per DT
+    GW_LS_COUNT = GW_LS_ROLLOUT_BACKLOG_POP + 3 * GW_LS_NDT
 };
 constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {

@@ -875,6 +875,53 @@ class VecCounterTrafficEnv(BaseEnv):
         self._last = (self._ep_next, out[1][-1], out[2][-1])
         return out
 
+    def rollout_backlog_population(self, policies, steps, max_steps=0, on_done=True, score=None, tally=None):
+        """``rollout_backlog`` for P scheduler policies at once, for a caller that tunes them (gw_rollout_backlog_population):
+        ``policies`` is ``actions.make_backlog_population``'s ``uint8[P][232]`` -- a tensor on the env's device, read in place,
+        or the numpy image, which is uploaded -- P divides ``num_envs``, and env ``e`` runs policy ``e // (num_envs // P)``
+        with the choices, steps, scores, resets and episode bookkeeping ``rollout_backlog`` would give it under that policy.
+        Nothing ``[steps][N]`` is stored.  Returns the ``int64[P][5]`` tally, one ``episode_tally`` row per policy
+        (``population_stats``): a new one of zeros, or the caller's ``tally``, ADDED into.  ``episode_state``,
+        ``episode_tally`` (which gets every policy's episodes too) and the observation each env acts on next are kept as
+        ``rollout_population(score=)`` keeps them.  The policies are not validated: a weight outside ``[0, SCORE_W_MAX]`` is
+        clamped where it is read (``actions.backlog_sample_population_numpy``).  One launch per 64 steps where ``num_envs // P``
+        is a multiple of 64 on a handle with a fused rollout; otherwise five small launches per step -- same results.
+        May be captured into a hipGraph once ``policies`` and ``tally`` are the caller's tensors: a replay reads the policies
+        the tensor holds then, so a search writes P policies, replays and reads P rows."""
+        torch = _torch()
+        from ..actions import EP_COLS, BACKLOG_STRIDE
+        ep, _ = self._episodes(max_steps, on_done, None, "rollout_backlog_population", needs_obs=False)
+        K, n = int(steps), self.num_envs
+        if K < 0:
+            raise ValueError("rollout_backlog_population: steps must be >= 0")
+        if type(policies) is torch.Tensor:
+            pols = policies
+            if not (pols.dtype is torch.uint8 and pols.device == self.device and pols.dim() == 2 and pols.shape[1] == BACKLOG_STRIDE
+                    and pols.is_contiguous()):
+                raise ValueError("policies must be a contiguous uint8 tensor of shape (P, %d) on %s" % (BACKLOG_STRIDE, self.device))
+        else:
+            image = np.asarray(policies)
+            if image.ndim != 2 or image.shape[1] != BACKLOG_STRIDE or image.dtype != np.uint8:
+                raise ValueError("policies must be actions.make_backlog_population()'s uint8[P][%d]" % BACKLOG_STRIDE)
+            pols = torch.from_numpy(np.array(image, order="C")).to(self.device)     # (a copy: the image may be read-only)
+        P = int(pols.shape[0])
+        if P < 1 or n % P:
+            raise ValueError("rollout_backlog_population: %d policies do not divide %d envs" % (P, n))
+        if tally is None:
+            tally = torch.zeros((P, EP_COLS), dtype=torch.int64, device=self.device)
+        elif not (type(tally) is torch.Tensor and tally.dtype is torch.int64 and tally.device == self.device
+                  and tuple(tally.shape) == (P, EP_COLS) and tally.is_contiguous()):
+            raise ValueError("tally must be a contiguous int64 tensor of shape (%d, %d) on %s" % (P, EP_COLS, self.device))
+        sc = self._score(score) if score is not None else None
+        pop = nat.BacklogPopulation(P, n // P, pols.data_ptr(), tally.data_ptr())
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_rollout_backlog_population(self._h, K, C.byref(pop), C.byref(ep),
+                                                            C.byref(sc) if sc is not None else None, self._ep_next.data_ptr(),
+                                                            self._stream()))
+        if K:
+            self._last = (self._ep_next,) + tuple(self._last[1:])
+        return tally
+
     def step_autoreset(self, action, max_steps=0, on_done=True, out=None, score=None):
         """One ``env.step()`` with autoreset -- ``rollout_autoreset`` of one step on 1-D tensors: the step, the episode
         bookkeeping and the reset of the envs whose episode it ended, in one launch.  Returns ``(obs, reward, done, ended,

@@ -44,6 +44,8 @@
  *                      caller's actions, the launch's resets, the score as the reward the agent remembers
  *   gw_rollout_backlog (builder-defined: the reference's RRM cannot read sender._mac._packetQueue) that loop with a genie
  *                      scheduler in the RRM's place, which assigns the band to the longest queue -- a baseline, not a reference path
+ *   gw_rollout_backlog_population   (builder-defined) the search that tunes that scheduler per configuration: P of its policies
+ *                      on num_envs / P envs each, ranked by their episode tallies
  *   gw_step_fb         gw_step + the step's feedback as one byte per env (the row a multi-GPU job gathers)
  *   gw_pack_feedback / gw_unpack_feedback   (multi-GPU exchange format; the reference is single-process)
  *   gw_pendulum_step   InvertedPendulumEnv.step              envs/inverted_pendulum.py:101-113
@@ -458,6 +460,39 @@ int gw_rollout_backlog(gw_env* env, int32_t steps, const gw_backlog_policy* pol,
                        int32_t* obs_next_dev, int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* seen_len_dev,
                        int32_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev,
                        void* stream);
+
+/* gw_rollout_backlog for P policies at once, for a caller that tunes the scheduler: what gw_rollout_population is to
+ * gw_rollout_episodes.  Nothing [steps][N] is stored; each policy's episodes are tallied into its own row. */
+typedef struct gw_backlog_population {
+    int32_t num_policies;                     /* P >= 1 */
+    int32_t envs_per_policy;                  /* M >= 1, P * M == num_envs; env e runs policy e / M */
+    const gw_backlog_policy* policies_dev;    /* gw_backlog_policy[P] in DEVICE memory, stride sizeof (232), 4-byte aligned */
+    int64_t* tally_dev;                       /* int64[P][GW_EP_COLS], ADDED into, never NULL */
+} gw_backlog_population;
+
+/* For every env e the choices, the steps, the scores, the resets, {age, ret}, obs_next_dev[e] and every state change are those
+ * of gw_rollout_backlog called with policy e / M; pop->tally_dev[p] receives the episode tally of policy p's envs and
+ * ep->tally_dev, where not NULL, the column sums of those rows.  score == NULL is the built-in reward.
+ * The policies lie in device memory and are never read back, so they are not validated: each w_len[i] is clamped into
+ * [0, GW_SCORE_W_MAX] where it is read, any byte of duration_of_len is valid, and every index is clamped as in
+ * gw_rollout_backlog -- any content is memory-safe and has one meaning (actions.backlog_sample_population_numpy restates it).
+ * Default mode, envs_per_policy a multiple of 64: ONE launch per 64 steps (ct_rollout_backlog_pop in ct_rollout_sfx.hip) on
+ * the handles that have ct_rollout_backlog; a block of 64 envs stages its policy's 232 bytes into LDS with one load per wave.
+ * Per-step form -- any other envs_per_policy, live PHY with default queues, a handle created under GW_ROLLOUT_EVENT_LOOP,
+ * rollout capacity 0, or any handle while GW_ROLLOUT_POLICY_UNFUSED is set (read per call): per step a choice launch that
+ * reads policy e / M, gw_delivered's copy, the step, the scored bookkeeping with the population's rows and gw_reset with the
+ * handle's mask, in the scratch rows gw_rollout_population_scored's per-step form uses (allocated by the first call that
+ * takes this form, counted by gw_state_bytes from then on, not in snapshots) -- same results, and the host's bound on the
+ * clocks is left as the fused form leaves it.  GW_ROLLOUT_STRICT turns the per-step form into GW_EUNSUPPORTED before anything
+ * is launched or allocated.  An explicit-queue handle has no per-env delivered counter: GW_EUNSUPPORTED before any launch.
+ * GW_EINVAL before any HIP call: env / pop / ep NULL; policies_dev, pop->tally_dev, ep->state_dev or obs_next_dev NULL;
+ * steps < 0; max_steps < 0; a score weight outside its bounds; policies_dev not 4-byte aligned; P < 1 or M < 1 (all of these
+ * also when steps == 0); P * M != num_envs.  steps == 0 with valid arguments is GW_OK.  Stream-ordered.
+ * There are no draws and no step0, so this call MAY be captured into a hipGraph under gw_rollout_autoreset_scored's rules: the
+ * score is read by value before the call returns and baked into the recording, the policies are NOT -- every replay reads
+ * what policies_dev holds when it runs, so a search loop is: write P policies, replay, read P rows. */
+int gw_rollout_backlog_population(gw_env* env, int32_t steps, const gw_backlog_population* pop, const gw_episodes* ep,
+                                  const gw_score* score, int32_t* obs_next_dev, void* stream);
 
 /* gw_transition_stats for rows recorded by gw_rollout_episodes: step k's observation seen is counter_bound where
  * ended_dev[k - 1] != 0; row 0 uses obs_prev_dev as it is. */
