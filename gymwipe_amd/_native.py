@@ -160,7 +160,9 @@ def build(force=False, quiet=True):
              or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
              or os.path.getmtime(os.path.join(CSRC, "gw_pyfast.c")) > os.path.getmtime(shim))
     if force or stale:
-        cmd = ["make", "-C", CSRC] + (["-B"] if force else [])
+        # one compile per source and library (csrc/Makefile): shared out over the cores, 16 jobs at the most
+        jobs = min(int(os.environ.get("MAX_JOBS") or os.cpu_count() or 1), 16)
+        cmd = ["make", "-j%d" % max(jobs, 1), "-C", CSRC] + (["-B"] if force else [])
         subprocess.check_call(cmd, stdout=subprocess.DEVNULL if quiet else None)
     return LIB_PATH
 

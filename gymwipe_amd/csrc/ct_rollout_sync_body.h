@@ -1,4 +1,5 @@
-// ct_rollout_sync_body.h -- the body of the step-synchronous rollout kernels (ct_rollout_sfx.hip), included once per kernel:
+// ct_rollout_sync_body.h -- the body of the step-synchronous rollout kernels (the ct_rollout_*.hip files; ct_rollout_sync.hip.h
+// says which family lives where), included once per kernel:
 // ct_rollout_sync_kernel (actions staged by the caller), ct_rollout_policy (actions drawn in the kernel), ct_rollout_pstats
 // (drawn in the kernel, the transitions tallied instead of stored) and their episodic forms ct_rollout_policy_ep /
 // ct_rollout_pstats_ep / ct_rollout_sync_ep (an env that ends an episode is reset inside the launch), ct_rollout_pop_ep, and the
@@ -13,7 +14,7 @@
 //   GW_ROLLOUT_SRC_FIRST            statements once per lane, before step 0
 //   GW_ROLLOUT_SRC_TAKE             statements at the start of step k that define `const int d, du`, the step's action
 //   GW_ROLLOUT_SRC_CHECKED(bad)     `bad` if an action can lie outside the action space, else false
-//                                   (ct_rollout_sfx.hip spells both pairs once: GW_ROLLOUT_STAGED_* and GW_ROLLOUT_DRAWN_*)
+//                                   (ct_rollout_sync.hip.h spells both pairs once: GW_ROLLOUT_STAGED_* and GW_ROLLOUT_DRAWN_*)
 //   GW_ROLLOUT_SRC_STEPPED(at, latest, r, dn)   the last statements of step k (index `at` of [K][N] outputs; k not yet
 //                                   advanced): its outcome where the kernel wants it -- GW_ROLLOUT_STORE_OUTPUTS, the three
 //                                   stores into the kernel's obs, reward and done, or a tally -- then the action taken, the

@@ -333,7 +333,7 @@ bool gw_env_below_limits(gw_env* env, void* stream)
     return env->t_bound + env->step_max < env->t_limit;
 }
 
-// The fused part of a rollout (ct_rollout_sfx.hip): chunks of up to rcap steps through launch(first step, the chunk) while the
+// The fused part of a rollout (ct_rollout_*.hip): chunks of up to rcap steps through launch(first step, the chunk) while the
 // handle has a fused form; *s = the steps done.  A launcher's GW_EUNSUPPORTED ends it (steps > rollout capacity 0,
 // max_duration > 254, ...): the caller goes on step by step, or, under GW_ROLLOUT_STRICT, fails.
 template <class F>

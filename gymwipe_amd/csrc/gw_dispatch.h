@@ -1,4 +1,4 @@
-// gw_dispatch.h -- how the launchers (ct_step*.hip, ct_rollout_sfx.hip) get from a handle's run-time values to ONE kernel
+// gw_dispatch.h -- how the launchers (ct_step*.hip, ct_rollout_*.hip) get from a handle's run-time values to ONE kernel
 // instantiation: nested around a generic lambda that names the kernel,
 //     gw_with_dt<GW_DTS_LIVE>(st.D, [&](auto dt) { gw_with_flag(st.prx_env != nullptr, [&](auto per_env) {
 //         hipLaunchKernelGGL((ct_step_live_kernel<decltype(dt)::value, decltype(per_env)::value>), ...); }); });

@@ -300,7 +300,8 @@ int gw_launch_step_sfx(const GwState& st, const GwDevConst& cst, const int32_t* 
                        uint64_t* rec, const GwSfxFns* fns);
 int gw_launch_reset_sfx(const GwState& st, const uint8_t* mask, int32_t* obs, void* stream, const GwSfxFns* fns);
 int gw_launch_init_sfx(const GwState& st, void* stream);
-// The rollout launchers (ct_rollout_sfx.hip).  What a call passes to every one of its launches travels as three small values:
+// The rollout launchers (ct_rollout_*.hip, one file per group of families: ct_rollout_sync.hip.h names each family's; the file
+// behind each declaration below).  What a call passes to every one of its launches travels as three small values:
 struct GwChunk {                        // one launch of a call: its steps, where it goes, what the host knows about it
     int K;
     void* stream;
@@ -323,24 +324,24 @@ struct GwRows {                         // a call's [K][N] outputs; a member a c
 };
 // Each fused form returns GW_EUNSUPPORTED where the handle (or the call) has none; the per-step forms' launches follow.
 int gw_launch_rollout_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device, const int32_t* duration,
-                          const GwRows& out);                                                       // gw_rollout
+                          const GwRows& out);                                                       // gw_rollout (ct_rollout_sfx.hip)
 int gw_launch_rollout_policy_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
-                                 const int32_t* obs_prev, const GwRows& out);                       // gw_rollout_policy
-#define GW_TS_STEPS 64                  // steps per ct_rollout_pstats launch at most: its LDS histogram's bit budget (ct_rollout_sfx.hip)
+                                 const int32_t* obs_prev, const GwRows& out);                       // gw_rollout_policy (ct_rollout_policy.hip)
+#define GW_TS_STEPS 64                  // steps per ct_rollout_pstats launch at most: its LDS histogram's bit budget (ct_rollout_stats.hip)
 int gw_launch_rollout_pstats_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
-                                 const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table);   // gw_rollout_policy_stats
+                                 const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table);   // gw_rollout_policy_stats (ct_rollout_stats.hip)
 // score (the three episodic forms that take one): nullptr, or the _scored call's weights -- the family with the step's score
 // where it has the reward; delivered: that call's packets per step
 int gw_launch_rollout_policy_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
                                     const gw_episodes& ep, const gw_score* score, const int32_t* obs_prev, int32_t* obs_next,
-                                    const GwRows& out, int32_t* delivered);                         // gw_rollout_episodes[_scored]
+                                    const GwRows& out, int32_t* delivered);                         // gw_rollout_episodes[_scored] (ct_rollout_policy.hip)
 int gw_launch_rollout_pstats_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
-                                    const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, int64_t* table);   // gw_rollout_episodes_stats
+                                    const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, int64_t* table);   // gw_rollout_episodes_stats (ct_rollout_stats.hip)
 int gw_launch_rollout_autoreset_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const int32_t* device,
                                     const int32_t* duration, const gw_episodes& ep, const gw_score* score, int32_t* obs_next,
-                                    const GwRows& out, int32_t* delivered);                         // gw_rollout_autoreset[_scored]
+                                    const GwRows& out, int32_t* delivered);                         // gw_rollout_autoreset[_scored] (ct_rollout_autoreset.hip)
 // gw_rollout_backlog: the scored autoreset form with the actions chosen in the launch from the queue lengths (out.device /
-// out.duration / seen_len receive them) ...
+// out.duration / seen_len receive them) ... (these four: ct_rollout_backlog.hip)
 int gw_launch_rollout_backlog_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_backlog_policy& pol,
                                   const gw_episodes& ep, const gw_score& score, int32_t* obs_next, const GwRows& out, int32_t* seen_len,
                                   int32_t* delivered);
@@ -353,17 +354,19 @@ int gw_launch_rollout_backlog_pop_sfx(const GwState& st, const GwDevConst& cst, 
 // ... and one step's choice for its per-step form, into row.device / row.duration
 int gw_launch_backlog_select_pop(const GwState& st, const GwDevConst& cst, const gw_backlog_population& pop, const GwRows& row, void* stream);
 // gw_rollout_population[_scored]: env e runs policy e / envs_per_policy (pol.cdf: the population's tables), nothing stored per step
+// (ct_rollout_pop.hip)
 int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
                                  const GwPolicyStream& pol, const gw_episodes& ep, const gw_score* score, const int32_t* obs_prev,
                                  int32_t* obs_next);
-// the table from recorded transitions (ended: nullptr, or gw_transition_stats_ep's rows)
+// the table from recorded transitions (ended: nullptr, or gw_transition_stats_ep's rows; ct_rollout_stats.hip)
 int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
                                const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
                                const uint8_t* done, const uint8_t* ended, int64_t* table, void* stream);
 // One step of the per-step forms.  The draw for step pol.step0 from `obs_in` into row.device / row.duration, env e from table
 // e / M (one table: M = st.N), with a scored call's copy of the delivered counters into deliv_before (or nullptr); and, behind
 // the step's launch, the episodes' bookkeeping on that row (ended, the handle's reset mask, obs_next): scored with deliv_before
-// where there is a score, into row e / M of pop_tally where there is one, the packets per step into delivered_out where kept.
+// where there is a score, into row e / M of pop_tally where there is one, the packets per step into delivered_out where kept.  (The draw:
+// ct_rollout_policy.hip; the bookkeeping: ct_rollout_autoreset.hip.)
 int gw_launch_policy_sample(const GwState& st, const GwDevConst& cst, const GwPolicyStream& pol, int64_t M, const int32_t* obs_in,
                             const GwRows& row, uint32_t* deliv_before, void* stream);
 int gw_launch_episodes_step(const GwState& st, const GwDevConst& cst, const gw_episodes& ep, const gw_score* score, int64_t M,
@@ -391,8 +394,8 @@ int gw_launch_unpack_feedback(int64_t count, int center, int pv, const uint8_t* 
 // Sender counts with a kernel instantiation of their own (template parameter DT; every other count runs DT = 0), one list
 // per kernel family.  Each family's launcher dispatches over its list (gw_dispatch.h) and nothing else restates it.
 #define GW_DTS_STEP          2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_step_sfx_kernel
-#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // ct_rollout_sync_kernel, ct_rollout_policy, ct_rollout_pstats, their _ep forms, ct_rollout_pop_ep, the three _eps forms, ct_rollout_backlog, ct_rollout_backlog_pop
-#define GW_DTS_ROLLOUT_LOOP  2, 3, 4, 6, 8, 16, 32          // ct_rollout_sfx_kernel (event loop)
+#define GW_DTS_ROLLOUT_SYNC  2, 3, 4, 5, 6, 7, 8, 16, 32    // every includer of ct_rollout_sync_body.h, through launch_fused (ct_rollout_sync.hip.h lists the families)
+#define GW_DTS_ROLLOUT_LOOP  2, 3, 4, 6, 8, 16, 32          // ct_rollout_sfx_kernel (event loop, ct_rollout_sfx.hip)
 #define GW_DTS_LIVE          2, 3, 4, 6, 8, 16, 32          // ct_step_live_kernel
 #define GW_DTS_GENERIC       2, 3, 4, 8, 16                 // ct_step_kernel on the table PHY
 #define GW_DTS_GENERIC_LIVE  4, 16                          // ct_step_kernel on the live PHY (DYN)

@@ -216,7 +216,7 @@ int gw_rollout(gw_env* env, int32_t steps, const int32_t* device_dev, const int3
  * the last row of an earlier call's obs_dev while writing the same buffer again, copy that row first.  The table is read stream-ordered (rewrite it on the same stream between
  * calls), never validated or read back: the clamp keeps any content memory-safe, and a drawn action is always inside the
  * action space (no GW_FLAG_BADACT).  Continue a stream of draws by advancing step0 by `steps`; shard it by env_id0.
- * Default mode: ONE launch per 64 steps (ct_rollout_policy in ct_rollout_sfx.hip), the draw at each step boundary inside it.
+ * Default mode: ONE launch per 64 steps (ct_rollout_policy in ct_rollout_policy.hip), the draw at each step boundary inside it.
  * Every other handle (explicit queues, live PHY, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0), or any
  * handle while GW_ROLLOUT_POLICY_UNFUSED is set: a sampling launch and a step launch per step, same results;
  * GW_ROLLOUT_STRICT turns that into GW_EUNSUPPORTED.  steps == 0 is GW_OK; a NULL pointer or steps < 0 is GW_EINVAL before
@@ -239,7 +239,7 @@ int gw_rollout_policy(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint6
  * accumulate).  obs_last_dev[e] (int32[N]) receives the env's last observation; it may be obs_prev_dev itself (an env reads its
  * own element before it writes it), which is how a caller continues: obs in place, step0 += steps.  return_dev (int32[N], may
  * be NULL): return_dev[e] += the env's reward sum over the call.  Allocates nothing, stream-ordered, the tables never
- * validated.  Default mode only (ct_rollout_pstats in ct_rollout_sfx.hip, one launch per 64 steps, the tally in LDS).  A handle
+ * validated.  Default mode only (ct_rollout_pstats in ct_rollout_stats.hip, one launch per 64 steps, the tally in LDS).  A handle
  * without that form -- explicit queues, live PHY, created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0, A > 640, a
  * histogram of 3 * A bins that does not fit LDS beside the kernel's tables (sender counts without a kernel of their own from
  * 12 up at max_duration 20), or any handle while GW_ROLLOUT_POLICY_UNFUSED is set -- gets GW_EUNSUPPORTED before anything is
@@ -279,7 +279,7 @@ typedef struct gw_episodes {
  * each env acts on next, its last one or counter_bound where it has just been reset.  Pass obs_next_dev as the next call's
  * obs_prev_dev; it may be the same array (an env reads its element before writing it), but neither overlaps the [steps][N]
  * outputs.  max_steps == 0 && on_done == 0 gives exactly gw_rollout_policy's outputs and state, ended all zero.
- * Default mode: ONE launch per 64 steps (ct_rollout_policy_ep in ct_rollout_sfx.hip), the reset in registers at the step
+ * Default mode: ONE launch per 64 steps (ct_rollout_policy_ep in ct_rollout_policy.hip), the reset in registers at the step
  * boundary.  Every other handle (as for gw_rollout_policy), or any handle while GW_ROLLOUT_POLICY_UNFUSED is set: per step a
  * sampling launch, a step launch, a bookkeeping launch and gw_reset's launch with a mask the handle owns -- same results;
  * GW_ROLLOUT_STRICT turns that into GW_EUNSUPPORTED.  steps == 0 is GW_OK; a NULL pointer other than tally_dev / stream,
@@ -309,7 +309,7 @@ int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_de
  * obs and done with reward 0 -- and still counts as a step of the episode: age += 1, ret += 0, the cause from the repeated
  * done.  A rejected action can so end an episode by the step limit, and the env is then reset.
  * max_steps == 0 && on_done == 0 gives exactly gw_rollout's outputs and state, ended all zero; {age, ret} still advance.
- * Default mode: ONE launch per 64 steps (ct_rollout_sync_ep in ct_rollout_sfx.hip), the reset in registers at the step
+ * Default mode: ONE launch per 64 steps (ct_rollout_sync_ep in ct_rollout_autoreset.hip), the reset in registers at the step
  * boundary.  Every other handle (explicit queues, live PHY, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0):
  * per step a step launch, a bookkeeping launch and gw_reset's launch with a mask the handle owns -- same results;
  * GW_ROLLOUT_STRICT turns that into GW_EUNSUPPORTED before anything is launched.  steps == 0 is GW_OK; a NULL pointer other
@@ -338,7 +338,7 @@ typedef struct gw_population {
  * tally untouched and gives gw_rollout_policy's trajectory per policy.  Stream-ordered.  Not for hipGraph capture: step0 is
  * baked into the recorded launch.
  * Fused form -- a handle that has one for gw_rollout_episodes, M % 64 == 0 (a wave then never spans two policies; a policy may
- * span many blocks) and GW_ROLLOUT_POLICY_UNFUSED unset: ONE launch per 64 steps (ct_rollout_pop_ep in ct_rollout_sfx.hip), at
+ * span many blocks) and GW_ROLLOUT_POLICY_UNFUSED unset: ONE launch per 64 steps (ct_rollout_pop_ep in ct_rollout_pop.hip), at
  * most 2 * GW_EP_COLS global adds per block; integer adds commute, so no result depends on their order of arrival.
  * Per-step form -- any other M, explicit queues, live PHY, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0:
  * per step a sampling launch, a step launch, a bookkeeping launch and gw_reset's launch with a mask the handle owns -- same
@@ -372,7 +372,7 @@ typedef struct gw_score {
  * the reward: reward_dev[k][e] = (float)score_k, ret += score_k; delivered_dev (int32[steps][N], never NULL) receives
  * delivered_k.  The draws, the episode causes, the resets, obs_next_dev, device_out_dev / duration_out_dev, obs_dev, done_dev
  * and ended_dev are exactly the parent's.  The score is read by value before the call returns.
- * Default mode: ONE launch per 64 steps (ct_rollout_policy_eps in ct_rollout_sfx.hip), the weights staged beside the table.
+ * Default mode: ONE launch per 64 steps (ct_rollout_policy_eps in ct_rollout_policy.hip), the weights staged beside the table.
  * Per-step form -- live PHY with default queues, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0, or any
  * handle while GW_ROLLOUT_POLICY_UNFUSED is set: per step a sampling launch that also copies each env's delivered counter
  * into a uint32[N] scratch row the HANDLE owns, a step launch, a bookkeeping launch that differences the counter and scores,
@@ -403,7 +403,7 @@ int gw_rollout_population_scored(gw_env* env, int32_t steps, const gw_population
  * An action outside the action space (GW_FLAG_BADACT) delivers nothing and scores exactly 0: its row repeats the current obs
  * and done, delivered 0, reward 0, and it is still a step of the episode.  No weight is read at an unchecked sender: the
  * index is clamped to [0, num_devices).
- * Default mode: ONE launch per 64 steps (ct_rollout_sync_eps in ct_rollout_sfx.hip), the weights in LDS.  Per-step form -- live
+ * Default mode: ONE launch per 64 steps (ct_rollout_sync_eps in ct_rollout_autoreset.hip), the weights in LDS.  Per-step form -- live
  * PHY with default queues, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0: per step gw_delivered's launch
  * into the uint32[N] scratch row above, a step launch, the scored bookkeeping launch and gw_reset's launch -- same results.
  * The row's rules are as above: the first call that takes this form allocates it (and so synchronises the device once),
@@ -442,7 +442,7 @@ typedef struct gw_backlog_policy {
  * So an action is always inside the action space (no GW_FLAG_BADACT), any byte in duration_of_len is valid, and replaying
  * device_out_dev / duration_out_dev through gw_rollout_autoreset_scored from the same state gives every other output,
  * {age, ret}, the tally and the state bit for bit.  score == NULL is {1, 0...}: the built-in reward.
- * Default mode: ONE launch per 64 steps (ct_rollout_backlog in ct_rollout_sfx.hip) on the handles that have
+ * Default mode: ONE launch per 64 steps (ct_rollout_backlog in ct_rollout_backlog.hip) on the handles that have
  * ct_rollout_sync_eps; the queues are brought to the current tick in registers at every step boundary, the policy lies in
  * LDS.  Per-step form -- live PHY with default queues, a handle created under GW_ROLLOUT_EVENT_LOOP, rollout capacity 0, or
  * any handle while GW_ROLLOUT_POLICY_UNFUSED is set (read per call): per step one small launch that reads each env's
@@ -476,7 +476,7 @@ typedef struct gw_backlog_population {
  * The policies lie in device memory and are never read back, so they are not validated: each w_len[i] is clamped into
  * [0, GW_SCORE_W_MAX] where it is read, any byte of duration_of_len is valid, and every index is clamped as in
  * gw_rollout_backlog -- any content is memory-safe and has one meaning (actions.backlog_sample_population_numpy restates it).
- * Default mode, envs_per_policy a multiple of 64: ONE launch per 64 steps (ct_rollout_backlog_pop in ct_rollout_sfx.hip) on
+ * Default mode, envs_per_policy a multiple of 64: ONE launch per 64 steps (ct_rollout_backlog_pop in ct_rollout_backlog.hip) on
  * the handles that have ct_rollout_backlog; a block of 64 envs stages its policy's 232 bytes into LDS with one load per wave.
  * Per-step form -- any other envs_per_policy, live PHY with default queues, a handle created under GW_ROLLOUT_EVENT_LOOP,
  * rollout capacity 0, or any handle while GW_ROLLOUT_POLICY_UNFUSED is set (read per call): per step a choice launch that

@@ -260,14 +260,19 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu(native_lib):
     assert L.gw_selftest_queue(1, 10, 0, 10) == nat.EINVAL
 
 
-def test_hot_kernels_use_no_scratch_memory(tmp_path):
+def test_hot_kernels_use_no_scratch_memory(tmp_path, native_lib):
     """Every step / rollout kernel must keep its state in registers: private_segment_fixed_size == 0 for each
     instantiation.  (Twice this build the compiler folded a select between array elements -- or between two arrays -- into
     dynamic addressing of a stack copy, which costs 10-15 % of a launch and shows up nowhere else.)  Cross-compiles the
-    device code only; no GPU needed."""
-    import re
+    device code only; no GPU needed.  The rollout families' files are taken from the directory, and the kernels seen must
+    include every instantiation of the catalogue's families (KERNEL_FAMILIES) that the built library has: a family in a file
+    this test does not compile fails here."""
+    import glob
     import shutil
-    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+    from gymwipe_amd import _native
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from util import kernel_instantiations
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
@@ -276,17 +281,47 @@ def test_hot_kernels_use_no_scratch_memory(tmp_path):
     flags = subprocess.run(["make", "-s", "-C", csrc, "print-flags"], check=True, capture_output=True, text=True).stdout.split()
     assert "--offload-arch=gfx950" in flags and "-ffp-contract=off" in flags, flags
     xoff = [f + ":xnack-" if f == "--offload-arch=gfx950" else f for f in flags]       # the second library's target
-    for src, fl in (("ct_step_sfx.hip", flags), ("ct_rollout_sfx.hip", flags), ("ct_step.hip", flags), ("ct_step_dyn.hip", flags),
-                    ("ct_step_sfx.hip", xoff), ("ct_rollout_sfx.hip", xoff)):
-        out = tmp_path / (src + ".s")
+    rollout = sorted(os.path.basename(f) for f in glob.glob(os.path.join(csrc, "ct_rollout*.hip")))
+    assert "ct_rollout_sfx.hip" in rollout and len(rollout) >= 6, rollout
+    jobs = ([(src, "any", flags) for src in ["ct_step_sfx.hip"] + rollout + ["ct_step.hip", "ct_step_dyn.hip"]]
+            + [(src, "xoff", xoff) for src in ["ct_step_sfx.hip"] + rollout])
+
+    def kernels_of(job):                                 # [(symbol, private segment)] of one file for one target
+        src, tag, fl = job
+        out = tmp_path / ("%s.%s.s" % (src, tag))
         subprocess.run([hipcc] + fl + ["-S", "--cuda-device-only", "-o", str(out), "-x", "hip", os.path.join(csrc, src)],
                        check=True, capture_output=True, timeout=900, cwd=csrc)
         text = out.read_text()
         sizes = re.findall(r"^\s+\.private_segment_fixed_size:\s+(\d+)", text, re.M)
         names = re.findall(r"^\s+\.name:\s+(\S+)", text, re.M)
         assert sizes and len(sizes) == len(names), src
-        bad = [(n, int(s)) for n, s in zip(names, sizes) if int(s) != 0]
-        assert not bad, "%s: kernels with scratch memory: %s" % (src, bad)
+        return [(n, int(s)) for n, s in zip(names, sizes)]
+
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+        results = list(pool.map(kernels_of, jobs))
+    seen = {"any": set(), "xoff": set()}
+    for (src, tag, _), kernels in zip(jobs, results):
+        bad = [(n, s) for n, s in kernels if s != 0]
+        assert not bad, "%s (%s): kernels with scratch memory: %s" % (src, tag, bad)
+        seen[tag] |= {n for n, _ in kernels}
+    # symbols -> the spelling kernel_instantiations uses
+    dem = subprocess.run(["c++filt"], input="\n".join(sorted(seen["any"])), capture_output=True, text=True, check=True).stdout
+    seen_names = {m.group(1) for m in re.finditer(r"(?:^|[\s:])(\w+<[^()]*>)\(", dem, re.M)}
+    want = {n for n in kernel_instantiations(_native.LIB_PATH, r"\w+") if n.split("<")[0] in KERNEL_FAMILIES}
+    assert len(want) >= 134
+    assert sorted(want - seen_names) == [], "instantiations of the library that no compiled file showed"
+
+
+def test_makefile_lists_every_source_in_csrc():
+    """csrc/Makefile's SRCS (`make print-srcs`: what every library, tools/build_variant.sh and tests/sanitize_cpu.sh build
+    from) is the .hip and .cpp files present in csrc/: a new family file cannot be left out of the build, nor a removed one
+    stay listed."""
+    csrc = os.path.join(ROOT, "gymwipe_amd", "csrc")
+    listed = subprocess.run(["make", "-s", "-C", csrc, "print-srcs"], check=True, capture_output=True, text=True).stdout.split()
+    present = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")))
+    assert len(listed) == len(set(listed)) and sorted(listed) == present
+    literal = [l for l in open(os.path.join(csrc, "Makefile")).read().split("\n") if re.match(r"SRCS\s*:=", l)]
+    assert len(literal) == 1 and literal[0].split(":=")[1].split() == listed, "SRCS is one literal line"
 
 
 def test_fastcall_shim_reaches_the_same_entry_points():

@@ -7,7 +7,7 @@ set -e
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 NAME=$1; SRC=${2:-$REPO/gymwipe_amd/csrc}; shift; shift || true
 FLAGS=$(make -s -C $REPO/gymwipe_amd/csrc print-flags | sed 's/--offload-arch=gfx950/--offload-arch=gfx950:xnack-/; s#-I../../include#-I'$REPO'/include#')
-SRCS="gw_api.cpp gw_plant_api.cpp plant_mfma.hip gw_grid_api.cpp grid_phy.hip gw_tables.cpp ct_step.hip ct_step_sfx.hip ct_step_dyn.hip ct_rollout_sfx.hip feedback_pack.hip gw_ctrl_api.cpp ctrl_step.hip"
+SRCS=$(make -s -C $SRC print-srcs)                      # the revision's own list (csrc/Makefile)
 cd $SRC
 /opt/rocm/bin/hipcc $FLAGS "$@" -shared -o $REPO/gymwipe_amd/lib/libgymwipe_amd_$NAME.so -x hip $SRCS
 echo built $REPO/gymwipe_amd/lib/libgymwipe_amd_$NAME.so
