@@ -9,6 +9,7 @@ packet of the assigned sender that the RRM decoded (actions.make_score(D, reward
 
     python examples/throughput_search.py [--envs 65536] [--policies 256] [--generations 10] [--baseline]
                                           [--tune-baseline [--counter-interval 0.03] [--tune-policies 64] [--tune-generations 8]]
+                                          [--controller [--controller-policies 64] [--controller-generations 8]]
 """
 import argparse
 import os
@@ -33,10 +34,14 @@ def main():
     ap.add_argument("--counter-interval", type=float, default=None, help="the senders' counter_interval (default: the reference's 1 ms)")
     ap.add_argument("--tune-policies", type=int, default=64)
     ap.add_argument("--tune-generations", type=int, default=8)
+    ap.add_argument("--controller", action="store_true",
+                    help="also search finite-state controllers (ControllerSearchAgent): memory and a delivered bit, no queue lengths")
+    ap.add_argument("--controller-policies", type=int, default=64)
+    ap.add_argument("--controller-generations", type=int, default=8)
     args = ap.parse_args()
 
     from gymwipe_amd import VecCounterTrafficEnv, actions
-    from gymwipe_amd.agents import BacklogSearchAgent, PopulationSearchAgent
+    from gymwipe_amd.agents import BacklogSearchAgent, ControllerSearchAgent, PopulationSearchAgent
 
     env = VecCounterTrafficEnv(args.envs, num_devices=args.devices, counter_interval=args.counter_interval)
     D, md = args.devices, int(env.config.max_duration)
@@ -84,6 +89,20 @@ def main():
         per_step = float(out[4].sum()) / (args.steps * args.envs)
         print("backlog scheduler%s %.4f packets per env-step; the search's best policy %.4f"
               % (" (tuned)" if policy is not None else "      ", per_step, e["best"] / args.episode_steps))
+    # 4. between the two: a finite-state controller knows what it did and whether the step it granted delivered enough, which a
+    #    real RRM knows too.  The search starts at stay-while-productive; every generation is one rollout_controller_population
+    #    call from the same state.
+    if args.controller:
+        search = ControllerSearchAgent(env, args.controller_policies, args.steps, args.episode_steps, seed=0, score=packets)
+        for _ in range(args.controller_generations):
+            c = search.step()
+            print("controller generation %2d  packets per episode: the mean controller %.3f  best %.3f"
+                  % (c["generation"], c["of_mu"], c["best"]))
+        rr = actions.round_robin_controller(D, md - 1, md)
+        both = actions.make_controller_population([rr, search.controller()] * (args.controller_policies // 2))
+        tally = search.evaluate(both, 0).cpu().numpy()
+        print("round-robin %.4f packets per env-step, the searched controller %.4f"
+              % (tally[0::2, 3].sum() / tally[0::2, 2].sum(), tally[1::2, 3].sum() / tally[1::2, 2].sum()))
     env.check()
 
 

@@ -347,3 +347,117 @@ def backlog_sample_population_numpy(population, envs_per_policy, qlen, max_durat
     seen = q[np.arange(len(q)), dev]
     dur = np.minimum(table[of, seen], int(max_duration) - 1)
     return dev.astype(np.int32), dur.astype(np.int32), seen.astype(np.int32)
+
+
+# ---- finite-state controllers inside the scored closed loop (gw_rollout_controller, include/gymwipe_amd.h) --------------------
+# A controller has S nodes.  The env's node n and the class c of the observation it acts on pick the row the action is drawn
+# from, cdf[n][c]; behind the step the node moves on the class of the new observation and on one bit, whether the step
+# delivered at least need[n] packets: n <- next[n][c'][b].  A step that ends an episode puts the env at node 0, class 1.
+FSC_MAX_STATES = 16             # GW_FSC_MAX_STATES
+
+
+def make_controller(num_devices, cdf, next, need, max_duration=20):
+    """The three arrays of a ``gw_controller``, checked: ``(cdf uint32[S][3][A], next uint8[S][3][2], need uint8[S])`` with
+    ``1 <= S <= FSC_MAX_STATES`` and ``A = num_devices * max_duration``.  ``cdf``: per (node, observation class) a row as
+    ``policy_cdf`` makes it -- integers in ``[0, 2^32)``, non-decreasing along a row.  ``next``: the node to move to by (node,
+    new observation class, delivered bit), each in ``[0, S)``.  ``need``: each node's delivered-packet threshold in
+    ``[0, 255]`` (0: the bit is always set; 255: never, a step delivers fewer).  The native calls validate none of this --
+    they clamp where they read (``controller_step_numpy``) -- so a controller built here means what it says."""
+    D, md = int(num_devices), int(max_duration)
+    if not 2 <= D <= MAX_DEVICES or md < 1:
+        raise ValueError("make_controller: num_devices must be in [2, %d] and max_duration >= 1" % MAX_DEVICES)
+    A = D * md
+    c, nx, nd = np.asarray(cdf), np.asarray(next), np.asarray(need)
+    if c.ndim != 3 or not 1 <= c.shape[0] <= FSC_MAX_STATES or c.shape[1:] != (3, A):
+        raise ValueError("make_controller: cdf must be [S][3][%d] with 1 <= S <= %d, got shape %s" % (A, FSC_MAX_STATES, c.shape))
+    S = c.shape[0]
+    if nx.shape != (S, 3, 2) or nd.shape != (S,):
+        raise ValueError("make_controller: next must be [%d][3][2] and need [%d], got shapes %s and %s" % (S, S, nx.shape, nd.shape))
+    for name, a in (("cdf", c), ("next", nx), ("need", nd)):
+        if a.dtype.kind not in "iu":
+            raise ValueError("make_controller: %s must hold integers" % name)
+    c, nx, nd = c.astype(np.int64), nx.astype(np.int64), nd.astype(np.int64)
+    if (c < 0).any() or (c > 0xffffffff).any() or (np.diff(c, axis=-1) < 0).any():
+        raise ValueError("make_controller: a cdf row leaves [0, 2^32) or decreases")
+    if (nx < 0).any() or (nx >= S).any():
+        raise ValueError("make_controller: a next entry lies outside [0, %d)" % S)
+    if (nd < 0).any() or (nd > 255).any():
+        raise ValueError("make_controller: a need entry lies outside [0, 255]")
+    return c.astype(np.uint32), nx.astype(np.uint8), nd.astype(np.uint8)
+
+
+def _controller_arrays(controller):
+    cdf, nxt, need = (np.asarray(a) for a in controller)
+    if cdf.ndim != 3 or cdf.shape[1] != 3 or not 1 <= cdf.shape[0] <= FSC_MAX_STATES:
+        raise ValueError("controller: cdf must be uint32[S][3][A] with 1 <= S <= %d" % FSC_MAX_STATES)
+    S = cdf.shape[0]
+    if cdf.dtype != np.uint32 or nxt.dtype != np.uint8 or need.dtype != np.uint8 or nxt.shape != (S, 3, 2) or need.shape != (S,):
+        raise ValueError("controller must be (uint32[S][3][A], uint8[S][3][2], uint8[S])")
+    return cdf, nxt, need
+
+
+def controller_step_numpy(seed, env_lo, env_hi, step, controller, node, obs, counter_bound, max_duration):
+    """CPU restatement of the controller's draw: ``(device, duration, node_used)`` for envs [env_lo, env_hi) at stream position
+    ``step``, each at ``node`` uint8[envs] and acting on ``obs`` int32[envs].  ``node_used = min(node, S - 1)`` -- the clamp
+    applies where the byte is read -- and the action is ``policy_sample_numpy``'s from row ``cdf[node_used][cls(obs)]``.
+    ``controller``: ``make_controller``'s arrays, or any arrays of their dtypes and shapes."""
+    cdf, _, _ = _controller_arrays(controller)
+    S, A = cdf.shape[0], cdf.shape[2]
+    n = np.minimum(np.asarray(node).astype(np.int64), S - 1)
+    cls = np.sign(np.asarray(obs).astype(np.int64) - int(counter_bound)).astype(np.int64) + 1
+    a = policy_count_numpy(cdf.reshape(3 * S, A), n * 3 + cls, policy_u_numpy(seed, env_lo, env_hi, step))
+    dev = a // int(max_duration)
+    return dev.astype(np.int32), (a - dev * int(max_duration)).astype(np.int32), n.astype(np.uint8)
+
+
+def controller_move_numpy(controller, node, obs, delivered, ended, counter_bound):
+    """CPU restatement of the controller's transition behind a step taken at ``node`` (clamped as the draw clamps it): where
+    ``ended != 0`` the env is at node 0; elsewhere at ``min(next[n][cls(obs)][delivered >= need[n]], S - 1)``, ``obs`` the
+    observation the step returned and ``delivered`` the packets it delivered.  Returns uint8[envs]."""
+    cdf, nxt, need = _controller_arrays(controller)
+    S = cdf.shape[0]
+    n = np.minimum(np.asarray(node).astype(np.int64), S - 1)
+    cls = np.sign(np.asarray(obs).astype(np.int64) - int(counter_bound)).astype(np.int64) + 1
+    b = (np.asarray(delivered).astype(np.int64) >= need.astype(np.int64)[n]).astype(np.int64)
+    to = np.minimum(nxt.astype(np.int64)[n, cls, b], S - 1)
+    return np.where(np.asarray(ended) != 0, 0, to).astype(np.uint8)
+
+
+def _one_hot_rows(D, duration, max_duration):
+    """uint32[D][3][A]: node i's three rows all draw (sender i, duration) with certainty."""
+    md = int(max_duration)
+    if not 0 <= int(duration) < md:
+        raise ValueError("duration must be in [0, %d)" % md)
+    p = np.zeros((D, 3, D * md))
+    for i in range(D):
+        p[i, :, i * md + int(duration)] = 1.0
+    return policy_cdf(p)
+
+
+def round_robin_controller(num_devices, duration, max_duration=20):
+    """D nodes: node i assigns sender i for ``duration`` and moves to node i + 1 (mod D) whatever happens."""
+    D = int(num_devices)
+    nxt = np.empty((D, 3, 2), np.uint8)
+    nxt[:] = ((np.arange(D) + 1) % D)[:, None, None]
+    return make_controller(D, _one_hot_rows(D, duration, max_duration), nxt, np.full(D, 255, np.uint8), max_duration)
+
+
+def stay_while_productive_controller(num_devices, duration, need, max_duration=20):
+    """D nodes: node i assigns sender i for ``duration``; it stays while the step delivered at least ``need`` packets and moves
+    to node i + 1 (mod D) otherwise.  ``need >= 255`` (or more than ``duration`` can carry) is ``round_robin_controller``."""
+    D = int(num_devices)
+    nxt = np.empty((D, 3, 2), np.uint8)
+    nxt[:, :, 0] = ((np.arange(D) + 1) % D)[:, None]
+    nxt[:, :, 1] = np.arange(D)[:, None]
+    return make_controller(D, _one_hot_rows(D, duration, max_duration), nxt, np.full(D, int(need), np.int64), max_duration)
+
+
+def make_controller_population(controllers):
+    """``(cdf uint32[P][S][3][A], next uint8[P][S][3][2], need uint8[P][S])`` from a sequence of controllers of one size: what
+    ``env.rollout_controller_population`` uploads."""
+    rows = [_controller_arrays(c) for c in controllers]
+    if not rows:
+        raise ValueError("make_controller_population: at least one controller")
+    if len({r[0].shape for r in rows}) != 1:
+        raise ValueError("make_controller_population: every controller needs the same S and A")
+    return tuple(np.stack([r[i] for r in rows]) for i in range(3))

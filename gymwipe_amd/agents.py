@@ -470,3 +470,120 @@ class BacklogSearchAgent:
         for _ in range(int(generations)):
             self.step()
         return self.history
+
+
+class ControllerSearchAgent:
+    """Cross-entropy search over finite-state controllers (``actions.make_controller``), one generation per
+    ``env.rollout_controller_population`` call: P candidate controllers of S nodes run on ``num_envs / P`` envs each inside
+    one launch per 64 steps and come back as a ``[P][5]`` episode tally.  A controller sees what an RRM sees -- the
+    observation class, what it did (its node) and whether the step it granted delivered enough -- not the queues.
+
+    The genome is real-valued, ``GENES = D + 8`` genes per node: D sender logits, a duration, ``need``, and the six ``next``
+    entries (by new observation class and delivered bit).  A genome's controller: node n draws its sender from
+    ``softmax(logits)`` for the duration rounded and clipped to ``[0, max_duration - 1]``, the same row for the three classes;
+    ``need`` rounded and clipped to ``[0, 255]``; each ``next`` gene rounded and taken modulo S.  ``mu`` starts at
+    ``actions.stay_while_productive_controller(D, max_duration - 1, need0)`` spread over S nodes (node n serves sender
+    ``n % D`` with logit ``LOGIT0``).  Per generation: candidate 0 is ``mu`` itself, the others ``mu + sigma * eps`` from a
+    seeded ``numpy.random.Generator``; ``evaluate(population, generation)`` -> the tally (``population``:
+    ``actions.make_controller_population``'s arrays); ``fitness = ret_sum / episodes`` (``-inf`` where a controller ended no
+    episode); ``mu`` and ``sigma`` become the mean and standard deviation of the elites' genomes, ``sigma`` floored at
+    ``SIGMA_MIN``.  ``history`` keeps ``{"generation", "fitness", "mean", "best", "of_mu"}`` per generation.
+
+    ``evaluate`` defaults to the env, as ``BacklogSearchAgent``'s does: a ``snapshot()`` taken at construction is restored
+    before every generation, and the episode state and the nodes are zeroed.  Pass a callable (and ``env=None`` with
+    ``num_devices``) to let anything else that returns a ``[P][5]`` tally stand in for the GPU.  ``score``
+    (``actions.make_score``) is passed on; the default counts delivered packets."""
+
+    LOGIT0 = 6.0
+    SIGMA_MIN = 0.25
+
+    def __init__(self, env, num_policies, steps, episode_steps, num_states=None, need0=8, elite_frac=0.25, sigma_logit=1.0,
+                 sigma_duration=2.0, sigma_need=1.5, sigma_next=0.5, seed=0, evaluate=None, num_devices=None, max_duration=None,
+                 score=None):
+        import numpy as np
+        from .actions import FSC_MAX_STATES, make_score
+        self.np = np
+        self.env = env
+        if env is None and (evaluate is None or num_devices is None):
+            raise ValueError("ControllerSearchAgent: without an env, pass evaluate and num_devices")
+        self.num_devices = D = int(env.num_devices if num_devices is None else num_devices)
+        if max_duration is None:
+            max_duration = env.MAX_ASSIGN_DURATION if env is not None else 20
+        self.max_duration = int(max_duration)
+        self.num_states = S = int(D if num_states is None else num_states)
+        if not 1 <= S <= FSC_MAX_STATES:
+            raise ValueError("ControllerSearchAgent: num_states must be in [1, %d]" % FSC_MAX_STATES)
+        self.num_policies, self.steps, self.episode_steps = int(num_policies), int(steps), int(episode_steps)
+        self.num_elites = max(1, int(round(float(elite_frac) * self.num_policies)))
+        if self.num_policies < 1 or self.num_elites > self.num_policies:
+            raise ValueError("ControllerSearchAgent: need 1 <= elites <= num_policies")
+        self.seed = int(seed)
+        self.rng = np.random.default_rng(self.seed)
+        self.GENES = D + 8
+        mu = np.zeros((S, self.GENES))
+        sigma = np.empty((S, self.GENES))
+        for n in range(S):
+            mu[n, n % D] = self.LOGIT0
+            mu[n, D], mu[n, D + 1] = self.max_duration - 1, need0
+            mu[n, D + 2:] = [(n + 1) % S, n] * 3                    # by class: {not enough: the next node, enough: stay}
+        sigma[:, :D], sigma[:, D], sigma[:, D + 1], sigma[:, D + 2:] = sigma_logit, sigma_duration, sigma_need, sigma_next
+        self.mu, self.sigma = mu.ravel(), sigma.ravel()
+        self.score = score if score is not None else make_score(D, reward=0, delivered=1)
+        self.evaluate = evaluate if evaluate is not None else self._evaluate_on_env
+        self._start = self._obs0 = None
+        if evaluate is None:
+            self._obs0 = env.reset().clone()                        # what every env sees at the snapshot
+            self._start = env.snapshot()
+        self.generation = 0
+        self.history = []
+
+    def _evaluate_on_env(self, population, generation):
+        env = self.env
+        env.restore(self._start)
+        env.episode_state.zero_()
+        env.controller_node.zero_()
+        return env.rollout_controller_population(population, self.steps, self.seed, max_steps=self.episode_steps, on_done=True,
+                                                 step0=generation * self.steps, obs_prev=self._obs0, score=self.score)
+
+    def controller(self, genome=None):
+        """A genome (default: the current mean) -> ``make_controller``'s arrays."""
+        from .actions import make_controller, policy_cdf
+        np = self.np
+        D, S, md = self.num_devices, self.num_states, self.max_duration
+        g = np.asarray(self.mu if genome is None else genome, np.float64).reshape(S, self.GENES)
+        z = g[:, :D] - g[:, :D].max(axis=1, keepdims=True)
+        p_sender = np.exp(z) / np.exp(z).sum(axis=1, keepdims=True)
+        dur = np.clip(np.rint(g[:, D]), 0, md - 1).astype(np.int64)
+        p = np.zeros((S, 3, D * md))
+        for n in range(S):
+            p[n, :, np.arange(D) * md + dur[n]] = p_sender[n][:, None]
+        need = np.clip(np.rint(g[:, D + 1]), 0, 255).astype(np.int64)
+        nxt = (np.rint(g[:, D + 2:]).astype(np.int64) % S).reshape(S, 3, 2)
+        return make_controller(D, policy_cdf(p), nxt, need, md)
+
+    def step(self):
+        """One generation; returns its ``history`` entry."""
+        from .actions import make_controller_population
+        np = self.np
+        genomes = self.mu + self.sigma * self.rng.standard_normal((self.num_policies, self.mu.size))
+        genomes[0] = self.mu
+        tally = self.evaluate(make_controller_population([self.controller(g) for g in genomes]), self.generation)
+        tally = np.asarray(tally.cpu() if hasattr(tally, "cpu") else tally).astype(np.int64)
+        if tally.shape != (self.num_policies, 5):
+            raise ValueError("evaluate must return a [%d][5] tally, got %s" % (self.num_policies, tally.shape))
+        episodes = tally[:, 0]
+        fitness = np.where(episodes > 0, tally[:, 3] / np.maximum(episodes, 1), -np.inf)
+        elites = genomes[np.argsort(-fitness, kind="stable")[:self.num_elites]]
+        self.mu = elites.mean(axis=0)
+        self.sigma = np.maximum(elites.std(axis=0), self.SIGMA_MIN)
+        ran = fitness[episodes > 0]
+        entry = {"generation": self.generation, "fitness": fitness, "mean": float(ran.mean()) if ran.size else float("-inf"),
+                 "best": float(fitness.max()), "of_mu": float(fitness[0])}
+        self.history.append(entry)
+        self.generation += 1
+        return entry
+
+    def fit(self, generations):
+        for _ in range(int(generations)):
+            self.step()
+        return self.history

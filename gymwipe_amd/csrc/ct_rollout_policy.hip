@@ -44,22 +44,6 @@ __global__ __launch_bounds__(64) void ct_rollout_policy(GwState st, GwDevConst c
 #include "ct_rollout_sync_body.h"
 }
 
-// ct_rollout_policy's source with the episode's book (obs_prev may be obs_next here): the draw after a step that ended an
-// episode is for the reset's observation, counter_bound (class 1).
-struct EpisodeActions : PolicyDraw {
-    int32_t* device_out;
-    int32_t* duration_out;
-    uint8_t* ended;
-    EpisodeBook ep;
-    __device__ __forceinline__ void stepped(size_t at, int k, int K, int32_t latest, uint32_t cause)
-    {
-        device_out[at] = d_cur;
-        duration_out[at] = du_cur;
-        ended[at] = (uint8_t)cause;
-        next(k, K, cause ? 0 : latest);
-    }
-};
-
 template <int DT, int MODE>
 __global__ __launch_bounds__(64) void ct_rollout_policy_ep(GwState st, GwDevConst c, int K, GwPolicyArgs p, GwEpisodeArgs ea,
                                                           int32_t* device_out, int32_t* duration_out, int32_t* obs, float* reward,
@@ -85,11 +69,6 @@ __global__ __launch_bounds__(64) void ct_rollout_policy_ep(GwState st, GwDevCons
 #include "ct_rollout_sync_body.h"
     GW_ROLLOUT_EP_TAIL(false, nullptr)
 }
-
-struct ScoredEpisodeActions : EpisodeActions {
-    StepScore sc;
-    int32_t* delivered_out;
-};
 
 // ct_rollout_policy_ep with the score where it has the reward: the reward row, the book's return -- and the packets per step.
 template <int DT, int MODE>

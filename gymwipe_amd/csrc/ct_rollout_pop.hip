@@ -8,12 +8,8 @@ namespace {
 // ---- a population of policies in one launch: gw_rollout_population (include/gymwipe_amd.h) ---------------------------------
 // Env e runs policy e / M.  A block is one wave of 64 consecutive envs and M is a multiple of 64 (the launcher refuses any
 // other), so a block has ONE policy, p = blockIdx.x * 64 / M: it stages that policy's [3][A] slice and flushes its episode
-// tally into that policy's row.  ct_rollout_policy_ep's source with nothing stored per step.
-struct PopulationActions : PolicyDraw {
-    int64_t* row;                                        // the block's policy: [GW_EP_COLS] of the caller's [P][GW_EP_COLS]
-    EpisodeBook ep;
-};
-
+// tally into that policy's row.  ct_rollout_policy_ep's source with nothing stored per step (PopulationActions,
+// ct_rollout_sync.hip.h).
 // p.cdf is [P][3][A] here, pop_tally [P][GW_EP_COLS]; ea.tally the call-wide row (or nullptr), which gets every block's words too:
 // at most 2 * GW_EP_COLS global adds per block.
 template <int DT, int MODE>
@@ -44,10 +40,6 @@ __global__ __launch_bounds__(64) void ct_rollout_pop_ep(GwState st, GwDevConst c
 #include "ct_rollout_sync_body.h"
     GW_ROLLOUT_EP_TAIL(true, src.row)
 }
-
-struct ScoredPopulationActions : PopulationActions {
-    StepScore sc;
-};
 
 // ct_rollout_pop_ep with the book's return the score.
 template <int DT, int MODE>

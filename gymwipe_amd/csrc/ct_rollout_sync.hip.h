@@ -4,8 +4,9 @@
 //   device side   the per-lane arrays (RegArr ... ArrSel, the event loop's too), the policy's draw (gw_policy_*, GwPolicyArgs,
 //                 PolicyDraw), the staged / drawn action hooks and GW_ROLLOUT_STORE_OUTPUTS, the episode's book and the episodic
 //                 tail (GwEpisodeArgs, EpisodeBook, GW_ROLLOUT_EP_*), the step's score (StepScore), and the sources that files
-//                 other than their kernel's derive from (StagedEpisodes, ScoredStagedEpisodes)
-//   host side     fused_unavailable, launch_fused, GW_KERNEL_OF, policy_args, episode_args
+//                 other than their kernel's derive from (StagedEpisodes, ScoredStagedEpisodes, ScoredEpisodeActions,
+//                 ScoredPopulationActions)
+//   host side     fused_unavailable, launch_fused, launch_fused_lds, GW_KERNEL_OF, policy_args, episode_args
 // The loop's body itself is ct_rollout_sync_body.h.  The step semantics and reference citations are those of ct_step_sfx.hip /
 // ct_common.hip.h.
 #pragma once
@@ -77,6 +78,10 @@ template <int N> struct ArrSel<true, N> { typedef LdsArr rw; typedef ConstMemArr
 //                           lengths, which the body brings to the current tick there (BacklogEpisodes; ct_rollout_backlog.hip).
 //   ct_rollout_backlog_pop  gw_rollout_backlog_population: ct_rollout_backlog with one policy per block, read from device memory,
 //                           and nothing stored per step (as ct_rollout_pop_eps; ct_rollout_backlog.hip).
+//   ct_rollout_fsc          gw_rollout_controller / gw_rollout_controller_population: ct_rollout_policy_eps / ct_rollout_pop_eps
+//   ct_rollout_fsc_pop      with a finite-state controller -- the env's node picks which three rows of the table the draw reads,
+//                           and moves on the new observation class and on whether the step delivered enough
+//                           (ct_rollout_fsc.hip).
 // A launcher stays in the file that holds every kernel it may launch.  The per-step forms' small row kernels live beside the
 // family they serve: policy_sample_kernel (ct_rollout_policy.hip), episodes_step_kernel (ct_rollout_autoreset.hip),
 // backlog_select_rows / backlog_select_pop_rows (ct_rollout_backlog.hip), transition_stats_rows (ct_rollout_stats.hip).
@@ -352,6 +357,40 @@ struct ScoredStagedEpisodes : StagedEpisodes {
     int d_cur;                                           // the sender step k was staged with, inside the action space or not
 };
 
+// The sources of ct_rollout_policy.hip's and ct_rollout_pop.hip's episodic kernels, which ct_rollout_fsc.hip's derive from.
+// ct_rollout_policy's source with the episode's book (obs_prev may be obs_next here): the draw after a step that ended an
+// episode is for the reset's observation, counter_bound (class 1).
+struct EpisodeActions : PolicyDraw {
+    int32_t* device_out;
+    int32_t* duration_out;
+    uint8_t* ended;
+    EpisodeBook ep;
+    __device__ __forceinline__ void stepped(size_t at, int k, int K, int32_t latest, uint32_t cause)
+    {
+        device_out[at] = d_cur;
+        duration_out[at] = du_cur;
+        ended[at] = (uint8_t)cause;
+        next(k, K, cause ? 0 : latest);
+    }
+};
+
+// ct_rollout_policy_eps' source
+struct ScoredEpisodeActions : EpisodeActions {
+    StepScore sc;
+    int32_t* delivered_out;
+};
+
+// ct_rollout_pop_ep's source (ct_rollout_pop.hip says what a block's row is)
+struct PopulationActions : PolicyDraw {
+    int64_t* row;                                        // the block's policy: [GW_EP_COLS] of the caller's [P][GW_EP_COLS]
+    EpisodeBook ep;
+};
+
+// ct_rollout_pop_eps' source
+struct ScoredPopulationActions : PopulationActions {
+    StepScore sc;
+};
+
 // ---- launching the step-synchronous family (host side) -------------------------------------------------------------------------
 // What a family keeps in the launch's dynamic LDS decides its availability rules beyond the handle's, and that LDS's size.
 enum GwFusedLds {
@@ -372,20 +411,20 @@ inline bool fused_unavailable(const GwState& st, const GwDevConst& cst, int K, G
 
 // One launch of kernel_of(dt, m) -- the family's instantiation for the handle's sender count and the launch's MODE -- over a
 // grid of 64-lane blocks, recorded in the family's slots from slot_base on.  The kernel's arguments are st, cst, K, args...
+// launch_fused_lds: with `dyn` bytes of dynamic LDS, for a family that sizes them itself (ct_rollout_fsc.hip; `fits`: refuse the
+// launch, before it, where they do not fit the block's LDS beside the instantiation's own).  launch_fused, behind it: sized by
+// what the family keeps there (GwFusedLds).
 template <class KERNEL_OF, class... ARGS>
-int launch_fused(const GwState& st, const GwDevConst& cst, const GwChunk& ch, int slot_base, GwFusedLds lds, KERNEL_OF kernel_of,
-                 const ARGS&... args)
+int launch_fused_lds(const GwState& st, const GwDevConst& cst, const GwChunk& ch, int slot_base, bool fits, size_t dyn,
+                     KERNEL_OF kernel_of, const ARGS&... args)
 {
     const unsigned grid = (unsigned)((st.N + 63) / 64);
     const int mode = gw_step_mode(cst, ch.below_limits, false);
-    const size_t A = (size_t)st.D * (size_t)cst.max_duration;
-    const size_t dyn = lds == GW_FUSED_NO_TABLE ? 0 : 3 * A * (sizeof(uint32_t) + (lds == GW_FUSED_TABLE_HIST ? TS_BIN_BYTES : 0)) +
-                                                      (lds == GW_FUSED_TABLE_SCORE ? (size_t)st.D * sizeof(int32_t) : 0);
     return gw_with_dt<GW_DTS_ROLLOUT_SYNC>(st.D, [&](auto dt) {          // (any other D: per-lane arrays in LDS)
         return gw_with_mode(mode, [&](auto m) {
             constexpr int DT = decltype(dt)::value, MODE = decltype(m)::value;
             const auto kernel = kernel_of(dt, m);
-            if (lds == GW_FUSED_TABLE_HIST || lds == GW_FUSED_TABLE_SCORE) {
+            if (fits) {
                 // The instantiation's own LDS, asked once (the same on every device).  One static per kernel: this generic
                 // lambda is instantiated per (KERNEL_OF, dt, m), and every GW_KERNEL_OF lambda is a type of its own, so
                 // ct_rollout_pstats and ct_rollout_pstats_ep do not share theirs.
@@ -401,6 +440,15 @@ int launch_fused(const GwState& st, const GwDevConst& cst, const GwChunk& ch, in
             return gw_launch_status();
         });
     });
+}
+template <class KERNEL_OF, class... ARGS>
+int launch_fused(const GwState& st, const GwDevConst& cst, const GwChunk& ch, int slot_base, GwFusedLds lds, KERNEL_OF kernel_of,
+                 const ARGS&... args)
+{
+    const size_t A = (size_t)st.D * (size_t)cst.max_duration;
+    const size_t dyn = lds == GW_FUSED_NO_TABLE ? 0 : 3 * A * (sizeof(uint32_t) + (lds == GW_FUSED_TABLE_HIST ? TS_BIN_BYTES : 0)) +
+                                                      (lds == GW_FUSED_TABLE_SCORE ? (size_t)st.D * sizeof(int32_t) : 0);
+    return launch_fused_lds(st, cst, ch, slot_base, lds == GW_FUSED_TABLE_HIST || lds == GW_FUSED_TABLE_SCORE, dyn, kernel_of, args...);
 }
 #define GW_KERNEL_OF(family) [](auto dt, auto m) { return &family<decltype(dt)::value, decltype(m)::value>; }
 

@@ -1091,6 +1091,66 @@ int gw_rollout_population_scored(gw_env* env, int32_t steps, const gw_population
                               obs_prev_dev, obs_next_dev, stream);
 }
 
+// The scored closed loops with a finite-state controller: their parents' checks in their order, the controller's between the
+// pointers and the score; then the fused form or a refusal, as the tallying calls have it (rollout_drive_tally).
+static int check_controller_states(int32_t S, const char* who)
+{
+    if (S < 1 || S > GW_FSC_MAX_STATES) return fail(GW_EINVAL, "%s: num_states must be in [1, %d]", who, GW_FSC_MAX_STATES);
+    return GW_OK;
+}
+
+int gw_rollout_controller(gw_env* env, int32_t steps, const gw_controller* ctl, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                          const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                          int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
+                          uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev, uint8_t* node_out_dev, void* stream)
+{
+    const char* const who = "gw_rollout_controller";
+    int rc = rollout_checks(env, steps,
+                            ctl && ctl->cdf_dev && ctl->next_dev && ctl->need_dev && ctl->node_dev && score && obs_prev_dev &&
+                                obs_next_dev && device_out_dev && duration_out_dev && obs_dev && reward_dev && done_dev && ended_dev &&
+                                delivered_dev && node_out_dev,
+                            who, true, ep);
+    if (rc || (rc = check_controller_states(ctl->num_states, who)) || (rc = check_score(score, who)) || steps == 0) return rc;
+    if ((rc = check_scored_handle(env, who)) || (rc = select_device(env))) return rc;
+    const int64_t N = env->st.N;
+    const GwPolicyStream pol = {ctl->cdf_dev, seed, step0, env_id0};
+    const GwRows out = {device_out_dev, duration_out_dev, obs_dev, reward_dev, done_dev, ended_dev};
+    return rollout_drive_tally(env, steps, stream, "no fused controller rollout for this handle and controller: there is no per-step form",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_fsc_sfx(env->st, env->cst_host, ch, *ctl, pol.at(s0), *ep, *score,
+                                             seen_before(s0, obs_prev_dev, obs_next_dev), obs_next_dev, out.at(s0 * N),
+                                             delivered_dev + s0 * N, node_out_dev + s0 * N);
+        });
+}
+
+int gw_rollout_controller_population(gw_env* env, int32_t steps, const gw_controller_population* pop, uint64_t seed, uint64_t step0,
+                                     uint64_t env_id0, const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev,
+                                     int32_t* obs_next_dev, void* stream)
+{
+    const char* const who = "gw_rollout_controller_population";
+    if (env && !pop) return fail(GW_EINVAL, "%s: pop is NULL", who);
+    int rc = rollout_checks(env, steps,
+                            pop && pop->cdf_dev && pop->next_dev && pop->need_dev && pop->node_dev && pop->tally_dev && score &&
+                                obs_prev_dev && obs_next_dev,
+                            who, true, ep);
+    if (rc || (rc = check_controller_states(pop->num_states, who)) || (rc = check_score(score, who))) return rc;
+    if (pop->num_policies < 1 || pop->envs_per_policy < 1)
+        return fail(GW_EINVAL, "%s: num_policies and envs_per_policy must be >= 1", who);
+    if (steps == 0) return GW_OK;
+    const int64_t N = env->st.N, M = pop->envs_per_policy;
+    if ((int64_t)pop->num_policies * M != N)
+        return fail(GW_EINVAL, "%s: %d policies x %d envs is not the handle's %lld envs", who, pop->num_policies, pop->envs_per_policy,
+                    (long long)N);
+    if ((rc = check_scored_handle(env, who)) || (rc = select_device(env))) return rc;
+    const GwPolicyStream pol = {pop->cdf_dev, seed, step0, env_id0};
+    return rollout_drive_tally(env, steps, stream,
+        "no fused controller population rollout for this handle, envs_per_policy and controller size: there is no per-step form",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_fsc_pop_sfx(env->st, env->cst_host, ch, *pop, pol.at(s0), *ep, *score,
+                                                 seen_before(s0, obs_prev_dev, obs_next_dev), obs_next_dev);
+        });
+}
+
 int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0, uint64_t env_id0,
                               const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
                               int64_t* table_dev, void* stream)
@@ -1371,9 +1431,9 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        static const char* const fam[10] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
+        static const char* const fam[12] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
                                             "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps", "ct_rollout_sync_eps",
-                                            "ct_rollout_backlog", "ct_rollout_backlog_pop"};
+                                            "ct_rollout_backlog", "ct_rollout_backlog_pop", "ct_rollout_fsc", "ct_rollout_fsc_pop"};
         const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
         snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }

@@ -358,6 +358,14 @@ int gw_launch_backlog_select_pop(const GwState& st, const GwDevConst& cst, const
 int gw_launch_rollout_pop_ep_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_population& pop,
                                  const GwPolicyStream& pol, const gw_episodes& ep, const gw_score* score, const int32_t* obs_prev,
                                  int32_t* obs_next);
+// gw_rollout_controller / gw_rollout_controller_population: the scored closed loops with a finite-state controller (pol.cdf: its
+// [S][3][A], or the population's [P][S][3][A]); fused or GW_EUNSUPPORTED, there is no per-step form (ct_rollout_fsc.hip)
+int gw_launch_rollout_fsc_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_controller& ctl,
+                              const GwPolicyStream& pol, const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev,
+                              int32_t* obs_next, const GwRows& out, int32_t* delivered, uint8_t* node_out);
+int gw_launch_rollout_fsc_pop_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const gw_controller_population& pop,
+                                  const GwPolicyStream& pol, const gw_episodes& ep, const gw_score& score, const int32_t* obs_prev,
+                                  int32_t* obs_next);
 // the table from recorded transitions (ended: nullptr, or gw_transition_stats_ep's rows; ct_rollout_stats.hip)
 int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
                                const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
@@ -424,7 +432,9 @@ enum {
     GW_LS_ROLLOUT_SYNC_EPS = GW_LS_ROLLOUT_POP_EPS + 3 * GW_LS_NDT,      // ct_rollout_sync_eps<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_BACKLOG = GW_LS_ROLLOUT_SYNC_EPS + 3 * GW_LS_NDT,      // ct_rollout_backlog<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_BACKLOG_POP = GW_LS_ROLLOUT_BACKLOG + 3 * GW_LS_NDT,   // ct_rollout_backlog_pop<DT, MODE>: 3 per DT
-    GW_LS_COUNT = GW_LS_ROLLOUT_BACKLOG_POP + 3 * GW_LS_NDT
+    GW_LS_ROLLOUT_FSC = GW_LS_ROLLOUT_BACKLOG_POP + 3 * GW_LS_NDT,       // ct_rollout_fsc<DT, MODE>: 3 per DT
+    GW_LS_ROLLOUT_FSC_POP = GW_LS_ROLLOUT_FSC + 3 * GW_LS_NDT,           // ct_rollout_fsc_pop<DT, MODE>: 3 per DT
+    GW_LS_COUNT = GW_LS_ROLLOUT_FSC_POP + 3 * GW_LS_NDT
 };
 constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {

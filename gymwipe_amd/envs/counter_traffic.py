@@ -208,6 +208,7 @@ class VecCounterTrafficEnv(BaseEnv):
         self._stats_buf = None                            # 64-step transition buffers (both allocated on first use)
         self._ep_state = self._ep_tally = self._ep_next = None   # rollout_episodes: {age, ret}[N], the episode tally, the
         self._ep_buf = None                               # observations acted on next; the fallback's ended rows (first use)
+        self._ctl_node = None                             # rollout_controller: each env's node (first use)
         self._custom = interpreter
         if interpreter is not None:                       # a user-supplied Interpreter replaces the fused one
             if explicit_queue:
@@ -283,6 +284,11 @@ class VecCounterTrafficEnv(BaseEnv):
                 self._ep_state.zero_()
             else:
                 self._ep_state.masked_fill_(m.bool().unsqueeze(1), 0)
+        if self._ctl_node is not None:                    # rollout_controller's nodes: a reset env starts at node 0
+            if m is None:
+                self._ctl_node.zero_()
+            else:
+                self._ctl_node.masked_fill_(m.bool(), 0)
         self._last = (obs,) + tuple(self._last[1:])       # the observation the agent acts on next (rollout_policy)
         return obs
 
@@ -918,6 +924,111 @@ class VecCounterTrafficEnv(BaseEnv):
             nat.check(self._L.gw_rollout_backlog_population(self._h, K, C.byref(pop), C.byref(ep),
                                                             C.byref(sc) if sc is not None else None, self._ep_next.data_ptr(),
                                                             self._stream()))
+        if K:
+            self._last = (self._ep_next,) + tuple(self._last[1:])
+        return tally
+
+    # -- finite-state controllers inside the scored closed loop (gw_rollout_controller) -----------------
+    @property
+    def controller_node(self):
+        """uint8[N] on the GPU: the node each env's controller is at, as ``rollout_controller`` /
+        ``rollout_controller_population`` read it before a call and leave it after; ``reset()`` zeroes the envs it resets.
+        The caller may write it."""
+        if self._ctl_node is None:
+            self._ctl_node = _torch().zeros(self.num_envs, dtype=_torch().uint8, device=self.device)
+        return self._ctl_node
+
+    def _controller(self, controller, population=False):
+        """A controller's three arrays as tensors on this env's GPU: ``(cdf int32 words [S][3][A], next uint8[S][3][2], need
+        uint8[S])``, each with a leading ``[P]`` for a population.  Shapes and dtypes are checked, contents are not (the native
+        calls clamp where they read).  Tensors that already lie on the device are used in place."""
+        torch = _torch()
+        from ..actions import FSC_MAX_STATES
+        A = self.num_devices * int(self.config.max_duration)
+        if len(controller) != 3:
+            raise ValueError("a controller is (cdf, next, need)")
+
+        def put(a, np_dtype, torch_dtype):
+            if isinstance(a, torch.Tensor):
+                if a.dtype is not torch_dtype:
+                    raise ValueError("a controller tensor must be %s, got %s" % (torch_dtype, a.dtype))
+                return a.to(self.device).contiguous()
+            a = np.asarray(a)
+            if a.dtype != np_dtype:
+                raise ValueError("a controller array must be %s, got %s" % (np.dtype(np_dtype), a.dtype))
+            a = np.array(a, order="C")                    # (a copy: the array may be read-only)
+            return torch.from_numpy(a.view(np.int32) if np_dtype is np.uint32 else a).to(self.device)
+        cdf, nxt, need = put(controller[0], np.uint32, torch.int32), put(controller[1], np.uint8, torch.uint8), \
+            put(controller[2], np.uint8, torch.uint8)
+        lead = cdf.dim() - 3
+        if lead != (1 if population else 0) or tuple(cdf.shape[-2:]) != (3, A) or not 1 <= cdf.shape[-3] <= FSC_MAX_STATES:
+            raise ValueError("controller cdf must have shape (%sS, 3, %d) with 1 <= S <= %d, got %s"
+                             % ("P, " if population else "", A, FSC_MAX_STATES, tuple(cdf.shape)))
+        head = tuple(cdf.shape[:-2])
+        if tuple(nxt.shape) != head + (3, 2) or tuple(need.shape) != head:
+            raise ValueError("controller next / need must have shapes %s / %s, got %s / %s"
+                             % (head + (3, 2), head, tuple(nxt.shape), tuple(need.shape)))
+        return cdf, nxt, need
+
+    def rollout_controller(self, controller, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, out=None,
+                           score=None):
+        """``rollout_episodes(score=)`` under a finite-state controller (gw_rollout_controller): ``controller`` is
+        ``actions.make_controller``'s ``(cdf, next, need)``; env ``e`` at node ``n`` draws from row ``cdf[n][cls(obs)]``, and
+        behind every step moves to ``next[n][cls(new obs)][delivered >= need[n]]`` -- to node 0 where the step ended an
+        episode (``actions.controller_step_numpy`` / ``controller_move_numpy`` restate both, with the clamps that make any
+        content memory-safe).  The nodes live in ``controller_node`` and continue across calls, as ``episode_state`` does;
+        advance ``step0`` by ``steps``.  Returns the scored ``rollout_episodes`` tuple plus ``node`` uint8[steps][N], the node
+        each step was taken at (``out``: eight tensors).  ``score``: ``actions.make_score``; ``None`` is the neutral score.  With
+        one node the call is ``rollout_episodes(score=)`` bit for bit.  One launch per 64 steps; a handle without the fused
+        rollout, or a controller that does not fit the block's LDS, is refused (``NativeError``, ``EUNSUPPORTED``) before
+        anything runs: there is no per-step form.  Not for hipGraph capture (``step0`` would be baked in)."""
+        torch = _torch()
+        from ..actions import make_score
+        ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_controller")
+        K = int(steps)
+        cdf, nxt, need = self._controller(controller)
+        kinds = (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8, torch.uint8, torch.int32, torch.uint8)
+        out = self._rows(K, kinds, out)
+        if K:
+            prev = self._apart(prev, out)
+        sc = self._score(score if score is not None else make_score(self.num_devices))
+        ctl = nat.Controller(int(cdf.shape[0]), cdf.data_ptr(), nxt.data_ptr(), need.data_ptr(), self.controller_node.data_ptr())
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_rollout_controller(self._h, K, C.byref(ctl), *self._stream_id(seed, step0, env_id0), C.byref(ep),
+                                                    C.byref(sc), prev.data_ptr(), self._ep_next.data_ptr(),
+                                                    *[t.data_ptr() for t in out], self._stream()))
+        if K:
+            self._last = (self._ep_next, out[3][-1], out[4][-1])
+        return out
+
+    def rollout_controller_population(self, controllers, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None,
+                                      tally=None, score=None):
+        """``rollout_controller`` for P controllers of one size at once, for a caller that ranks them
+        (gw_rollout_controller_population): ``controllers`` is ``actions.make_controller_population``'s ``(cdf [P][S][3][A],
+        next [P][S][3][2], need [P][S])`` -- tensors on the env's device are read in place -- P divides ``num_envs``, and env
+        ``e`` runs controller ``e // (num_envs // P)`` (``env_id0`` shifts the stream, not the controller index).  Nothing
+        ``[steps][N]`` is stored.  Returns the ``int64[P][5]`` tally as ``rollout_population(score=)`` does: a new one of
+        zeros, or the caller's ``tally``, ADDED into.  ``num_envs // P`` must be a multiple of 64; there is no per-step form."""
+        torch = _torch()
+        from ..actions import EP_COLS, make_score
+        ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_controller_population")
+        K, n = int(steps), self.num_envs
+        cdf, nxt, need = self._controller(controllers, population=True)
+        P = int(cdf.shape[0])
+        if P < 1 or n % P:
+            raise ValueError("rollout_controller_population: %d controllers do not divide %d envs" % (P, n))
+        if tally is None:
+            tally = torch.zeros((P, EP_COLS), dtype=torch.int64, device=self.device)
+        elif not (type(tally) is torch.Tensor and tally.dtype is torch.int64 and tally.device == self.device
+                  and tuple(tally.shape) == (P, EP_COLS) and tally.is_contiguous()):
+            raise ValueError("tally must be a contiguous int64 tensor of shape (%d, %d) on %s" % (P, EP_COLS, self.device))
+        sc = self._score(score if score is not None else make_score(self.num_devices))
+        pop = nat.ControllerPopulation(P, n // P, int(cdf.shape[1]), cdf.data_ptr(), nxt.data_ptr(), need.data_ptr(),
+                                       self.controller_node.data_ptr(), tally.data_ptr())
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_rollout_controller_population(self._h, K, C.byref(pop), *self._stream_id(seed, step0, env_id0),
+                                                               C.byref(ep), C.byref(sc), prev.data_ptr(), self._ep_next.data_ptr(),
+                                                               self._stream()))
         if K:
             self._last = (self._ep_next,) + tuple(self._last[1:])
         return tally

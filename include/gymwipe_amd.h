@@ -494,6 +494,68 @@ typedef struct gw_backlog_population {
 int gw_rollout_backlog_population(gw_env* env, int32_t steps, const gw_backlog_population* pop, const gw_episodes* ep,
                                   const gw_score* score, int32_t* obs_next_dev, void* stream);
 
+/* ---- finite-state controllers inside the scored closed loop ----
+ * A policy table over the observation class cannot remember what it did.  A controller has S nodes, 1 <= S <=
+ * GW_FSC_MAX_STATES: the env's node and the observation class pick the row the action is drawn from, and the node then moves
+ * on the new observation class and on one bit -- whether the step delivered at least the node's threshold of packets.  Both
+ * are things a real RRM knows.  Three arrays in DEVICE memory, never validated and never read back on the host:
+ *   cdf  uint32[S][3][A]   for each (node, class) a row as gw_rollout_policy takes it, A = num_devices * max_duration
+ *   next uint8[S][3][2]    the node to move to, by (node, new class, bit)
+ *   need uint8[S]          each node's delivered-packet threshold
+ * and each env's node in the caller's node_dev uint8[N], read at the start of a call and written at its end as {age, ret} is
+ * (the caller's array, not handle state: snapshots do not hold it).  For env e:
+ *   at the start of a call   n = min(node_dev[e], S - 1), c = cls(obs_prev_dev[e])
+ *   step k's action          gw_rollout_policy's draw from row cdf[n][c] with u(seed, env_id0 + e, step0 + k)
+ *   the step runs            delivered_k, score_k and the episode's book exactly as in gw_rollout_episodes_scored
+ *   behind EVERY step        the step ended an episode: n = 0, c = 1 (the reset's observation); otherwise c = cls(obs_k),
+ *                            b = (delivered_k >= need[n]), n = min(next[n][c][b], S - 1) -- need[n] and next[n] of the node
+ *                            the step was taken at
+ *   at the end of a call     node_dev[e] = n, obs_next_dev[e] as in the parents
+ * The clamps apply where the bytes are read, so any content is memory-safe and has one meaning
+ * (actions.controller_step_numpy restates it).  A call split at any step gives the rows of one call; with S == 1 the call is
+ * gw_rollout_episodes_scored bit for bit. */
+#define GW_FSC_MAX_STATES 16
+typedef struct gw_controller {
+    int32_t num_states;                       /* S */
+    const uint32_t* cdf_dev;                  /* uint32[S][3][A] */
+    const uint8_t* next_dev;                  /* uint8[S][3][2] */
+    const uint8_t* need_dev;                  /* uint8[S] */
+    uint8_t* node_dev;                        /* uint8[N], in/out */
+} gw_controller;
+typedef struct gw_controller_population {
+    int32_t num_policies;                     /* P >= 1 */
+    int32_t envs_per_policy;                  /* M >= 1, P * M == num_envs; env e runs controller e / M */
+    int32_t num_states;                       /* one S for all */
+    const uint32_t* cdf_dev;                  /* uint32[P][S][3][A] */
+    const uint8_t* next_dev;                  /* uint8[P][S][3][2] */
+    const uint8_t* need_dev;                  /* uint8[P][S] */
+    uint8_t* node_dev;                        /* uint8[N], in/out */
+    int64_t* tally_dev;                       /* int64[P][GW_EP_COLS], ADDED into, never NULL */
+} gw_controller_population;
+
+/* gw_rollout_controller: gw_rollout_episodes_scored's outputs, and node_out_dev uint8[steps][N], the node each step was taken
+ * at.  gw_rollout_controller_population: gw_rollout_population_scored's tallies -- env e runs controller e / M, env_id0 shifts
+ * the stream and not the controller index; pop->tally_dev[p] receives the episodes of controller p's envs and ep->tally_dev,
+ * where not NULL, the column sums.
+ * ONE launch per 64 steps (ct_rollout_fsc / ct_rollout_fsc_pop in ct_rollout_fsc.hip); the controller's tables lie in the
+ * block's LDS.  There is no per-step form.  GW_EUNSUPPORTED, before any launch and with the state and node_dev untouched: a
+ * handle without a fused rollout for gw_rollout_episodes (explicit queues, live PHY, a handle created under
+ * GW_ROLLOUT_EVENT_LOOP, rollout capacity 0); GW_ROLLOUT_POLICY_UNFUSED set; envs_per_policy not a multiple of 64 (the
+ * population call); a controller whose (3 S A + num_devices) words and 7 S bytes do not fit the 65 536 bytes of a block's LDS
+ * beside the kernel's own tables.
+ * GW_EINVAL before any HIP call: env / ctl / pop / ep / score NULL; any array of the controller, node_dev and node_out_dev
+ * included, any output, ep->state_dev, obs_prev_dev or obs_next_dev NULL; steps < 0; max_steps < 0; S outside
+ * [1, GW_FSC_MAX_STATES]; a score weight outside its bounds; P < 1 or M < 1 (all of these also when steps == 0);
+ * P * M != num_envs.  steps == 0 with valid arguments is GW_OK.  Stream-ordered.  Not for hipGraph capture: step0 would be
+ * baked into the recording. */
+int gw_rollout_controller(gw_env* env, int32_t steps, const gw_controller* ctl, uint64_t seed, uint64_t step0, uint64_t env_id0,
+                          const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                          int32_t* device_out_dev, int32_t* duration_out_dev, int32_t* obs_dev, float* reward_dev,
+                          uint8_t* done_dev, uint8_t* ended_dev, int32_t* delivered_dev, uint8_t* node_out_dev, void* stream);
+int gw_rollout_controller_population(gw_env* env, int32_t steps, const gw_controller_population* pop, uint64_t seed, uint64_t step0,
+                                     uint64_t env_id0, const gw_episodes* ep, const gw_score* score, const int32_t* obs_prev_dev,
+                                     int32_t* obs_next_dev, void* stream);
+
 /* gw_transition_stats for rows recorded by gw_rollout_episodes: step k's observation seen is counter_bound where
  * ended_dev[k - 1] != 0; row 0 uses obs_prev_dev as it is. */
 int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev,
