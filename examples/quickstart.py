@@ -111,6 +111,17 @@ rec = loop.get_state("received")
 print("control loop: angle %.3f deg, %d samples reached the controller, %d commands the actuator, motor velocity %.3f"
       % (float(linfo["Sensor angle"][0]), int(rec[0, 0]), int(rec[0, 1]), float(loop.get_state("u")[0])))
 
+# 5c. start over, every env from an angle of its own, and compare four cyclic band schedules in one launch
+from gymwipe_amd import actions
+zero = torch.zeros(4096, dtype=torch.float64)
+angles = torch.linspace(-0.3, 0.3, 1024, dtype=torch.float64).repeat(4)           # the same 1 024 angles for every schedule
+loop.set_initial_state(torch.stack([zero, zero, angles, zero], 1))
+loop.reset_envs()
+scheds = actions.make_ctrl_schedules([[(0, 0)], [(0, 19)], [(0, 5), (1, 5)], [(0, 19), (1, 19)]])
+tally, sums = loop.rollout_schedules(scheds, episodes=(40, 0.0), steps=40)      # env e follows schedule e // 1024
+print("control loop: mean sum of |angle| over a 40-step episode, nobody assigned / sensor only / alternating 5 / alternating 19:",
+      [round(v, 1) for v in (sums[:, 3] / sums[:, 0]).tolist()])
+
 # 6. the reference's PHY-grid benchmark (tests/test_benchmark.py), 1 024 replicas of a 16-device grid
 import numpy as np
 grid = gymwipe_amd.VecPhyGrid(1024, 16, np.random.default_rng(0).uniform(0, 1e-2, (1024, 16)))

@@ -33,6 +33,7 @@ EXPORTS = (
     "gw_plant_config_default", "gw_plant_create", "gw_plant_destroy", "gw_plant_update", "gw_plant_set_input",
     "gw_plant_state_ptr", "gw_plant_get_state", "gw_plant_feedback", "gw_plant_update_feedback", "gw_now_ptr", "gw_pendulum_step",
     "gw_ctrl_config_default", "gw_ctrl_create", "gw_ctrl_destroy", "gw_ctrl_step", "gw_ctrl_get_state",
+    "gw_ctrl_set_initial", "gw_ctrl_reset", "gw_ctrl_rollout", "gw_ctrl_rollout_schedules",
     "gw_grid_config_default", "gw_grid_create", "gw_grid_destroy", "gw_grid_run", "gw_grid_get_state", "gw_grid_set_position",
 )
 
@@ -73,6 +74,12 @@ class CtrlConfig(C.Structure):
         ("A", C.c_double * 16), ("B", C.c_double * 4), ("x0", C.c_double * 4), ("u0", C.c_double),
         ("ctrl_start_tick", C.c_int32), ("ctrl_period_ticks", C.c_int32),
     ]
+
+
+class CtrlEpisodes(C.Structure):
+    """gw_ctrl_episodes (include/gymwipe_amd.h): an episode of the control loop ends at ``max_steps`` steps (0: no limit) or when
+    |angle in degrees| exceeds ``fail_deg`` (<= 0: no limit)."""
+    _fields_ = [("max_steps", C.c_int32), ("pad", C.c_int32), ("fail_deg", C.c_double)]
 
 
 class PlantConfig(C.Structure):
@@ -308,6 +315,12 @@ def lib():
     L.gw_ctrl_destroy.argtypes, L.gw_ctrl_destroy.restype = [vp], C.c_int
     L.gw_ctrl_step.argtypes, L.gw_ctrl_step.restype = [vp, vp, vp, vp, vp, vp, vp], C.c_int
     L.gw_ctrl_get_state.argtypes, L.gw_ctrl_get_state.restype = [vp, C.c_char_p, vp, C.c_size_t], C.c_int
+    L.gw_ctrl_set_initial.argtypes, L.gw_ctrl_set_initial.restype = [vp, vp, vp, vp, vp], C.c_int
+    L.gw_ctrl_reset.argtypes, L.gw_ctrl_reset.restype = [vp, vp, vp, vp], C.c_int
+    L.gw_ctrl_rollout.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(CtrlEpisodes), vp, vp, vp, vp, vp]
+    L.gw_ctrl_rollout.restype = C.c_int
+    L.gw_ctrl_rollout_schedules.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.POINTER(CtrlEpisodes), vp, vp]
+    L.gw_ctrl_rollout_schedules.restype = C.c_int
     L.gw_plant_update_feedback.argtypes, L.gw_plant_update_feedback.restype = [vp, vp, C.c_int64, vp, vp, vp, vp], C.c_int
     L.gw_now_ptr.argtypes, L.gw_now_ptr.restype = [vp, C.POINTER(vp), C.POINTER(i64)], C.c_int
     L.gw_pendulum_step.argtypes, L.gw_pendulum_step.restype = [vp, vp, vp, vp, vp, vp, vp, vp], C.c_int

@@ -461,3 +461,36 @@ def make_controller_population(controllers):
     if len({r[0].shape for r in rows}) != 1:
         raise ValueError("make_controller_population: every controller needs the same S and A")
     return tuple(np.stack([r[i] for r in rows]) for i in range(3))
+
+
+# ---- control loop: cyclic band schedules (gw_ctrl_rollout_schedules) --------------------------------------------------------------------
+CTRL_SCHEDULE_MAX = 64          # entries of one schedule
+CTRL_TALLY_COLS = 4             # episodes ended, of those by fail_deg, steps taken, sum of the costs of the ended episodes
+
+
+def make_ctrl_schedules(schedules, L=None):
+    """``uint8[P][L][2]`` = (device, duration) from a list of lists of ``(device, duration)`` pairs: what
+    ``VecControlLoopEnv.rollout_schedules`` uploads.  ``L`` defaults to the longest list; a shorter schedule is padded
+    cyclically (entry j is its entry ``j % len``), which changes what it does only if ``L`` is no multiple of its length."""
+    rows = [[(int(d), int(u)) for d, u in s] for s in schedules]
+    if not rows or any(not r for r in rows):
+        raise ValueError("make_ctrl_schedules: at least one schedule, each with at least one entry")
+    L = max(len(r) for r in rows) if L is None else int(L)
+    if not 1 <= L <= CTRL_SCHEDULE_MAX or any(len(r) > L for r in rows):
+        raise ValueError("make_ctrl_schedules: 1 <= L <= %d, no schedule longer than L" % CTRL_SCHEDULE_MAX)
+    if any(not (0 <= v <= 255) for r in rows for pair in r for v in pair):
+        raise ValueError("make_ctrl_schedules: device and duration are bytes")
+    return np.array([[r[j % len(r)] for j in range(L)] for r in rows], np.uint8).reshape(len(rows), L, 2)
+
+
+def ctrl_schedule_numpy(schedules, age, envs_per_schedule, max_duration=20):
+    """The action env e takes at episode age ``age[e]`` under ``schedules`` (uint8[P][L][2]): entry ``age % L`` of schedule
+    ``e // envs_per_schedule``, clamped where it is read -- device to {0, 1}, duration to [0, max_duration - 1].  Returns
+    ``(device, duration)`` as int32[N]."""
+    sch = np.asarray(schedules)
+    if sch.dtype != np.uint8 or sch.ndim != 3 or sch.shape[2] != 2:
+        raise ValueError("ctrl_schedule_numpy: schedules is uint8[P][L][2]")
+    age = np.asarray(age, np.int64)
+    p = np.arange(age.shape[0]) // int(envs_per_schedule)
+    row = sch[p, age % sch.shape[1]].astype(np.int32)
+    return np.minimum(row[:, 0], 1).astype(np.int32), np.minimum(row[:, 1], int(max_duration) - 1).astype(np.int32)

@@ -1,0 +1,56 @@
+// ctrl_common.hip.h -- what the control-loop kernels share: ctrl_step_kernel (ctrl_step.hip: one step per launch) and the fused
+// kernels of ctrl_rollout.hip (K steps per launch).  A lane's state, its two queues during a step, and the staging of a step's
+// appends.  The step itself is text: ctrl_step_body.h.
+#pragma once
+#include "ct_common.hip.h"
+
+namespace gwk {
+
+constexpr int CR = 4, CRRM = 3;                             // radios (3 network devices + RRM), index of the RRM
+
+struct Lane {                                               // everything indexed by a run-time device id goes through
+    double now, wake, x[4], u, ang;                         // selects below: a dynamically indexed member array would
+    uint32_t ktick, got1, got2, ntx, ncmd, nsub, fl;        // send the whole struct to scratch memory
+    uint32_t rxs[CR];
+};
+
+__device__ __forceinline__ uint32_t pick(const uint32_t (&a)[CR], int i)
+{
+    return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3]));
+}
+
+// Queue handling of one step.  The values a step appends (the sensor's sample of every tick: up to 22; the controller's
+// command every `period` ticks) are staged in LDS, one column per lane, and written to the rings once, at the end of the
+// step; the first PRE entries at the addressed queue's head are loaded before the walk.  A pop therefore never waits for
+// memory inside the window loop (round 1: one dependent 8-byte load per transmission, one scattered 8-byte store per tick).
+//   queue = the last `len` values of its append stream; this step's appends are the last `app` of it:
+//   the head is a value of this step iff len <= app (then it is append number app - len).
+constexpr int NEW0 = 24, NEW1 = 24, PRE = 8;
+
+struct Q {                                                 // one queue during a step (scalars only: no dynamic indexing)
+    uint32_t head, len, app, head0, tail0;
+};
+
+__device__ __forceinline__ void q_push(Q& q, double* s_col, double v)      // deque(maxlen=100): drop the oldest when full
+{
+    if (q.len == GW_QUEUE_CAP) { q.head = (q.head + 1u) & GW_RING_MASK; q.len--; }
+    s_col[q.app << 6] = v;                                 // column of this lane: element j at [j * 64]
+    q.app++;
+    q.len++;
+}
+
+// a step's opening: nothing appended yet, and where the queue stood
+__device__ __forceinline__ void q_open(Q& q)
+{
+    q.app = 0u;
+    q.head0 = q.head;
+    q.tail0 = (q.head + q.len) & GW_RING_MASK;
+}
+
+// this step's appends -> the ring: value j of the queue sits in slot (tail0 + j) & mask
+__device__ __forceinline__ void q_flush(const Q& q, double* ring, const double* col)
+{
+    for (uint32_t j = 0; j < q.app; ++j) ring[(q.tail0 + j) & GW_RING_MASK] = col[j << 6];
+}
+
+} // namespace gwk

@@ -1,0 +1,229 @@
+// ctrl_rollout.hip -- the closed control loop beyond one step per launch: per-env initial states and reset (small kernels), and
+// K steps fused into one launch, with optional episodes (gw_ctrl_rollout) or with P cyclic schedules read from LDS and only a
+// per-env tally written (gw_ctrl_rollout_schedules).  BUILDER-DEFINED as the whole control loop is; the specification is the
+// event-driven ControlLoopModel of the test infrastructure, a reset env being a freshly constructed model of its own x0 / u0.
+// The step is ctrl_step_kernel's, from the same text (ctrl_step_body.h).  What fusion changes around it: the link tables go to
+// LDS once per launch, the env's state stays in registers across the K steps and is loaded and stored once; a step's appends
+// are still staged in the lane's LDS columns and flushed to its rings at the end of each step, and the head prefetch stays
+// per step -- a lane only ever reads ring slots it wrote itself, in program order (or the zeros gw_ctrl_create left there).
+#include "ctrl_common.hip.h"
+
+using namespace gwk;
+
+namespace {
+
+constexpr int S = GW_MAX_NSTATES;
+constexpr int SCHED_MAX = 64;                                // entries of a schedule (gw_ctrl_rollout_schedules: 1 <= L <= 64)
+
+// The loop of both fused kernels, one lane per env.  SCHED: the action is entry `age % Ls` of the block's schedule in LDS
+// (clamped into the action space where it is read) and nothing is stored per step; else it is row k of the caller's [K][N]
+// arrays, step k + 1's loaded while step k is walked, and the step's outputs are stores nothing waits for.
+// (A __forceinline__ template, not a kernel: the kernels below are plain functions.)
+template <bool SCHED>
+__device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCtrlEpi& s, const int steps, const bool episodes,
+                                                  const uint32_t max_steps, const double fail_deg, const uint8_t* s_trans,
+                                                  const double* s_ber, double* col0, double* col1, const int64_t e,
+                                                  const int32_t* __restrict__ device, const int32_t* __restrict__ duration,
+                                                  int32_t* __restrict__ obs, float* __restrict__ reward,
+                                                  double* __restrict__ angle_deg, uint8_t* __restrict__ ended,
+                                                  const uint8_t* s_sched, const uint32_t Ls, double* __restrict__ tally)
+{
+    const GwDevConst k = *(const GW_AS_CONST GwDevConst*)c.cst;
+    Lane L;
+    L.now = c.now[e]; L.wake = c.wake[e]; L.u = c.u[e]; L.ang = c.ang[e]; L.ktick = c.ktick[e];
+    for (int i = 0; i < 4; ++i) L.x[i] = c.x[e * 4 + i];
+    Q q0, q1;
+    { const uint32_t hl = c.qhl[e]; q0.head = hl & 0xffu; q0.len = hl >> 8; }
+    { const uint32_t hl = c.qhl[c.N + e]; q1.head = hl & 0xffu; q1.len = hl >> 8; }
+#pragma unroll
+    for (int j = 0; j < CR; ++j) L.rxs[j] = c.rxs[j * c.N + e];
+    L.got1 = c.got[e * 2]; L.got2 = c.got[e * 2 + 1];
+    L.ntx = c.ntx[e]; L.ncmd = c.ncmd[e]; L.nsub = c.nsub[e]; L.fl = c.flags[e];
+    double* ring0 = c.pay + ((size_t)e * 2 + 0) * GW_RING_PHYS;
+    double* ring1 = c.pay + ((size_t)e * 2 + 1) * GW_RING_PHYS;
+    uint32_t age = 0u;
+    double cost = 0.0;
+    if (episodes) { age = s.age[e]; cost = s.cost[e]; }
+    const double deg_per_rad = 180.0 / 3.141592653589793;
+
+    uint32_t at_sched = 0u, n_ended = 0u, n_failed = 0u;    // SCHED: the entry the env acts on next, and its tally
+    double cost_ended = 0.0;
+    int d_next = 0, du_next = 0;
+    if (SCHED) at_sched = age % Ls;
+    else if (steps > 0) { d_next = device[e]; du_next = duration[e]; }
+
+    for (int step = 0; step < steps; ++step) {
+        const int64_t at = (int64_t)step * c.N + e;
+        int d_now, du_now;
+        if (SCHED) {                                          // a byte outside the action space is clamped where it is read
+            d_now = (int)gw_min_u32((uint32_t)s_sched[at_sched * 2u], 1u);
+            du_now = (int)gw_min_u32((uint32_t)s_sched[at_sched * 2u + 1u], (uint32_t)k.max_duration - 1u);
+        } else {
+            d_now = d_next; du_now = du_next;
+            if (step + 1 < steps) { d_next = device[at + c.N]; du_next = duration[at + c.N]; }
+        }
+        const int d = d_now, du = du_now;
+        q_open(q0);
+        q_open(q1);
+#include "ctrl_step_body.h"
+        const double deg = L.x[2] * deg_per_rad;             // InvertedPendulumInterpreter, envs/inverted_pendulum.py:27-57
+        if (!SCHED) {
+            obs[at] = (int32_t)deg;
+            reward[at] = (float)fabs(180.0 - deg);
+            if (angle_deg) angle_deg[at] = deg;
+        }
+        q_flush(q0, ring0, col0);
+        q_flush(q1, ring1, col1);
+        if (episodes) {                                       // the episode rule: the step's own outputs stand, then the env is reset
+            age++;
+            cost = cost + fabs(deg);
+            const uint32_t cause = ((max_steps > 0u && age == max_steps) ? 1u : 0u) | ((fail_deg > 0.0 && fabs(deg) > fail_deg) ? 2u : 0u);
+            if (!SCHED) ended[at] = (uint8_t)cause;
+            at_sched = at_sched + 1u == Ls ? 0u : at_sched + 1u;
+            if (cause) {                                      // gw_ctrl_reset for this one env, in registers; flags are sticky
+                n_ended++;
+                n_failed += cause >> 1;
+                cost_ended = cost_ended + cost;
+                L.now = 0.0; L.wake = 0.0; L.ang = 0.0; L.ktick = 0u;
+                for (int i = 0; i < 4; ++i) L.x[i] = s.x_init[e * 4 + i];
+                L.u = s.u_init[e];
+                q0.head = q0.len = 0u; q1.head = q1.len = 0u;
+#pragma unroll
+                for (int j = 0; j < CR; ++j) L.rxs[j] = 0u;
+                L.got1 = L.got2 = 0u;
+                L.ntx = L.ncmd = L.nsub = 0u;
+                age = 0u; cost = 0.0; at_sched = 0u;
+            }
+        }
+    }
+
+    c.now[e] = L.now; c.wake[e] = L.wake; c.u[e] = L.u; c.ang[e] = L.ang; c.ktick[e] = L.ktick;
+    for (int i = 0; i < 4; ++i) c.x[e * 4 + i] = L.x[i];
+    c.qhl[e] = (uint16_t)(q0.head | (q0.len << 8));
+    c.qhl[c.N + e] = (uint16_t)(q1.head | (q1.len << 8));
+#pragma unroll
+    for (int j = 0; j < CR; ++j) c.rxs[j * c.N + e] = (uint8_t)L.rxs[j];
+    c.got[e * 2] = L.got1; c.got[e * 2 + 1] = L.got2;
+    c.ntx[e] = L.ntx; c.ncmd[e] = L.ncmd; c.nsub[e] = L.nsub; c.flags[e] = L.fl;
+    if (episodes) { s.age[e] = age; s.cost[e] = cost; }
+    if (SCHED) {
+        tally[e * 4 + 0] = (double)n_ended; tally[e * 4 + 1] = (double)n_failed;
+        tally[e * 4 + 2] = (double)steps;   tally[e * 4 + 3] = cost_ended;
+    }
+}
+
+__global__ __launch_bounds__(64) void ctrl_rollout_kernel(GwCtrlDev c, GwCtrlEpi s, int steps, int episodes, uint32_t max_steps,
+                                                          double fail_deg, const int32_t* __restrict__ device,
+                                                          const int32_t* __restrict__ duration, int32_t* __restrict__ obs,
+                                                          float* __restrict__ reward, double* __restrict__ angle_deg,
+                                                          uint8_t* __restrict__ ended)
+{
+    __shared__ double s_new0[NEW0 * 64], s_new1[NEW1 * 64];
+    __shared__ uint8_t s_trans[CR * CR * S];
+    __shared__ double s_ber[CR * CR * S];
+    for (int i = threadIdx.x; i < CR * CR * S; i += blockDim.x) { s_trans[i] = c.trans[i]; s_ber[i] = c.ber[i]; }
+    __syncthreads();
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= c.N) return;
+    ctrl_rollout_lane<false>(c, s, steps, episodes != 0, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
+                             s_new1 + (threadIdx.x & 63), e, device, duration, obs, reward, angle_deg, ended, nullptr, 1u, nullptr);
+}
+
+// every 64-env block follows one schedule (the host refuses N / P that is no multiple of 64): its 2 Ls bytes in LDS
+__global__ __launch_bounds__(64) void ctrl_rollout_sched_kernel(GwCtrlDev c, GwCtrlEpi s, int steps, uint32_t max_steps, double fail_deg,
+                                                                const uint8_t* __restrict__ sched, uint32_t envs_per_schedule,
+                                                                uint32_t Ls, double* __restrict__ tally)
+{
+    __shared__ double s_new0[NEW0 * 64], s_new1[NEW1 * 64];
+    __shared__ uint8_t s_trans[CR * CR * S];
+    __shared__ double s_ber[CR * CR * S];
+    __shared__ uint8_t s_sched[SCHED_MAX * 2];
+    for (int i = threadIdx.x; i < CR * CR * S; i += blockDim.x) { s_trans[i] = c.trans[i]; s_ber[i] = c.ber[i]; }
+    const uint32_t p = (uint32_t)(((int64_t)blockIdx.x * 64) / envs_per_schedule);
+    for (uint32_t i = threadIdx.x; i < 2u * Ls && i < (uint32_t)SCHED_MAX * 2u; i += blockDim.x) s_sched[i] = sched[(size_t)p * 2u * Ls + i];
+    __syncthreads();
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= c.N) return;
+    ctrl_rollout_lane<true>(c, s, steps, true, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
+                            s_new1 + (threadIdx.x & 63), e, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s_sched, Ls, tally);
+}
+
+// x_init / u_init of every env <- one state (gw_ctrl_create); the episode record starts at 0
+__global__ void ctrl_fill_initial_kernel(int64_t N, GwCtrlEpi s, double x0, double x1, double x2, double x3, double u0)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    s.x_init[e * 4 + 0] = x0; s.x_init[e * 4 + 1] = x1; s.x_init[e * 4 + 2] = x2; s.x_init[e * 4 + 3] = x3;
+    s.u_init[e] = u0;
+    s.age[e] = 0u; s.cost[e] = 0.0;
+}
+
+__global__ void ctrl_set_initial_kernel(int64_t N, GwCtrlEpi s, const double* __restrict__ x0, const double* __restrict__ u0,
+                                        const uint8_t* __restrict__ mask)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N || (mask && !mask[e])) return;
+    for (int i = 0; i < 4; ++i) s.x_init[e * 4 + i] = x0[e * 4 + i];
+    if (u0) s.u_init[e] = u0[e];
+}
+
+// the masked envs -> exactly what ctrl_init_kernel leaves, with the env's own initial state; flags stay (sticky)
+__global__ void ctrl_reset_kernel(GwCtrlDev c, GwCtrlEpi s, const uint8_t* __restrict__ mask, int32_t* __restrict__ obs)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= c.N) return;
+    double angle = c.x[e * 4 + 2];
+    if (!mask || mask[e]) {
+        c.now[e] = 0.0; c.wake[e] = 0.0; c.u[e] = s.u_init[e]; c.ang[e] = 0.0; c.ktick[e] = 0u;
+        for (int i = 0; i < 4; ++i) c.x[e * 4 + i] = s.x_init[e * 4 + i];
+        angle = s.x_init[e * 4 + 2];
+        c.qhl[e] = 0; c.qhl[c.N + e] = 0;
+        for (int j = 0; j < CR; ++j) c.rxs[j * c.N + e] = 0;
+        c.got[e * 2] = 0u; c.got[e * 2 + 1] = 0u;
+        c.ntx[e] = 0u; c.ncmd[e] = 0u; c.nsub[e] = 0u;
+        s.age[e] = 0u; s.cost[e] = 0.0;
+    }
+    if (obs) obs[e] = (int32_t)(angle * (180.0 / 3.141592653589793));
+}
+
+inline int launched() { return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP; }
+
+} // namespace
+
+int gw_ctrl_launch_fill_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, double u0, void* stream)
+{
+    hipLaunchKernelGGL(ctrl_fill_initial_kernel, dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c.N, s, x0[0],
+                       x0[1], x0[2], x0[3], u0);
+    return launched();
+}
+
+int gw_ctrl_launch_set_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, const double* u0, const uint8_t* mask,
+                               void* stream)
+{
+    hipLaunchKernelGGL(ctrl_set_initial_kernel, dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c.N, s, x0, u0,
+                       mask);
+    return launched();
+}
+
+int gw_ctrl_launch_reset(const GwCtrlDev& c, const GwCtrlEpi& s, const uint8_t* mask, int32_t* obs, void* stream)
+{
+    hipLaunchKernelGGL(ctrl_reset_kernel, dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c, s, mask, obs);
+    return launched();
+}
+
+int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const int32_t* device, const int32_t* duration,
+                           const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg, uint8_t* ended, void* stream)
+{
+    hipLaunchKernelGGL(ctrl_rollout_kernel, dim3((unsigned)((c.N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, c, s, (int)steps,
+                       ep ? 1 : 0, ep ? (uint32_t)ep->max_steps : 0u, ep ? ep->fail_deg : 0.0, device, duration, obs, reward, angle_deg,
+                       ended);
+    return launched();
+}
+
+int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const uint8_t* sched, int32_t P, int32_t L,
+                                     const gw_ctrl_episodes& ep, double* tally, void* stream)
+{
+    hipLaunchKernelGGL(ctrl_rollout_sched_kernel, dim3((unsigned)(c.N / 64)), dim3(64), 0, (hipStream_t)stream, c, s, (int)steps,
+                       (uint32_t)ep.max_steps, ep.fail_deg, sched, (uint32_t)(c.N / P), (uint32_t)L, tally);
+    return launched();
+}

@@ -1,0 +1,126 @@
+// ctrl_step_body.h -- one env.step() of the closed control loop for one lane: the body of ctrl_step_kernel (ctrl_step.hip, where
+// the rules and their sources are stated), moved here word for word so that the fused kernels of ctrl_rollout.hip run the same
+// step.  Text included inside a kernel, not a function, as ct_rollout_sync_body.h is and for its reason: as a __forceinline__
+// function ctrl_step_kernel came out with other registers (accum_offset 164 -> 168); included, it is instruction for instruction
+// what it was.
+// The including kernel provides, in scope: c (GwCtrlDev), k (GwDevConst), S (= GW_MAX_NSTATES), s_trans / s_ber (the link tables
+// in LDS, [CR][CR][S]), L (Lane), q0 / q1 (Q, opened: q_open), col0 / col1 (the lane's LDS columns), ring0 / ring1 (its rings),
+// deg_per_rad, and the step's action `const int d, du`.  The text defines no name outside its own braces.
+    if ((unsigned)d >= 2u || (unsigned)du >= (unsigned)k.max_duration) {
+        L.fl |= GW_FLAG_BADACT;                              // envs/inverted_pendulum.py:102 asserts; flagged and skipped here
+    } else {
+        const StepMath m(k);
+        const double slot = k.slot, br = k.bit_rate, hd = k.hdr_dur, hdr_bits = k.hdr_bits, interval = k.counter_interval;
+        const int mh = k.mac_hdr;
+        double* ringd = d == 0 ? ring0 : ring1;
+        // the first PRE values at the head of the addressed queue, issued now: they land during the announcement
+        double pre[PRE];
+        {
+            const uint32_t h0 = d == 0 ? q0.head : q1.head;
+#pragma unroll
+            for (int i = 0; i < PRE; ++i) pre[i] = ringd[(h0 + (uint32_t)i) & GW_RING_MASK];
+        }
+        // the control tick test `(tick - start) % period == 0` as a running phase: one modulo per step, not per tick
+        uint32_t phase = L.ktick >= c.start ? (L.ktick - c.start) % c.period : 0u;
+
+        // one counter tick: the sensor's process was created first, so it runs first at every tick time
+        auto tick_all = [&]() __attribute__((always_inline)) {
+            q_push(q0, col0, L.x[2]);                                           // sensor: sample, queue, ...
+            double nx[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {                                      // ... then the plant advances one substep
+                double acc = c.A[i * 4 + 0] * L.x[0];
+                acc = acc + c.A[i * 4 + 1] * L.x[1];
+                acc = acc + c.A[i * 4 + 2] * L.x[2];
+                acc = acc + c.A[i * 4 + 3] * L.x[3];
+                nx[i] = acc + c.B[i] * L.u;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) L.x[i] = nx[i];
+            L.nsub++;
+            const uint32_t kk = L.ktick;                                        // controller
+            if (kk >= c.start) {
+                if (phase == 0u && L.ang != 0.0) {
+                    q_push(q1, col1, -L.ang);
+                    L.ncmd++;
+                }
+                phase = phase + 1u == c.period ? 0u : phase + 1u;
+            }
+            L.ktick = kk + 1u;
+            L.wake = L.wake + interval;                                         // running sum, as everywhere
+        };
+        auto ticks_until = [&](double t, bool inclusive) __attribute__((always_inline)) {
+            while (inclusive ? (L.wake <= t) : (L.wake < t)) {
+                if (L.wake == t) L.fl |= GW_FLAG_TIE;
+                tick_all();
+            }
+        };
+        // every radio but `from` hears a transmission: its noise state moves (simple_stack.py:130-157)
+        auto all_hear = [&](int from) {
+#pragma unroll
+            for (int j = 0; j < CR; ++j)
+                if (j != from) L.rxs[j] = s_trans[(j * CR + from) * S + L.rxs[j]];  // j is a compile-time index here
+        };
+
+        const double t_a = L.now;
+        const int slots = du * k.duration_factor;
+        const int Ld = ndigits(slots);
+        const TxTimes an = tx_times(m, t_a, hd, m.over_rate((double)(Ld * 8)));
+        L.ntx++;
+        all_hear(CRRM);
+        const bool granted = receive(m, s_ber[(d * CR + CRRM) * S + pick(L.rxs, d)], an, br, hdr_bits,
+                                     (double)(Ld * 8) * k.coded_factor, L.fl);
+        const double t_r = an.t_e;
+        const double t_end = t_r + (double)(slots + 1) * slot;
+        if (granted) {
+            const double stopw = t_r + (double)slots * slot;
+            double cur = t_r;
+            ticks_until(cur, false);                                            // the MAC's initialisation is URGENT: it goes first
+            const int dst = d + 1;                                              // sensor -> controller, controller -> actuator
+            const uint32_t sz = (uint32_t)(k.mac_hdr + k.net_hdr) + (d == 0 ? 2u : 1u);
+            const double need = m.over_rate((double)(sz * 8u));
+            const double pd = m.over_rate((double)(((int)sz - mh) * 8));
+            for (;;) {
+                bool closed = false;
+                while ((d == 0 ? q0.len : q1.len) == 0u) {                      // wait for packet-added or the window timeout
+                    if (L.wake < stopw) { cur = L.wake; tick_all(); }
+                    else { closed = true; break; }
+                }
+                if (closed) break;
+                if (!((stopw - cur) > need)) break;
+                // the head value (a tick may have dropped older entries meanwhile: head/len say where the head is now)
+                Q& qd = d == 0 ? q0 : q1;
+                double v;
+                if (qd.len <= qd.app) {                                         // appended in this step: from the LDS column
+                    v = (d == 0 ? col0 : col1)[(qd.app - qd.len) << 6];
+                } else {
+                    const uint32_t i = (qd.head - qd.head0) & GW_RING_MASK;     // how many older entries have gone already
+                    if (i < (uint32_t)PRE) {
+                        v = pre[0];
+#pragma unroll
+                        for (int j = 1; j < PRE; ++j) v = (i == (uint32_t)j) ? pre[j] : v;
+                    } else {
+                        v = ringd[qd.head];
+                    }
+                }
+                qd.head = (qd.head + 1u) & GW_RING_MASK;
+                qd.len--;
+                const TxTimes x = tx_times(m, cur, hd, pd);
+                L.ntx++;
+                all_hear(d);
+                const bool ok = receive(m, s_ber[(dst * CR + d) * S + pick(L.rxs, dst)], x, br, hdr_bits,
+                                        (double)(((int)sz - mh) * 8) * k.coded_factor, L.fl);
+                if (!(x.t_e < t_end)) L.fl |= GW_FLAG_CARRY;
+                ticks_until(x.t_e, false);                                      // ticks during the transmission
+                if (ok) {                                                       // ... then the delivery at t_e ...
+                    if (d == 0) { L.ang = v * deg_per_rad; L.got1++; }          // degrees(value), control/inverted_pendulum.py:41
+                    else { L.u = v; L.got2++; }
+                }
+                ticks_until(x.t_e, true);                                       // ... then a tick falling exactly on it
+                cur = x.t_e;
+                if (!(cur < stopw)) break;
+            }
+        }
+        ticks_until(t_end, true);
+        L.now = t_end;
+    }

@@ -15,6 +15,7 @@ struct gw_ctrl {
     gw_ctrl_config cfg;
     GwHostTables tab;
     GwCtrlDev dev;
+    GwCtrlEpi epi;                     // per-env initial state and episode record (not part of the step kernel's argument)
     void* blocks[24];
     int nblocks;
 };
@@ -125,13 +126,17 @@ int gw_ctrl_create(const gw_ctrl_config* cfg, gw_ctrl** out)
     CA(d.ktick, N); CA(d.got, N * 2); CA(d.ntx, N); CA(d.ncmd, N); CA(d.nsub, N); CA(d.flags, N);
     CA(d.qhl, N * 2); CA(d.rxs, N * R); CA(d.pay, N * 2 * GW_RING_PHYS);
     CA(d_cst, 1); CA(d_trans, tcount); CA(d_ber, tcount);
+    CA(c->epi.x_init, N * 4); CA(c->epi.u_init, N); CA(c->epi.cost, N); CA(c->epi.age, N);
 #undef CA
     d.cst = d_cst; d.trans = d_trans; d.ber = d_ber;
     CTRL_HIP(hipMemcpy(d_cst, &k, sizeof k, hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemcpy(d_trans, c->tab.trans, tcount, hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemcpy(d_ber, c->tab.ber, tcount * sizeof(double), hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemset(d.pay, 0, (size_t)N * 2 * GW_RING_PHYS * sizeof(double)), gw_ctrl_destroy(c));
-    if (gw_ctrl_launch_init(d, cfg->x0, cfg->u0, nullptr)) { gw_ctrl_destroy(c); return gw_set_error(GW_EHIP, "control-loop init launch failed"); }
+    if (gw_ctrl_launch_init(d, cfg->x0, cfg->u0, nullptr) || gw_ctrl_launch_fill_initial(d, c->epi, cfg->x0, cfg->u0, nullptr)) {
+        gw_ctrl_destroy(c);
+        return gw_set_error(GW_EHIP, "control-loop init launch failed");
+    }
     CTRL_HIP(hipDeviceSynchronize(), gw_ctrl_destroy(c));
     *out = c;
     return GW_OK;
@@ -145,6 +150,60 @@ int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
     if (gw_ctrl_launch_step(c->dev, device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop step launch failed");
+    return GW_OK;
+}
+
+int gw_ctrl_set_initial(gw_ctrl* c, const double* x0_dev, const double* u0_dev, const uint8_t* mask_dev, void* stream)
+{
+    if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
+    if (!x0_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_set_initial: x0_dev is NULL");
+    CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
+    if (gw_ctrl_launch_set_initial(c->dev, c->epi, x0_dev, u0_dev, mask_dev, stream))
+        return gw_set_error(GW_EHIP, "control-loop set_initial launch failed");
+    return GW_OK;
+}
+
+int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* stream)
+{
+    if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
+    CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
+    if (gw_ctrl_launch_reset(c->dev, c->epi, mask_dev, obs_dev, stream))
+        return gw_set_error(GW_EHIP, "control-loop reset launch failed");
+    return GW_OK;
+}
+
+int gw_ctrl_rollout(gw_ctrl* c, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev, const gw_ctrl_episodes* ep,
+                    int32_t* obs_dev, float* reward_dev, double* angle_deg_dev, uint8_t* ended_dev, void* stream)
+{
+    if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
+    if (!device_dev || !duration_dev || !obs_dev || !reward_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout: NULL device pointer");
+    if (ep && !ended_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout: ended_dev is NULL (required with episodes)");
+    if (ep && ep->max_steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout: max_steps < 0");
+    if (steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout: steps < 0");
+    if (steps == 0) return GW_OK;
+    CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
+    if (gw_ctrl_launch_rollout(c->dev, c->epi, steps, device_dev, duration_dev, ep, obs_dev, reward_dev, angle_deg_dev, ended_dev, stream))
+        return gw_set_error(GW_EHIP, "control-loop rollout launch failed");
+    return GW_OK;
+}
+
+int gw_ctrl_rollout_schedules(gw_ctrl* c, int32_t steps, const uint8_t* sched_dev, int32_t P, int32_t L, const gw_ctrl_episodes* ep,
+                              double* tally_dev, void* stream)
+{
+    if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
+    if (!sched_dev || !tally_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_schedules: NULL device pointer");
+    if (!ep) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_schedules: ep is NULL (episodes are required)");
+    if (ep->max_steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_schedules: max_steps < 0");
+    if (steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_schedules: steps < 0");
+    if (P < 1) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_schedules: P must be >= 1");
+    if (L < 1 || L > 64) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_schedules: L must be in [1, 64]");
+    if (steps == 0) return GW_OK;
+    const int64_t N = c->dev.N;
+    if (N % P != 0 || (N / P) % 64 != 0)
+        return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_schedules: num_envs / P must be a whole multiple of 64 (one schedule per block)");
+    CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
+    if (gw_ctrl_launch_rollout_schedules(c->dev, c->epi, steps, sched_dev, P, L, *ep, tally_dev, stream))
+        return gw_set_error(GW_EHIP, "control-loop schedule rollout launch failed");
     return GW_OK;
 }
 
@@ -166,6 +225,10 @@ int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst, size_t bytes)
     else if (!strcmp(field, "commands")) { src = d.ncmd; need = N * sizeof(uint32_t); }
     else if (!strcmp(field, "substeps")) { src = d.nsub; need = N * sizeof(uint32_t); }
     else if (!strcmp(field, "flags")) { src = d.flags; need = N * sizeof(uint32_t); }
+    else if (!strcmp(field, "age")) { src = c->epi.age; need = N * sizeof(uint32_t); }
+    else if (!strcmp(field, "cost")) { src = c->epi.cost; need = N * sizeof(double); }
+    else if (!strcmp(field, "x_init")) { src = c->epi.x_init; need = N * 4 * sizeof(double); }
+    else if (!strcmp(field, "u_init")) { src = c->epi.u_init; need = N * sizeof(double); }
     if (src) {
         if (bytes != need) return gw_set_error(GW_EFIELD, "field %s needs %zu bytes, got %zu", field, need, bytes);
         CTRL_HIP(hipMemcpy(dst, src, need, hipMemcpyDeviceToHost), (void)0);

@@ -254,6 +254,20 @@ struct GwCtrlDev {
 int gw_ctrl_launch_step(const GwCtrlDev& c, const int32_t* device, const int32_t* duration, int32_t* obs, float* reward,
                         double* angle_deg, void* stream);
 int gw_ctrl_launch_init(const GwCtrlDev& c, const double* x0, double u0, void* stream);
+// Per-env initial state and episode record (ctrl_rollout.hip).  A struct of its own: GwCtrlDev is ctrl_step_kernel's by-value
+// argument, and a field added there would change that kernel's code.
+struct GwCtrlEpi {
+    double *x_init, *u_init, *cost;            // [N][4], [N], [N]
+    uint32_t* age;                             // [N]
+};
+int gw_ctrl_launch_fill_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, double u0, void* stream);
+int gw_ctrl_launch_set_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, const double* u0, const uint8_t* mask,
+                               void* stream);
+int gw_ctrl_launch_reset(const GwCtrlDev& c, const GwCtrlEpi& s, const uint8_t* mask, int32_t* obs, void* stream);
+int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const int32_t* device, const int32_t* duration,
+                           const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg, uint8_t* ended, void* stream);
+int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const uint8_t* sched, int32_t P, int32_t L,
+                                     const gw_ctrl_episodes& ep, double* tally, void* stream);
 int gw_fill_dev_const(const gw_config& cfg, const GwHostTables& tab, GwDevConst& k);   // gw_api.cpp
 int gw_validate_config(const gw_config& cfg);                                           // gw_api.cpp
 

@@ -142,7 +142,10 @@ class VecControlLoopEnv(BaseEnv):
     but never runs.  Builder-defined where the reference leaves it open -- see ``gw_ctrl_config`` in
     include/gymwipe_amd.h for the rules -- and checked bit for bit against an event-driven model of those rules.
     Same gym surface as ``VecInvertedPendulumEnv``: ``step({"device": int32[N] in {0 sensor, 1 controller},
-    "duration": int32[N]}) -> (obs, reward, done, {"Sensor angle": deg})``."""
+    "duration": int32[N]}) -> (obs, reward, done, {"Sensor angle": deg})``.
+    Beyond one step per launch: ``set_initial_state`` / ``reset_envs`` (an initial state per env; a masked reset that leaves a
+    fresh env), ``rollout`` (K steps in one launch, optionally with episodes that end at a time limit or a failure angle and
+    reset inside the launch) and ``rollout_schedules`` (P cyclic band schedules, a per-env tally, nothing stored per step)."""
     SENSOR, CONTROLLER, ACTUATOR = 0, 1, 2
 
     def __init__(self, num_envs, device="cuda:0", ctrl_start_tick=None, ctrl_period_ticks=None, positions=None, x0=None,
@@ -207,9 +210,105 @@ class VecControlLoopEnv(BaseEnv):
                                            self._angle.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
         return self._obs, self._rew, self._done, {"Sensor angle": self._angle}
 
+    # -- per-env initial states, reset, and K steps in one launch (gw_ctrl_set_initial / _reset / _rollout / _rollout_schedules) --
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    def _mask(self, mask):
+        """``mask`` as uint8[N] on the env's GPU (None: every env); returns the tensor, to be kept alive across the call."""
+        torch = self._torch
+        if mask is None:
+            return None
+        m = torch.as_tensor(mask).to(device=self.device)
+        m = (m != 0).to(torch.uint8).contiguous()
+        assert m.shape == (self.num_envs,)
+        return m
+
+    def set_initial_state(self, x0, u0=None, mask=None):
+        """Give the masked envs (None: all) initial states of their own: ``x0`` f64[N][4] (a single state of 4 is broadcast),
+        ``u0`` f64[N] or a number (None: keep).  Takes effect at the env's next reset -- ``reset_envs`` or the end of an
+        episode inside ``rollout`` / ``rollout_schedules``; the running state is not touched."""
+        torch = self._torch
+        x = torch.as_tensor(x0, dtype=torch.float64).to(self.device)
+        x = x.expand(self.num_envs, 4).contiguous() if x.dim() == 1 else x.contiguous()
+        assert x.shape == (self.num_envs, 4)
+        u = None
+        if u0 is not None:
+            u = torch.as_tensor(u0, dtype=torch.float64).to(self.device)
+            u = u.expand(self.num_envs).contiguous()
+        m = self._mask(mask)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_ctrl_set_initial(self._h, x.data_ptr(), u.data_ptr() if u is not None else None,
+                                                  m.data_ptr() if m is not None else None, self._stream()))
+
+    def reset_envs(self, mask=None):
+        """Put the masked envs (None: all) back into the state a fresh env of their own initial state has -- clock, queues,
+        noise states, counters and the episode record (``age``, ``cost``) 0; ``flags`` are sticky and stay -- and return the
+        observations of all N envs.  (``reset()`` keeps the reference's meaning: it resets nothing.)"""
+        torch = self._torch
+        m = self._mask(mask)
+        self._stepped = True                               # the observation buffer now holds what the GPU wrote
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_ctrl_reset(self._h, m.data_ptr() if m is not None else None, self._obs.data_ptr(), self._stream()))
+        return self._obs
+
+    @staticmethod
+    def _episodes(episodes):
+        """``episodes``: None or the pair ``(max_steps, fail_deg)``, 0 = no limit."""
+        if episodes is None:
+            return None
+        max_steps, fail_deg = episodes
+        return nat.CtrlEpisodes(int(max_steps), 0, float(fail_deg))
+
+    def rollout(self, device, duration, episodes=None, out=None):
+        """K consecutive steps from pre-staged actions ``int32[K][N]`` in ONE launch, the env's state in registers in between.
+        Without ``episodes`` the results equal K calls of ``step`` bit for bit and the third tensor is ``done`` (all False).
+        With ``episodes`` (``(max_steps, fail_deg)``, 0 = no limit): after each step ``age += 1``, ``cost += |angle|``; an env
+        whose age reaches ``max_steps`` (bit 0) or whose |angle| exceeds ``fail_deg`` (bit 1) has ended, the third tensor
+        holds those bits, and the env is reset inside the launch as ``reset_envs`` would.  ``out``: ``(obs int32, reward
+        float32, ended uint8, angle float64)``, each [K][N] on the env's GPU, written in place.
+        Returns ``(obs, reward, done_or_ended, {"Sensor angle": angle})``."""
+        torch = self._torch
+        dev = torch.as_tensor(device).to(device=self.device, dtype=torch.int32).contiguous()
+        dur = torch.as_tensor(duration).to(device=self.device, dtype=torch.int32).contiguous()
+        K, n = dev.shape[0], self.num_envs
+        assert dev.shape == (K, n) and dur.shape == dev.shape
+        ep = self._episodes(episodes)
+        if out is None:
+            out = (torch.empty((K, n), dtype=torch.int32, device=self.device), torch.empty((K, n), dtype=torch.float32, device=self.device),
+                   torch.zeros((K, n), dtype=torch.uint8, device=self.device), torch.empty((K, n), dtype=torch.float64, device=self.device))
+        obs, rew, ended, ang = out
+        for t, dt in zip(out, (torch.int32, torch.float32, torch.uint8, torch.float64)):
+            assert t.shape == (K, n) and t.dtype == dt and t.is_contiguous() and t.device == dev.device
+        if ep is None:
+            ended.zero_()
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_ctrl_rollout(self._h, K, dev.data_ptr(), dur.data_ptr(), C.byref(ep) if ep is not None else None,
+                                              obs.data_ptr(), rew.data_ptr(), ang.data_ptr(), ended.data_ptr(), self._stream()))
+        return obs, rew, ended, {"Sensor angle": ang}
+
+    def rollout_schedules(self, schedules, episodes, steps):
+        """Evaluate P cyclic schedules (``actions.make_ctrl_schedules``: uint8[P][L][2]) for ``steps`` steps in one launch, env e
+        under schedule ``e // (N / P)``, acting on entry ``age % L``; nothing is stored per step.  Returns ``(tally f64[N][4],
+        sums f64[P][4])``: per env {episodes ended, of those by fail_deg, steps taken, sum of the costs of the ended
+        episodes}, and their sums per schedule."""
+        torch = self._torch
+        sch = torch.as_tensor(schedules)
+        if sch.dtype != torch.uint8 or sch.dim() != 3 or sch.shape[2] != 2:
+            raise ValueError("schedules must be uint8[P][L][2] (actions.make_ctrl_schedules)")
+        sch = sch.to(self.device).contiguous()
+        P, L = int(sch.shape[0]), int(sch.shape[1])
+        ep = self._episodes(episodes)
+        tally = torch.zeros((self.num_envs, 4), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_ctrl_rollout_schedules(self._h, int(steps), sch.data_ptr(), P, L,
+                                                        C.byref(ep) if ep is not None else None, tally.data_ptr(), self._stream()))
+        return tally, tally.view(P, self.num_envs // P, 4).sum(1)
+
     _FIELDS = {"now": ((), "f8"), "wake": ((), "f8"), "u": ((), "f8"), "angle_deg": ((), "f8"), "x": ((4,), "f8"),
                "rx_power": ((4,), "f8"), "qlen": ((2,), "i4"), "received": ((2,), "u4"), "n_tx": ((), "u4"),
-               "commands": ((), "u4"), "substeps": ((), "u4"), "flags": ((), "u4")}
+               "commands": ((), "u4"), "substeps": ((), "u4"), "flags": ((), "u4"),
+               "age": ((), "u4"), "cost": ((), "f8"), "x_init": ((4,), "f8"), "u_init": ((), "f8")}
 
     def get_state(self, field):
         import numpy as np

@@ -741,8 +741,47 @@ int gw_ctrl_destroy(gw_ctrl* c);
 int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_dev, int32_t* obs_dev, float* reward_dev,
                  double* angle_deg_dev, void* stream);
 /* host copies: "now","wake","u","angle_deg" f64[N] | "x" f64[N][4] | "rx_power" f64[N][4] | "qlen" int32[N][2] |
- *              "received" u32[N][2] (controller, actuator) | "n_tx","commands","substeps","flags" u32[N] */
+ *              "received" u32[N][2] (controller, actuator) | "n_tx","commands","substeps","flags" u32[N] |
+ *              "age" u32[N], "cost" f64[N] (the running episode's record) | "x_init" f64[N][4], "u_init" f64[N] */
 int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst_host, size_t bytes);
+
+/* Per-env initial state and reset.  Every env keeps an initial state of its own (x_init, u_init; cfg.x0 / cfg.u0 at create) and
+ * the record of its running episode: age (steps taken) and cost (sum of |angle in degrees| the steps reported), both 0 at create.
+ * gw_ctrl_set_initial stores x0_dev f64[N][4] (and u0_dev f64[N] unless NULL) for the envs with mask_dev[e] != 0 (NULL: all);
+ * it changes no env's running state.  gw_ctrl_reset puts the masked envs into exactly the state gw_ctrl_create leaves, with the
+ * env's own initial state: clock, wake and tick 0, controller angle 0, both queues empty (head = len = 0), noise states 0,
+ * received, n_tx, commands, substeps, age and cost 0.  flags are sticky and stay.  Envs outside the mask are untouched, bit
+ * for bit.  obs_dev (NULL ok) receives (int32) degrees(x[2]) of all N envs. */
+int gw_ctrl_set_initial(gw_ctrl* c, const double* x0_dev, const double* u0_dev, const uint8_t* mask_dev, void* stream);
+int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* stream);
+
+typedef struct gw_ctrl_episodes {
+    int32_t max_steps;                      /* an episode ends when its age reaches this; 0: no limit */
+    int32_t pad;
+    double  fail_deg;                       /* ... or when |angle in degrees| exceeds this; <= 0: no limit */
+} gw_ctrl_episodes;
+
+/* K = steps calls of gw_ctrl_step in one launch: step k reads device_dev / duration_dev [k][N] and writes obs_dev, reward_dev,
+ * angle_deg_dev (NULL ok) [k][N].  ep == NULL: outputs and every state field equal `steps` calls of gw_ctrl_step bit for bit
+ * (an action outside the action space is flagged and skipped as there; age and cost do not move).  With ep: after each step
+ * age += 1 and cost += fabs(deg) (deg: the f64 angle the step reports; one running f64 sum per env in step order); the env has
+ * ended if fail_deg > 0 && fabs(deg) > fail_deg (bit 1 of ended_dev[k][e]) or max_steps > 0 && age == max_steps (bit 0); the
+ * step's own outputs are written, then the env is reset inside the launch exactly as gw_ctrl_reset resets it (a flagged and
+ * skipped step reports the unchanged angle and counts like any other).  age and cost
+ * live in the handle: two calls of K/2 steps equal one call of K.  ended_dev is required iff ep.  steps == 0: GW_OK, no launch;
+ * steps < 0, a NULL pointer, ep->max_steps < 0: GW_EINVAL before any device call. */
+int gw_ctrl_rollout(gw_ctrl* c, int32_t steps, const int32_t* device_dev, const int32_t* duration_dev, const gw_ctrl_episodes* ep,
+                    int32_t* obs_dev, float* reward_dev, double* angle_deg_dev, uint8_t* ended_dev, void* stream);
+
+/* P cyclic schedules evaluated in one launch, nothing stored per step.  sched_dev: u8[P][L][2] = {device, duration}; env e follows
+ * schedule e / (N / P) and acts on its entry age % L (a reset restarts the schedule).  A byte outside the action space is clamped
+ * where it is read: device to {0, 1}, duration to [0, max_duration - 1].  Episodes as in gw_ctrl_rollout (ep is required).
+ * tally_dev f64[N][4] is overwritten per env: {episodes ended, of those by fail_deg, steps taken, sum of the costs of the ended
+ * episodes} -- per env, not per schedule: deterministic, no f64 atomics; the [P] reduction is the caller's.
+ * 1 <= L <= 64, P >= 1 (else GW_EINVAL); N % P == 0 and (N / P) % 64 == 0 (else GW_EUNSUPPORTED): every 64-env block then
+ * follows one schedule.  Refusals come before any launch. */
+int gw_ctrl_rollout_schedules(gw_ctrl* c, int32_t steps, const uint8_t* sched_dev, int32_t P, int32_t L, const gw_ctrl_episodes* ep,
+                              double* tally_dev, void* stream);
 
 /* Host-only self-test hook (no GPU needed): fuzzes the MAC-queue encoding the default kernel uses
  * against an explicit deque(maxlen=100).  Returns the number of mismatches (0 = identical). */

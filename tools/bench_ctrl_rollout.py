@@ -1,0 +1,200 @@
+#!/usr/bin/env python3
+"""
+The control loop's fused rollout beside what it replaces (profiles/ctrl_rollout/README.md).
+
+VecControlLoopEnv, N envs, calls of K = 64 steps, every env with an initial angle of its own.  Seven legs in ONE process,
+alternated call by call so that clock and thermal drift hit all alike, each leg on a handle of its own:
+  a   K x env.step                                      the only form there was; ctrl_step_kernel is unchanged
+  b   env.rollout, no episodes                          the same actions in one launch
+  c   env.rollout with episodes                         max_steps / fail_deg, ended rows written
+  cs  per step: env.step, the rule in torch,            what c replaces: the bookkeeping on the device, one host read per step
+      env.reset_envs(mask)                              (does any env end?) as a caller would write it
+  cn  the same without the host read                    reset_envs(mask) issued every step, no synchronise
+  d   env.reset_envs + env.rollout_schedules            P schedules, no [K][N] array at all, a per-env tally
+  dc  env.reset_envs + env.rollout with episodes        fed d's schedules expanded to [K][N] actions along every env's own ages
+                                                        (found once, before the timing, by a per-step composition): the same
+                                                        trajectory, which is why both legs restart their envs in every call
+A timed unit is one call of K steps between two HIP events and two wall-clock reads, the second after a synchronise; units are
+repeated until every leg has at least `--seconds` of stream time and at least `--min-repeats` units.  Before the timing, b's
+outputs are checked against a's, c's `ended` against cs's and d's tally against dc's `ended`, each pair from one state.
+Reported per leg: median, min and max of the wall-clock and event microseconds per step; the ratios of the wall-clock medians;
+and the run-to-run spread of leg a ((max - min) / median), against which b/a is to be read.  One JSON line; --out appends it to
+a file.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=32768)
+    ap.add_argument("--steps", type=int, default=64, help="K: steps per call")
+    ap.add_argument("--schedules", type=int, default=64, help="P of legs d and dc")
+    ap.add_argument("--length", type=int, default=8, help="L of the schedules")
+    ap.add_argument("--max-steps", type=int, default=25)
+    ap.add_argument("--fail-deg", type=float, default=90.0)
+    ap.add_argument("--seconds", type=float, default=0.25, help="stream time per leg at least")
+    ap.add_argument("--min-repeats", type=int, default=5)
+    ap.add_argument("--legs", default="a,b,c,cs,cn,d,dc")
+    ap.add_argument("--label", default="")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+
+    import torch
+    from gymwipe_amd import VecControlLoopEnv, actions
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_ctrl_rollout needs a GPU: a timing taken anywhere else says nothing")
+    N, K, P, L = args.envs, args.steps, args.schedules, args.length
+    dev = torch.device("cuda:0")
+    episodes = (args.max_steps, args.fail_deg)
+    rng = np.random.default_rng(0)
+    a_dev = torch.from_numpy(rng.integers(0, 2, (K, N)).astype(np.int32)).to(dev)
+    a_dur = torch.from_numpy(rng.integers(0, 20, (K, N)).astype(np.int32)).to(dev)
+    x0 = np.zeros((N, 4))
+    x0[:, 2] = rng.uniform(-1.5, 1.5, N)                                # an initial angle of its own for every env
+    x0[:, 3] = rng.uniform(-1.0, 1.0, N)
+    sched_np = actions.make_ctrl_schedules([list(zip(rng.integers(0, 2, L).tolist(), rng.integers(0, 20, L).tolist()))
+                                            for _ in range(P)], L)
+    sched = torch.from_numpy(sched_np).to(dev)
+    p_of = torch.arange(N, device=dev) // (N // P)
+    x_dev = torch.empty((K, N), dtype=torch.int32, device=dev)         # d's schedules expanded: filled in below
+    x_dur = torch.empty((K, N), dtype=torch.int32, device=dev)
+
+    def new_env():
+        env = VecControlLoopEnv(N, device=dev)
+        env.set_initial_state(torch.from_numpy(x0))
+        env.reset_envs()
+        return env
+
+    names = [x for x in args.legs.split(",") if x]
+    envs = {n: new_env() for n in names}
+    out = (torch.empty((K, N), dtype=torch.int32, device=dev), torch.empty((K, N), dtype=torch.float32, device=dev),
+           torch.empty((K, N), dtype=torch.uint8, device=dev), torch.empty((K, N), dtype=torch.float64, device=dev))
+    age = {n: torch.zeros(N, dtype=torch.int32, device=dev) for n in ("cs", "cn")}
+    cost = {n: torch.zeros(N, dtype=torch.float64, device=dev) for n in ("cs", "cn")}
+    ended_rows = torch.empty((K, N), dtype=torch.uint8, device=dev)
+
+    def leg_a(env):
+        for k in range(K):
+            env.step({"device": a_dev[k], "duration": a_dur[k]})
+
+    def leg_b(env):
+        env.rollout(a_dev, a_dur, out=out)
+
+    def leg_c(env):
+        env.rollout(a_dev, a_dur, episodes=episodes, out=out)
+
+    def composed(n, read):
+        def leg(env):
+            ag, co = age[n], cost[n]
+            for k in range(K):
+                _, _, _, info = env.step({"device": a_dev[k], "duration": a_dur[k]})
+                mag = info["Sensor angle"].abs()
+                ag += 1
+                co += mag
+                cause = (ag == args.max_steps).to(torch.uint8) | ((mag > args.fail_deg).to(torch.uint8) << 1)
+                ended_rows[k] = cause
+                if not read or bool(cause.any()):
+                    env.reset_envs(cause)
+                    gone = cause != 0
+                    ag.masked_fill_(gone, 0)
+                    co.masked_fill_(gone, 0.0)
+        return leg
+
+    tally = {}
+
+    def leg_d(env):
+        env.reset_envs()
+        tally["d"] = env.rollout_schedules(sched, episodes, K)[0]
+
+    def leg_dc(env):
+        env.reset_envs()
+        env.rollout(x_dev, x_dur, episodes=episodes, out=out)
+
+    def expand_schedules():
+        """x_dev / x_dur <- the action every env takes at each of K steps from a reset, under its schedule and the episode rule."""
+        env = new_env()
+        ag = torch.zeros(N, dtype=torch.int64, device=dev)
+        for k in range(K):
+            row = sched[p_of, ag % L].to(torch.int32)
+            x_dev[k], x_dur[k] = row[:, 0].clamp(max=1), row[:, 1].clamp(max=19)
+            _, _, _, info = env.step({"device": x_dev[k], "duration": x_dur[k]})
+            mag = info["Sensor angle"].abs()
+            ag += 1
+            gone = (ag == args.max_steps) | (mag > args.fail_deg)
+            env.reset_envs(gone)
+            ag.masked_fill_(gone, 0)
+        env.close()
+
+    legs = {"a": leg_a, "b": leg_b, "c": leg_c, "cs": composed("cs", True), "cn": composed("cn", False), "d": leg_d, "dc": leg_dc}
+
+    # the legs mean what they say: from one state b gives a's last rows, and c ends the envs its composition ends
+    if "a" in names and "b" in names:
+        leg_a(envs["a"])
+        leg_b(envs["b"])
+        assert torch.equal(envs["a"]._obs, out[0][-1]) and torch.equal(envs["a"]._angle, out[3][-1]), "rollout differs from K steps"
+    if "c" in names and "cs" in names:
+        leg_c(envs["c"])
+        want = out[2].clone()
+        legs["cs"](envs["cs"])
+        assert torch.equal(want, ended_rows) and bool(want.any()), "the composition ends other envs than the fused call"
+    if "dc" in names:
+        expand_schedules()
+    if "d" in names and "dc" in names:
+        leg_d(envs["d"])
+        leg_dc(envs["dc"])
+        ends = (out[2] != 0).sum(0).to(torch.float64)
+        assert torch.equal(tally["d"][:, 0], ends) and bool(ends.any()), "the expanded actions end other envs than the schedules"
+    for n in names:                                                     # warm-up: first launches, allocator, caches
+        legs[n](envs[n])
+    torch.cuda.synchronize(dev)
+    wall = {n: [] for n in names}
+    event = {n: [] for n in names}
+    total = {n: 0.0 for n in names}
+    while min(total.values()) < args.seconds or min(len(v) for v in wall.values()) < args.min_repeats:
+        for n in names:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            e0.record()
+            legs[n](envs[n])
+            e1.record()
+            torch.cuda.synchronize(dev)
+            t1 = time.perf_counter()
+            ms = e0.elapsed_time(e1)
+            wall[n].append((t1 - t0) / K * 1e6)
+            event[n].append(ms * 1e3 / K)
+            total[n] += ms * 1e-3
+
+    def summary(xs):
+        return {"median": round(float(np.median(xs)), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
+
+    res = {"label": args.label, "gpu": torch.cuda.get_device_name(dev), "envs": N, "steps": K, "schedules": P, "length": L,
+           "max_steps": args.max_steps, "fail_deg": args.fail_deg, "repeats": {n: len(wall[n]) for n in names}}
+    for n in names:
+        res[n] = {"wall_us_per_step": summary(wall[n]), "event_us_per_step": summary(event[n]), "stream_seconds": round(total[n], 3)}
+    med = {n: res[n]["wall_us_per_step"]["median"] for n in names}
+    res["ratios"] = {"%s/%s" % (x, y): round(med[x] / med[y], 3)
+                     for x, y in (("b", "a"), ("c", "cs"), ("c", "cn"), ("c", "b"), ("d", "dc"), ("d", "c")) if x in med and y in med}
+    if "a" in names:
+        w = res["a"]["wall_us_per_step"]
+        res["spread_a"] = round((w["max"] - w["min"]) / w["median"], 3)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    for env in envs.values():
+        env.close()
+
+
+if __name__ == "__main__":
+    main()
