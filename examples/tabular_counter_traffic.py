@@ -31,17 +31,39 @@ def main():
     ap.add_argument("--gamma", type=float, default=0.9)
     ap.add_argument("--tau", type=float, default=0.5)
     ap.add_argument("--episode-steps", type=int, default=8, help="episode length inside the launch; 0: reset() per iteration instead")
+    ap.add_argument("--score-packets", action="store_true",
+                    help="learn from the packets a step delivered (the table's eighth column), not from the built-in reward")
     args = ap.parse_args()
+    if args.score_packets and not args.episode_steps:
+        ap.error("--score-packets counts packets per episode: it needs --episode-steps > 0")
 
     import torch
-    from gymwipe_amd import VecCounterTrafficEnv
+    from gymwipe_amd import VecCounterTrafficEnv, actions
     from gymwipe_amd.agents import TabularCounterTrafficAgent
 
     env = VecCounterTrafficEnv(args.envs, num_devices=args.devices)
-    agent = TabularCounterTrafficAgent(env, gamma=args.gamma, tau=args.tau, episode_steps=args.episode_steps or None)
+    score = actions.make_score(args.devices, reward=0, delivered=1) if args.score_packets else None
+    agent = TabularCounterTrafficAgent(env, gamma=args.gamma, tau=args.tau, episode_steps=args.episode_steps or None, score=score)
+
+    def fmt(mean, err):
+        return "%+.4f" % mean if err is None else "%+.4f +- %.4f" % (mean, err)
+
+    def packets_per_episode():
+        """The current policy from a reset, in whole episodes: the eighth column's sum over the episodes that ended."""
+        env.reset()
+        env.episode_tally.zero_()
+        steps = -(-args.steps // args.episode_steps) * args.episode_steps
+        t = env.rollout_episodes_stats(agent.policy_cdf(), steps, agent.seed, max_steps=args.episode_steps, step0=agent.stream_pos,
+                                       packets=True)
+        agent.stream_pos += steps
+        return float(t[..., 7].sum().cpu()) / max(int(env.episode_tally[0].cpu()), 1)
+
+    what = "score" if args.score_packets else "reward"
+    if args.score_packets:
+        uniform = packets_per_episode()                  # (Q = 0: the Boltzmann policy is uniform)
     env.reset()
     mean, err = agent.evaluate(args.steps)
-    print("before: mean reward per step %+.4f +- %.4f" % (mean, err))
+    print("before: mean %s per step %s" % (what, fmt(mean, err)))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.iterations):
@@ -55,9 +77,11 @@ def main():
           % (args.iterations, args.steps, args.sweeps, args.iterations * args.steps * args.envs / dt / 1e9))
     env.reset()
     mean, err = agent.evaluate(args.steps)
-    print("after:  mean reward per step %+.4f +- %.4f   (pairs visited: %d of %d)"
-          % (mean, err, int((agent.table[..., 0] > 0).sum()), 3 * agent.nb_actions))
-    if args.episode_steps:
+    print("after:  mean %s per step %s   (pairs visited: %d of %d)"
+          % (what, fmt(mean, err), int((agent.table[..., 0] > 0).sum()), 3 * agent.nb_actions))
+    if args.score_packets:
+        print("packets per episode of %d steps: learned policy %.2f, uniform policy %.2f" % (args.episode_steps, packets_per_episode(), uniform))
+    elif args.episode_steps:
         print("episodes: %(episodes)d ended (%(by_done)d by done), mean length %(mean_length).2f, "
               "mean return %(mean_return)+.3f +- %(return_stderr).3f" % env.episode_stats())
     env.check()

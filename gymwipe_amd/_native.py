@@ -27,7 +27,7 @@ CFG_PER_ENV_GEOMETRY = 32
 
 EXPORTS = (
     "gw_abi_version", "gw_last_error", "gw_device_count", "gw_config_default", "gw_create",
-    "gw_destroy", "gw_reset", "gw_step", "gw_step_fb", "gw_rollout", "gw_rollout_policy", "gw_rollout_policy_stats", "gw_transition_stats", "gw_rollout_episodes", "gw_rollout_episodes_stats", "gw_transition_stats_ep", "gw_rollout_autoreset", "gw_rollout_population", "gw_rollout_episodes_scored", "gw_rollout_population_scored", "gw_rollout_autoreset_scored", "gw_rollout_backlog", "gw_rollout_backlog_population", "gw_rollout_controller", "gw_rollout_controller_population", "gw_set_position", "gw_set_positions", "gw_received", "gw_delivered", "gw_enqueue", "gw_pack_feedback", "gw_unpack_feedback", "gw_get_state",
+    "gw_destroy", "gw_reset", "gw_step", "gw_step_fb", "gw_rollout", "gw_rollout_policy", "gw_rollout_policy_stats", "gw_transition_stats", "gw_rollout_episodes", "gw_rollout_episodes_stats", "gw_transition_stats_ep", "gw_rollout_autoreset", "gw_rollout_population", "gw_rollout_episodes_scored", "gw_rollout_population_scored", "gw_rollout_autoreset_scored", "gw_rollout_backlog", "gw_rollout_backlog_population", "gw_rollout_controller", "gw_rollout_controller_population", "gw_rollout_policy_stats_delivered", "gw_rollout_episodes_stats_delivered", "gw_transition_stats_delivered", "gw_set_position", "gw_set_positions", "gw_received", "gw_delivered", "gw_enqueue", "gw_pack_feedback", "gw_unpack_feedback", "gw_get_state",
     "gw_stats_read", "gw_clear_flags", "gw_state_bytes", "gw_snapshot_bytes", "gw_get_snapshot", "gw_set_state", "gw_link_info", "gw_noise_states", "gw_selftest_queue", "gw_selftest_runq",
     "gw_selftest_fastmath", "gw_selftest_launches",
     "gw_plant_config_default", "gw_plant_create", "gw_plant_destroy", "gw_plant_update", "gw_plant_set_input",
@@ -279,6 +279,12 @@ def lib():
     L.gw_rollout_controller_population.argtypes = [vp, i32, C.POINTER(ControllerPopulation), C.c_uint64, C.c_uint64, C.c_uint64,
                                                    C.POINTER(Episodes), C.POINTER(Score), vp, vp, vp]
     L.gw_rollout_controller_population.restype = C.c_int
+    L.gw_rollout_policy_stats_delivered.argtypes = L.gw_rollout_policy_stats.argtypes
+    L.gw_rollout_policy_stats_delivered.restype = C.c_int
+    L.gw_rollout_episodes_stats_delivered.argtypes = L.gw_rollout_episodes_stats.argtypes
+    L.gw_rollout_episodes_stats_delivered.restype = C.c_int
+    L.gw_transition_stats_delivered.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gw_transition_stats_delivered.restype = C.c_int
     L.gw_received.argtypes, L.gw_received.restype = [vp, vp, vp], C.c_int
     L.gw_enqueue.argtypes, L.gw_enqueue.restype = [vp, i32, vp, vp], C.c_int
     L.gw_pack_feedback.argtypes, L.gw_pack_feedback.restype = [vp, C.c_int64, vp, vp, vp, vp, i32, vp], C.c_int

@@ -143,9 +143,12 @@ def policy_sample_population_numpy(seed, env_lo, env_hi, step, cdfs, envs_per_po
 
 # ---- the table of a closed loop (gw_rollout_policy_stats / gw_transition_stats, include/gymwipe_amd.h) -----------------------
 TS_COLS = 7                     # n, r_sum, r_sq, next below / at / above the bound, done
+TSD_COLS = 8                    # ... and the sum of min(delivered, TSD_DELIVERED_MAX): the _delivered calls' table (GW_TSD_COLS)
+TSD_DELIVERED_MAX = 65535
 
 
-def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center, max_duration, num_devices, ended=None):
+def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center, max_duration, num_devices, ended=None,
+                           delivered=None):
     """CPU restatement of both entry points' table: ``int64[3][A][TS_COLS]`` over (observation class, flat action) from
     recorded transitions ``[steps][N]``.  Step k's observation seen is ``obs_prev`` for k = 0 and row k - 1 of ``obs``
     afterwards -- or, with ``ended`` (``[steps][N]``, what ``rollout_episodes`` records: gw_transition_stats_ep), ``center``
@@ -153,14 +156,16 @@ def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center
     ``cls = sign(obs_seen - center) + 1``, ``a = device * max_duration + duration``.  Columns: transitions,
     reward sum, reward-square sum, next observation below / at / above ``center``, ``done != 0``.  A row whose action lies
     outside the action space is skipped (the env did nothing in that step); a reward is rounded to nearest (ties to even) and
-    clamped to [-10, 10], anything that is not a number counting as -10."""
+    clamped to [-10, 10], anything that is not a number counting as -10.
+    ``delivered`` (``[steps][N]`` integers, what the scored calls record: gw_transition_stats_delivered): the table is
+    ``int64[3][A][TSD_COLS]``, its eighth column the sum of the counts, each clamped to ``[0, TSD_DELIVERED_MAX]``."""
     md, D = int(max_duration), int(num_devices)
     A = D * md
     dev = np.asarray(device).astype(np.int64)
     dur = np.asarray(duration).astype(np.int64)
     nxt = np.asarray(obs).astype(np.int64)
     steps = dev.shape[0]
-    table = np.zeros((3, A, TS_COLS), np.int64)
+    table = np.zeros((3, A, TS_COLS if delivered is None else TSD_COLS), np.int64)
     if steps == 0:
         return table
     after = nxt[:-1] if ended is None else np.where(np.asarray(ended)[:-1] != 0, int(center), nxt[:-1])
@@ -174,13 +179,38 @@ def transition_stats_numpy(obs_prev, device, duration, obs, reward, done, center
     ncl = (np.sign(nxt - int(center)) + 1)[ok]
     r = r[ok]
     dn = (np.asarray(done)[ok] != 0).astype(np.int64)
-    flat = table.reshape(3 * A, TS_COLS)
+    flat = table.reshape(3 * A, table.shape[-1])
     np.add.at(flat[:, 0], row, 1)
     np.add.at(flat[:, 1], row, r)
     np.add.at(flat[:, 2], row, r * r)
     np.add.at(flat, (row, 3 + ncl), 1)
     np.add.at(flat[:, 6], row, dn)
+    if delivered is not None:
+        np.add.at(flat[:, 7], row, np.clip(np.asarray(delivered).astype(np.int64), 0, TSD_DELIVERED_MAX)[ok])
     return table
+
+
+def table_score(table, score, max_duration):
+    """The score sum of every bin of an eight-column table under ``score`` (``make_score``'s image): int64 ``[3][A]``,
+    ``score[0] * table[..., 1] + score[1 + a // max_duration] * table[..., 7]``.  A step's score is linear in its reward and in
+    the packets it delivered, and the flat action names the sender whose weight applies, so the sums of the two are all the
+    table has to carry -- whichever score is applied afterwards.  ``table``: a numpy array or a torch tensor (the result lives
+    where it does)."""
+    score = np.asarray(score)
+    if score.shape != (1 + MAX_DEVICES,):
+        raise ValueError("score must be make_score()'s int32[%d]" % (1 + MAX_DEVICES))
+    if table.ndim != 3 or table.shape[0] != 3 or table.shape[2] != TSD_COLS:
+        raise ValueError("table must be [3][A][%d], got %s" % (TSD_COLS, tuple(table.shape)))
+    A, md = int(table.shape[1]), int(max_duration)
+    if md < 1 or A % md or A // md > MAX_DEVICES:
+        raise ValueError("table_score: %d actions are not num_devices x max_duration %d" % (A, md))
+    w = score.astype(np.int64)
+    w_sender = w[1 + np.arange(A) // md]
+    if isinstance(table, np.ndarray):
+        return int(w[0]) * table[..., 1].astype(np.int64) + w_sender[None, :] * table[..., 7].astype(np.int64)
+    import torch
+    t = table.to(torch.int64)
+    return int(w[0]) * t[..., 1] + torch.from_numpy(w_sender).to(t.device)[None, :] * t[..., 7]
 
 
 # ---- episodes inside a closed loop (gw_rollout_episodes, include/gymwipe_amd.h) -------------------------------------------------

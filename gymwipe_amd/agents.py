@@ -205,18 +205,27 @@ class TabularCounterTrafficAgent:
     max_duration flat actions, so its Q function is a ``[3][A]`` table and everything it learns from is the table of
     ``env.rollout_policy_stats`` -- visits, reward sums, where the next observation landed, how often ``done`` fired, per
     (observation class, action).  ``collect`` is one launch per 64 steps and no per-env array; ``learn`` and ``evaluate`` are
-    arithmetic on ``[3][A]`` tensors on the GPU.  Nothing here is sized by the number of envs."""
+    arithmetic on ``[3][A]`` tensors on the GPU.  Nothing here is sized by the number of envs.
 
-    def __init__(self, env, gamma=0.99, tau=1.0, seed=123, episode_steps=None):
+    ``score`` (``actions.make_score``): the agent learns from the step's score instead of the built-in reward, whose return
+    telescopes to 0 or ``-payload_value`` per episode and is highest for the policy that assigns nothing.  It then keeps the
+    eight-column table (``packets=True``: the packets delivered per bin beside the reward sum) and ``learn`` uses
+    ``actions.table_score / n`` in place of ``r_sum / n`` -- exact, because the score is linear and the flat action names the
+    sender.  ``evaluate`` returns the mean score per step and ``None`` for the standard error: the table holds no score
+    squares.  ``score=None`` is the agent above, unchanged."""
+
+    def __init__(self, env, gamma=0.99, tau=1.0, seed=123, episode_steps=None, score=None):
         import torch
         self.torch = torch
         self.env = env
         self.episode_steps = None if episode_steps is None else int(episode_steps)   # episodes inside the launch (see _rollout)
         self.dev = env.device
-        self.nb_actions = int(env.num_devices) * int(env.config.max_duration)
+        self.max_duration = int(env.config.max_duration)
+        self.nb_actions = int(env.num_devices) * self.max_duration
         self.gamma, self.tau = float(gamma), float(tau)
+        self.score = score
         self.q = torch.zeros((3, self.nb_actions), dtype=torch.float64, device=self.dev)
-        self.table = torch.zeros((3, self.nb_actions, 7), dtype=torch.int64, device=self.dev)     # everything collected so far
+        self.table = torch.zeros((3, self.nb_actions, 7 if score is None else 8), dtype=torch.int64, device=self.dev)   # everything collected so far
         self.seed, self.stream_pos = int(seed), 0
 
     def policy_cdf(self):
@@ -232,11 +241,12 @@ class TabularCounterTrafficAgent:
         steps = int(steps)
         if self.env._last[0] is None:
             self.env.reset()
+        kw = {} if self.score is None else {"packets": True}
         if self.episode_steps is None:
-            self.env.rollout_policy_stats(self.policy_cdf(), steps, self.seed, step0=self.stream_pos, table=table)
+            self.env.rollout_policy_stats(self.policy_cdf(), steps, self.seed, step0=self.stream_pos, table=table, **kw)
         else:
             self.env.rollout_episodes_stats(self.policy_cdf(), steps, self.seed, max_steps=self.episode_steps, on_done=True,
-                                            step0=self.stream_pos, table=table)
+                                            step0=self.stream_pos, table=table, **kw)
         self.stream_pos += steps
         return table
 
@@ -245,29 +255,41 @@ class TabularCounterTrafficAgent:
         return self._rollout(steps, self.table)
 
     @staticmethod
-    def q_iteration(q, table, gamma, sweeps=1):
-        """``sweeps`` sweeps of Q-iteration on the empirical model of the visited pairs of ``table`` (int64[3][A][7]):
-        ``Q[s,a] <- r_sum/n + gamma * (1 - done/n) * sum_s' next[s']/n * max_a' Q[s',a']``; unvisited pairs keep their value.
-        Returns the new Q (float64[3][A], same device)."""
+    def q_iteration(q, table, gamma, sweeps=1, r_sum=None):
+        """``sweeps`` sweeps of Q-iteration on the empirical model of the visited pairs of ``table`` (int64[3][A][7], or the
+        eight-column table): ``Q[s,a] <- r_sum/n + gamma * (1 - done/n) * sum_s' next[s']/n * max_a' Q[s',a']``; unvisited
+        pairs keep their value.  ``r_sum`` ([3][A], e.g. ``actions.table_score``'s): what a pair's transitions earned in all,
+        in place of the table's reward sums.  Returns the new Q (float64[3][A], same device)."""
         import torch
         t = table.to(torch.float64)
         n = t[..., 0]
         visited = n > 0
         nn = torch.clamp(n, min=1.0)
-        r_mean, cont, p_next = t[..., 1] / nn, 1.0 - t[..., 6] / nn, t[..., 3:6] / nn.unsqueeze(-1)
+        earned = t[..., 1] if r_sum is None else r_sum.to(torch.float64)
+        r_mean, cont, p_next = earned / nn, 1.0 - t[..., 6] / nn, t[..., 3:6] / nn.unsqueeze(-1)
         for _ in range(int(sweeps)):
             v = q.max(dim=1).values                            # [3]: the value of each observation class
             q = torch.where(visited, r_mean + gamma * cont * (p_next * v).sum(dim=-1), q)
         return q
 
     def learn(self, sweeps=1):
-        self.q = self.q_iteration(self.q, self.table, self.gamma, sweeps)
+        if self.score is None:
+            self.q = self.q_iteration(self.q, self.table, self.gamma, sweeps)
+        else:
+            from .actions import table_score
+            self.q = self.q_iteration(self.q, self.table, self.gamma, sweeps, r_sum=table_score(self.table, self.score, self.max_duration))
         return self.q
 
     def evaluate(self, steps):
         """Mean reward per env-step under the current policy over ``steps`` further steps of all N envs, and its standard
-        error: ``(mean, stderr)`` from n, r_sum and r_sq of a table of this call's own (``self.table`` is not touched)."""
+        error: ``(mean, stderr)`` from n, r_sum and r_sq of a table of this call's own (``self.table`` is not touched).
+        With a ``score``: ``(mean score per env-step, None)`` -- the table sums scores, not their squares, so it has no
+        standard error to give."""
         torch = self.torch
+        if self.score is not None:
+            from .actions import table_score
+            t = self._rollout(steps, torch.zeros_like(self.table))
+            return float(table_score(t, self.score, self.max_duration).sum().cpu()) / float(t[..., 0].sum().cpu()), None
         t = self._rollout(steps, torch.zeros_like(self.table)).to(torch.float64)
         n, r_sum, r_sq = (float(x) for x in t[..., :3].sum(dim=(0, 1)).cpu())
         mean = r_sum / n

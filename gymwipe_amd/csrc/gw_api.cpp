@@ -837,6 +837,36 @@ int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_d
                             table_dev, stream);
 }
 
+// The _delivered forms of the tallying calls: their parents' checks and chunking under their own names, the table [3][A][GW_TSD_COLS].
+int gw_rollout_policy_stats_delivered(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0,
+                                      uint64_t env_id0, const int32_t* obs_prev_dev, int32_t* obs_last_dev, int32_t* return_dev,
+                                      int64_t* table_dev, void* stream)
+{
+    int rc = rollout_checks(env, steps, cdf_dev && obs_prev_dev && obs_last_dev && table_dev, "gw_rollout_policy_stats_delivered");
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
+    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
+    return rollout_drive_tally(env, steps, stream,
+        "gw_rollout_policy_stats_delivered: no fused policy rollout for this handle, and no record of packets to compose the table from",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_pstats_d_sfx(env->st, env->cst_host, ch, pol.at(s0), seen_before(s0, obs_prev_dev, obs_last_dev),
+                                                  obs_last_dev, return_dev, table_dev);
+        });
+}
+
+int gw_transition_stats_delivered(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev,
+                                  const int32_t* duration_dev, const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                                  const uint8_t* ended_dev, const int32_t* delivered_dev, int64_t* table_dev, void* stream)
+{
+    int rc = rollout_checks(env, steps,
+                            obs_prev_dev && device_dev && duration_dev && obs_dev && reward_dev && done_dev && delivered_dev && table_dev,
+                            "gw_transition_stats_delivered");
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
+    if (gw_launch_transition_stats_d(env->st.N, steps, env->st.D, env->cst_host.max_duration, env->cst_host.counter_bound, obs_prev_dev,
+                                     device_dev, duration_dev, obs_dev, reward_dev, done_dev, ended_dev, delivered_dev, table_dev, stream))
+        return fail(GW_EHIP, "transition statistics kernel launch failed");
+    return GW_OK;
+}
+
 // ---- the episodic calls and their scored forms (include/gymwipe_amd.h, gw_score) ------------------------------------------------
 // Each pair of entry points is one body: `who` names the call in its messages; `scored` says which of the two it is, and then
 // `score` and delivered_dev (where the call has one) are among the pointers rollout_checks wants -- behind it `score` is nullptr
@@ -1165,6 +1195,21 @@ int gw_rollout_episodes_stats(gw_env* env, int32_t steps, const uint32_t* cdf_de
         });
 }
 
+int gw_rollout_episodes_stats_delivered(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0,
+                                        uint64_t env_id0, const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                                        int64_t* table_dev, void* stream)
+{
+    int rc = rollout_checks(env, steps, cdf_dev && obs_prev_dev && obs_next_dev && table_dev, "gw_rollout_episodes_stats_delivered", true, ep);
+    if (rc || steps == 0 || (rc = select_device(env))) return rc;
+    const GwPolicyStream pol = {cdf_dev, seed, step0, env_id0};
+    return rollout_drive_tally(env, steps, stream,
+        "gw_rollout_episodes_stats_delivered: no fused episodic rollout for this handle: gw_rollout_episodes_scored, then gw_transition_stats_delivered",
+        [&](int32_t s0, const GwChunk& ch) {
+            return gw_launch_rollout_pstats_epd_sfx(env->st, env->cst_host, ch, pol.at(s0), *ep, seen_before(s0, obs_prev_dev, obs_next_dev),
+                                                    obs_next_dev, table_dev);
+        });
+}
+
 int gw_delivered(gw_env* env, uint32_t* out_dev, void* stream)
 {
     if (!env || !out_dev) return fail(GW_EINVAL, "env/out is NULL");
@@ -1431,9 +1476,11 @@ static void launch_slot_name(int slot, char* out, size_t cap)
         const int i = slot - GW_LS_ROLLOUT_POLICY;
         snprintf(out, cap, "ct_rollout_policy<%d, %d>", dts[i / 3], i % 3);
     } else {
-        static const char* const fam[12] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
+        static const char* const fam[14] = {"ct_rollout_pstats", "ct_rollout_policy_ep", "ct_rollout_pstats_ep", "ct_rollout_sync_ep",
                                             "ct_rollout_pop_ep", "ct_rollout_policy_eps", "ct_rollout_pop_eps", "ct_rollout_sync_eps",
-                                            "ct_rollout_backlog", "ct_rollout_backlog_pop", "ct_rollout_fsc", "ct_rollout_fsc_pop"};
+                                            "ct_rollout_backlog", "ct_rollout_backlog_pop", "ct_rollout_fsc", "ct_rollout_fsc_pop",
+                                            "ct_rollout_pstats_d", "ct_rollout_pstats_epd"};
+        static_assert(GW_LS_COUNT == GW_LS_ROLLOUT_PSTATS + 14 * 3 * GW_LS_NDT, "a family without a name");
         const int f = (slot - GW_LS_ROLLOUT_PSTATS) / (3 * GW_LS_NDT), i = (slot - GW_LS_ROLLOUT_PSTATS) % (3 * GW_LS_NDT);
         snprintf(out, cap, "%s<%d, %d>", fam[f], dts[i / 3], i % 3);
     }

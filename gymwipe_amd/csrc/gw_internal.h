@@ -384,6 +384,15 @@ int gw_launch_rollout_fsc_pop_sfx(const GwState& st, const GwDevConst& cst, cons
 int gw_launch_transition_stats(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
                                const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
                                const uint8_t* done, const uint8_t* ended, int64_t* table, void* stream);
+// The three tallying forms with the packets a step delivered in an eighth column (table: [3][A][GW_TSD_COLS]; delivered: the
+// recorded rows' int32[K][N]; ct_rollout_stats.hip)
+int gw_launch_rollout_pstats_d_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                   const int32_t* obs_prev, int32_t* obs_last, int32_t* ret, int64_t* table);   // gw_rollout_policy_stats_delivered
+int gw_launch_rollout_pstats_epd_sfx(const GwState& st, const GwDevConst& cst, const GwChunk& ch, const GwPolicyStream& pol,
+                                     const gw_episodes& ep, const int32_t* obs_prev, int32_t* obs_next, int64_t* table);   // gw_rollout_episodes_stats_delivered
+int gw_launch_transition_stats_d(int64_t N, int K, int D, int max_duration, int counter_bound, const int32_t* obs_prev,
+                                 const int32_t* device, const int32_t* duration, const int32_t* obs, const float* reward,
+                                 const uint8_t* done, const uint8_t* ended, const int32_t* delivered, int64_t* table, void* stream);
 // One step of the per-step forms.  The draw for step pol.step0 from `obs_in` into row.device / row.duration, env e from table
 // e / M (one table: M = st.N), with a scored call's copy of the delivered counters into deliv_before (or nullptr); and, behind
 // the step's launch, the episodes' bookkeeping on that row (ended, the handle's reset mask, obs_next): scored with deliv_before
@@ -448,7 +457,9 @@ enum {
     GW_LS_ROLLOUT_BACKLOG_POP = GW_LS_ROLLOUT_BACKLOG + 3 * GW_LS_NDT,   // ct_rollout_backlog_pop<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_FSC = GW_LS_ROLLOUT_BACKLOG_POP + 3 * GW_LS_NDT,       // ct_rollout_fsc<DT, MODE>: 3 per DT
     GW_LS_ROLLOUT_FSC_POP = GW_LS_ROLLOUT_FSC + 3 * GW_LS_NDT,           // ct_rollout_fsc_pop<DT, MODE>: 3 per DT
-    GW_LS_COUNT = GW_LS_ROLLOUT_FSC_POP + 3 * GW_LS_NDT
+    GW_LS_ROLLOUT_PSTATS_D = GW_LS_ROLLOUT_FSC_POP + 3 * GW_LS_NDT,      // ct_rollout_pstats_d<DT, MODE>: 3 per DT
+    GW_LS_ROLLOUT_PSTATS_EPD = GW_LS_ROLLOUT_PSTATS_D + 3 * GW_LS_NDT,   // ct_rollout_pstats_epd<DT, MODE>: 3 per DT
+    GW_LS_COUNT = GW_LS_ROLLOUT_PSTATS_EPD + 3 * GW_LS_NDT
 };
 constexpr int gw_ls_dt(int DT)                             // index of DT in GW_LS_DTS (a count without a slot of its own: DT = 0's)
 {

@@ -208,6 +208,7 @@ class VecCounterTrafficEnv(BaseEnv):
         self._stats_buf = None                            # 64-step transition buffers (both allocated on first use)
         self._ep_state = self._ep_tally = self._ep_next = None   # rollout_episodes: {age, ret}[N], the episode tally, the
         self._ep_buf = None                               # observations acted on next; the fallback's ended rows (first use)
+        self._packets_buf = None                          # ... and, with packets=True, its delivered rows (first use)
         self._ctl_node = None                             # rollout_controller: each env's node (first use)
         self._custom = interpreter
         if interpreter is not None:                       # a user-supplied Interpreter replaces the fused one
@@ -489,10 +490,11 @@ class VecCounterTrafficEnv(BaseEnv):
         """The action stream's identity as the three 64-bit words of the C-ABI."""
         return int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), int(env_id0) & (2 ** 64 - 1)
 
-    def _compose_stats(self, K, table, seen, episodic, record):
+    def _compose_stats(self, K, table, seen, episodic, record, packets=False):
         """A tallying call on a handle without its fused form, composed from the two other calls in chunks of at most 64 steps
         into buffers the env keeps: ``record(s, k, out)`` runs steps ``s .. s + k`` from the observations ``seen`` into the
-        rows ``out`` and returns what each env acts on next; ``transition_stats`` adds the rows into ``table``."""
+        rows ``out`` and returns what each env acts on next; ``transition_stats`` adds the rows into ``table``.  ``packets``
+        (episodic only): ``out`` has a seventh row, the packets per step, which goes into the table's eighth column."""
         torch = _torch()
         n = self.num_envs
         if self._stats_buf is None:
@@ -503,11 +505,16 @@ class VecCounterTrafficEnv(BaseEnv):
             if self._ep_buf is None:
                 self._ep_buf = torch.empty((64, n), dtype=torch.uint8, device=self.device)
             bufs = bufs + (self._ep_buf,)
+        if packets:
+            if self._packets_buf is None:
+                self._packets_buf = torch.empty((64, n), dtype=torch.int32, device=self.device)
+            bufs = bufs + (self._packets_buf,)
         for s in range(0, K, 64):
             k = min(64, K - s)
             out = tuple(b[:k] for b in bufs)
             nxt = record(s, k, out)
-            self.transition_stats(seen, *out[:5], table=table, ended=out[5] if episodic else None)
+            self.transition_stats(seen, *out[:5], table=table, ended=out[5] if episodic else None,
+                                  delivered=out[6] if packets else None)
             seen.copy_(nxt)
 
     def rollout_policy(self, cdf, steps, seed, step0=0, env_id0=0, obs_prev=None, out=None):
@@ -538,11 +545,12 @@ class VecCounterTrafficEnv(BaseEnv):
             self._last = (obs[-1], rew[-1], done[-1])
         return dev, dur, obs, rew, done
 
-    def _stats_table(self, table):
-        """The ``int64[3][A][TS_COLS]`` table on this env's GPU: the caller's (added into) or a new one of zeros."""
+    def _stats_table(self, table, packets=False):
+        """The ``int64[3][A][TS_COLS]`` table on this env's GPU (``packets``: ``[3][A][TSD_COLS]``): the caller's (added into) or
+        a new one of zeros."""
         torch = _torch()
-        from ..actions import TS_COLS
-        shape = (3, self.num_devices * int(self.config.max_duration), TS_COLS)
+        from ..actions import TS_COLS, TSD_COLS
+        shape = (3, self.num_devices * int(self.config.max_duration), TSD_COLS if packets else TS_COLS)
         if table is None:
             return torch.zeros(shape, dtype=torch.int64, device=self.device)
         if not (type(table) is torch.Tensor and table.dtype is torch.int64 and table.device == self.device
@@ -550,29 +558,40 @@ class VecCounterTrafficEnv(BaseEnv):
             raise ValueError("table must be a contiguous int64 tensor of shape %s on %s" % (shape, self.device))
         return table
 
-    def transition_stats(self, obs_prev, device, duration, obs, reward, done, table=None, ended=None):
+    def transition_stats(self, obs_prev, device, duration, obs, reward, done, table=None, ended=None, delivered=None):
         """Recorded transitions ``[steps][N]`` (what ``rollout_policy`` returns; ``obs_prev`` int32[N] is what step 0 acted on)
         added into ``table`` (gw_transition_stats; ``actions.transition_stats_numpy`` restates it): ``int64[3][A][7]`` over
         (observation class, flat action).  Returns the table (a new one of zeros when none is passed).
         ``ended`` (uint8[steps][N], what ``rollout_episodes`` returns; gw_transition_stats_ep): an env whose step k - 1 ended
-        an episode acted on the reset's observation at step k."""
+        an episode acted on the reset's observation at step k.
+        ``delivered`` (int32[steps][N], what the scored calls return -- ``rollout_episodes(score=)``, ``rollout_autoreset(score=)``
+        with its ``ended``; gw_transition_stats_delivered): the table is ``int64[3][A][8]``, its eighth column the packets
+        delivered, each step's count clamped to [0, 65 535]; ``actions.table_score`` turns it into any score's sum per bin."""
         torch = _torch()
-        table = self._stats_table(table)
+        table = self._stats_table(table, packets=delivered is not None)
         K, n = int(obs.shape[0]), self.num_envs
         args = []
         rows = [(obs_prev, torch.int32), (device, torch.int32), (duration, torch.int32), (obs, torch.int32),
                 (reward, torch.float32), (done, torch.uint8)] + ([(ended, torch.uint8)] if ended is not None else [])
+        if delivered is not None:
+            rows.append((delivered, torch.int32))
         for t, dt in rows:
             t = torch.as_tensor(t).to(device=self.device, dtype=dt).contiguous()
             if tuple(t.shape) != ((n,) if not args else (K, n)):
                 raise ValueError("transition_stats: obs_prev is [N], the other arrays [steps][N]; got %s" % (tuple(t.shape),))
             args.append(t)
-        call = self._L.gw_transition_stats if ended is None else self._L.gw_transition_stats_ep
+        ptrs = [t.data_ptr() for t in args]
         with torch.cuda.device(self.device):
-            nat.check(call(self._h, K, *[t.data_ptr() for t in args], table.data_ptr(), self._stream()))
+            if delivered is not None:
+                if ended is None:
+                    ptrs.insert(6, None)
+                nat.check(self._L.gw_transition_stats_delivered(self._h, K, *ptrs, table.data_ptr(), self._stream()))
+            else:
+                call = self._L.gw_transition_stats if ended is None else self._L.gw_transition_stats_ep
+                nat.check(call(self._h, K, *ptrs, table.data_ptr(), self._stream()))
         return table
 
-    def rollout_policy_stats(self, cdf, steps, seed, step0=0, env_id0=0, obs_prev=None, table=None, returns=None):
+    def rollout_policy_stats(self, cdf, steps, seed, step0=0, env_id0=0, obs_prev=None, table=None, returns=None, packets=False):
         """``rollout_policy`` for a caller that wants the tally, not the transitions (gw_rollout_policy_stats): the same
         ``steps`` steps, draws and state changes, and every transition ADDED into ``table`` -- ``int64[3][A][7]`` over
         (observation class ``sign(obs_seen - COUNTER_BOUND) + 1``, flat action ``device * max_duration + duration``) with the
@@ -581,14 +600,18 @@ class VecCounterTrafficEnv(BaseEnv):
         observation is kept as ``reset()`` keeps its own, so a following ``rollout_policy`` / ``rollout_policy_stats``
         continues from it; advance ``step0`` by ``steps``.  Nothing here is sized by ``steps * N``.
         A handle without the fused form (explicit queues, live PHY, ...) runs ``rollout_policy`` in chunks of at most 64 steps
-        into buffers the env keeps, then ``transition_stats``: the same table."""
+        into buffers the env keeps, then ``transition_stats``: the same table.
+        ``packets=True`` (gw_rollout_policy_stats_delivered): the table is ``int64[3][A][8]``, its eighth column the data
+        packets of the assigned sender the RRM decoded, summed per bin (``actions.table_score`` applies a score to it).  Only
+        the fused form has it: ``rollout_policy`` keeps no record of packets to compose the table from, so a handle without
+        the fused form raises ``GW_EUNSUPPORTED`` (use ``rollout_episodes_stats(packets=True)``, whose fallback records them)."""
         torch = _torch()
         if self._custom is not None:
             raise ValueError("rollout_policy_stats needs the built-in interpreter")
         K, n = int(steps), self.num_envs
         prev = self._obs_prev(obs_prev, "rollout_policy_stats")
         cdf_t = self._policy_table(cdf)
-        table = self._stats_table(table)
+        table = self._stats_table(table, packets)
         if returns is not None and not (type(returns) is torch.Tensor and returns.dtype is torch.int32 and returns.device == self.device
                                         and tuple(returns.shape) == (n,) and returns.is_contiguous()):
             raise ValueError("returns must be a contiguous int32[N] tensor on the env's GPU")
@@ -598,11 +621,11 @@ class VecCounterTrafficEnv(BaseEnv):
         if last is None:
             last = self._stats_last = torch.empty(n, dtype=torch.int32, device=self.device)
         seed, step0, env_id0 = self._stream_id(seed, step0, env_id0)
+        call = self._L.gw_rollout_policy_stats_delivered if packets else self._L.gw_rollout_policy_stats
         with torch.cuda.device(self.device):
-            rc = self._L.gw_rollout_policy_stats(self._h, K, cdf_t.data_ptr(), seed, step0, env_id0, prev.data_ptr(),
-                                                 last.data_ptr(), returns.data_ptr() if returns is not None else None,
-                                                 table.data_ptr(), self._stream())
-        if rc == nat.EUNSUPPORTED and not os.environ.get("GW_ROLLOUT_STRICT"):
+            rc = call(self._h, K, cdf_t.data_ptr(), seed, step0, env_id0, prev.data_ptr(), last.data_ptr(),
+                      returns.data_ptr() if returns is not None else None, table.data_ptr(), self._stream())
+        if rc == nat.EUNSUPPORTED and not packets and not os.environ.get("GW_ROLLOUT_STRICT"):
             def record(s, k, out):                         # refused before anything ran: compose it from the two other calls
                 self.rollout_policy(cdf_t, k, seed, step0=step0 + s, env_id0=env_id0, obs_prev=last, out=out)
                 if returns is not None:
@@ -694,30 +717,43 @@ class VecCounterTrafficEnv(BaseEnv):
             self._last = (self._ep_next, out[3][-1], out[4][-1])
         return out
 
-    def rollout_episodes_stats(self, cdf, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, table=None):
+    def rollout_episodes_stats(self, cdf, steps, seed, max_steps=0, on_done=True, step0=0, env_id0=0, obs_prev=None, table=None,
+                               packets=False):
         """``rollout_episodes`` for a caller that wants the tally, not the transitions (gw_rollout_episodes_stats): the same
         steps, draws, resets and episode bookkeeping, every transition ADDED into ``table`` (``rollout_policy_stats``' table)
         under the class of the observation the env acted on -- the reset's after an episode's end.  Returns the table.  A
         handle without the fused form runs ``rollout_episodes`` in chunks of at most 64 steps into buffers the env keeps, then
-        ``transition_stats(..., ended=...)``: the same table."""
+        ``transition_stats(..., ended=...)``: the same table.
+        ``packets=True`` (gw_rollout_episodes_stats_delivered): the table is ``int64[3][A][8]``, its eighth column the data
+        packets of the assigned sender the RRM decoded, summed per bin; the episodes' ``{age, ret}`` and tally keep the built-in
+        reward -- the table is score-free, ``actions.table_score`` applies any score to it afterwards.  The fallback records
+        with ``rollout_episodes(score=actions.make_score(D))`` -- the neutral score, under which ``reward`` is the built-in
+        reward -- and ``transition_stats(..., delivered=)``: the same table; an explicit-queue handle, which keeps no delivered
+        counter per env, is refused there with ``GW_EUNSUPPORTED``."""
         torch = _torch()
         ep, prev = self._episodes(max_steps, on_done, obs_prev, "rollout_episodes_stats")
         K, n = int(steps), self.num_envs
         cdf_t = self._policy_table(cdf)
-        table = self._stats_table(table)
+        table = self._stats_table(table, packets)
         if K == 0:
             return table
         seed, step0, env_id0 = self._stream_id(seed, step0, env_id0)
+        call = self._L.gw_rollout_episodes_stats_delivered if packets else self._L.gw_rollout_episodes_stats
         with torch.cuda.device(self.device):
-            rc = self._L.gw_rollout_episodes_stats(self._h, K, cdf_t.data_ptr(), seed, step0, env_id0, C.byref(ep),
-                                                   prev.data_ptr(), self._ep_next.data_ptr(), table.data_ptr(), self._stream())
+            rc = call(self._h, K, cdf_t.data_ptr(), seed, step0, env_id0, C.byref(ep), prev.data_ptr(), self._ep_next.data_ptr(),
+                      table.data_ptr(), self._stream())
         if rc == nat.EUNSUPPORTED and not os.environ.get("GW_ROLLOUT_STRICT"):
             seen = prev.clone()
+            neutral = None
+            if packets:
+                from ..actions import make_score
+                neutral = make_score(self.num_devices)
 
             def record(s, k, out):                         # refused before anything ran: compose it from the two other calls
-                self.rollout_episodes(cdf_t, k, seed, max_steps, on_done, step0=step0 + s, env_id0=env_id0, obs_prev=seen, out=out)
+                self.rollout_episodes(cdf_t, k, seed, max_steps, on_done, step0=step0 + s, env_id0=env_id0, obs_prev=seen, out=out,
+                                      score=neutral)
                 return self._ep_next
-            self._compose_stats(K, table, seen, True, record)
+            self._compose_stats(K, table, seen, True, record, packets)
         else:
             nat.check(rc)
         self._last = (self._ep_next,) + tuple(self._last[1:])

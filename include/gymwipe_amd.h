@@ -562,6 +562,37 @@ int gw_transition_stats_ep(gw_env* env, int32_t steps, const int32_t* obs_prev_d
                            const int32_t* duration_dev, const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev,
                            const uint8_t* ended_dev, int64_t* table_dev, void* stream);
 
+/* The tally with the packets a step delivered.  A step's score (gw_score) is linear, w_reward * reward + w_delivered[device] *
+ * delivered, and the flat action names the sender (a / max_duration): a bin's score sum under ANY gw_score is
+ *     w_reward * column 1 + w_delivered[a / max_duration] * column 7
+ * so the table carries one more sum per bin and no weights; the caller applies whichever score afterwards. */
+#define GW_TSD_COLS 8
+/* int64 table[3][A][GW_TSD_COLS], row-major: columns 0-6 are GW_TS_COLS' columns,
+ *   7 delivered   sum of min(delivered, 65 535) over the bin's transitions -- delivered: the data packets of the assigned sender
+ *                 the RRM decoded in the step (what gw_rollout_episodes_scored records).  A step delivers at most 100 + 100 *
+ *                 (counter ticks inside its window) packets -- 25 600 with one tick per duration unit and max_duration 254,
+ *                 9 at the default configuration -- so the clamp binds only where a window spans more than 654 ticks.
+ *
+ * gw_rollout_policy_stats_delivered / gw_rollout_episodes_stats_delivered: the arguments, draws, state changes, episode
+ * bookkeeping (the built-in reward's: the table is score-free), availability and refusals of gw_rollout_policy_stats /
+ * gw_rollout_episodes_stats, the table one column wider (ct_rollout_pstats_d / ct_rollout_pstats_epd in ct_rollout_stats.hip: the
+ * sum rides in bits the histogram's second word had left, no LDS byte and no atomic more).  GW_EUNSUPPORTED before anything is
+ * launched where the parents answer it; the episodic call is then composed from gw_rollout_episodes_scored with the neutral
+ * score and gw_transition_stats_delivered, the other one from nothing (gw_rollout_policy records no packets). */
+int gw_rollout_policy_stats_delivered(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0,
+                                      uint64_t env_id0, const int32_t* obs_prev_dev, int32_t* obs_last_dev, int32_t* return_dev,
+                                      int64_t* table_dev, void* stream);
+int gw_rollout_episodes_stats_delivered(gw_env* env, int32_t steps, const uint32_t* cdf_dev, uint64_t seed, uint64_t step0,
+                                        uint64_t env_id0, const gw_episodes* ep, const int32_t* obs_prev_dev, int32_t* obs_next_dev,
+                                        int64_t* table_dev, void* stream);
+/* gw_transition_stats / gw_transition_stats_ep (ended_dev NULL / not NULL) with a row of packets per step, delivered_dev
+ * int32[steps][N], into the eight-column table.  A negative count is 0, one above 65 535 is 65 535; a row whose action lies
+ * outside the action space is skipped.  Every handle.  A NULL pointer other than ended_dev / stream, or steps < 0, is
+ * GW_EINVAL before any HIP call; steps == 0 is GW_OK. */
+int gw_transition_stats_delivered(gw_env* env, int32_t steps, const int32_t* obs_prev_dev, const int32_t* device_dev,
+                                  const int32_t* duration_dev, const int32_t* obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                                  const uint8_t* ended_dev, const int32_t* delivered_dev, int64_t* table_dev, void* stream);
+
 /* Cumulative number of data packets the RRM has decoded per env since gw_create: uint32[N], device pointer
  * (default mode).  A custom Interpreter (envs/core.py:59-159) differences this across a step to learn how many
  * packets of the assigned sender the RRM sniffed (networking/devices.py:163-168). */

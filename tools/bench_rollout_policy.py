@@ -34,6 +34,7 @@ median wall time per step over --windows calls of K steps:
                                              the per-env return in torch (one table for all envs: rollout_episodes has no
                                              population; the per-policy tally is left out, which favours this leg)
   R1 / R0 / R2 / R3                          the same four for the records form, env.rollout_episodes(score=...)
+The delivered-tally legs (--packets; profiles/rollout_stats_delivered/README.md): D1 / D0 / D2, see packets_legs().
 Each form is timed `--repeats` times over `--windows` windows (wall clock around a device synchronize); one JSON line with the
 best, the median and the spread.  GW_TREE names the checkout whose gymwipe_amd package (and built library) is measured --
 default: this file's own -- so one job can run a and b on the parent commit's build and c on this one's; a form the measured
@@ -142,6 +143,92 @@ def scored_legs(args):
     print(json.dumps(res))
 
 
+def packets_legs(args):
+    """--packets (profiles/rollout_stats_delivered/README.md): episodes of T steps (--episodes, default 8), the tally with the
+    packets a step delivered; the legs alternate in one process, --repeats rounds each, wall time per step over --windows calls
+    of K steps:
+      D1 env.rollout_episodes_stats(packets=True)   the eight-column table inside the launch
+      D0 env.rollout_episodes_stats()               its parent on the same build: what the eighth column costs
+      D2 the composition a caller has without it    rollout_episodes(score=neutral) into [K][N] rows, then the eight columns
+                                                    with torch index_add_ (scatter-add) on the same stream
+    D1 and D2 must build the same table from the same steps (checked once, before the timing, on two fresh handles)."""
+    import torch
+    from gymwipe_amd import VecCounterTrafficEnv, actions
+
+    N, D, K, T, W = args.envs, args.devices, args.steps, args.episodes or 8, args.windows
+    dev = torch.device("cuda:0")
+    md = 20
+    A = D * md
+    rng = np.random.default_rng(7)
+    p = rng.dirichlet(np.full(A, 0.3), size=3)
+    if args.onehot:                                            # three non-empty bins instead of 3 * A: next to no flush
+        p = np.zeros((3, A))
+        p[:, 1 * md + md - 1] = 1.0
+    cdf = actions.policy_cdf(p)
+    neutral = actions.make_score(D)
+    kinds = (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8, torch.uint8, torch.int32)
+    center = 65536
+
+    def new_env(cols):
+        e = VecCounterTrafficEnv(N, num_devices=D, device=dev)
+        e.reset()
+        e.bench = {"cdf": e._policy_table(cdf), "table": torch.zeros((3, A, cols), dtype=torch.int64, device=dev), "step0": 0,
+                   "rows": tuple(torch.empty((K, N), dtype=t, device=dev) for t in kinds)}
+        return e
+
+    def fused(e, packets):
+        b = e.bench
+        e.rollout_episodes_stats(b["cdf"], K, 5, max_steps=T, step0=b["step0"], table=b["table"], **({"packets": True} if packets else {}))
+        b["step0"] += K
+
+    def composed(e):
+        b = e.bench
+        first = e._last[0].clone()
+        d, u, obs, rew, done, ended, dl = e.rollout_episodes(b["cdf"], K, 5, max_steps=T, step0=b["step0"], out=b["rows"], score=neutral)
+        b["step0"] += K
+        seen = torch.cat([first.unsqueeze(0), torch.where(ended[:-1] != 0, torch.full_like(obs[:-1], center), obs[:-1])])
+        row = ((torch.sign(seen - center) + 1).to(torch.int64) * A + d.to(torch.int64) * md + u.to(torch.int64)).reshape(-1)
+        r = rew.reshape(-1).to(torch.int64)
+        col = (torch.sign(obs - center) + 1).reshape(-1).to(torch.int64)
+        flat = b["table"].view(3 * A, 8)
+        flat[:, 0].index_add_(0, row, torch.ones_like(row))
+        flat[:, 1].index_add_(0, row, r)
+        flat[:, 2].index_add_(0, row, r * r)
+        flat.view(-1).index_add_(0, row * 8 + 3 + col, torch.ones_like(row))
+        flat[:, 6].index_add_(0, row, (done.reshape(-1) != 0).to(torch.int64))
+        flat[:, 7].index_add_(0, row, dl.reshape(-1).to(torch.int64).clamp(0, 65535))
+
+    a, b = new_env(8), new_env(8)
+    for _ in range(2):
+        fused(a, True)
+        composed(b)
+    assert torch.equal(a.bench["table"], b.bench["table"]) and int(a.bench["table"][..., 0].sum()) == 2 * N * K, "D1 and D2 differ"
+    assert int(a.bench["table"][..., 7].sum()) > 0
+    del a, b
+    envs = {"D1": new_env(8), "D0": new_env(7), "D2": new_env(8)}
+    legs = {"D1": lambda: fused(envs["D1"], True), "D0": lambda: fused(envs["D0"], False), "D2": lambda: composed(envs["D2"])}
+    times = {name: [] for name in legs}
+    for rnd in range(args.repeats + 1):                        # round 0: warm-up (first launches, allocator)
+        for name in (list(legs) if rnd % 2 else list(reversed(legs))):      # (a leg's place in the round alternates)
+            fn = legs[name]
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(W):
+                fn()
+            torch.cuda.synchronize(dev)
+            if rnd:
+                times[name].append((time.perf_counter() - t0) / (K * W) * 1e6)
+    for e in envs.values():
+        e.check()
+    res = {"label": args.label, "envs": N, "devices": D, "steps": K, "windows": W, "episodes": T, "rounds": args.repeats,
+           "onehot": bool(args.onehot), "device": torch.cuda.get_device_name(0)}
+    for name, t in times.items():
+        res[name] = {"us_per_step_median": round(float(np.median(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
+    res["ratios"] = {"D1/D0": round(res["D1"]["us_per_step_median"] / res["D0"]["us_per_step_median"], 3),
+                     "D2/D1": round(res["D2"]["us_per_step_median"] / res["D1"]["us_per_step_median"], 3)}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
@@ -154,9 +241,14 @@ def main():
     ap.add_argument("--episodes", type=int, default=0, help="episode length T of the forms p, e, q, f (must divide --steps)")
     ap.add_argument("--scored", action="store_true", help="run the scored legs instead of --forms")
     ap.add_argument("--policies", type=int, default=64, help="P of the scored population legs")
+    ap.add_argument("--packets", action="store_true", help="run the delivered-tally legs instead of --forms")
+    ap.add_argument("--onehot", action="store_true",
+                    help="--packets: a policy that always takes one action, so that a block's histogram has one bin per class to flush")
     args = ap.parse_args()
     if args.scored:
         return scored_legs(args)
+    if args.packets:
+        return packets_legs(args)
 
     import torch
     from gymwipe_amd import VecCounterTrafficEnv, actions
