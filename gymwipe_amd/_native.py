@@ -35,6 +35,7 @@ EXPORTS = (
     "gw_ctrl_config_default", "gw_ctrl_create", "gw_ctrl_destroy", "gw_ctrl_step", "gw_ctrl_get_state",
     "gw_ctrl_set_initial", "gw_ctrl_reset", "gw_ctrl_rollout", "gw_ctrl_rollout_schedules",
     "gw_grid_config_default", "gw_grid_create", "gw_grid_destroy", "gw_grid_run", "gw_grid_get_state", "gw_grid_set_position",
+    "gw_grid_selftest_width",
 )
 
 
@@ -336,6 +337,7 @@ def lib():
     L.gw_grid_run.argtypes, L.gw_grid_run.restype = [vp, C.c_double, vp], C.c_int
     L.gw_grid_get_state.argtypes, L.gw_grid_get_state.restype = [vp, C.c_char_p, vp, C.c_size_t], C.c_int
     L.gw_grid_set_position.argtypes, L.gw_grid_set_position.restype = [vp, i32, vp, vp, vp], C.c_int
+    L.gw_grid_selftest_width.argtypes, L.gw_grid_selftest_width.restype = [vp, i64, i32], i32
     if L.gw_abi_version() != ABI_VERSION:
         raise ImportError("gymwipe_amd: ABI mismatch (library %d, python %d); rebuild"
                           % (L.gw_abi_version(), ABI_VERSION))

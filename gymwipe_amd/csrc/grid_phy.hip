@@ -81,6 +81,17 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask, int lane)
     return __popcll(mask & ((1ull << lane) - 1ull));
 }
 
+// mobile handles: behind txp's [N][n][n] powers of the transmissions on the air lie [N][n][n] powers of stale links (row of
+// the radio that uses them) and [N][n][2] masks (links that exist, links that are stale), all 8 bytes wide (gw_grid_create)
+__device__ __forceinline__ double* grid_link_row(const GwGridDev& g, int64_t env, int lane)
+{
+    return g.txp + (g.N + env) * g.n * g.n + (int64_t)lane * g.n;
+}
+__device__ __forceinline__ unsigned long long* grid_link_masks(const GwGridDev& g, int64_t env, int lane)
+{
+    return (unsigned long long*)(g.txp + 2 * g.N * g.n * g.n) + (env * g.n + lane) * 2;
+}
+
 template <bool MOBILE, int GW>
 __global__ __launch_bounds__(64) void grid_run_kernel(GwGridDev g, double seconds)
 {
@@ -116,6 +127,13 @@ __global__ __launch_bounds__(64) void grid_run_kernel(GwGridDev g, double second
         L.queued = 0; L.rx_src = 0; L.rxi_src = 0;
     }
     if (MOBILE && me) { s_px[lane] = L.px; s_py[lane] = L.py; }
+    // mobile: links in stand-by (physical.py:371-386).  A link exists from the first transmission between its two radios; a move
+    // that leaves them 3000 m or more apart does not update it, and transmissions that start later still see its old
+    // attenuation.  Per radio: the links that exist, those that are stale, and the stale links' powers (this radio's own row)
+    unsigned long long linked = 0, stale = 0;
+    double* const lnk = MOBILE && have ? grid_link_row(g, env, lane) : nullptr;
+    unsigned long long* const msk = MOBILE && have ? grid_link_masks(g, env, lane) : nullptr;
+    if (MOBILE && me) { linked = msk[0]; stale = msk[1]; }
     __syncthreads();
     GwGridEnv E;                                         // group-uniform: now, eid, counters
     if (have) E = g.envs[env];
@@ -230,10 +248,12 @@ __global__ __launch_bounds__(64) void grid_run_kernel(GwGridDev g, double second
         case EV_NOTIFY: {
             const double stop_dev = __shfl(L.tx_stop, dev, GW);
             if (mine) L.tx_on = 1;
+            if (MOBILE && mine) linked |= (n == 64 ? ~0ull : ((1ull << n) - 1ull)) & ~(1ull << dev);
             if (me && lane != dev) {                      // _onNewTransmission at every other radio
                 double p;
                 if (MOBILE) {
-                    p = fspl_power(L.px, L.py, s_px[dev], s_py[dev], g.tx_power_dbm, g.twenty_log_f);
+                    p = ((stale >> dev) & 1ull) ? lnk[dev] : fspl_power(L.px, L.py, s_px[dev], s_py[dev], g.tx_power_dbm, g.twenty_log_f);
+                    linked |= 1ull << dev;
                     s_prx[dev * n + lane] = p;            // _transmissionToReceivedPower[t]
                 } else p = s_prx[dev * n + lane];
                 L.rx_power = L.rx_power + p;
@@ -348,6 +368,7 @@ __global__ __launch_bounds__(64) void grid_run_kernel(GwGridDev g, double second
         }
         case EV_MOVE: {                                   // mover process: tests/test_benchmark.py:73-85
             if (MOBILE) {
+                const double ox = s_px[dev], oy = s_py[dev];             // where the mover was
                 if (mine) {
                     const double xo = -g.move_span + (g.move_span - (-g.move_span)) * grid_uniform(g.seed, (unsigned long long)env, (unsigned)lane, L.move_k, 1u);
                     const double yo = -g.move_span + (g.move_span - (-g.move_span)) * grid_uniform(g.seed, (unsigned long long)env, (unsigned)lane, L.move_k, 2u);
@@ -361,6 +382,26 @@ __global__ __launch_bounds__(64) void grid_run_kernel(GwGridDev g, double second
                 // (one wave per workgroup, LDS operations of a wave complete in order: the positions just written are what the
                 //  group's other lanes read below; a workgroup barrier has no place inside a handler only some groups run)
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                {   // the mover's links: within 3000 m they follow; beyond, one that exists keeps the value it had
+                    bool fresh = false, freeze = false;
+                    if (me && lane != dev) {
+                        const double dx = L.px - s_px[dev], dy = L.py - s_py[dev];
+                        fresh = sqrt(dx * dx + dy * dy) < 3000.0;
+                        freeze = !fresh && ((linked >> dev) & 1ull) && !((stale >> dev) & 1ull);
+                        if (fresh) stale &= ~(1ull << dev);
+                        if (freeze) { lnk[dev] = fspl_power(L.px, L.py, ox, oy, g.tx_power_dbm, g.twenty_log_f); stale |= 1ull << dev; }
+                    }
+                    const unsigned long long mf = (__ballot(fresh) >> gsh) & gmask;
+                    unsigned long long mz = (__ballot(freeze) >> gsh) & gmask;
+                    if (mine) {
+                        stale = (stale & ~mf) | mz;
+                        while (mz) {
+                            const int i = __ffsll((long long)mz) - 1;
+                            mz &= mz - 1;
+                            lnk[i] = fspl_power(s_px[i], s_py[i], ox, oy, g.tx_power_dbm, g.twenty_log_f);
+                        }
+                    }
+                }
                 const unsigned long long on_air = (__ballot(me && L.tx_on) >> gsh) & gmask;
                 // (A) the mover's own transmission, heard by everyone else: _onAttenuationChange (simple_stack.py:119-128)
                 if ((on_air >> dev) & 1ull) {
@@ -411,6 +452,7 @@ __global__ __launch_bounds__(64) void grid_run_kernel(GwGridDev g, double second
     __syncthreads();
     if (MOBILE && have) { for (int i = lane; i < n * n; i += GW) g.txp[env * n * n + i] = s_prx[i]; }
     if (me) g.lanes[env * n + lane] = L;
+    if (MOBILE && me) { msk[0] = linked; msk[1] = stale; }
     if (have && lane == 0) {
         E.now = now; E.eid = eid; E.events = n_events; E.n_tx = n_tx;
         g.envs[env] = E;
@@ -432,6 +474,7 @@ __global__ __launch_bounds__(64) void grid_set_position_kernel(GwGridDev g, int 
     if (me) L = g.lanes[env * n + lane];
     else { memset(&L, 0, sizeof L); }
     const double now = g.envs[env].now;
+    const double ox = g.lanes[env * n + dev].px, oy = g.lanes[env * n + dev].py;   // where the radio was
     if (me && lane == dev) { L.px = xs[env]; L.py = ys[env]; }
     if (me) { s_px[lane] = L.px; s_py[lane] = L.py; }
     __syncthreads();
@@ -445,6 +488,31 @@ __global__ __launch_bounds__(64) void grid_set_position_kernel(GwGridDev g, int 
             L.ber = ber_bpsk(sig, noise, g.ten_log_br, g.sqrt2pi);
         }
     };
+    {   // the moved radio's links in stand-by, as in the MOVE handler
+        double* const lnk = grid_link_row(g, env, lane);
+        unsigned long long* const msk = grid_link_masks(g, env, lane);
+        unsigned long long linked = 0, stale = 0;
+        if (me) { linked = msk[0]; stale = msk[1]; }
+        bool fresh = false, freeze = false;
+        if (me && lane != dev) {
+            const double dx = L.px - s_px[dev], dy = L.py - s_py[dev];
+            fresh = sqrt(dx * dx + dy * dy) < 3000.0;
+            freeze = !fresh && ((linked >> dev) & 1ull) && !((stale >> dev) & 1ull);
+            if (fresh) stale &= ~(1ull << dev);
+            if (freeze) { lnk[dev] = fspl_power(L.px, L.py, ox, oy, g.tx_power_dbm, g.twenty_log_f); stale |= 1ull << dev; }
+        }
+        const unsigned long long mf = __ballot(fresh);
+        unsigned long long mz = __ballot(freeze);
+        if (me && lane == dev) {
+            stale = (stale & ~mf) | mz;
+            while (mz) {
+                const int i = __ffsll((long long)mz) - 1;
+                mz &= mz - 1;
+                lnk[i] = fspl_power(s_px[i], s_py[i], ox, oy, g.tx_power_dbm, g.twenty_log_f);
+            }
+        }
+        if (me) msk[1] = stale;
+    }
     const unsigned long long on_air = __ballot(me && L.tx_on);
     if (((on_air >> dev) & 1ull) && me && lane != dev) {
         const double dx = L.px - s_px[dev], dy = L.py - s_py[dev];
@@ -510,23 +578,21 @@ __global__ void grid_init_kernel(GwGridDev g, const double* __restrict__ delays,
 
 } // namespace
 
-int gw_grid_launch_run(const GwGridDev& g, double seconds, void* stream)
+int gw_grid_launch_run(const GwGridDev& g, double seconds, void* stream, int* width_ran)
 {
-    // lanes per replica: the power of two that holds its radios; 64 / GW replicas share a wave
-    int gw = g.n <= 4 ? 4 : (g.n <= 8 ? 8 : (g.n <= 16 ? 16 : (g.n <= 32 ? 32 : 64)));
-    // ... unless that leaves SIMDs without a wave (1 024 of them): a small batch spreads out first (4 096 replicas of 4 radios:
-    // groups of 16 lanes, four replicas per wave, 1 024 waves -- sixteen per wave would be 256 waves on a quarter of the chip)
-    while (gw < 64 && (g.N * gw + 63) / 64 < 1024) gw *= 2;
+    const int gw = gw_grid_pick_width(g.N, g.n);         // lanes per replica (gw_internal.h)
     const int per_wave = 64 / gw;
     const size_t lds = (size_t)per_wave * ((size_t)g.n * g.n + 2 * (size_t)g.n) * sizeof(double);
     const unsigned grid = (unsigned)((g.N + per_wave - 1) / per_wave);
     hipStream_t s = (hipStream_t)stream;
-#define GW_GRID(M_, W_) hipLaunchKernelGGL((grid_run_kernel<M_, W_>), dim3(grid), dim3(64), lds, s, g, seconds)
+    int ran = 0;                                         // written by the branch that launches (gw_grid_selftest_width)
+#define GW_GRID(M_, W_) do { ran = W_; hipLaunchKernelGGL((grid_run_kernel<M_, W_>), dim3(grid), dim3(64), lds, s, g, seconds); } while (0)
     if (g.mobile) { switch (gw) { case 4: GW_GRID(true, 4); break; case 8: GW_GRID(true, 8); break; case 16: GW_GRID(true, 16); break;
                                   case 32: GW_GRID(true, 32); break; default: GW_GRID(true, 64); break; } }
     else          { switch (gw) { case 4: GW_GRID(false, 4); break; case 8: GW_GRID(false, 8); break; case 16: GW_GRID(false, 16); break;
                                   case 32: GW_GRID(false, 32); break; default: GW_GRID(false, 64); break; } }
 #undef GW_GRID
+    if (width_ran) *width_ran = ran;
     return hipGetLastError() == hipSuccess ? GW_OK : GW_EHIP;
 }
 

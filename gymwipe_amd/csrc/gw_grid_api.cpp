@@ -15,6 +15,7 @@ struct gw_grid {
     GwGridDev dev;
     void* blocks[6];
     int nblocks;
+    int last_width;             // lanes per replica of the last gw_grid_run (gw_grid_selftest_width); 0 before any run
 };
 
 #define GRID_HIP(expr, cleanup)                                                                   \
@@ -100,7 +101,9 @@ int gw_grid_create(const gw_grid_config* cfg, const double* delays, gw_grid** ou
         gw_grid_destroy(g);
         return gw_set_error(GW_ENOMEM, "hipMalloc failed in gw_grid_create");
     }
-    if (cfg->mobile && !alloc((void**)&d_txp, (size_t)N * n * n * sizeof(double))) { gw_grid_destroy(g); return gw_set_error(GW_ENOMEM, "hipMalloc failed"); }
+    // mobile: powers of the transmissions on the air, powers of stale links, link masks (grid_phy.hip: grid_link_row / _masks)
+    const size_t txp_words = 2 * (size_t)N * n * n + 2 * (size_t)N * n;
+    if (cfg->mobile && !alloc((void**)&d_txp, txp_words * sizeof(double))) { gw_grid_destroy(g); return gw_set_error(GW_ENOMEM, "hipMalloc failed"); }
     if (hipMalloc((void**)&d_delays, ((size_t)N * n + 2 * (size_t)n) * sizeof(double)) != hipSuccess) { gw_grid_destroy(g); return gw_set_error(GW_ENOMEM, "hipMalloc failed"); }
     d_pos = d_delays + (size_t)N * n;
     d.prx = d_prx;
@@ -121,7 +124,7 @@ int gw_grid_create(const gw_grid_config* cfg, const double* delays, gw_grid** ou
         std::vector<double> pos((size_t)2 * n);
         for (int i = 0; i < n; ++i) { pos[2 * i] = cfg->pos[i][0]; pos[2 * i + 1] = cfg->pos[i][1]; }
         GRID_HIP(hipMemcpy(d_pos, pos.data(), pos.size() * sizeof(double), hipMemcpyHostToDevice), ((void)hipFree(d_delays), gw_grid_destroy(g)));
-        if (d_txp) GRID_HIP(hipMemset(d_txp, 0, (size_t)N * n * n * sizeof(double)), ((void)hipFree(d_delays), gw_grid_destroy(g)));
+        if (d_txp) GRID_HIP(hipMemset(d_txp, 0, txp_words * sizeof(double)), ((void)hipFree(d_delays), gw_grid_destroy(g)));
     }
     if (gw_grid_launch_init(d, d_delays, d_pos, thermal, nullptr)) { (void)hipFree(d_delays); gw_grid_destroy(g); return gw_set_error(GW_EHIP, "grid init launch failed"); }
     GRID_HIP(hipDeviceSynchronize(), ((void)hipFree(d_delays), gw_grid_destroy(g)));
@@ -148,8 +151,18 @@ int gw_grid_run(gw_grid* g, double seconds, void* stream)
     const double expect = 12.0 * g->dev.n * (seconds / g->cfg.send_interval + 2.0)
                         + (g->cfg.mobile ? g->dev.n * (seconds / g->cfg.move_interval + 2.0) : 0.0);
     g->dev.max_events = (uint32_t)(expect * 8.0 < 4.0e9 ? expect * 8.0 + 1000.0 : 4.0e9);
-    if (gw_grid_launch_run(g->dev, seconds, stream)) return gw_set_error(GW_EHIP, "grid run launch failed");
+    int ran = 0;
+    if (gw_grid_launch_run(g->dev, seconds, stream, &ran)) return gw_set_error(GW_EHIP, "grid run launch failed");
+    g->last_width = ran;
     return GW_OK;
+}
+
+int32_t gw_grid_selftest_width(const gw_grid* g, int64_t num_envs, int32_t num_devices)
+{
+    if (g) return g->last_width;
+    if (num_envs <= 0) return gw_set_error(GW_EINVAL, "num_envs must be positive");
+    if (num_devices < 1 || num_devices > GW_GRID_MAX_DEVICES) return gw_set_error(GW_EINVAL, "num_devices must be in [1, %d]", GW_GRID_MAX_DEVICES);
+    return gw_grid_pick_width(num_envs, num_devices);
 }
 
 int gw_grid_set_position(gw_grid* g, int32_t device, const double* x_host, const double* y_host, void* stream)

@@ -228,10 +228,21 @@ struct GwGridDev {
     double slot, send_interval, bit_rate, hdr_bits, pay_bits, hdr_dur, pay_dur, ten_log_br, sqrt2pi;
     uint32_t max_events, mobile;        // bound on events per launch (a logic error must not hang the GPU)
     double   move_interval, move_span, tx_power_dbm, twenty_log_f;
-    double*  txp;                       // [N][n][n] mobile: received power of transmission i stored at radio j
+    double*  txp;                       // [N][n][n] mobile: received power of transmission i stored at radio j; behind it the
+                                        // stand-by state of the links (grid_phy.hip: grid_link_row, grid_link_masks)
     unsigned long long seed;
 };
-int gw_grid_launch_run(const GwGridDev& g, double seconds, void* stream);
+// Lanes per replica of grid_run_kernel<MOBILE, GW>: the power of two that holds its n radios, 64 / GW replicas per wave ...
+// unless that leaves SIMDs without a wave (1 024 of them): a small batch spreads out first (4 096 replicas of 4 radios:
+// groups of 16 lanes, four replicas per wave, 1 024 waves -- sixteen per wave would be 256 waves on a quarter of the chip).
+// Pure: the launcher and gw_grid_selftest_width both ask here.
+static inline int gw_grid_pick_width(int64_t N, int n)
+{
+    int gw = n <= 4 ? 4 : (n <= 8 ? 8 : (n <= 16 ? 16 : (n <= 32 ? 32 : 64)));
+    while (gw < 64 && N <= (65536 - 64) / gw) gw *= 2;      // fewer than 1 024 waves: (N * gw + 63) / 64 < 1024, without the product
+    return gw;
+}
+int gw_grid_launch_run(const GwGridDev& g, double seconds, void* stream, int* width_ran);   // width_ran: the GW it launched
 int gw_grid_launch_set_position(const GwGridDev& g, int dev, const double* xs, const double* ys, void* stream);
 int gw_grid_launch_init(const GwGridDev& g, const double* delays_dev, const double* pos_dev, double thermal, void* stream);
 

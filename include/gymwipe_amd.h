@@ -739,12 +739,20 @@ int gw_grid_run(gw_grid* g, double seconds, void* stream);
 /* Position.set(x, y) of device `device` in every replica at the replicas' current time (devices/core.py:77-86):
  * the attenuation of every link of that device changes and every radio that is hearing a transmission over
  * such a link updates its received power and re-integrates its bit errors (simple_stack.py:119-128).
+ * A move that leaves two radios 3000 m or more apart puts their link in stand-by (physical.py:371-386): powers already
+ * stored stay, and transmissions that start later are still received over the link's old attenuation, until a move brings
+ * the two within 3000 m again.
  * x_host / y_host: double[N].  Needs cfg.mobile != 0 (per-replica geometry); set move_interval very large to
  * have scripted moves only. */
 int gw_grid_set_position(gw_grid* g, int32_t device, const double* x_host, const double* y_host, void* stream);
 /* host copies: "now" f64[N] | "events","n_tx","flags","on_air" u32[N] (on_air = transmissions currently active) | "n_sent","hdr_ok","hdr_fail","pay_ok","pay_fail" u32[N][n]
  *              | "rx_power" f64[N][n] | "pos" f64[N][n][2] */
 int gw_grid_get_state(gw_grid* g, const char* field, void* dst_host, size_t bytes);
+/* Test hook (cf. gw_selftest_launches): the lanes per replica (4, 8, 16, 32 or 64) of grid_run_kernel<mobile, width>.
+ * With a handle: the width of that handle's last gw_grid_run, 0 before any run (num_envs / num_devices are ignored).
+ * With g == NULL: the width the launcher would pick for (num_envs, num_devices); needs no GPU.  Negative GW_E* code for
+ * num_envs <= 0 or num_devices outside [1, GW_GRID_MAX_DEVICES]. */
+int32_t gw_grid_selftest_width(const gw_grid* g, int64_t num_envs, int32_t num_devices);
 
 /* ---- Control loop (second half): the pendulum env with its loop closed -------------------------------
  * BUILDER-DEFINED: the reference intends this loop (plants/sliding_pendulum.py:116-155, control/inverted_pendulum.py:16-69,

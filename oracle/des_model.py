@@ -1358,7 +1358,7 @@ def grid_positions(n):
 class GridDevice(Device):
     """SendingDevice (tests/test_benchmark.py:20-50): a PHY and a sender process, no MAC."""
 
-    def __init__(self, world, index, x, y, send_interval, initial_delay):
+    def __init__(self, world, index, x, y, send_interval, initial_delay, tx_power_dbm=GRID_TX_POWER_DBM):
         Device.__init__(self, world.sim, "Device%d" % index, x, y)
         self.index = index
         self.phy = Phy(world.sim, self, world.band)
@@ -1371,19 +1371,19 @@ class GridDevice(Device):
             while True:
                 yield sim.timeout(send_interval)
                 packet = Pkt(MacHeader(bytes([0] * 5 + [index % 255]), bytes([255] * 6), 0), Blob(GRID_MESSAGE))
-                cmd = Cmd(sim, "SEND", packet=packet, power=GRID_TX_POWER_DBM, mcs=self.mcs)
+                cmd = Cmd(sim, "SEND", packet=packet, power=tx_power_dbm, mcs=self.mcs)
                 self.n_sent += 1
                 self.phy.mac_in.trigger(cmd)
         sim.process(sender())
 
 
-def scenario_grid(n, initial_delays, sim_time, moves=None, positions=None):
+def scenario_grid(n, initial_delays, sim_time, moves=None, positions=None, tx_power_dbm=GRID_TX_POWER_DBM):
     """Run the grid for `sim_time` seconds.  `initial_delays[i]` replaces random.uniform(0, SEND_INTERVAL)
     (tests/test_benchmark.py:67); `moves` (optional) is a list of (time, device, x, y) position updates
     standing in for the mover processes (:73-85).  Returns per-device counters and final state."""
     w = World()
     pos = positions or grid_positions(n)
-    devs = [GridDevice(w, i, pos[i][0], pos[i][1], GRID_SEND_INTERVAL, initial_delays[i]) for i in range(n)]
+    devs = [GridDevice(w, i, pos[i][0], pos[i][1], GRID_SEND_INTERVAL, initial_delays[i], tx_power_dbm) for i in range(n)]
     if moves:
         def mover():
             last = 0.0
@@ -1430,13 +1430,13 @@ def grid_uniform(seed, replica, device, k, which):
     return (h >> 11) * (1.0 / 9007199254740992.0)
 
 
-def scenario_mobile_grid(n, initial_delays, sim_time, seed=0, replica=0, runs=None):
+def scenario_mobile_grid(n, initial_delays, sim_time, seed=0, replica=0, runs=None, tx_power_dbm=GRID_TX_POWER_DBM):
     """device_grid + mobile_device_grid: every device also runs a mover process that, from a random phase
     in [0, MOVE_INTERVAL), shifts its position by uniform(-.2, .2) in x and y every MOVE_INTERVAL
     (a random walk: `initialPos` aliases the live position object, tests/test_benchmark.py:76-82)."""
     w = World()
     pos = grid_positions(n)
-    devs = [GridDevice(w, i, pos[i][0], pos[i][1], GRID_SEND_INTERVAL, initial_delays[i]) for i in range(n)]
+    devs = [GridDevice(w, i, pos[i][0], pos[i][1], GRID_SEND_INTERVAL, initial_delays[i], tx_power_dbm) for i in range(n)]
     sim = w.sim
 
     def mover(dv):

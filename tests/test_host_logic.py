@@ -464,7 +464,8 @@ def test_bench_self_launch_happens_before_torch_is_imported():
 # ---- the kernel catalogue: every instantiation of the step / rollout families has a GPU parity recipe ----------------------
 KERNEL_FAMILIES = ("ct_step_sfx_kernel", "ct_rollout_sync_kernel", "ct_rollout_sfx_kernel", "pend_step_kernel",
                    "ct_step_kernel", "ct_step_live_kernel")
-# templated kernels outside this catalogue, with checkers of their own (tests/test_grid.py, tests/test_control_loop.py);
+# templated kernels outside this catalogue, with checkers of their own (grid_run_kernel: tests/test_grid.py at lane-group width 64,
+# tests/test_grid_widths.py at the packed widths -- test_grid_tests_reach_every_instantiation below; tests/test_control_loop.py);
 # episodes_step_kernel<SCORED>: the per-step forms' bookkeeping, no DT x MODE family and not in the launch record -- <false> is
 # what the per-step sections of tests/test_rollout_episodes.py, test_rollout_autoreset.py and test_rollout_population.py run,
 # <true> what those of tests/test_rollout_scored.py and test_rollout_autoreset_scored.py run, each against the oracle
@@ -523,3 +524,56 @@ def test_launch_record_query_without_a_gpu(native_lib):
     assert native_lib.gw_selftest_launches(None, buf, len(buf)) == need and len(buf.value) == need
     assert native_lib.gw_selftest_launches(None, None, 8) < 0
     assert native_lib.gw_selftest_launches(None, buf, -1) < 0
+
+
+# ---- the PHY grid's lane-group width: the launcher's rule, and the instantiations the grid tests reach -----------------------
+def test_grid_width_rule_at_its_boundaries(native_lib):
+    """gw_grid_selftest_width(NULL, N, n): what gw_grid_run would launch, without a GPU.  The minimal width (the power of two
+    >= n, at least 4) is kept from the batch size at which it fills 1 024 waves, and doubles below that."""
+    from gymwipe_amd import _native as nat
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_grid_widths as gwt
+    width = native_lib.gw_grid_selftest_width
+    for gw0, n, first in ((4, 4, 16369), (8, 8, 8185), (16, 16, 4093), (32, 32, 2047)):
+        assert width(None, first, n) == gw0 and width(None, first - 1, n) == 2 * gw0, (gw0, n, first)
+        assert width(None, 1 << 40, n) == gw0 and width(None, first, n - 1 if n > 4 else 1) == gw0
+    assert [width(None, N, 33) for N in (1, 2047, 1 << 20)] == [64, 64, 64]
+    assert [width(None, (1 << 63) - 1, n) for n in (1, 4, 5, 16, 17, 33)] == [4, 4, 8, 16, 32, 64]     # no N * width product
+    assert [width(None, N, 64) for N in (1, 1 << 20)] == [64, 64]
+    assert [width(None, N, 1) for N in (1, 1023, 2046, 2047, 4092, 4093, 8184, 8185, 16368, 16369, 1 << 30)] \
+        == [64, 64, 64, 32, 32, 16, 16, 8, 8, 4, 4]
+    for n in (1, 2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 64):
+        for N in (1, 6, 1024, 2046, 2047, 4092, 4093, 8184, 8185, 16368, 16369, 100000):
+            assert width(None, N, n) == gwt.launcher_width(N, n), (N, n)
+    for N, n in ((0, 4), (-1, 4), (16, 0), (16, -3), (16, 65)):
+        assert width(None, N, n) == nat.EINVAL, (N, n)
+        assert b"num_" in native_lib.gw_last_error()
+
+
+def test_grid_tests_reach_every_instantiation(native_lib):
+    """The (mobile, width) pairs tests/test_grid_widths.py runs (each case asserts the width it ran), with width 64 from
+    tests/test_grid.py, are exactly the grid_run_kernel<...> instantiations of the library; and every case of either file
+    lands on the width it is listed under."""
+    from gymwipe_amd import _native
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_grid_widths as gwt
+    import test_kernel_variants as kv
+    from util import kernel_instantiations
+    lib_set = kernel_instantiations(_native.LIB_PATH, "grid_run_kernel")
+    assert len(lib_set) == 10
+    import test_grid as tg
+
+    def cases(fn):                                       # tests/test_grid.py's parametrisations: (n, N, T)
+        return [(n, N) for mark in fn.pytestmark if mark.name == "parametrize" for n, N, _ in mark.args[1]]
+    small = {False: cases(tg.test_grid_kernel_matches_event_driven_oracle), True: cases(tg.test_mobile_grid_kernel_matches_event_driven_oracle)}
+    assert len(small[False]) >= 7 and len(small[True]) >= 5
+    pairs = set(gwt.WIDTH_PAIRS)
+    for mobile, shapes in small.items():
+        pairs |= {(mobile, native_lib.gw_grid_selftest_width(None, N, n)) for n, N in shapes}
+    assert {m for m, w in pairs if w == 64} == {False, True}
+    assert {"grid_run_kernel<%s, %d>" % ("true" if m else "false", w) for m, w in pairs} == lib_set
+    for w, n, N in gwt.STATIC_CASES + gwt.MOBILE_CASES + gwt.BER_STATIC_CASES + gwt.BER_MOBILE_CASES:
+        assert native_lib.gw_grid_selftest_width(None, N, n) == w == gwt.launcher_width(N, n), (w, n, N)
+        per_wave = 64 // w
+        assert w == 64 or N % per_wave != 0 or n < w, "the last wave partial or a group with idle lanes: %s" % ((w, n, N),)
+    assert not any(name.startswith("grid_run_kernel") for name in kv.RECIPES)
