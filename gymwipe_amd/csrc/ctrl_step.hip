@@ -13,8 +13,11 @@
 //     ct_step.hip, whose helpers are shared.
 // One lane per environment; both MAC queues are explicit rings of payload values (packet sizes are constant); a step's
 // appends are staged in LDS and flushed once, the addressed queue's head is prefetched.
-// Event order at equal times follows the insertion rule: ticks before t first, then the delivery at t (its
-// completion event was queued when the transmission started, more than a tick interval ago), then a tick at t.
+// Event order at equal times follows the insertion rule: a tick at t runs BEFORE the delivery of a transmission that ends
+// at t.  The tick's event was queued one interval ago; the delivery is not the transmission's completion event itself but
+// two events further on (the receiving MAC's process starts, then hands the payload up), both queued at t, behind the tick.
+// So the controller answers, and the plant moves, on what they held before the packet.  A tick on the step's end belongs to
+// the step.  Either tie raises GW_FLAG_TIE.
 #include "ctrl_common.hip.h"
 
 using namespace gwk;

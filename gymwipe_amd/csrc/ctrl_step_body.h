@@ -111,12 +111,11 @@
                 const bool ok = receive(m, s_ber[(dst * CR + d) * S + pick(L.rxs, dst)], x, br, hdr_bits,
                                         (double)(((int)sz - mh) * 8) * k.coded_factor, L.fl);
                 if (!(x.t_e < t_end)) L.fl |= GW_FLAG_CARRY;
-                ticks_until(x.t_e, false);                                      // ticks during the transmission
-                if (ok) {                                                       // ... then the delivery at t_e ...
+                ticks_until(x.t_e, true);                                       // ticks during the transmission, one exactly on its end
+                if (ok) {                                                       // included; then the delivery at t_e
                     if (d == 0) { L.ang = v * deg_per_rad; L.got1++; }          // degrees(value), control/inverted_pendulum.py:41
                     else { L.u = v; L.got2++; }
                 }
-                ticks_until(x.t_e, true);                                       // ... then a tick falling exactly on it
                 cur = x.t_e;
                 if (!(cur < stopw)) break;
             }

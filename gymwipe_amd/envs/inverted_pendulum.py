@@ -149,7 +149,7 @@ class VecControlLoopEnv(BaseEnv):
     SENSOR, CONTROLLER, ACTUATOR = 0, 1, 2
 
     def __init__(self, num_envs, device="cuda:0", ctrl_start_tick=None, ctrl_period_ticks=None, positions=None, x0=None,
-                 A=None, B=None, u0=None):
+                 A=None, B=None, u0=None, counter_interval=None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gymwipe_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -169,6 +169,8 @@ class VecControlLoopEnv(BaseEnv):
         if positions is not None:                          # sensor, controller, actuator, RRM
             for i, (x, y) in enumerate(positions):
                 cfg.net.pos[i][0], cfg.net.pos[i][1] = float(x), float(y)
+        if counter_interval is not None:                   # seconds between two counter ticks (sensor sample + plant substep)
+            cfg.net.counter_interval = float(counter_interval)
         if x0 is not None:
             for i, v in enumerate(x0):
                 cfg.x0[i] = float(v)

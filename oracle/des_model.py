@@ -997,7 +997,7 @@ class ControlLoopModel:
     SENSOR, CONTROLLER, ACTUATOR = 0, 1, 2
 
     def __init__(self, positions=((0.0, 0.0), (0.0, -1.0), (0.5, 0.0)), rrm_pos=(0.0, 1.0), start=20, period=10,
-                 A=None, B=None, x0=(0.0, 0.0, 0.05, 0.0), u0=0.1):
+                 A=None, B=None, x0=(0.0, 0.0, 0.05, 0.0), u0=0.1, counter_interval=None):
         if A is None:                        # input sign chosen so that the reference's control law (u = -angle) damps
             A, B = default_plant_matrices()
             B = [-b for b in B]
@@ -1010,12 +1010,15 @@ class ControlLoopModel:
         self.start, self.period = start, period
         self.tick = 0
         self.n_cmd = 0
+        self.interval = interval = COUNTER_INTERVAL if counter_interval is None else counter_interval
+        self.wake = 0.0                      # when the next counter tick falls: a running sum, as the event heap keeps it
 
         def sensor_proc():
             while True:
                 sensor.send(Blob(self.plant.x[2], 2), controller.mac_addr)
                 self.plant.step()
-                yield sim.timeout(COUNTER_INTERVAL)
+                self.wake = sim.now + interval
+                yield sim.timeout(interval)
 
         def controller_proc():
             k = 0
@@ -1025,7 +1028,7 @@ class ControlLoopModel:
                     self.n_cmd += 1
                 k += 1
                 self.tick = k
-                yield sim.timeout(COUNTER_INTERVAL)
+                yield sim.timeout(interval)
 
         def receiver(dev, on_receive):
             def loop():
