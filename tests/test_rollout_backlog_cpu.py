@@ -26,9 +26,9 @@ PROLOGUE = 6
 MODERATE = 0.02                         # counter_interval at which the queues stay between 0 and 14
 
 
-def new_oracle(D, n, counter_interval=None, mult=None, start_time=None):
+def new_oracle(D, n, counter_interval=None, mult=None, start_time=None, positions=None, rrm_pos=None):
     from oracle.ct_oracle import CtOracle, default_config
-    cfg = default_config(D, mult=mult, start_time=start_time)
+    cfg = default_config(D, positions=positions, mult=mult, rrm_pos=rrm_pos, start_time=start_time)
     if counter_interval is not None:
         cfg.counter_interval = counter_interval
     return CtOracle(n, D, config=cfg, nthreads=8)

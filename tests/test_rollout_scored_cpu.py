@@ -86,9 +86,10 @@ def fixed_policy(D, sender, duration):
     return actions.policy_cdf(p)
 
 
-def new_oracle(D, n):
+def new_oracle(D, n, **cfg):
+    """``cfg``: default_config's layout arguments (positions, rrm_pos, start_time, ...); none is the default layout."""
     from oracle.ct_oracle import CtOracle, default_config
-    return CtOracle(n, D, config=default_config(D), nthreads=4)
+    return CtOracle(n, D, config=default_config(D, **cfg), nthreads=4)
 
 
 # ---- the oracle composition -----------------------------------------------------------------------------------------------------

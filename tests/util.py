@@ -14,6 +14,21 @@ def action_stream(seed, steps, num_envs, num_devices, max_duration=20):
     return dev, dur
 
 
+LOSSY_RADII = (1.0, 3.4168, 4.5, 5.5459, 2.0)            # by i % 5: delivers all, partly decoded, never granted (x 2), delivers all
+LOSSY_PARTLY, LOSSY_NEVER = (1,), (2, 3)                   # the residues i % 5 of the partly decoded and the never-granted senders
+
+
+def lossy_layout(num_devices):
+    """The layout on which packets are lost and grants refused: the RRM at the origin, sender i at angle 2 pi i / D and radius
+    LOSSY_RADII[i % 5].  Returns (positions, rrm_position) as VecCounterTrafficEnv and oracle.ct_oracle.default_config take
+    them.  A sender at 3.4168 m decodes the announcement but only some of its data packets reach the RRM; one at 4.5 m or
+    5.5459 m never decodes an announcement, so it is never granted the band (tests/test_rollout_lossy_cpu.py gates both)."""
+    D = int(num_devices)
+    pos = [(LOSSY_RADII[i % 5] * float(np.cos(2.0 * np.pi * i / D)), LOSSY_RADII[i % 5] * float(np.sin(2.0 * np.pi * i / D)))
+           for i in range(D)]
+    return pos, (0.0, 0.0)
+
+
 STATE_FIELDS = ("now", "wake", "counter", "qlen", "queue", "received", "latest_diff",
                 "last_abs", "rx_power", "flags")
 STAT_FIELDS = ("n_tx", "n_delivered", "n_appended", "n_popped", "n_dropped")
