@@ -8,6 +8,14 @@ candidate averaged over envs that start from different angles -- one launch per 
 
 Cost of an episode: the sum of |angle in degrees| over its steps.  With the shipped gain (kp = 1 on degrees) the more the
 controller talks the harder it drives the plant, so "nobody assigned" and "sensor only" are printed beside the best schedule.
+
+    python examples/control_schedule_search.py --feedback [--bins 3] [--airtime-price 0.002]
+
+searches angle-feedback schedulers instead (env.rollout_feedback): a policy is B - 1 thresholds on |observed angle| and one
+cyclic schedule per bin, so "leave the band alone while the pendulum is near upright" is a candidate.  The per-step sum above
+favours whoever takes short steps, so this search ranks by the time-weighted mean |angle| (area / elapsed, degrees) plus
+--airtime-price times the duration units assigned per second of simulated time, and prints the best open-loop schedule -- the
+same search with one bin -- under the same ranking beside the result.
 """
 import argparse
 import os
@@ -28,6 +36,9 @@ def main():
     ap.add_argument("--angle", type=float, default=0.3, help="initial angles are drawn from [-angle, angle] rad")
     ap.add_argument("--generations", type=int, default=6)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--feedback", action="store_true", help="search angle-feedback schedulers (thresholds and per-bin schedules)")
+    ap.add_argument("--bins", type=int, default=3, help="B of --feedback, 1 .. 8")
+    ap.add_argument("--airtime-price", type=float, default=0.002, help="degrees per duration unit assigned per simulated second")
     args = ap.parse_args()
 
     import torch
@@ -42,6 +53,11 @@ def main():
     env.set_initial_state(torch.from_numpy(np.tile(x0, (P, 1))))        # every schedule meets the same M initial states
     episodes = (args.episode_steps, 0.0)                                # a time limit, no failure angle
     steps = args.episode_steps * args.episodes
+
+    if args.feedback:
+        feedback_search(args, env, actions, rng, episodes, steps)
+        env.close()
+        return
 
     def evaluate(candidates):
         """Mean episode cost of each schedule: every env restarts, runs whole episodes, and the tally is summed per schedule."""
@@ -77,6 +93,59 @@ def main():
     print("mean cost per episode of %d steps over %d initial angles: best %.1f | nobody assigned %.1f | sensor only %.1f"
           % (args.episode_steps, M, best_cost, cost[0], cost[1]))
     env.close()
+
+
+def feedback_search(args, env, actions, rng, episodes, steps):
+    """Random search over (thresholds, one schedule per bin), and over open-loop schedules as policies of one bin, both ranked
+    by area / elapsed + price * airtime / elapsed from the tally of one launch per generation and kind."""
+    P, L, B = args.schedules, args.length, args.bins
+
+    def evaluate(candidates):
+        env.reset_envs()
+        sched, edges = actions.make_ctrl_feedback([c[1] for c in candidates], [c[0] for c in candidates], L)
+        _, sums = env.rollout_feedback(sched, edges, episodes, steps, abs_key=True)
+        sums = sums.cpu().numpy()
+        error, airtime = sums[:, 6] / sums[:, 5], sums[:, 4] / sums[:, 5]
+        score = error + args.airtime_price * airtime
+        return np.where(np.isfinite(score), score, np.inf), error, airtime
+
+    def random_schedule():
+        return list(zip(rng.integers(0, 2, L).tolist(), rng.integers(0, 20, L).tolist()))
+
+    def random_policy(bins):
+        return sorted(rng.integers(1, 60, bins - 1).tolist()), [random_schedule() for _ in range(bins)]
+
+    def mutated(policy):
+        edges, scheds = list(policy[0]), [list(s) for s in policy[1]]
+        if edges and rng.integers(0, 3) == 0:                           # move a threshold ...
+            j = int(rng.integers(0, len(edges)))
+            edges[j] = int(np.clip(edges[j] + rng.integers(-5, 6), 1, 89))
+        else:                                                           # ... or rewrite one entry of one bin's schedule
+            scheds[int(rng.integers(0, len(scheds)))][int(rng.integers(0, L))] = (int(rng.integers(0, 2)), int(rng.integers(0, 20)))
+        return edges, scheds
+
+    best = {}
+    for g in range(args.generations):
+        for kind, bins in (("feedback", B), ("open loop", 1)):
+            have = best.get(kind)
+            keep = [have[0]] if have else []
+            if kind == "feedback" and B > 1 and not have:               # idle near upright, alternate beyond: the README's policy
+                keep = [([2] + [89] * (B - 2), [[(0, 0)] * L] + [[(0, 19), (1, 19)] * (L // 2) + [(0, 19)] * (L % 2)] * (B - 1))]
+            candidates = keep + [mutated(have[0]) if have and i % 2 else random_policy(bins) for i in range(P - len(keep))]
+            score, error, airtime = evaluate(candidates)
+            i = int(score.argmin())
+            if not have or score[i] < have[1]:
+                best[kind] = (candidates[i], float(score[i]), float(error[i]), float(airtime[i]))
+            print("generation %d, %-9s: best of %d score %.3f (error %.3f deg, airtime %.1f units/s), median score %.3g"
+                  % (g, kind, P, score[i], error[i], airtime[i], float(np.median(score))))
+    for kind in ("feedback", "open loop"):
+        (edges, scheds), score, error, airtime = best[kind]
+        print("best %s: score %.3f = %.3f deg time-weighted mean |angle| + %g x %.1f duration units per second"
+              % (kind, score, error, args.airtime_price, airtime))
+        if edges:
+            print("  thresholds on |observed angle|: %s" % edges)
+        for b, sch in enumerate(scheds):
+            print("  bin %d (device, duration) x %d: %s" % (b, L, sch))
 
 
 if __name__ == "__main__":

@@ -33,7 +33,7 @@ EXPORTS = (
     "gw_plant_config_default", "gw_plant_create", "gw_plant_destroy", "gw_plant_update", "gw_plant_set_input",
     "gw_plant_state_ptr", "gw_plant_get_state", "gw_plant_feedback", "gw_plant_update_feedback", "gw_now_ptr", "gw_pendulum_step",
     "gw_ctrl_config_default", "gw_ctrl_create", "gw_ctrl_destroy", "gw_ctrl_step", "gw_ctrl_get_state",
-    "gw_ctrl_set_initial", "gw_ctrl_reset", "gw_ctrl_rollout", "gw_ctrl_rollout_schedules",
+    "gw_ctrl_set_initial", "gw_ctrl_reset", "gw_ctrl_rollout", "gw_ctrl_rollout_schedules", "gw_ctrl_rollout_feedback",
     "gw_grid_config_default", "gw_grid_create", "gw_grid_destroy", "gw_grid_run", "gw_grid_get_state", "gw_grid_set_position",
     "gw_grid_selftest_width",
 )
@@ -81,6 +81,22 @@ class CtrlEpisodes(C.Structure):
     """gw_ctrl_episodes (include/gymwipe_amd.h): an episode of the control loop ends at ``max_steps`` steps (0: no limit) or when
     |angle in degrees| exceeds ``fail_deg`` (<= 0: no limit)."""
     _fields_ = [("max_steps", C.c_int32), ("pad", C.c_int32), ("fail_deg", C.c_double)]
+
+
+CTRL_FB_MAX_BINS, CTRL_FB_COLS, CTRL_FB_ABS = 8, 8, 1
+
+
+class CtrlFeedback(C.Structure):
+    """gw_ctrl_feedback: P angle-feedback policies of B bins, a cyclic schedule of L (device, duration) bytes per bin; the key is
+    the env's int32 observation, or its absolute value with ``CTRL_FB_ABS`` in ``flags``."""
+    _fields_ = [("num_policies", C.c_int32), ("num_bins", C.c_int32), ("length", C.c_int32), ("flags", C.c_int32),
+                ("edges_dev", C.c_void_p), ("sched_dev", C.c_void_p)]
+
+
+class CtrlFeedbackRows(C.Structure):
+    """gw_ctrl_feedback_rows: the six per-step outputs, each [steps][N]; only ``angle_deg_dev`` may be NULL."""
+    _fields_ = [("device_out_dev", C.c_void_p), ("duration_out_dev", C.c_void_p), ("obs_dev", C.c_void_p),
+                ("reward_dev", C.c_void_p), ("angle_deg_dev", C.c_void_p), ("ended_dev", C.c_void_p)]
 
 
 class PlantConfig(C.Structure):
@@ -328,6 +344,9 @@ def lib():
     L.gw_ctrl_rollout.restype = C.c_int
     L.gw_ctrl_rollout_schedules.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.POINTER(CtrlEpisodes), vp, vp]
     L.gw_ctrl_rollout_schedules.restype = C.c_int
+    L.gw_ctrl_rollout_feedback.argtypes = [vp, C.c_int32, C.POINTER(CtrlFeedback), C.POINTER(CtrlEpisodes), C.POINTER(CtrlFeedbackRows),
+                                           vp, vp]
+    L.gw_ctrl_rollout_feedback.restype = C.c_int
     L.gw_plant_update_feedback.argtypes, L.gw_plant_update_feedback.restype = [vp, vp, C.c_int64, vp, vp, vp, vp], C.c_int
     L.gw_now_ptr.argtypes, L.gw_now_ptr.restype = [vp, C.POINTER(vp), C.POINTER(i64)], C.c_int
     L.gw_pendulum_step.argtypes, L.gw_pendulum_step.restype = [vp, vp, vp, vp, vp, vp, vp, vp], C.c_int

@@ -524,3 +524,55 @@ def ctrl_schedule_numpy(schedules, age, envs_per_schedule, max_duration=20):
     p = np.arange(age.shape[0]) // int(envs_per_schedule)
     row = sch[p, age % sch.shape[1]].astype(np.int32)
     return np.minimum(row[:, 0], 1).astype(np.int32), np.minimum(row[:, 1], int(max_duration) - 1).astype(np.int32)
+
+
+# ---- control loop: angle-feedback band schedulers (gw_ctrl_rollout_feedback) -----------------------------------------------------------
+CTRL_FB_MAX_BINS = 8            # bins of one policy
+CTRL_FB_COLS = 8                # the schedule tally's four, then: durations assigned, time elapsed, sum of |angle| dt, steps in bin 0
+
+
+def make_ctrl_feedback(policies, edges, L=None):
+    """``(sched uint8[P][B][L][2], edges int32[P][B - 1])`` from P policies, each a list of B cyclic schedules of
+    ``(device, duration)`` pairs, and their B - 1 edges each: what ``VecControlLoopEnv.rollout_feedback`` uploads.  An env whose
+    key (its int32 observation, or the absolute value of it) has ``n`` edges at or below it acts on schedule ``n`` of its policy.
+    ``L`` defaults to the longest schedule; shorter ones are padded cyclically as ``make_ctrl_schedules`` pads.  The edges need
+    not be sorted."""
+    pols = [list(p) for p in policies]
+    if not pols or any(not p for p in pols):
+        raise ValueError("make_ctrl_feedback: at least one policy, each with at least one bin")
+    B = len(pols[0])
+    if not 1 <= B <= CTRL_FB_MAX_BINS or any(len(p) != B for p in pols):
+        raise ValueError("make_ctrl_feedback: every policy needs the same number of bins, 1 <= B <= %d" % CTRL_FB_MAX_BINS)
+    edge_rows = [[int(v) for v in r] for r in edges]
+    if len(edge_rows) != len(pols) or any(len(r) != B - 1 for r in edge_rows):
+        raise ValueError("make_ctrl_feedback: B - 1 edges for each policy")
+    if any(not (-2 ** 31 <= v < 2 ** 31) for r in edge_rows for v in r):
+        raise ValueError("make_ctrl_feedback: an edge is an int32")
+    if L is None:
+        L = max((len(s) for p in pols for s in p), default=0)
+    sched = np.stack([make_ctrl_schedules(p, L) for p in pols])
+    return sched, np.array(edge_rows, np.int32).reshape(len(pols), B - 1)
+
+
+def ctrl_feedback_numpy(sched, edges, x_angle_rad, age, envs_per_policy, abs_key, max_duration=20):
+    """The action env e takes in a state whose angle is ``x_angle_rad[e]`` at episode age ``age[e]``, rules 1-3 of
+    ``gw_ctrl_rollout_feedback``: ``o = int32(min(max(angle * (180 / pi), -1e9), 1e9))`` (NaN gives -1e9), the key is ``o`` or
+    ``|o|``, the bin is the number of the policy's edges at or below the key, the action entry ``age % L`` of that bin's schedule
+    of policy ``e // envs_per_policy``, clamped where it is read -- device to {0, 1}, duration to [0, max_duration - 1].
+    Returns ``(device, duration, bin)`` as int32[N]."""
+    sch, edg = np.asarray(sched), np.asarray(edges)
+    if sch.dtype != np.uint8 or sch.ndim != 4 or sch.shape[3] != 2:
+        raise ValueError("ctrl_feedback_numpy: sched is uint8[P][B][L][2]")
+    P, B, L = sch.shape[:3]
+    if edg.dtype != np.int32 or edg.shape != (P, B - 1):
+        raise ValueError("ctrl_feedback_numpy: edges is int32[P][B - 1]")
+    deg = np.asarray(x_angle_rad, np.float64) * (180.0 / 3.141592653589793)
+    deg = np.where(np.isnan(deg), -1e9, deg)                         # fmax(NaN, -1e9) is -1e9
+    o = np.minimum(np.maximum(deg, -1e9), 1e9).astype(np.int64)      # truncation toward zero, as the int32 cast
+    key = np.abs(o) if abs_key else o
+    age = np.asarray(age, np.int64)
+    p = np.arange(age.shape[0]) // int(envs_per_policy)
+    bins = (edg[p].astype(np.int64) <= key[:, None]).sum(1)
+    row = sch[p, bins, age % L].astype(np.int32)
+    return (np.minimum(row[:, 0], 1).astype(np.int32), np.minimum(row[:, 1], int(max_duration) - 1).astype(np.int32),
+            bins.astype(np.int32))

@@ -207,6 +207,33 @@ int gw_ctrl_rollout_schedules(gw_ctrl* c, int32_t steps, const uint8_t* sched_de
     return GW_OK;
 }
 
+int gw_ctrl_rollout_feedback(gw_ctrl* c, int32_t steps, const gw_ctrl_feedback* fb, const gw_ctrl_episodes* ep,
+                             const gw_ctrl_feedback_rows* rows, double* tally_dev, void* stream)
+{
+    if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
+    if (!fb) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: fb is NULL");
+    if (!ep) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: ep is NULL (episodes are required)");
+    if (!tally_dev || !fb->sched_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: NULL device pointer");
+    if (ep->max_steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: max_steps < 0");
+    if (steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: steps < 0");
+    if (fb->num_policies < 1) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: P must be >= 1");
+    if (fb->num_bins < 1 || fb->num_bins > GW_CTRL_FB_MAX_BINS)
+        return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: B must be in [1, %d]", GW_CTRL_FB_MAX_BINS);
+    if (fb->length < 1 || fb->length > 64) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: L must be in [1, 64]");
+    if (fb->num_bins > 1 && !fb->edges_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: edges_dev is NULL with B > 1");
+    if (rows && (!rows->device_out_dev || !rows->duration_out_dev || !rows->obs_dev || !rows->reward_dev || !rows->ended_dev))
+        return gw_set_error(GW_EINVAL, "gw_ctrl_rollout_feedback: NULL pointer in rows (only angle_deg_dev may be NULL)");
+    if (steps == 0) return GW_OK;
+    const int64_t N = c->dev.N;
+    const int32_t P = fb->num_policies;
+    if (N % P != 0 || (N / P) % 64 != 0)
+        return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_feedback: num_envs / P must be a whole multiple of 64 (one policy per block)");
+    CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
+    if (gw_ctrl_launch_rollout_feedback(c->dev, c->epi, steps, *fb, *ep, rows, tally_dev, stream))
+        return gw_set_error(GW_EHIP, "control-loop feedback rollout launch failed");
+    return GW_OK;
+}
+
 int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst, size_t bytes)
 {
     if (!c || !field || !dst) return gw_set_error(GW_EINVAL, "handle/field/dst is NULL");

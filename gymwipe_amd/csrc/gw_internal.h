@@ -279,6 +279,9 @@ int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps
                            const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg, uint8_t* ended, void* stream);
 int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const uint8_t* sched, int32_t P, int32_t L,
                                      const gw_ctrl_episodes& ep, double* tally, void* stream);
+int gw_ctrl_launch_rollout_feedback(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const gw_ctrl_feedback& fb,
+                                    const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows, double* tally,
+                                    void* stream);                                      // ctrl_rollout_feedback.hip
 int gw_fill_dev_const(const gw_config& cfg, const GwHostTables& tab, GwDevConst& k);   // gw_api.cpp
 int gw_validate_config(const gw_config& cfg);                                           // gw_api.cpp
 

@@ -145,7 +145,8 @@ class VecControlLoopEnv(BaseEnv):
     "duration": int32[N]}) -> (obs, reward, done, {"Sensor angle": deg})``.
     Beyond one step per launch: ``set_initial_state`` / ``reset_envs`` (an initial state per env; a masked reset that leaves a
     fresh env), ``rollout`` (K steps in one launch, optionally with episodes that end at a time limit or a failure angle and
-    reset inside the launch) and ``rollout_schedules`` (P cyclic band schedules, a per-env tally, nothing stored per step)."""
+    reset inside the launch), ``rollout_schedules`` (P cyclic band schedules, a per-env tally, nothing stored per step) and
+    ``rollout_feedback`` (P angle-feedback schedulers: the env's own angle picks which of B schedules it acts on)."""
     SENSOR, CONTROLLER, ACTUATOR = 0, 1, 2
 
     def __init__(self, num_envs, device="cuda:0", ctrl_start_tick=None, ctrl_period_ticks=None, positions=None, x0=None,
@@ -306,6 +307,42 @@ class VecControlLoopEnv(BaseEnv):
             nat.check(self._L.gw_ctrl_rollout_schedules(self._h, int(steps), sch.data_ptr(), P, L,
                                                         C.byref(ep) if ep is not None else None, tally.data_ptr(), self._stream()))
         return tally, tally.view(P, self.num_envs // P, 4).sum(1)
+
+    def rollout_feedback(self, sched, edges, episodes, steps, abs_key=True, record=False):
+        """Evaluate P angle-feedback band schedulers (``actions.make_ctrl_feedback``: ``sched`` uint8[P][B][L][2], ``edges``
+        int32[P][B - 1]) for ``steps`` steps in one launch, env e under policy ``e // (N / P)``.  Before each step the env's key
+        is the int32 observation of its current state (``abs_key``: the absolute value of it), its bin the number of its
+        policy's edges at or below the key, its action entry ``age % L`` of that bin's schedule; episodes as in ``rollout``
+        (required).  Both tensors are read on the GPU when the launch runs.  Returns ``(tally f64[N][8], sums f64[P][8])``: per
+        env {episodes ended, of those by fail_deg, steps taken, sum of the costs of the ended episodes, durations assigned,
+        time elapsed, sum of |angle| dt, steps taken in bin 0} and their sums per policy -- a policy's time-weighted mean
+        error is ``sums[p, 6] / sums[p, 5]``, its airtime per second ``sums[p, 4] / sums[p, 5]``.  ``record=True`` returns
+        as a third value the dict of the six [steps][N] rows: ``device``, ``duration``, ``obs``, ``reward``, ``angle``,
+        ``ended``."""
+        torch = self._torch
+        sch, edg = torch.as_tensor(sched), torch.as_tensor(edges)
+        if sch.dtype != torch.uint8 or sch.dim() != 4 or sch.shape[3] != 2:
+            raise ValueError("sched must be uint8[P][B][L][2] (actions.make_ctrl_feedback)")
+        P, B, L = int(sch.shape[0]), int(sch.shape[1]), int(sch.shape[2])
+        if edg.dtype != torch.int32 or tuple(edg.shape) != (P, B - 1):
+            raise ValueError("edges must be int32[P][B - 1] (actions.make_ctrl_feedback)")
+        sch, edg = sch.to(self.device).contiguous(), edg.to(self.device).contiguous()
+        ep = self._episodes(episodes)
+        K, n = int(steps), self.num_envs
+        fb = nat.CtrlFeedback(P, B, L, nat.CTRL_FB_ABS if abs_key else 0, edg.data_ptr() if B > 1 else None, sch.data_ptr())
+        tally = torch.zeros((n, nat.CTRL_FB_COLS), dtype=torch.float64, device=self.device)
+        rows = out = None
+        if record:
+            dts = (("device", torch.int32), ("duration", torch.int32), ("obs", torch.int32), ("reward", torch.float32),
+                   ("angle", torch.float64), ("ended", torch.uint8))
+            out = {name: torch.empty((max(K, 0), n), dtype=dt, device=self.device) for name, dt in dts}
+            if K > 0:                                      # (an empty tensor has no address to pass)
+                rows = nat.CtrlFeedbackRows(*(out[name].data_ptr() for name, _ in dts))
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_ctrl_rollout_feedback(self._h, K, C.byref(fb), C.byref(ep) if ep is not None else None,
+                                                       C.byref(rows) if rows is not None else None, tally.data_ptr(), self._stream()))
+        sums = tally.view(P, n // P, nat.CTRL_FB_COLS).sum(1)
+        return (tally, sums, out) if record else (tally, sums)
 
     _FIELDS = {"now": ((), "f8"), "wake": ((), "f8"), "u": ((), "f8"), "angle_deg": ((), "f8"), "x": ((4,), "f8"),
                "rx_power": ((4,), "f8"), "qlen": ((2,), "i4"), "received": ((2,), "u4"), "n_tx": ((), "u4"),

@@ -822,6 +822,50 @@ int gw_ctrl_rollout(gw_ctrl* c, int32_t steps, const int32_t* device_dev, const 
 int gw_ctrl_rollout_schedules(gw_ctrl* c, int32_t steps, const uint8_t* sched_dev, int32_t P, int32_t L, const gw_ctrl_episodes* ep,
                               double* tally_dev, void* stream);
 
+/* P angle-feedback band schedulers evaluated in one launch: before each step the env looks at its own pendulum and picks, by the
+ * angle, which of B cyclic schedules it acts on.  Step k of env e, with p = e / (N / P):
+ *   1. deg = x[2] * (180.0 / 3.141592653589793) of the env's CURRENT state -- the angle its last step reported, or that of its
+ *      own x_init where the previous step ended an episode: the value gw_ctrl_reset reports.
+ *      o = (int32_t) fmin(fmax(deg, -1e9), 1e9): the observation for every |deg| < 1e9, and defined beyond (NaN gives -1e9).
+ *      key = (flags & GW_CTRL_FB_ABS) ? |o| : o.
+ *   2. bin = #{ j < B - 1 : edges[p][j] <= key }.  The edges need not be sorted: any content has this one meaning.
+ *   3. the action is entry age % L of sched[p][bin], age being the running episode's age in the handle; a byte outside the
+ *      action space is clamped where it is read as in gw_ctrl_rollout_schedules (device to {0, 1}, duration to
+ *      [0, max_duration - 1]), so no step is ever flagged GW_FLAG_BADACT.
+ *   4. the step and the episode rule run exactly as gw_ctrl_rollout with ep runs them for that action (ep is required): age,
+ *      cost, both ending bits, the in-launch reset to a fresh env of its own x_init / u_init.
+ *   5. with rows: row k receives the action taken and what gw_ctrl_rollout would write (angle_deg_dev may be NULL).
+ *   6. tally_dev f64[N][GW_CTRL_FB_COLS] is overwritten per env, one running f64 each in step order: columns 0-3 are
+ *      gw_ctrl_rollout_schedules' four; 4 the sum of the durations assigned; 5 `elapsed`, the sum of dt, dt being the env's
+ *      clock after the step, BEFORE any reset, minus its clock before the step; 6 area = area + fabs(deg_k) * dt with deg_k
+ *      the angle the step reports; 7 the steps taken in bin 0.  A policy's time-weighted mean error is sum(col 6) / sum(col 5),
+ *      its airtime per second sum(col 4) / sum(col 5); the [P] reduction is the caller's.
+ * No handle state is added: two calls of K/2 leave the state, and write the rows, of one call of K.  The policies are read
+ * stream-ordered from device memory when the launch runs; they are never validated and never read back.
+ * GW_EINVAL: a NULL c / fb / ep / tally_dev / sched_dev, edges_dev NULL with B > 1, a NULL required pointer in rows, steps < 0,
+ * max_steps < 0, P < 1, B outside [1, GW_CTRL_FB_MAX_BINS], L outside [1, 64] -- before any device call and, as in
+ * gw_ctrl_rollout_schedules, before steps == 0 is looked at.  steps == 0 is then GW_OK with no launch, the handle not read and
+ * the tally untouched.  GW_EUNSUPPORTED, state untouched, before any device call: N % P != 0 or (N / P) % 64 != 0 (every 64-env
+ * block follows one policy). */
+#define GW_CTRL_FB_MAX_BINS 8
+#define GW_CTRL_FB_COLS     8
+#define GW_CTRL_FB_ABS      1      /* flags: the key is |o| instead of o */
+typedef struct gw_ctrl_feedback {
+    int32_t num_policies;          /* P >= 1; env e follows policy e / (N / P) */
+    int32_t num_bins;              /* B in [1, GW_CTRL_FB_MAX_BINS] */
+    int32_t length;                /* L in [1, 64] */
+    int32_t flags;                 /* GW_CTRL_FB_ABS or 0 */
+    const int32_t* edges_dev;      /* int32[P][B - 1]; may be NULL iff B == 1 */
+    const uint8_t* sched_dev;      /* uint8[P][B][L][2] = {device, duration} */
+} gw_ctrl_feedback;
+typedef struct gw_ctrl_feedback_rows {   /* all [steps][N]; angle_deg_dev may be NULL, the others not */
+    int32_t *device_out_dev, *duration_out_dev, *obs_dev;
+    float* reward_dev; double* angle_deg_dev; uint8_t* ended_dev;
+} gw_ctrl_feedback_rows;
+int gw_ctrl_rollout_feedback(gw_ctrl* c, int32_t steps, const gw_ctrl_feedback* fb, const gw_ctrl_episodes* ep,
+                             const gw_ctrl_feedback_rows* rows /* NULL: nothing stored per step */,
+                             double* tally_dev /* f64[N][GW_CTRL_FB_COLS], overwritten, never NULL */, void* stream);
+
 /* Host-only self-test hook (no GPU needed): fuzzes the MAC-queue encoding the default kernel uses
  * against an explicit deque(maxlen=100).  Returns the number of mismatches (0 = identical). */
 int gw_selftest_queue(uint64_t seed, int32_t operations, int32_t mult, int32_t counter_bound);

@@ -2,7 +2,7 @@
 """
 The control loop's fused rollout beside what it replaces (profiles/ctrl_rollout/README.md).
 
-VecControlLoopEnv, N envs, calls of K = 64 steps, every env with an initial angle of its own.  Seven legs in ONE process,
+VecControlLoopEnv, N envs, calls of K = 64 steps, every env with an initial angle of its own.  Ten legs in ONE process,
 alternated call by call so that clock and thermal drift hit all alike, each leg on a handle of its own:
   a   K x env.step                                      the only form there was; ctrl_step_kernel is unchanged
   b   env.rollout, no episodes                          the same actions in one launch
@@ -14,9 +14,16 @@ alternated call by call so that clock and thermal drift hit all alike, each leg 
   dc  env.reset_envs + env.rollout with episodes        fed d's schedules expanded to [K][N] actions along every env's own ages
                                                         (found once, before the timing, by a per-step composition): the same
                                                         trajectory, which is why both legs restart their envs in every call
+  f   env.rollout_feedback, no rows                     P angle-feedback policies of --bins bins (profiles/ctrl_feedback/README.md)
+  fn  per step: torch searchsorted (bucketize per       what f replaces, without a host read: the bin from the observation, the
+      policy) + gather, env.step, the rule in torch,    action gathered from the policies, reset_envs(mask) issued every step
+      env.reset_envs(mask)
+  f1  env.reset_envs + env.rollout_feedback, no rows    fed d's schedules as policies of ONE bin: d's trajectory, so f1/d is what
+                                                        the feedback kernel costs beyond the schedule kernel when it has nothing to decide
 A timed unit is one call of K steps between two HIP events and two wall-clock reads, the second after a synchronise; units are
 repeated until every leg has at least `--seconds` of stream time and at least `--min-repeats` units.  Before the timing, b's
-outputs are checked against a's, c's `ended` against cs's and d's tally against dc's `ended`, each pair from one state.
+outputs are checked against a's, c's `ended` against cs's, d's tally against dc's `ended`, f's state against fn's and f1's
+tally against d's, each pair from one state.
 Reported per leg: median, min and max of the wall-clock and event microseconds per step; the ratios of the wall-clock medians;
 and the run-to-run spread of leg a ((max - min) / median), against which b/a is to be read.  One JSON line; --out appends it to
 a file.
@@ -42,7 +49,8 @@ def main():
     ap.add_argument("--fail-deg", type=float, default=90.0)
     ap.add_argument("--seconds", type=float, default=0.25, help="stream time per leg at least")
     ap.add_argument("--min-repeats", type=int, default=5)
-    ap.add_argument("--legs", default="a,b,c,cs,cn,d,dc")
+    ap.add_argument("--bins", type=int, default=3, help="B of legs f and fn")
+    ap.add_argument("--legs", default="a,b,c,cs,cn,d,dc,f,fn,f1")
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -65,6 +73,11 @@ def main():
                                             for _ in range(P)], L)
     sched = torch.from_numpy(sched_np).to(dev)
     p_of = torch.arange(N, device=dev) // (N // P)
+    B = args.bins
+    fb_np = actions.make_ctrl_feedback([[list(zip(rng.integers(0, 2, L).tolist(), rng.integers(0, 20, L).tolist())) for _ in range(B)]
+                                        for _ in range(P)], [sorted(rng.choice(90, B - 1, replace=False).tolist()) for _ in range(P)], L)
+    fb_sched, fb_edges = torch.from_numpy(fb_np[0]).to(dev), torch.from_numpy(fb_np[1]).to(dev)     # keys |o|, sorted edges in [0, 90)
+    one_bin, no_edges = sched[:, None].contiguous(), torch.empty((P, 0), dtype=torch.int32, device=dev)
     x_dev = torch.empty((K, N), dtype=torch.int32, device=dev)         # d's schedules expanded: filled in below
     x_dur = torch.empty((K, N), dtype=torch.int32, device=dev)
 
@@ -134,7 +147,32 @@ def main():
             ag.masked_fill_(gone, 0)
         env.close()
 
-    legs = {"a": leg_a, "b": leg_b, "c": leg_c, "cs": composed("cs", True), "cn": composed("cn", False), "d": leg_d, "dc": leg_dc}
+    def leg_f(env):
+        tally["f"] = env.rollout_feedback(fb_sched, fb_edges, episodes, K)[0]
+
+    fn_age = torch.zeros(N, dtype=torch.int64, device=dev)
+    fn_obs = []
+
+    def leg_fn(env):
+        if not fn_obs:
+            fn_obs.append(env.reset_envs(torch.zeros(N, dtype=torch.uint8, device=dev)))    # resets nothing: the observations
+        obs, ag = fn_obs[0], fn_age
+        for k in range(K):
+            key = obs.abs()
+            b = torch.searchsorted(fb_edges[p_of], key[:, None], right=True)[:, 0] if B > 1 else torch.zeros_like(ag)
+            row = fb_sched[p_of, b, ag % L].to(torch.int32)
+            _, _, _, info = env.step({"device": row[:, 0].clamp(max=1), "duration": row[:, 1].clamp(max=19)})
+            mag = info["Sensor angle"].abs()
+            ag += 1
+            cause = (ag == args.max_steps).to(torch.uint8) | ((mag > args.fail_deg).to(torch.uint8) << 1)
+            obs = env.reset_envs(cause)
+            ag.masked_fill_(cause != 0, 0)
+
+    def leg_f1(env):
+        env.reset_envs()
+        tally["f1"] = env.rollout_feedback(one_bin, no_edges, episodes, K)[0]
+
+    legs = {"f": leg_f, "fn": leg_fn, "f1": leg_f1, "a": leg_a, "b": leg_b, "c": leg_c, "cs": composed("cs", True), "cn": composed("cn", False), "d": leg_d, "dc": leg_dc}
 
     # the legs mean what they say: from one state b gives a's last rows, and c ends the envs its composition ends
     if "a" in names and "b" in names:
@@ -153,6 +191,17 @@ def main():
         leg_dc(envs["dc"])
         ends = (out[2] != 0).sum(0).to(torch.float64)
         assert torch.equal(tally["d"][:, 0], ends) and bool(ends.any()), "the expanded actions end other envs than the schedules"
+    if "f" in names and "fn" in names:
+        leg_f(envs["f"])
+        leg_fn(envs["fn"])
+        for field in ("x", "now", "u", "n_tx"):
+            assert (envs["f"].get_state(field) == envs["fn"].get_state(field)).all(), "the composition leaves another %s than the feedback call" % field
+        assert (envs["f"].get_state("age") == fn_age.cpu().numpy()).all(), "the composition's episodes are not the feedback call's"
+        assert bool((tally["f"][:, 0] > 0).any()) and bool((tally["f"][:, 7] > 0).any()) and bool((tally["f"][:, 7] < K).any())
+    if "f1" in names and "d" in names:
+        leg_d(envs["d"])
+        leg_f1(envs["f1"])
+        assert torch.equal(tally["f1"][:, :4], tally["d"]), "one bin does not give the schedule call's tally"
     for n in names:                                                     # warm-up: first launches, allocator, caches
         legs[n](envs[n])
     torch.cuda.synchronize(dev)
@@ -177,13 +226,13 @@ def main():
     def summary(xs):
         return {"median": round(float(np.median(xs)), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
 
-    res = {"label": args.label, "gpu": torch.cuda.get_device_name(dev), "envs": N, "steps": K, "schedules": P, "length": L,
+    res = {"label": args.label, "gpu": torch.cuda.get_device_name(dev), "envs": N, "steps": K, "schedules": P, "length": L, "bins": B,
            "max_steps": args.max_steps, "fail_deg": args.fail_deg, "repeats": {n: len(wall[n]) for n in names}}
     for n in names:
         res[n] = {"wall_us_per_step": summary(wall[n]), "event_us_per_step": summary(event[n]), "stream_seconds": round(total[n], 3)}
     med = {n: res[n]["wall_us_per_step"]["median"] for n in names}
     res["ratios"] = {"%s/%s" % (x, y): round(med[x] / med[y], 3)
-                     for x, y in (("b", "a"), ("c", "cs"), ("c", "cn"), ("c", "b"), ("d", "dc"), ("d", "c")) if x in med and y in med}
+                     for x, y in (("b", "a"), ("c", "cs"), ("c", "cn"), ("c", "b"), ("d", "dc"), ("d", "c"), ("f", "fn"), ("f1", "d"), ("f", "c")) if x in med and y in med}
     if "a" in names:
         w = res["a"]["wall_us_per_step"]
         res["spread_a"] = round((w["max"] - w["min"]) / w["median"], 3)
