@@ -6,8 +6,9 @@ candidate averaged over envs that start from different angles -- one launch per 
 
     python examples/control_schedule_search.py [--schedules 64] [--envs-per-schedule 64] [--length 8] [--generations 6]
 
-Cost of an episode: the sum of |angle in degrees| over its steps.  With the shipped gain (kp = 1 on degrees) the more the
-controller talks the harder it drives the plant, so "nobody assigned" and "sensor only" are printed beside the best schedule.
+Cost of an episode: the sum of |angle in degrees| over its steps.  With the default gains (the reference's shipped kp = 1 on
+degrees) the more the controller talks the harder it drives the plant, so "nobody assigned" and "sensor only" are printed
+beside the best schedule; --gains, below, searches the controller as well.
 
     python examples/control_schedule_search.py --feedback [--bins 3] [--airtime-price 0.002]
 
@@ -16,6 +17,13 @@ cyclic schedule per bin, so "leave the band alone while the pendulum is near upr
 favours whoever takes short steps, so this search ranks by the time-weighted mean |angle| (area / elapsed, degrees) plus
 --airtime-price times the duration units assigned per second of simulated time, and prints the best open-loop schedule -- the
 same search with one bin -- under the same ranking beside the result.
+
+    python examples/control_schedule_search.py --gains [--envs-per-pair 8]
+
+ranks controllers and schedulers together: G sets of PID gains (env.set_gains, laid across the envs of every schedule by
+actions.make_ctrl_gains) times the P schedules named below, all G x P pairs in ONE env.rollout_schedules launch, and again in
+one env.rollout_feedback launch with every schedule turned into "idle while |angle| < 2 degrees, else the schedule".  The
+tally is reduced to a [G][P] table here; printed are the table, the best gains per schedule, and the shipped gains' row.
 """
 import argparse
 import os
@@ -39,10 +47,16 @@ def main():
     ap.add_argument("--feedback", action="store_true", help="search angle-feedback schedulers (thresholds and per-bin schedules)")
     ap.add_argument("--bins", type=int, default=3, help="B of --feedback, 1 .. 8")
     ap.add_argument("--airtime-price", type=float, default=0.002, help="degrees per duration unit assigned per simulated second")
+    ap.add_argument("--gains", action="store_true", help="rank a grid of PID gain sets x schedules in one launch")
+    ap.add_argument("--envs-per-pair", type=int, default=8, help="initial angles per (gain set, schedule) pair of --gains")
     args = ap.parse_args()
 
     import torch
     from gymwipe_amd import VecControlLoopEnv, actions
+
+    if args.gains:
+        gains_grid(args, torch, VecControlLoopEnv, actions)
+        return
 
     P, M, L = args.schedules, args.envs_per_schedule, args.length
     N = P * M
@@ -146,6 +160,58 @@ def feedback_search(args, env, actions, rng, episodes, steps):
             print("  thresholds on |observed angle|: %s" % edges)
         for b, sch in enumerate(scheds):
             print("  bin %d (device, duration) x %d: %s" % (b, L, sch))
+
+
+GAIN_SETS = [(1.0, 0.0, 0.0), (0.5, 0.0, 0.0), (0.2, 0.0, 0.0), (0.1, 0.0, 0.0), (0.05, 0.0, 0.0), (0.02, 0.0, 0.0),
+             (0.05, 0.01, 0.0), (0.1, 0.0, 0.2)]                       # (kp, ki, kd); the first is the shipped set
+SCHEDULES = [("alternate 19/19", [(0, 19), (1, 19)]), ("19/5", [(0, 19), (1, 5)]), ("8/8", [(0, 8), (1, 8)]),
+             ("3/3", [(0, 3), (1, 3)]), ("19/19/5", [(0, 19), (0, 19), (1, 5)]), ("12/2", [(0, 12), (1, 2)]),
+             ("sensor only", [(0, 19)]), ("nobody", [(0, 0)])]
+
+
+def gains_grid(args, torch, VecControlLoopEnv, actions):
+    """G gain sets x P schedules, m initial angles per pair: env e runs schedule e // (G m) under gain set (e // m) % G."""
+    G, P, m = len(GAIN_SETS), len(SCHEDULES), args.envs_per_pair
+    if (G * m) % 64:
+        sys.exit("--envs-per-pair times %d gain sets must be a multiple of 64 (one schedule per 64-env block)" % G)
+    N = P * G * m
+    rng = np.random.default_rng(args.seed)
+    x0 = np.zeros((m, 4))
+    x0[:, 2] = rng.uniform(-args.angle, args.angle, m)
+    env = VecControlLoopEnv(N, gains=actions.make_ctrl_gains(GAIN_SETS, N, envs_per_set=m))
+    env.set_initial_state(torch.from_numpy(np.tile(x0, (P * G, 1))))    # every pair meets the same m initial states
+    episodes = (args.episode_steps, 0.0)
+    steps = args.episode_steps * args.episodes
+    names = [n for n, _ in SCHEDULES]
+    scheds = [s for _, s in SCHEDULES]
+
+    def table(title, unit, cell):
+        """``cell`` [P][G] -> the [G][P] table, the best gains per schedule, the shipped gains' row."""
+        t = np.where(np.isfinite(cell), cell, np.inf).T
+        print("%s (%s); rows: gain sets, columns: schedules" % (title, unit))
+        print("%-20s" % "(kp, ki, kd)" + "".join("%16s" % n for n in names))
+        for g in range(G):
+            print("%-20s" % (GAIN_SETS[g],) + "".join("%16.4g" % v for v in t[g]))
+        for p in range(P):
+            g = int(t[:, p].argmin())
+            print("  %-16s best gains %-18s %10.4g | shipped gains %10.4g" % (names[p], GAIN_SETS[g], t[g, p], t[0, p]))
+        g, p = np.unravel_index(int(t.argmin()), t.shape)
+        print("  best pair: gains %s with schedule '%s': %.4g; the shipped gains' best: %.4g ('%s')"
+              % (GAIN_SETS[g], names[p], t[g, p], t[0].min(), names[int(t[0].argmin())]))
+
+    env.reset_envs()
+    tally, _ = env.rollout_schedules(actions.make_ctrl_schedules(scheds), episodes, steps)
+    cell = tally.view(P, G, m, 4).sum(2).cpu().numpy()                  # the caller's reduction: per (schedule, gain set)
+    assert (cell[..., 0] == m * args.episodes).all()
+    table("open-loop schedules: mean episode cost", "sum of |angle in degrees| over %d steps" % args.episode_steps,
+          cell[..., 3] / cell[..., 0])
+
+    env.reset_envs()                                                    # the same pairs, the schedule only while |angle| >= 2 degrees
+    sched, edges = actions.make_ctrl_feedback([[[(0, 0)], s] for s in scheds], [[2]] * P)
+    tally, _ = env.rollout_feedback(sched, edges, episodes, steps, abs_key=True)
+    cell = tally.view(P, G, m, tally.shape[1]).sum(2).cpu().numpy()
+    table("\nfeedback: idle below 2 degrees, else the schedule", "time-weighted mean |angle| in degrees", cell[..., 6] / cell[..., 5])
+    env.close()
 
 
 if __name__ == "__main__":

@@ -121,6 +121,9 @@ scheds = actions.make_ctrl_schedules([[(0, 0)], [(0, 19)], [(0, 5), (1, 5)], [(0
 tally, sums = loop.rollout_schedules(scheds, episodes=(40, 0.0), steps=40)      # env e follows schedule e // 1024
 print("control loop: mean sum of |angle| over a 40-step episode, nobody assigned / sensor only / alternating 5 / alternating 19:",
       [round(v, 1) for v in (sums[:, 3] / sums[:, 0]).tolist()])
+loop.set_gains((0.1, 0.0, 0.0))                       # the controller's PID gains (kp, ki, kd), per env if given as [N][3]; default (1, 0, 0)
+loop.reset_envs()
+print("control loop: the same with kp = 0.1:", [round(v, 1) for v in (lambda s: s[:, 3] / s[:, 0])(loop.rollout_schedules(scheds, (40, 0.0), 40)[1]).tolist()])
 
 # 6. the reference's PHY-grid benchmark (tests/test_benchmark.py), 1 024 replicas of a 16-device grid
 import numpy as np

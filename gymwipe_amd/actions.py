@@ -576,3 +576,41 @@ def ctrl_feedback_numpy(sched, edges, x_angle_rad, age, envs_per_policy, abs_key
     row = sch[p, bins, age % L].astype(np.int32)
     return (np.minimum(row[:, 0], 1).astype(np.int32), np.minimum(row[:, 1], int(max_duration) - 1).astype(np.int32),
             bins.astype(np.int32))
+
+
+# ---- control loop: per-env PID gains (gw_ctrl_set_gains) -----------------------------------------------------------------------------------
+CTRL_DEFAULT_GAINS = (1.0, 0.0, 0.0)    # the reference's shipped gains (control/inverted_pendulum.py:48-50): what every env starts with
+
+
+def make_ctrl_gains(gain_sets, num_envs, envs_per_set=None):
+    """``float64[N][3]`` = {kp, ki, kd} per env from G gain sets: what ``VecControlLoopEnv.set_gains`` uploads.  Env e gets set
+    ``(e // envs_per_set) % G``.  The default ``envs_per_set = N // G`` gives G contiguous groups; a smaller value repeats the
+    sets, which lays all G inside each schedule's (or policy's) block of envs: with P schedules, ``envs_per_set = N // (P * G)``
+    makes ``rollout_schedules`` evaluate the whole G x P grid, env e being pair ``((e // envs_per_set) % G, e // (N // P))``."""
+    sets = np.asarray(gain_sets, np.float64)
+    if sets.ndim != 2 or sets.shape[1] != 3 or sets.shape[0] < 1:
+        raise ValueError("make_ctrl_gains: gain_sets is G x 3 = (kp, ki, kd), G >= 1")
+    N, G = int(num_envs), sets.shape[0]
+    if N < 1 or N % G != 0:
+        raise ValueError("make_ctrl_gains: num_envs must be a whole multiple of the number of gain sets")
+    per = N // G if envs_per_set is None else int(envs_per_set)
+    if per < 1 or N % (per * G) != 0:
+        raise ValueError("make_ctrl_gains: num_envs must be a whole multiple of envs_per_set * G")
+    return np.ascontiguousarray(sets[(np.arange(N) // per) % G])
+
+
+def ctrl_pid_numpy(gains, ang, last):
+    """The controller's rule at a control tick (``gw_ctrl_set_gains`` in include/gymwipe_amd.h; ``control()`` of the reference's
+    control/inverted_pendulum.py:46-69), vectorised: ``gains`` f64[N][3] (or one set of 3), ``ang`` the controller's angle in
+    degrees, ``last`` its last error.  ``e = |ang|``, ``pid = ((kp e) + (ki (e + last))) + (kd (e - last))``; a command goes out
+    iff ``ang != 0`` and its value is ``pid`` where ``ang < 0``, else ``-pid``.  Returns ``(value, send, new_last)``; ``value``
+    is meaningful where ``send``."""
+    g = np.asarray(gains, np.float64)
+    ang, last = np.asarray(ang, np.float64), np.asarray(last, np.float64)
+    if g.shape[-1] != 3:
+        raise ValueError("ctrl_pid_numpy: gains is f64[N][3] or one (kp, ki, kd)")
+    kp, ki, kd = g[..., 0], g[..., 1], g[..., 2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = np.fabs(ang)
+        pid = ((kp * e) + (ki * (e + last))) + (kd * (e - last))
+    return np.where(ang < 0.0, pid, -pid), ang != 0.0, e + np.zeros_like(last)

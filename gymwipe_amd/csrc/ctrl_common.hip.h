@@ -1,6 +1,6 @@
 // ctrl_common.hip.h -- what the control-loop kernels share: ctrl_step_kernel (ctrl_step.hip: one step per launch) and the fused
 // kernels of ctrl_rollout.hip (K steps per launch).  A lane's state, its two queues during a step, and the staging of a step's
-// appends.  The step itself is text: ctrl_step_body.h.
+// appends, and the controller's gains where a kernel reads them.  The step itself is text: ctrl_step_body.h.
 #pragma once
 #include "ct_common.hip.h"
 
@@ -13,6 +13,25 @@ struct Lane {                                               // everything indexe
     uint32_t ktick, got1, got2, ntx, ncmd, nsub, fl;        // send the whole struct to scratch memory
     uint32_t rxs[CR];
 };
+
+// The controller of one env in the PID instantiations (ctrl_step_body.h under GW_CTRL_PID): its gains and its last error, four
+// f64 in registers across all steps of a launch.  GwCtrlPid's block holds them as {kp, ki, kd, last_error}, 32 bytes per env:
+// two 16-byte loads when a launch opens, one 8-byte store of `last` when it closes (nothing inside a launch changes a gain).
+struct Pid {
+    double kp, ki, kd, last;
+};
+
+__device__ __forceinline__ void pid_load(Pid& G, const GwCtrlPid& g, int64_t e)
+{
+    const double2* p = reinterpret_cast<const double2*>(g.pid + e * 4);       // hipMalloc'ed, 32-byte records: 16-byte aligned
+    const double2 a = p[0], b = p[1];
+    G.kp = a.x; G.ki = a.y; G.kd = b.x; G.last = b.y;
+}
+
+__device__ __forceinline__ void pid_store(const Pid& G, const GwCtrlPid& g, int64_t e)
+{
+    g.pid[e * 4 + 3] = G.last;
+}
 
 __device__ __forceinline__ uint32_t pick(const uint32_t (&a)[CR], int i)
 {

@@ -18,10 +18,12 @@ constexpr int SCHED_MAX = 64;                                // entries of a sch
 // The loop of both fused kernels, one lane per env.  SCHED: the action is entry `age % Ls` of the block's schedule in LDS
 // (clamped into the action space where it is read) and nothing is stored per step; else it is row k of the caller's [K][N]
 // arrays, step k + 1's loaded while step k is walked, and the step's outputs are stores nothing waits for.
+// PID: the controller is the PID on the env's own gains (the step's text included under GW_CTRL_PID), its four f64 loaded from
+// g and held in registers across the K steps, `last` cleared by the in-launch reset and stored back once; else g is not read.
 // (A __forceinline__ template, not a kernel: the kernels below are plain functions.)
-template <bool SCHED>
-__device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCtrlEpi& s, const int steps, const bool episodes,
-                                                  const uint32_t max_steps, const double fail_deg, const uint8_t* s_trans,
+template <bool SCHED, bool PID>
+__device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const int steps,
+                                                  const bool episodes, const uint32_t max_steps, const double fail_deg, const uint8_t* s_trans,
                                                   const double* s_ber, double* col0, double* col1, const int64_t e,
                                                   const int32_t* __restrict__ device, const int32_t* __restrict__ duration,
                                                   int32_t* __restrict__ obs, float* __restrict__ reward,
@@ -41,6 +43,8 @@ __device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCt
     L.ntx = c.ntx[e]; L.ncmd = c.ncmd[e]; L.nsub = c.nsub[e]; L.fl = c.flags[e];
     double* ring0 = c.pay + ((size_t)e * 2 + 0) * GW_RING_PHYS;
     double* ring1 = c.pay + ((size_t)e * 2 + 1) * GW_RING_PHYS;
+    Pid G;
+    if (PID) pid_load(G, g, e);
     uint32_t age = 0u;
     double cost = 0.0;
     if (episodes) { age = s.age[e]; cost = s.cost[e]; }
@@ -65,7 +69,13 @@ __device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCt
         const int d = d_now, du = du_now;
         q_open(q0);
         q_open(q1);
+        if constexpr (PID) {
+#define GW_CTRL_PID
 #include "ctrl_step_body.h"
+#undef GW_CTRL_PID
+        } else {
+#include "ctrl_step_body.h"
+        }
         const double deg = L.x[2] * deg_per_rad;             // InvertedPendulumInterpreter, envs/inverted_pendulum.py:27-57
         if (!SCHED) {
             obs[at] = (int32_t)deg;
@@ -93,6 +103,7 @@ __device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCt
                 L.got1 = L.got2 = 0u;
                 L.ntx = L.ncmd = L.nsub = 0u;
                 age = 0u; cost = 0.0; at_sched = 0u;
+                if (PID) G.last = 0.0;
             }
         }
     }
@@ -106,6 +117,7 @@ __device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCt
     c.got[e * 2] = L.got1; c.got[e * 2 + 1] = L.got2;
     c.ntx[e] = L.ntx; c.ncmd[e] = L.ncmd; c.nsub[e] = L.nsub; c.flags[e] = L.fl;
     if (episodes) { s.age[e] = age; s.cost[e] = cost; }
+    if (PID) pid_store(G, g, e);
     if (SCHED) {
         tally[e * 4 + 0] = (double)n_ended; tally[e * 4 + 1] = (double)n_failed;
         tally[e * 4 + 2] = (double)steps;   tally[e * 4 + 3] = cost_ended;
@@ -125,8 +137,8 @@ __global__ __launch_bounds__(64) void ctrl_rollout_kernel(GwCtrlDev c, GwCtrlEpi
     __syncthreads();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= c.N) return;
-    ctrl_rollout_lane<false>(c, s, steps, episodes != 0, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
-                             s_new1 + (threadIdx.x & 63), e, device, duration, obs, reward, angle_deg, ended, nullptr, 1u, nullptr);
+    ctrl_rollout_lane<false, false>(c, s, GwCtrlPid{nullptr}, steps, episodes != 0, max_steps, fail_deg, s_trans, s_ber,
+                                    s_new0 + (threadIdx.x & 63), s_new1 + (threadIdx.x & 63), e, device, duration, obs, reward, angle_deg, ended, nullptr, 1u, nullptr);
 }
 
 // every 64-env block follows one schedule (the host refuses N / P that is no multiple of 64): its 2 Ls bytes in LDS
@@ -144,7 +156,45 @@ __global__ __launch_bounds__(64) void ctrl_rollout_sched_kernel(GwCtrlDev c, GwC
     __syncthreads();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= c.N) return;
-    ctrl_rollout_lane<true>(c, s, steps, true, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
+    ctrl_rollout_lane<true, false>(c, s, GwCtrlPid{nullptr}, steps, true, max_steps, fail_deg, s_trans, s_ber,
+                                   s_new0 + (threadIdx.x & 63), s_new1 + (threadIdx.x & 63), e, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s_sched, Ls, tally);
+}
+
+// The two kernels above in their PID instantiation: what a handle launches once gw_ctrl_set_gains has been called on it.  The
+// gains' block is the LAST argument: in front of `steps` the schedule kernel came out with a 68-byte private segment that no
+// instruction touches; behind the parents' arguments, whose offsets then stay what they are, it has none.
+__global__ __launch_bounds__(64) void ctrl_rollout_pid_kernel(GwCtrlDev c, GwCtrlEpi s, int steps, int episodes, uint32_t max_steps,
+                                                          double fail_deg, const int32_t* __restrict__ device,
+                                                          const int32_t* __restrict__ duration, int32_t* __restrict__ obs,
+                                                          float* __restrict__ reward, double* __restrict__ angle_deg,
+                                                          uint8_t* __restrict__ ended, GwCtrlPid g)
+{
+    __shared__ double s_new0[NEW0 * 64], s_new1[NEW1 * 64];
+    __shared__ uint8_t s_trans[CR * CR * S];
+    __shared__ double s_ber[CR * CR * S];
+    for (int i = threadIdx.x; i < CR * CR * S; i += blockDim.x) { s_trans[i] = c.trans[i]; s_ber[i] = c.ber[i]; }
+    __syncthreads();
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= c.N) return;
+    ctrl_rollout_lane<false, true>(c, s, g, steps, episodes != 0, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
+                             s_new1 + (threadIdx.x & 63), e, device, duration, obs, reward, angle_deg, ended, nullptr, 1u, nullptr);
+}
+
+__global__ __launch_bounds__(64) void ctrl_rollout_sched_pid_kernel(GwCtrlDev c, GwCtrlEpi s, int steps, uint32_t max_steps, double fail_deg,
+                                                                const uint8_t* __restrict__ sched, uint32_t envs_per_schedule,
+                                                                uint32_t Ls, double* __restrict__ tally, GwCtrlPid g)
+{
+    __shared__ double s_new0[NEW0 * 64], s_new1[NEW1 * 64];
+    __shared__ uint8_t s_trans[CR * CR * S];
+    __shared__ double s_ber[CR * CR * S];
+    __shared__ uint8_t s_sched[SCHED_MAX * 2];
+    for (int i = threadIdx.x; i < CR * CR * S; i += blockDim.x) { s_trans[i] = c.trans[i]; s_ber[i] = c.ber[i]; }
+    const uint32_t p = (uint32_t)(((int64_t)blockIdx.x * 64) / envs_per_schedule);
+    for (uint32_t i = threadIdx.x; i < 2u * Ls && i < (uint32_t)SCHED_MAX * 2u; i += blockDim.x) s_sched[i] = sched[(size_t)p * 2u * Ls + i];
+    __syncthreads();
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= c.N) return;
+    ctrl_rollout_lane<true, true>(c, s, g, steps, true, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
                             s_new1 + (threadIdx.x & 63), e, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s_sched, Ls, tally);
 }
 
@@ -165,6 +215,23 @@ __global__ void ctrl_set_initial_kernel(int64_t N, GwCtrlEpi s, const double* __
     if (e >= N || (mask && !mask[e])) return;
     for (int i = 0; i < 4; ++i) s.x_init[e * 4 + i] = x0[e * 4 + i];
     if (u0) s.u_init[e] = u0[e];
+}
+
+// the gains of the masked envs <- gains[N][3]; last_error, the block's fourth column, is running state and is not touched
+__global__ void ctrl_set_gains_kernel(int64_t N, GwCtrlPid g, const double* __restrict__ gains, const uint8_t* __restrict__ mask)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N || (mask && !mask[e])) return;
+    for (int i = 0; i < 3; ++i) g.pid[e * 4 + i] = gains[e * 3 + i];
+}
+
+// the controller's part of a reset, launched behind ctrl_reset_kernel on a handle with gains set (a kernel of its own: that
+// one keeps its code): the last error of the masked envs <- 0; the gains survive a reset, as x_init does
+__global__ void ctrl_reset_pid_kernel(int64_t N, GwCtrlPid g, const uint8_t* __restrict__ mask)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N || (mask && !mask[e])) return;
+    g.pid[e * 4 + 3] = 0.0;
 }
 
 // the masked envs -> exactly what ctrl_init_kernel leaves, with the env's own initial state; flags stay (sticky)
@@ -205,25 +272,46 @@ int gw_ctrl_launch_set_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const dou
     return launched();
 }
 
-int gw_ctrl_launch_reset(const GwCtrlDev& c, const GwCtrlEpi& s, const uint8_t* mask, int32_t* obs, void* stream)
+int gw_ctrl_launch_set_gains(const GwCtrlDev& c, const GwCtrlPid& g, const double* gains, const uint8_t* mask, void* stream)
 {
-    hipLaunchKernelGGL(ctrl_reset_kernel, dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c, s, mask, obs);
+    hipLaunchKernelGGL(ctrl_set_gains_kernel, dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c.N, g, gains, mask);
     return launched();
 }
 
-int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const int32_t* device, const int32_t* duration,
-                           const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg, uint8_t* ended, void* stream)
+int gw_ctrl_launch_reset(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, const uint8_t* mask, int32_t* obs, void* stream)
 {
-    hipLaunchKernelGGL(ctrl_rollout_kernel, dim3((unsigned)((c.N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, c, s, (int)steps,
-                       ep ? 1 : 0, ep ? (uint32_t)ep->max_steps : 0u, ep ? ep->fail_deg : 0.0, device, duration, obs, reward, angle_deg,
-                       ended);
+    const dim3 grid((unsigned)((c.N + 255) / 256)), block(256);
+    hipLaunchKernelGGL(ctrl_reset_kernel, grid, block, 0, (hipStream_t)stream, c, s, mask, obs);
+    if (g) hipLaunchKernelGGL(ctrl_reset_pid_kernel, grid, block, 0, (hipStream_t)stream, c.N, *g, mask);
     return launched();
 }
 
-int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const uint8_t* sched, int32_t P, int32_t L,
-                                     const gw_ctrl_episodes& ep, double* tally, void* stream)
+int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, int32_t steps, const int32_t* device,
+                           const int32_t* duration, const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg,
+                           uint8_t* ended, void* stream)
 {
-    hipLaunchKernelGGL(ctrl_rollout_sched_kernel, dim3((unsigned)(c.N / 64)), dim3(64), 0, (hipStream_t)stream, c, s, (int)steps,
-                       (uint32_t)ep.max_steps, ep.fail_deg, sched, (uint32_t)(c.N / P), (uint32_t)L, tally);
+    const dim3 grid((unsigned)((c.N + 63) / 64)), block(64);
+    const int episodes = ep ? 1 : 0;
+    const uint32_t max_steps = ep ? (uint32_t)ep->max_steps : 0u;
+    const double fail_deg = ep ? ep->fail_deg : 0.0;
+    if (g)
+        hipLaunchKernelGGL(ctrl_rollout_pid_kernel, grid, block, 0, (hipStream_t)stream, c, s, (int)steps, episodes, max_steps, fail_deg, device,
+                           duration, obs, reward, angle_deg, ended, *g);
+    else
+        hipLaunchKernelGGL(ctrl_rollout_kernel, grid, block, 0, (hipStream_t)stream, c, s, (int)steps, episodes, max_steps, fail_deg, device,
+                           duration, obs, reward, angle_deg, ended);
+    return launched();
+}
+
+int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, int32_t steps, const uint8_t* sched,
+                                     int32_t P, int32_t L, const gw_ctrl_episodes& ep, double* tally, void* stream)
+{
+    const dim3 grid((unsigned)(c.N / 64)), block(64);
+    if (g)
+        hipLaunchKernelGGL(ctrl_rollout_sched_pid_kernel, grid, block, 0, (hipStream_t)stream, c, s, (int)steps, (uint32_t)ep.max_steps,
+                           ep.fail_deg, sched, (uint32_t)(c.N / P), (uint32_t)L, tally, *g);
+    else
+        hipLaunchKernelGGL(ctrl_rollout_sched_kernel, grid, block, 0, (hipStream_t)stream, c, s, (int)steps, (uint32_t)ep.max_steps,
+                           ep.fail_deg, sched, (uint32_t)(c.N / P), (uint32_t)L, tally);
     return launched();
 }

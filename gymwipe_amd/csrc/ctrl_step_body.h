@@ -6,6 +6,9 @@
 // The including kernel provides, in scope: c (GwCtrlDev), k (GwDevConst), S (= GW_MAX_NSTATES), s_trans / s_ber (the link tables
 // in LDS, [CR][CR][S]), L (Lane), q0 / q1 (Q, opened: q_open), col0 / col1 (the lane's LDS columns), ring0 / ring1 (its rings),
 // deg_per_rad, and the step's action `const int d, du`.  The text defines no name outside its own braces.
+// The controller's rule is a compile-time switch, a preprocessor symbol because the text is no template: included with
+// GW_CTRL_PID defined, the controller is the reference's three-term PID on the env's own gains and last error, G (Pid), which the
+// including kernel then provides as well; included without, it is the same rule at gains (1, 0, 0), folded, and no G is named.
     if ((unsigned)d >= 2u || (unsigned)du >= (unsigned)k.max_duration) {
         L.fl |= GW_FLAG_BADACT;                              // envs/inverted_pendulum.py:102 asserts; flagged and skipped here
     } else {
@@ -40,10 +43,22 @@
             L.nsub++;
             const uint32_t kk = L.ktick;                                        // controller
             if (kk >= c.start) {
-                if (phase == 0u && L.ang != 0.0) {
+#ifdef GW_CTRL_PID
+                if (phase == 0u) {                                              // control(), control/inverted_pendulum.py:54-68:
+                    const double err = fabs(L.ang);                             // abs(sp - angle), sp = 0
+                    const double pid = ((G.kp * err) + (G.ki * (err + G.last))) + (G.kd * (err - G.last));
+                    G.last = err;                                               // calcVelocity runs whether or not anything is sent
+                    if (L.ang != 0.0) {
+                        q_push(q1, col1, L.ang < 0.0 ? pid : -pid);
+                        L.ncmd++;
+                    }
+                }
+#else
+                if (phase == 0u && L.ang != 0.0) {                              // the same rule at gains (1, 0, 0)
                     q_push(q1, col1, -L.ang);
                     L.ncmd++;
                 }
+#endif
                 phase = phase + 1u == c.period ? 0u : phase + 1u;
             }
             L.ktick = kk + 1u;

@@ -16,6 +16,8 @@ struct gw_ctrl {
     GwHostTables tab;
     GwCtrlDev dev;
     GwCtrlEpi epi;                     // per-env initial state and episode record (not part of the step kernel's argument)
+    GwCtrlPid pid;                     // per-env gains and last error: {1, 0, 0, 0} from gw_ctrl_create on
+    bool pid_on;                       // gw_ctrl_set_gains has been called: the launches take the PID instantiations, for good
     void* blocks[24];
     int nblocks;
 };
@@ -41,6 +43,9 @@ int calloc_dev(gw_ctrl* c, T** out, size_t count)
     *out = (T*)q;
     return GW_OK;
 }
+
+// the launchers' controller argument: NULL (the kernels with the default rule compiled in) until gains have been set
+inline const GwCtrlPid* pid_of(const gw_ctrl* c) { return c->pid_on ? &c->pid : nullptr; }
 
 } // namespace
 
@@ -127,12 +132,19 @@ int gw_ctrl_create(const gw_ctrl_config* cfg, gw_ctrl** out)
     CA(d.qhl, N * 2); CA(d.rxs, N * R); CA(d.pay, N * 2 * GW_RING_PHYS);
     CA(d_cst, 1); CA(d_trans, tcount); CA(d_ber, tcount);
     CA(c->epi.x_init, N * 4); CA(c->epi.u_init, N); CA(c->epi.cost, N); CA(c->epi.age, N);
+    CA(c->pid.pid, N * 4);
 #undef CA
     d.cst = d_cst; d.trans = d_trans; d.ber = d_ber;
     CTRL_HIP(hipMemcpy(d_cst, &k, sizeof k, hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemcpy(d_trans, c->tab.trans, tcount, hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemcpy(d_ber, c->tab.ber, tcount * sizeof(double), hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemset(d.pay, 0, (size_t)N * 2 * GW_RING_PHYS * sizeof(double)), gw_ctrl_destroy(c));
+    {
+        const double def[4] = {1.0, 0.0, 0.0, 0.0};          // the reference's shipped gains, and a fresh controller's last error
+        std::vector<double> fill((size_t)N * 4);
+        for (size_t i = 0; i < fill.size(); ++i) fill[i] = def[i & 3];
+        CTRL_HIP(hipMemcpy(c->pid.pid, fill.data(), fill.size() * sizeof(double), hipMemcpyHostToDevice), gw_ctrl_destroy(c));
+    }
     if (gw_ctrl_launch_init(d, cfg->x0, cfg->u0, nullptr) || gw_ctrl_launch_fill_initial(d, c->epi, cfg->x0, cfg->u0, nullptr)) {
         gw_ctrl_destroy(c);
         return gw_set_error(GW_EHIP, "control-loop init launch failed");
@@ -148,7 +160,7 @@ int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_
     if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
     if (!device_dev || !duration_dev || !obs_dev || !reward_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_step: NULL device pointer");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_step(c->dev, device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream))
+    if (gw_ctrl_launch_step(c->dev, pid_of(c), device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop step launch failed");
     return GW_OK;
 }
@@ -163,11 +175,22 @@ int gw_ctrl_set_initial(gw_ctrl* c, const double* x0_dev, const double* u0_dev, 
     return GW_OK;
 }
 
+int gw_ctrl_set_gains(gw_ctrl* c, const double* gains_dev, const uint8_t* mask_dev, void* stream)
+{
+    if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
+    if (!gains_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_set_gains: gains_dev is NULL");
+    CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
+    if (gw_ctrl_launch_set_gains(c->dev, c->pid, gains_dev, mask_dev, stream))
+        return gw_set_error(GW_EHIP, "control-loop set_gains launch failed");
+    c->pid_on = true;
+    return GW_OK;
+}
+
 int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* stream)
 {
     if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_reset(c->dev, c->epi, mask_dev, obs_dev, stream))
+    if (gw_ctrl_launch_reset(c->dev, c->epi, pid_of(c), mask_dev, obs_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop reset launch failed");
     return GW_OK;
 }
@@ -182,7 +205,7 @@ int gw_ctrl_rollout(gw_ctrl* c, int32_t steps, const int32_t* device_dev, const 
     if (steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout: steps < 0");
     if (steps == 0) return GW_OK;
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_rollout(c->dev, c->epi, steps, device_dev, duration_dev, ep, obs_dev, reward_dev, angle_deg_dev, ended_dev, stream))
+    if (gw_ctrl_launch_rollout(c->dev, c->epi, pid_of(c), steps, device_dev, duration_dev, ep, obs_dev, reward_dev, angle_deg_dev, ended_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop rollout launch failed");
     return GW_OK;
 }
@@ -202,7 +225,7 @@ int gw_ctrl_rollout_schedules(gw_ctrl* c, int32_t steps, const uint8_t* sched_de
     if (N % P != 0 || (N / P) % 64 != 0)
         return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_schedules: num_envs / P must be a whole multiple of 64 (one schedule per block)");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_rollout_schedules(c->dev, c->epi, steps, sched_dev, P, L, *ep, tally_dev, stream))
+    if (gw_ctrl_launch_rollout_schedules(c->dev, c->epi, pid_of(c), steps, sched_dev, P, L, *ep, tally_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop schedule rollout launch failed");
     return GW_OK;
 }
@@ -229,7 +252,7 @@ int gw_ctrl_rollout_feedback(gw_ctrl* c, int32_t steps, const gw_ctrl_feedback* 
     if (N % P != 0 || (N / P) % 64 != 0)
         return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_feedback: num_envs / P must be a whole multiple of 64 (one policy per block)");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_rollout_feedback(c->dev, c->epi, steps, *fb, *ep, rows, tally_dev, stream))
+    if (gw_ctrl_launch_rollout_feedback(c->dev, c->epi, pid_of(c), steps, *fb, *ep, rows, tally_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop feedback rollout launch failed");
     return GW_OK;
 }
@@ -266,6 +289,14 @@ int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst, size_t bytes)
         std::vector<uint16_t> hl((size_t)N * 2);
         CTRL_HIP(hipMemcpy(hl.data(), d.qhl, hl.size() * sizeof(uint16_t), hipMemcpyDeviceToHost), (void)0);
         for (int64_t e = 0; e < N; ++e) for (int q = 0; q < 2; ++q) ((int32_t*)dst)[e * 2 + q] = hl[(size_t)q * N + e] >> 8;
+        return GW_OK;
+    }
+    if (!strcmp(field, "gains") || !strcmp(field, "last_error")) {     // f64[N][3] / f64[N]: columns of the {kp, ki, kd, last_error} block
+        const bool gains = field[0] == 'g';
+        const size_t cols = gains ? 3 : 1;
+        if (bytes != (size_t)N * cols * sizeof(double)) return gw_set_error(GW_EFIELD, "field %s needs %zu bytes", field, (size_t)N * cols * sizeof(double));
+        CTRL_HIP(hipMemcpy2D(dst, cols * sizeof(double), c->pid.pid + (gains ? 0 : 3), 4 * sizeof(double), cols * sizeof(double), (size_t)N,
+                             hipMemcpyDeviceToHost), (void)0);
         return GW_OK;
     }
     if (!strcmp(field, "rx_power")) {                      // f64[N][4]

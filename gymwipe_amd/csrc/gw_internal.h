@@ -262,26 +262,37 @@ struct GwCtrlDev {
     const uint8_t* trans;                      // [4][4][S]
     const double*  ber;                        // [4][4][S]
 };
-int gw_ctrl_launch_step(const GwCtrlDev& c, const int32_t* device, const int32_t* duration, int32_t* obs, float* reward,
-                        double* angle_deg, void* stream);
-int gw_ctrl_launch_init(const GwCtrlDev& c, const double* x0, double u0, void* stream);
 // Per-env initial state and episode record (ctrl_rollout.hip).  A struct of its own: GwCtrlDev is ctrl_step_kernel's by-value
 // argument, and a field added there would change that kernel's code.
 struct GwCtrlEpi {
     double *x_init, *u_init, *cost;            // [N][4], [N], [N]
     uint32_t* age;                             // [N]
 };
+// Per-env controller: the PID gains and the controller's last error (the rule: include/gymwipe_amd.h, gw_ctrl_set_gains).  One
+// block f64[N][4] = {kp, ki, kd, last_error}; a struct of its own for GwCtrlEpi's reason.  The launchers below take it by pointer:
+// NULL launches the kernels with the default rule compiled in (no gains read), else their PID instantiations.
+struct GwCtrlPid {
+    double* pid;                               // [N][4]
+};
+int gw_ctrl_launch_step(const GwCtrlDev& c, const GwCtrlPid* g, const int32_t* device, const int32_t* duration, int32_t* obs,
+                        float* reward, double* angle_deg, void* stream);
+int gw_ctrl_launch_init(const GwCtrlDev& c, const double* x0, double u0, void* stream);
 int gw_ctrl_launch_fill_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, double u0, void* stream);
 int gw_ctrl_launch_set_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, const double* u0, const uint8_t* mask,
                                void* stream);
-int gw_ctrl_launch_reset(const GwCtrlDev& c, const GwCtrlEpi& s, const uint8_t* mask, int32_t* obs, void* stream);
-int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const int32_t* device, const int32_t* duration,
-                           const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg, uint8_t* ended, void* stream);
-int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const uint8_t* sched, int32_t P, int32_t L,
-                                     const gw_ctrl_episodes& ep, double* tally, void* stream);
-int gw_ctrl_launch_rollout_feedback(const GwCtrlDev& c, const GwCtrlEpi& s, int32_t steps, const gw_ctrl_feedback& fb,
-                                    const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows, double* tally,
-                                    void* stream);                                      // ctrl_rollout_feedback.hip
+int gw_ctrl_launch_set_gains(const GwCtrlDev& c, const GwCtrlPid& g, const double* gains, const uint8_t* mask, void* stream);
+int gw_ctrl_launch_reset(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, const uint8_t* mask, int32_t* obs, void* stream);
+int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, int32_t steps, const int32_t* device,
+                           const int32_t* duration, const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg,
+                           uint8_t* ended, void* stream);
+int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, int32_t steps, const uint8_t* sched,
+                                     int32_t P, int32_t L, const gw_ctrl_episodes& ep, double* tally, void* stream);
+int gw_ctrl_launch_rollout_feedback(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, int32_t steps,
+                                    const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
+                                    double* tally, void* stream);                       // ctrl_rollout_feedback.hip
+int gw_ctrl_launch_rollout_feedback_pid(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, int32_t steps,
+                                        const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
+                                        double* tally, void* stream);                   // ctrl_rollout_feedback_pid.hip
 int gw_fill_dev_const(const gw_config& cfg, const GwHostTables& tab, GwDevConst& k);   // gw_api.cpp
 int gw_validate_config(const gw_config& cfg);                                           // gw_api.cpp
 

@@ -146,11 +146,14 @@ class VecControlLoopEnv(BaseEnv):
     Beyond one step per launch: ``set_initial_state`` / ``reset_envs`` (an initial state per env; a masked reset that leaves a
     fresh env), ``rollout`` (K steps in one launch, optionally with episodes that end at a time limit or a failure angle and
     reset inside the launch), ``rollout_schedules`` (P cyclic band schedules, a per-env tally, nothing stored per step) and
-    ``rollout_feedback`` (P angle-feedback schedulers: the env's own angle picks which of B schedules it acts on)."""
+    ``rollout_feedback`` (P angle-feedback schedulers: the env's own angle picks which of B schedules it acts on).
+    The controller is the reference's three-term PID on gains every env holds of its own: ``set_gains`` (or ``gains=`` here);
+    the default, the reference's shipped (1, 0, 0), commands ``-angle``.  Gains laid across the envs of each schedule
+    (``actions.make_ctrl_gains``) make the rollout calls rank controllers and schedulers together."""
     SENSOR, CONTROLLER, ACTUATOR = 0, 1, 2
 
     def __init__(self, num_envs, device="cuda:0", ctrl_start_tick=None, ctrl_period_ticks=None, positions=None, x0=None,
-                 A=None, B=None, u0=None, counter_interval=None):
+                 A=None, B=None, u0=None, counter_interval=None, gains=None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gymwipe_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -194,6 +197,8 @@ class VecControlLoopEnv(BaseEnv):
             self._angle = torch.empty(n, dtype=torch.float64, device=self.device)
             self._done = torch.zeros(n, dtype=torch.uint8, device=self.device)
         self._stepped = False
+        if gains is not None:                              # (None: the handle never reads gains; its kernels have (1, 0, 0) folded in)
+            self.set_gains(gains)
 
     def reset(self):
         """envs/inverted_pendulum.py:95-99: returns an observation, resets nothing."""
@@ -244,10 +249,28 @@ class VecControlLoopEnv(BaseEnv):
             nat.check(self._L.gw_ctrl_set_initial(self._h, x.data_ptr(), u.data_ptr() if u is not None else None,
                                                   m.data_ptr() if m is not None else None, self._stream()))
 
+    def set_gains(self, gains, mask=None):
+        """Give the masked envs (None: all) PID gains of their own: ``gains`` f64[N][3] = (kp, ki, kd), a tensor or an array, on
+        the GPU or not (one set of 3 is broadcast; ``actions.make_ctrl_gains`` lays G sets across the envs).  At every control
+        tick the controller computes ``e = |angle|``, ``pid = kp e + ki (e + last_error) + kd (e - last_error)``,
+        ``last_error = e`` and, unless its angle is 0, commands ``pid`` against the angle's sign.  No running state is touched,
+        ``last_error`` included; the gains survive every reset.  From the first call on the handle launches the kernels that
+        read the gains; with (1, 0, 0) they compute what the default kernels compute."""
+        torch = self._torch
+        g = torch.as_tensor(gains, dtype=torch.float64).to(self.device)
+        if tuple(g.shape) == (3,):
+            g = g.expand(self.num_envs, 3)
+        if tuple(g.shape) != (self.num_envs, 3):
+            raise ValueError("gains must be (kp, ki, kd) or float64[num_envs][3]")
+        g = g.contiguous()
+        m = self._mask(mask)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_ctrl_set_gains(self._h, g.data_ptr(), m.data_ptr() if m is not None else None, self._stream()))
+
     def reset_envs(self, mask=None):
         """Put the masked envs (None: all) back into the state a fresh env of their own initial state has -- clock, queues,
-        noise states, counters and the episode record (``age``, ``cost``) 0; ``flags`` are sticky and stay -- and return the
-        observations of all N envs.  (``reset()`` keeps the reference's meaning: it resets nothing.)"""
+        noise states, counters, the episode record (``age``, ``cost``) and the controller's ``last_error`` 0; ``flags`` are
+        sticky and stay, and so do the gains -- and return the observations of all N envs.  (``reset()`` keeps the reference's meaning: it resets nothing.)"""
         torch = self._torch
         m = self._mask(mask)
         self._stepped = True                               # the observation buffer now holds what the GPU wrote
@@ -347,7 +370,8 @@ class VecControlLoopEnv(BaseEnv):
     _FIELDS = {"now": ((), "f8"), "wake": ((), "f8"), "u": ((), "f8"), "angle_deg": ((), "f8"), "x": ((4,), "f8"),
                "rx_power": ((4,), "f8"), "qlen": ((2,), "i4"), "received": ((2,), "u4"), "n_tx": ((), "u4"),
                "commands": ((), "u4"), "substeps": ((), "u4"), "flags": ((), "u4"),
-               "age": ((), "u4"), "cost": ((), "f8"), "x_init": ((4,), "f8"), "u_init": ((), "f8")}
+               "age": ((), "u4"), "cost": ((), "f8"), "x_init": ((4,), "f8"), "u_init": ((), "f8"),
+               "gains": ((3,), "f8"), "last_error": ((), "f8")}
 
     def get_state(self, field):
         import numpy as np

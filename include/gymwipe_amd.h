@@ -759,7 +759,8 @@ int32_t gw_grid_selftest_width(const gw_grid* g, int64_t num_envs, int32_t num_d
  * envs/inverted_pendulum.py:60-113) but never runs it -- nobody sets `receiving`, and the env cannot be constructed.  Three
  * network devices (sensor 0, controller 1, actuator 2 -- not assignable) and the RRM; the sensor queues the plant angle
  * every counter tick and the plant then advances one substep x <- A x + B u; every ctrl_period_ticks from ctrl_start_tick on
- * the controller queues -angle_deg (the shipped PID gains kp = 1, ki = kd = 0) unless its angle is 0; packets decoded by
+ * the controller runs the reference's three-term PID rule on gains of its env's own (gw_ctrl_set_gains, below); their default,
+ * the reference's shipped gains kp = 1, ki = kd = 0, queues -angle_deg unless the angle is 0; packets decoded by
  * their destination's receive-mode MAC are handed up (controller: angle := degrees(value); actuator: u := value);
  * observation and reward as InvertedPendulumInterpreter computes them.  Checked bit for bit against an event-driven
  * model of the same rules; parity with the reference is unpinned by construction. */
@@ -781,7 +782,8 @@ int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_
                  double* angle_deg_dev, void* stream);
 /* host copies: "now","wake","u","angle_deg" f64[N] | "x" f64[N][4] | "rx_power" f64[N][4] | "qlen" int32[N][2] |
  *              "received" u32[N][2] (controller, actuator) | "n_tx","commands","substeps","flags" u32[N] |
- *              "age" u32[N], "cost" f64[N] (the running episode's record) | "x_init" f64[N][4], "u_init" f64[N] */
+ *              "age" u32[N], "cost" f64[N] (the running episode's record) | "x_init" f64[N][4], "u_init" f64[N] |
+ *              "gains" f64[N][3] {kp, ki, kd}, "last_error" f64[N] (the controller, gw_ctrl_set_gains) */
 int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst_host, size_t bytes);
 
 /* Per-env initial state and reset.  Every env keeps an initial state of its own (x_init, u_init; cfg.x0 / cfg.u0 at create) and
@@ -789,10 +791,28 @@ int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst_host, size_t byte
  * gw_ctrl_set_initial stores x0_dev f64[N][4] (and u0_dev f64[N] unless NULL) for the envs with mask_dev[e] != 0 (NULL: all);
  * it changes no env's running state.  gw_ctrl_reset puts the masked envs into exactly the state gw_ctrl_create leaves, with the
  * env's own initial state: clock, wake and tick 0, controller angle 0, both queues empty (head = len = 0), noise states 0,
- * received, n_tx, commands, substeps, age and cost 0.  flags are sticky and stay.  Envs outside the mask are untouched, bit
- * for bit.  obs_dev (NULL ok) receives (int32) degrees(x[2]) of all N envs. */
+ * received, n_tx, commands, substeps, age, cost and the controller's last_error 0.  flags are sticky and stay, and so do the
+ * gains.  Envs outside the mask are untouched, bit for bit.  obs_dev (NULL ok) receives (int32) degrees(x[2]) of all N envs. */
 int gw_ctrl_set_initial(gw_ctrl* c, const double* x0_dev, const double* u0_dev, const uint8_t* mask_dev, void* stream);
 int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* stream);
+
+/* The controller: control() of control/inverted_pendulum.py:46-69, on gains {kp, ki, kd} and a last_error that every env holds
+ * of its own, all f64; {1, 0, 0} (the reference's shipped gains) and 0 at create.  At a control tick -- a tick at or after
+ * ctrl_start_tick whose (tick - ctrl_start_tick) % ctrl_period_ticks is 0 -- with ang the controller's angle in degrees:
+ *     e    = fabs(ang)                                              abs(sp - angle), sp = 0
+ *     pid  = ((kp * e) + (ki * (e + last))) + (kd * (e - last))     this association, no contraction
+ *     last = e                                                      also when nothing is sent
+ *     if (ang != 0.0) queue (ang < 0.0 ? pid : -pid) for the actuator, commands += 1
+ * ki * (e + last) is the reference's term as written, not an integral.  Before ctrl_start_tick nothing is evaluated and last
+ * stays.  With (1, 0, 0) the queued value is -ang bit for bit wherever e + last is finite; a NaN ang queues -pid, a NaN.  No
+ * gain is validated: any f64 has this one meaning.  A reset (gw_ctrl_reset, or the end of an episode inside a rollout) puts
+ * last_error back to 0 and leaves the gains.
+ * gw_ctrl_set_gains stores gains_dev f64[N][3] = {kp, ki, kd} for the envs with mask_dev[e] != 0 (NULL: all); it touches no
+ * running state, last_error included, is stream-ordered and allocates nothing.  A NULL c or gains_dev: GW_EINVAL before any
+ * device call.  A handle on which it has never been called launches kernels with the default gains compiled in, which read
+ * no gains; its first call switches the handle, for good, to the kernels that read them.  Results do not depend on which
+ * kernels run: a handle set to (1, 0, 0) computes what an unswitched one computes, and its last_error moves. */
+int gw_ctrl_set_gains(gw_ctrl* c, const double* gains_dev, const uint8_t* mask_dev, void* stream);
 
 typedef struct gw_ctrl_episodes {
     int32_t max_steps;                      /* an episode ends when its age reaches this; 0: no limit */
