@@ -24,6 +24,15 @@ ranks controllers and schedulers together: G sets of PID gains (env.set_gains, l
 actions.make_ctrl_gains) times the P schedules named below, all G x P pairs in ONE env.rollout_schedules launch, and again in
 one env.rollout_feedback launch with every schedule turned into "idle while |angle| < 2 degrees, else the schedule".  The
 tally is reduced to a [G][P] table here; printed are the table, the best gains per schedule, and the shipped gains' row.
+
+    python examples/control_schedule_search.py --disturbance 0.01 [--envs-per-pair 8] [--disturbance-steps 120]
+
+ranks the same G x P grid twice by the time-weighted mean |angle|, every env starting upright: on the exact plant, where all
+there is to regulate is the transient of the first command, and with seeded noise of weight A on the pendulum's angular rate at
+every plant substep (env.set_disturbance), something to hold the pendulum against.  Env j of every cell gets noise stream j
+(actions.make_ctrl_disturbance(streams=arange(N) % envs_per_pair)): all cells face the same m noise sequences, so two cells'
+difference is a paired one.  Printed are both rankings side by side and, for the two best disturbed cells, in how many of the
+m sequences the better one wins.
 """
 import argparse
 import os
@@ -49,11 +58,17 @@ def main():
     ap.add_argument("--airtime-price", type=float, default=0.002, help="degrees per duration unit assigned per simulated second")
     ap.add_argument("--gains", action="store_true", help="rank a grid of PID gain sets x schedules in one launch")
     ap.add_argument("--envs-per-pair", type=int, default=8, help="initial angles per (gain set, schedule) pair of --gains")
+    ap.add_argument("--disturbance", type=float, default=None, metavar="A",
+                    help="rank the gain x schedule grid with and without plant noise of weight A on x[3], common random numbers")
+    ap.add_argument("--disturbance-steps", type=int, default=120, help="steps per env of --disturbance")
     args = ap.parse_args()
 
     import torch
     from gymwipe_amd import VecControlLoopEnv, actions
 
+    if args.disturbance is not None:
+        disturbance_grid(args, torch, VecControlLoopEnv, actions)
+        return
     if args.gains:
         gains_grid(args, torch, VecControlLoopEnv, actions)
         return
@@ -212,6 +227,56 @@ def gains_grid(args, torch, VecControlLoopEnv, actions):
     cell = tally.view(P, G, m, tally.shape[1]).sum(2).cpu().numpy()
     table("\nfeedback: idle below 2 degrees, else the schedule", "time-weighted mean |angle| in degrees", cell[..., 6] / cell[..., 5])
     env.close()
+
+
+def disturbance_grid(args, torch, VecControlLoopEnv, actions):
+    """gains_grid's layout, every env from x0 = 0: the time-weighted mean |angle| of every (gain set, schedule) cell on the exact
+    plant and under noise, m noise streams shared by all cells."""
+    closing = [(n, s) for n, s in SCHEDULES if any(d == 1 and u > 0 for d, u in s)]     # the schedules that let the controller talk:
+    G, P, m = len(GAIN_SETS), len(closing), args.envs_per_pair          # without it there is no loop to rank
+    if (G * m) % 64:
+        sys.exit("--envs-per-pair times %d gain sets must be a multiple of 64 (one schedule per 64-env block)" % G)
+    N = P * G * m
+    episodes = (0, 0.0)                                                 # no episode ends: one long run per env
+    steps = args.disturbance_steps
+    names = [n for n, _ in closing]
+    sched, edges = actions.make_ctrl_feedback([[s] for _, s in closing], [[]] * P)      # one bin: the open-loop schedules
+    weights, key = actions.make_ctrl_disturbance((0.0, 0.0, 0.0, args.disturbance), N, seed=args.seed, streams=np.arange(N) % m)
+
+    def run(disturbed):
+        env = VecControlLoopEnv(N, x0=(0.0, 0.0, 0.0, 0.0), gains=actions.make_ctrl_gains(GAIN_SETS, N, envs_per_set=m))
+        if disturbed:
+            env.set_disturbance(weights, key)
+        tally, _ = env.rollout_feedback(sched, edges, episodes, steps, abs_key=True)
+        t = tally.view(P, G, m, tally.shape[1]).cpu().numpy()
+        env.close()
+        err = t[..., 6] / t[..., 5]                                     # [P][G][m]: per env, area / elapsed
+        return np.where(np.isfinite(err), err, np.inf)
+
+    calm, noisy = run(False), run(True)
+    assert (calm == calm[..., :1]).all()                                # on the exact plant the m envs of a cell are copies
+    c, n = calm[..., 0], noisy.mean(2)
+    order_c, order_n = np.argsort(c, axis=None), np.argsort(n, axis=None)
+    rank_c, rank_n = np.empty(P * G, int), np.empty(P * G, int)
+    rank_c[order_c], rank_n[order_n] = np.arange(P * G), np.arange(P * G)
+
+    def cell(i):
+        p, g = np.unravel_index(i, c.shape)
+        return "%-16s %-18s" % (names[p], GAIN_SETS[g])
+    print("time-weighted mean |angle| in degrees over %d steps from upright; noise weight %g on the angular rate, %d streams shared by all %d cells"
+          % (steps, args.disturbance, m, P * G))
+    print("%4s  %-35s %10s %10s %6s   |  %-35s %10s %10s %6s" % ("rank", "exact plant: schedule, gains", "exact", "disturbed", "there",
+                                                               "disturbed: schedule, gains", "disturbed", "spread", "exact"))
+    for r in range(min(10, P * G)):
+        i, j = order_c[r], order_n[r]
+        print("%4d  %s %10.4g %10.4g %6d   |  %s %10.4g %10.4g %6d"
+              % (r + 1, cell(i), c.flat[i], n.flat[i], rank_n[i] + 1, cell(j), n.flat[j],
+                 noisy.reshape(P * G, m)[j].max() - noisy.reshape(P * G, m)[j].min(), rank_c[j] + 1))
+    a, b = noisy.reshape(P * G, m)[order_n[0]], noisy.reshape(P * G, m)[order_n[1]]
+    print("the best disturbed cell against the second: means %.4g and %.4g, spread over streams %.4g and %.4g; paired on the same"
+          " stream it wins in %d of %d" % (a.mean(), b.mean(), a.max() - a.min(), b.max() - b.min(), int((a < b).sum()), m))
+    print("the exact plant's winner is rank %d of %d under disturbance; the disturbed winner is rank %d on the exact plant"
+          % (rank_n[order_c[0]] + 1, P * G, rank_c[order_n[0]] + 1))
 
 
 if __name__ == "__main__":

@@ -124,6 +124,9 @@ print("control loop: mean sum of |angle| over a 40-step episode, nobody assigned
 loop.set_gains((0.1, 0.0, 0.0))                       # the controller's PID gains (kp, ki, kd), per env if given as [N][3]; default (1, 0, 0)
 loop.reset_envs()
 print("control loop: the same with kp = 0.1:", [round(v, 1) for v in (lambda s: s[:, 3] / s[:, 0])(loop.rollout_schedules(scheds, (40, 0.0), 40)[1]).tolist()])
+loop.set_disturbance((0.0, 0.0, 0.0, 0.01))           # seeded noise on the plant's state at every substep, one key per env (default: its own)
+loop.reset_envs()
+print("control loop: ... and a plant that is pushed:", [round(v, 1) for v in (lambda s: s[:, 3] / s[:, 0])(loop.rollout_schedules(scheds, (40, 0.0), 40)[1]).tolist()])
 
 # 6. the reference's PHY-grid benchmark (tests/test_benchmark.py), 1 024 replicas of a 16-device grid
 import numpy as np

@@ -614,3 +614,53 @@ def ctrl_pid_numpy(gains, ang, last):
         e = np.fabs(ang)
         pid = ((kp * e) + (ki * (e + last))) + (kd * (e - last))
     return np.where(ang < 0.0, pid, -pid), ang != 0.0, e + np.zeros_like(last)
+
+
+# ---- control loop: seeded plant disturbances per env (gw_ctrl_set_disturbance) ------------------------------------------------------------
+_M64 = (1 << 64) - 1
+_STREAM_STEP = 0x9E3779B97F4A7C15                          # key[e] = seed ^ (streams[e] * this mod 2^64)
+
+
+def make_ctrl_disturbance(g, num_envs, seed=0, streams=None, envs_per_set=None):
+    """``(g float64[N][4], key uint64[N])``: what ``VecControlLoopEnv.set_disturbance`` uploads.  ``g`` is one weight vector of 4
+    or G of them, laid across the envs the way ``make_ctrl_gains`` lays gains (env e gets set ``(e // envs_per_set) % G``, by
+    default G contiguous groups).  ``key[e] = seed ^ (streams[e] * 0x9E3779B97F4A7C15 mod 2^64)``; ``streams`` defaults to
+    ``arange(N)``, every env a noise sequence of its own.  Envs with equal stream numbers face the same sequence:
+    ``streams = arange(N) % envs_per_policy`` gives env j of every policy (or schedule, or gain set) the same disturbance --
+    common random numbers, the only way two candidates' tallies can be compared at less than the spread between sequences."""
+    sets = np.asarray(g, np.float64)
+    if sets.ndim == 1:
+        sets = sets[None]
+    if sets.ndim != 2 or sets.shape[1] != 4 or sets.shape[0] < 1:
+        raise ValueError("make_ctrl_disturbance: g is 4 weights, one per plant state, or G x 4")
+    N, G = int(num_envs), sets.shape[0]
+    if N < 1 or N % G != 0:
+        raise ValueError("make_ctrl_disturbance: num_envs must be a whole multiple of the number of sets")
+    per = N // G if envs_per_set is None else int(envs_per_set)
+    if per < 1 or N % (per * G) != 0:
+        raise ValueError("make_ctrl_disturbance: num_envs must be a whole multiple of envs_per_set * G")
+    if streams is None:
+        st = np.arange(N, dtype=np.uint64)
+    else:
+        st = np.asarray(streams)
+        if st.shape != (N,) or st.dtype.kind not in "iu":
+            raise ValueError("make_ctrl_disturbance: streams is an integer array of num_envs stream numbers")
+        st = st.astype(np.uint64)                         # (a negative number means its two's complement)
+    with np.errstate(over="ignore"):
+        key = np.uint64(int(seed) & _M64) ^ (st * np.uint64(_STREAM_STEP))
+    return np.ascontiguousarray(sets[(np.arange(N) // per) % G]), key
+
+
+def ctrl_noise_numpy(key, n):
+    """The disturbance's draw ``w`` for key ``key`` at count ``n`` (``gw_ctrl_set_disturbance`` in include/gymwipe_amd.h),
+    vectorised on numpy uint64 (both broadcast): uniform on [-1, 1), a multiple of 2^-31.  An env whose record was set n
+    substeps ago adds ``g[i] * ctrl_noise_numpy(key, n)`` to ``x[i]`` at the end of its next substep."""
+    u = np.uint64
+    key, n = np.asarray(key).astype(np.uint64), np.asarray(n).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        z = key ^ (n * u(0xD1B54A32D192ED03))
+        z = z + u(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+        z = z ^ (z >> u(31))
+    return (z >> u(32)).astype(np.uint32).view(np.int32).astype(np.float64) * 2.0 ** -31

@@ -1,6 +1,7 @@
 // ctrl_common.hip.h -- what the control-loop kernels share: ctrl_step_kernel (ctrl_step.hip: one step per launch) and the fused
 // kernels of ctrl_rollout.hip (K steps per launch).  A lane's state, its two queues during a step, and the staging of a step's
-// appends, and the controller's gains where a kernel reads them.  The step itself is text: ctrl_step_body.h.
+// appends, the controller's gains where a kernel reads them, and the plant's disturbance where a kernel draws it.  The step
+// itself is text: ctrl_step_body.h.
 #pragma once
 #include "ct_common.hip.h"
 
@@ -31,6 +32,45 @@ __device__ __forceinline__ void pid_load(Pid& G, const GwCtrlPid& g, int64_t e)
 __device__ __forceinline__ void pid_store(const Pid& G, const GwCtrlPid& g, int64_t e)
 {
     g.pid[e * 4 + 3] = G.last;
+}
+
+// The plant disturbance of one env in the disturbance instantiations (ctrl_step_body.h under GW_CTRL_DIST): its four weights,
+// its key and the count of draws, in registers across all steps of a launch.  GwCtrlDist's block holds {g[4], key, n}, 48
+// bytes per env: three 16-byte loads when a launch opens, one 8-byte store of n when it closes.  `nc` is n * DIST_STEP mod
+// 2^64 carried as a running sum: one multiply per launch, an add per draw.
+constexpr uint64_t DIST_STEP = 0xD1B54A32D192ED03ull;
+
+struct Dist {
+    double g[4];
+    uint64_t key, n, nc;
+};
+
+__device__ __forceinline__ void dist_load(Dist& W, const GwCtrlDist& w, int64_t e)
+{
+    const ulonglong2* p = reinterpret_cast<const ulonglong2*>(w.rec + e * 6);  // hipMalloc'ed, 48-byte records: 16-byte aligned
+    const ulonglong2 a = p[0], b = p[1], d = p[2];
+    W.g[0] = __longlong_as_double((long long)a.x); W.g[1] = __longlong_as_double((long long)a.y);
+    W.g[2] = __longlong_as_double((long long)b.x); W.g[3] = __longlong_as_double((long long)b.y);
+    W.key = d.x; W.n = d.y;
+    W.nc = d.y * DIST_STEP;
+}
+
+__device__ __forceinline__ void dist_store(const Dist& W, const GwCtrlDist& w, int64_t e)
+{
+    w.rec[e * 6 + 5] = W.n;
+}
+
+// one draw: the mixer of gw_policy_u (ct_rollout_sync.hip.h) on key ^ (n * DIST_STEP), its top 32 bits as a signed integer
+// times 2^-31 -- uniform on [-1, 1), a multiple of 2^-31, every operation exact
+__device__ __forceinline__ double dist_draw(Dist& W)
+{
+    uint64_t z = (W.key ^ W.nc) + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    W.n += 1ull;
+    W.nc += DIST_STEP;
+    return (double)(int32_t)(uint32_t)(z >> 32) * 0x1p-31;
 }
 
 __device__ __forceinline__ uint32_t pick(const uint32_t (&a)[CR], int i)

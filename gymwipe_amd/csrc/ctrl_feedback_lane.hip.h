@@ -1,7 +1,7 @@
 // ctrl_feedback_lane.hip.h -- the lane loop of the angle-feedback rollout kernels and the staging of a block's policy, shared by
-// ctrl_rollout_feedback.hip (the kernels with the default controller folded in) and ctrl_rollout_feedback_pid.hip (their PID
-// instantiations: per-env gains).  What the loop does is stated at the top of ctrl_rollout_feedback.hip.  Everything here is
-// local to the including file (an unnamed namespace): each of the two compiles its own instantiations.
+// ctrl_rollout_feedback.hip (the kernels with the default controller folded in), ctrl_rollout_feedback_pid.hip (their PID
+// instantiations: per-env gains) and ctrl_rollout_feedback_dist.hip (their disturbance instantiations: per-env plant noise).  What the loop does is stated at the top of ctrl_rollout_feedback.hip.  Everything here is
+// local to the including file (an unnamed namespace): each of the three compiles its own instantiations.
 #pragma once
 #include "ctrl_common.hip.h"
 
@@ -23,9 +23,11 @@ struct FbRows {                                              // gw_ctrl_feedback
 // The loop of both kernels, one lane per env.  ROWS: row k receives the action taken and what gw_ctrl_rollout would write,
 // stores nothing waits for.  PID: the controller is the PID on the env's own gains, as in ctrl_rollout.hip's loop.
 // (A __forceinline__ template, not a kernel: the kernels below are plain functions.)
-template <bool ROWS, bool PID>
-__device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const int steps,
-                                                   const uint32_t max_steps, const double fail_deg, const uint8_t* s_trans, const double* s_ber, double* col0,
+// DIST (with PID): the plant is disturbed, as in that loop -- the env's record in registers, its count stored back once, a reset
+// leaves it alone.
+template <bool ROWS, bool PID, bool DIST>
+__device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w,
+                                                   const int steps, const uint32_t max_steps, const double fail_deg, const uint8_t* s_trans, const double* s_ber, double* col0,
                                                    double* col1, const int64_t e, const uint8_t* s_sched, const int32_t* s_edges,
                                                    const uint32_t* s_par, const FbRows& r, double* __restrict__ tally)
 {
@@ -44,6 +46,8 @@ __device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwC
     double* ring1 = c.pay + ((size_t)e * 2 + 1) * GW_RING_PHYS;
     Pid G;
     if (PID) pid_load(G, g, e);
+    Dist W;
+    if (DIST) dist_load(W, w, e);
     uint32_t age = s.age[e];
     double cost = s.cost[e];
     const double deg_per_rad = 180.0 / 3.141592653589793;
@@ -69,7 +73,13 @@ __device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwC
         const double t_before = L.now;
         q_open(q0);
         q_open(q1);
-        if constexpr (PID) {
+        if constexpr (DIST) {
+#define GW_CTRL_PID
+#define GW_CTRL_DIST
+#include "ctrl_step_body.h"
+#undef GW_CTRL_DIST
+#undef GW_CTRL_PID
+        } else if constexpr (PID) {
 #define GW_CTRL_PID
 #include "ctrl_step_body.h"
 #undef GW_CTRL_PID
@@ -122,6 +132,7 @@ __device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwC
     c.ntx[e] = L.ntx; c.ncmd[e] = L.ncmd; c.nsub[e] = L.nsub; c.flags[e] = L.fl;
     s.age[e] = age; s.cost[e] = cost;
     if (PID) pid_store(G, g, e);
+    if (DIST) dist_store(W, w, e);
     double* t = tally + e * GW_CTRL_FB_COLS;
     t[0] = (double)n_ended; t[1] = (double)n_failed; t[2] = (double)steps; t[3] = cost_ended;
     t[4] = airtime;         t[5] = elapsed;          t[6] = area;          t[7] = (double)n_bin0;

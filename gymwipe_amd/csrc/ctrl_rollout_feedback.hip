@@ -29,7 +29,7 @@ __global__ __launch_bounds__(64) void ctrl_rollout_fb_kernel(GwCtrlDev c, GwCtrl
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= c.N) return;
     const FbRows none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ctrl_feedback_lane<false, false>(c, s, GwCtrlPid{nullptr}, steps, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
+    ctrl_feedback_lane<false, false, false>(c, s, GwCtrlPid{nullptr}, GwCtrlDist{nullptr}, steps, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
                                      s_new1 + (threadIdx.x & 63), e, s_sched, s_edges, s_par, none, tally);
 }
 
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(64) void ctrl_rollout_fb_rows_kernel(GwCtrlDev c, G
     __syncthreads();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= c.N) return;
-    ctrl_feedback_lane<true, false>(c, s, GwCtrlPid{nullptr}, steps, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
+    ctrl_feedback_lane<true, false, false>(c, s, GwCtrlPid{nullptr}, GwCtrlDist{nullptr}, steps, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
                                     s_new1 + (threadIdx.x & 63), e, s_sched, s_edges, s_par, rows, tally);
 }
 

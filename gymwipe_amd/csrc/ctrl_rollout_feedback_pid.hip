@@ -23,7 +23,7 @@ __global__ __launch_bounds__(64) void ctrl_rollout_fb_pid_kernel(GwCtrlDev c, Gw
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= c.N) return;
     const FbRows none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ctrl_feedback_lane<false, true>(c, s, g, steps, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
+    ctrl_feedback_lane<false, true, false>(c, s, g, GwCtrlDist{nullptr}, steps, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
                                     s_new1 + (threadIdx.x & 63), e, s_sched, s_edges, s_par, none, tally);
 }
 
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(64) void ctrl_rollout_fb_rows_pid_kernel(GwCtrlDev 
     __syncthreads();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= c.N) return;
-    ctrl_feedback_lane<true, true>(c, s, g, steps, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
+    ctrl_feedback_lane<true, true, false>(c, s, g, GwCtrlDist{nullptr}, steps, max_steps, fail_deg, s_trans, s_ber, s_new0 + (threadIdx.x & 63),
                                    s_new1 + (threadIdx.x & 63), e, s_sched, s_edges, s_par, rows, tally);
 }
 

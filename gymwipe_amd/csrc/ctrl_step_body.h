@@ -9,6 +9,9 @@
 // The controller's rule is a compile-time switch, a preprocessor symbol because the text is no template: included with
 // GW_CTRL_PID defined, the controller is the reference's three-term PID on the env's own gains and last error, G (Pid), which the
 // including kernel then provides as well; included without, it is the same rule at gains (1, 0, 0), folded, and no G is named.
+// The plant disturbance is a second switch, GW_CTRL_DIST, only ever defined together with GW_CTRL_PID: every substep then ends
+// with one draw of the env's own counter-based noise added to the plant's state (gw_ctrl_set_disturbance in
+// include/gymwipe_amd.h), on W (Dist), which the including kernel provides; without it no W is named and the plant is exact.
     if ((unsigned)d >= 2u || (unsigned)du >= (unsigned)k.max_duration) {
         L.fl |= GW_FLAG_BADACT;                              // envs/inverted_pendulum.py:102 asserts; flagged and skipped here
     } else {
@@ -38,8 +41,16 @@
                 acc = acc + c.A[i * 4 + 3] * L.x[3];
                 nx[i] = acc + c.B[i] * L.u;
             }
+#ifdef GW_CTRL_DIST
+            {                                                                  // ... and is pushed: x = nx + g * w, the product
+                const double w = dist_draw(W);                                 // rounded, then the sum (no contraction); n += 1
+#pragma unroll
+                for (int i = 0; i < 4; ++i) L.x[i] = nx[i] + W.g[i] * w;
+            }
+#else
 #pragma unroll
             for (int i = 0; i < 4; ++i) L.x[i] = nx[i];
+#endif
             L.nsub++;
             const uint32_t kk = L.ktick;                                        // controller
             if (kk >= c.start) {

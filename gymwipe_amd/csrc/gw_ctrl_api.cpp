@@ -18,6 +18,8 @@ struct gw_ctrl {
     GwCtrlEpi epi;                     // per-env initial state and episode record (not part of the step kernel's argument)
     GwCtrlPid pid;                     // per-env gains and last error: {1, 0, 0, 0} from gw_ctrl_create on
     bool pid_on;                       // gw_ctrl_set_gains has been called: the launches take the PID instantiations, for good
+    GwCtrlDist dist;                   // per-env plant disturbance {g[4], key, n}: all 0 from gw_ctrl_create on
+    bool dist_on;                      // gw_ctrl_set_disturbance has been called: the disturbance instantiations, for good (pid_on too)
     void* blocks[24];
     int nblocks;
 };
@@ -133,12 +135,14 @@ int gw_ctrl_create(const gw_ctrl_config* cfg, gw_ctrl** out)
     CA(d_cst, 1); CA(d_trans, tcount); CA(d_ber, tcount);
     CA(c->epi.x_init, N * 4); CA(c->epi.u_init, N); CA(c->epi.cost, N); CA(c->epi.age, N);
     CA(c->pid.pid, N * 4);
+    CA(c->dist.rec, N * 6);
 #undef CA
     d.cst = d_cst; d.trans = d_trans; d.ber = d_ber;
     CTRL_HIP(hipMemcpy(d_cst, &k, sizeof k, hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemcpy(d_trans, c->tab.trans, tcount, hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemcpy(d_ber, c->tab.ber, tcount * sizeof(double), hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemset(d.pay, 0, (size_t)N * 2 * GW_RING_PHYS * sizeof(double)), gw_ctrl_destroy(c));
+    CTRL_HIP(hipMemset(c->dist.rec, 0, (size_t)N * 6 * sizeof(uint64_t)), gw_ctrl_destroy(c));    // g = 0, key = 0, n = 0
     {
         const double def[4] = {1.0, 0.0, 0.0, 0.0};          // the reference's shipped gains, and a fresh controller's last error
         std::vector<double> fill((size_t)N * 4);
@@ -160,7 +164,8 @@ int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_
     if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
     if (!device_dev || !duration_dev || !obs_dev || !reward_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_step: NULL device pointer");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_step(c->dev, pid_of(c), device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream))
+    if (c->dist_on ? gw_ctrl_launch_step_dist(c->dev, c->pid, c->dist, device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream)
+                   : gw_ctrl_launch_step(c->dev, pid_of(c), device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop step launch failed");
     return GW_OK;
 }
@@ -186,6 +191,19 @@ int gw_ctrl_set_gains(gw_ctrl* c, const double* gains_dev, const uint8_t* mask_d
     return GW_OK;
 }
 
+int gw_ctrl_set_disturbance(gw_ctrl* c, const double* g_dev, const uint64_t* key_dev, const uint8_t* mask_dev, void* stream)
+{
+    if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
+    if (!g_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_set_disturbance: g_dev is NULL");
+    if (!key_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_set_disturbance: key_dev is NULL");
+    CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
+    if (gw_ctrl_launch_set_disturbance(c->dev, c->dist, g_dev, key_dev, mask_dev, stream))
+        return gw_set_error(GW_EHIP, "control-loop set_disturbance launch failed");
+    c->dist_on = true;                 // the disturbance instantiations are PID instantiations: a reset clears last_error
+    c->pid_on = true;                  // from here on, as on a handle that has set gains
+    return GW_OK;
+}
+
 int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* stream)
 {
     if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
@@ -205,7 +223,10 @@ int gw_ctrl_rollout(gw_ctrl* c, int32_t steps, const int32_t* device_dev, const 
     if (steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout: steps < 0");
     if (steps == 0) return GW_OK;
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_rollout(c->dev, c->epi, pid_of(c), steps, device_dev, duration_dev, ep, obs_dev, reward_dev, angle_deg_dev, ended_dev, stream))
+    if (c->dist_on ? gw_ctrl_launch_rollout_dist(c->dev, c->epi, c->pid, c->dist, steps, device_dev, duration_dev, ep, obs_dev, reward_dev,
+                                                 angle_deg_dev, ended_dev, stream)
+                   : gw_ctrl_launch_rollout(c->dev, c->epi, pid_of(c), steps, device_dev, duration_dev, ep, obs_dev, reward_dev, angle_deg_dev,
+                                            ended_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop rollout launch failed");
     return GW_OK;
 }
@@ -225,7 +246,8 @@ int gw_ctrl_rollout_schedules(gw_ctrl* c, int32_t steps, const uint8_t* sched_de
     if (N % P != 0 || (N / P) % 64 != 0)
         return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_schedules: num_envs / P must be a whole multiple of 64 (one schedule per block)");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_rollout_schedules(c->dev, c->epi, pid_of(c), steps, sched_dev, P, L, *ep, tally_dev, stream))
+    if (c->dist_on ? gw_ctrl_launch_rollout_schedules_dist(c->dev, c->epi, c->pid, c->dist, steps, sched_dev, P, L, *ep, tally_dev, stream)
+                   : gw_ctrl_launch_rollout_schedules(c->dev, c->epi, pid_of(c), steps, sched_dev, P, L, *ep, tally_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop schedule rollout launch failed");
     return GW_OK;
 }
@@ -252,7 +274,8 @@ int gw_ctrl_rollout_feedback(gw_ctrl* c, int32_t steps, const gw_ctrl_feedback* 
     if (N % P != 0 || (N / P) % 64 != 0)
         return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_feedback: num_envs / P must be a whole multiple of 64 (one policy per block)");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_rollout_feedback(c->dev, c->epi, pid_of(c), steps, *fb, *ep, rows, tally_dev, stream))
+    if (c->dist_on ? gw_ctrl_launch_rollout_feedback_dist(c->dev, c->epi, c->pid, c->dist, steps, *fb, *ep, rows, tally_dev, stream)
+                   : gw_ctrl_launch_rollout_feedback(c->dev, c->epi, pid_of(c), steps, *fb, *ep, rows, tally_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop feedback rollout launch failed");
     return GW_OK;
 }
@@ -297,6 +320,13 @@ int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst, size_t bytes)
         if (bytes != (size_t)N * cols * sizeof(double)) return gw_set_error(GW_EFIELD, "field %s needs %zu bytes", field, (size_t)N * cols * sizeof(double));
         CTRL_HIP(hipMemcpy2D(dst, cols * sizeof(double), c->pid.pid + (gains ? 0 : 3), 4 * sizeof(double), cols * sizeof(double), (size_t)N,
                              hipMemcpyDeviceToHost), (void)0);
+        return GW_OK;
+    }
+    if (!strcmp(field, "disturbance") || !strcmp(field, "noise_key") || !strcmp(field, "noise_count")) {
+        // f64[N][4] / u64[N] / u64[N]: columns of the {g[4], key, n} records
+        const size_t cols = field[0] == 'd' ? 4 : 1, first = field[0] == 'd' ? 0 : (field[6] == 'k' ? 4 : 5);
+        if (bytes != (size_t)N * cols * 8) return gw_set_error(GW_EFIELD, "field %s needs %zu bytes", field, (size_t)N * cols * 8);
+        CTRL_HIP(hipMemcpy2D(dst, cols * 8, c->dist.rec + first, 6 * 8, cols * 8, (size_t)N, hipMemcpyDeviceToHost), (void)0);
         return GW_OK;
     }
     if (!strcmp(field, "rx_power")) {                      // f64[N][4]

@@ -293,6 +293,25 @@ int gw_ctrl_launch_rollout_feedback(const GwCtrlDev& c, const GwCtrlEpi& s, cons
 int gw_ctrl_launch_rollout_feedback_pid(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, int32_t steps,
                                         const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
                                         double* tally, void* stream);                   // ctrl_rollout_feedback_pid.hip
+// Per-env plant disturbance (the rule: include/gymwipe_amd.h, gw_ctrl_set_disturbance).  One block of 48-byte records
+// {g[4] f64, key u64, n u64}, addressed as u64[N][6]; a struct of its own for GwCtrlEpi's reason.  A handle that has set a
+// disturbance launches the *_dist launchers below and no other step or rollout launcher: their kernels are the PID
+// instantiations with the rule at the end of every plant substep.
+struct GwCtrlDist {
+    uint64_t* rec;                             // [N][6]
+};
+int gw_ctrl_launch_set_disturbance(const GwCtrlDev& c, const GwCtrlDist& w, const double* g, const uint64_t* key, const uint8_t* mask,
+                                   void* stream);                                       // ctrl_rollout_dist.hip, as the next two
+int gw_ctrl_launch_rollout_dist(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, int32_t steps,
+                                const int32_t* device, const int32_t* duration, const gw_ctrl_episodes* ep, int32_t* obs, float* reward,
+                                double* angle_deg, uint8_t* ended, void* stream);
+int gw_ctrl_launch_rollout_schedules_dist(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, int32_t steps,
+                                          const uint8_t* sched, int32_t P, int32_t L, const gw_ctrl_episodes& ep, double* tally, void* stream);
+int gw_ctrl_launch_step_dist(const GwCtrlDev& c, const GwCtrlPid& g, const GwCtrlDist& w, const int32_t* device, const int32_t* duration,
+                             int32_t* obs, float* reward, double* angle_deg, void* stream);      // ctrl_step_dist.hip
+int gw_ctrl_launch_rollout_feedback_dist(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, int32_t steps,
+                                         const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
+                                         double* tally, void* stream);                  // ctrl_rollout_feedback_dist.hip
 int gw_fill_dev_const(const gw_config& cfg, const GwHostTables& tab, GwDevConst& k);   // gw_api.cpp
 int gw_validate_config(const gw_config& cfg);                                           // gw_api.cpp
 

@@ -149,11 +149,13 @@ class VecControlLoopEnv(BaseEnv):
     ``rollout_feedback`` (P angle-feedback schedulers: the env's own angle picks which of B schedules it acts on).
     The controller is the reference's three-term PID on gains every env holds of its own: ``set_gains`` (or ``gains=`` here);
     the default, the reference's shipped (1, 0, 0), commands ``-angle``.  Gains laid across the envs of each schedule
-    (``actions.make_ctrl_gains``) make the rollout calls rank controllers and schedulers together."""
+    (``actions.make_ctrl_gains``) make the rollout calls rank controllers and schedulers together.
+    The plant is exact unless ``set_disturbance`` (or ``disturbance=`` here) gives envs seeded noise on their plant's state:
+    something to hold the pendulum against after the transient, keyed per env so that candidates can face the same noise."""
     SENSOR, CONTROLLER, ACTUATOR = 0, 1, 2
 
     def __init__(self, num_envs, device="cuda:0", ctrl_start_tick=None, ctrl_period_ticks=None, positions=None, x0=None,
-                 A=None, B=None, u0=None, counter_interval=None, gains=None):
+                 A=None, B=None, u0=None, counter_interval=None, gains=None, disturbance=None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gymwipe_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -199,6 +201,8 @@ class VecControlLoopEnv(BaseEnv):
         self._stepped = False
         if gains is not None:                              # (None: the handle never reads gains; its kernels have (1, 0, 0) folded in)
             self.set_gains(gains)
+        if disturbance is not None:                        # (None: the plant is exact and the handle's kernels draw nothing)
+            self.set_disturbance(disturbance)
 
     def reset(self):
         """envs/inverted_pendulum.py:95-99: returns an observation, resets nothing."""
@@ -267,10 +271,47 @@ class VecControlLoopEnv(BaseEnv):
         with torch.cuda.device(self.device):
             nat.check(self._L.gw_ctrl_set_gains(self._h, g.data_ptr(), m.data_ptr() if m is not None else None, self._stream()))
 
+    def set_disturbance(self, g, key=None, mask=None):
+        """Disturb the plant of the masked envs (None: all): ``g`` f64[N][4], one weight per plant state (a single vector of 4
+        is broadcast), and ``key``, one 64-bit noise key per env -- numpy uint64[N], or an int64 tensor holding the bit
+        patterns; None: ``actions.make_ctrl_disturbance``'s default keys, a sequence of its own for every env.  From then on
+        every plant substep of those envs ends with ``x[i] += g[i] * w``, ``w`` uniform on [-1, 1) and a function of the env's
+        key and of the count of substeps since this call alone (``actions.ctrl_noise_numpy``): envs with equal keys face the
+        same noise.  The count restarts here and nowhere else: a reset keeps g, key and count, so that every episode of an env
+        meets fresh noise.  No other running state is touched.  From the first call on the handle launches the kernels that
+        draw, which also read the gains; with ``g = 0`` they compute what the gains' kernels compute."""
+        import numpy as np
+        torch = self._torch
+        gt = torch.as_tensor(g, dtype=torch.float64).to(self.device)
+        if tuple(gt.shape) == (4,):
+            gt = gt.expand(self.num_envs, 4)
+        if tuple(gt.shape) != (self.num_envs, 4):
+            raise ValueError("g must be 4 weights or float64[num_envs][4]")
+        gt = gt.contiguous()
+        if key is None:
+            from .. import actions
+            key = actions.make_ctrl_disturbance(np.zeros(4), self.num_envs)[1]
+        if isinstance(key, torch.Tensor):
+            if key.dtype != torch.int64:
+                raise ValueError("key as a tensor is int64[num_envs] holding the keys' bit patterns")
+            kt = key.to(self.device)
+        else:
+            ka = np.asarray(key)
+            if ka.dtype != np.uint64:
+                raise ValueError("key is numpy uint64[num_envs] (or an int64 tensor holding the bit patterns)")
+            kt = torch.from_numpy(np.ascontiguousarray(ka).view(np.int64)).to(self.device)
+        if tuple(kt.shape) != (self.num_envs,):
+            raise ValueError("key holds one key per env")
+        kt = kt.contiguous()
+        m = self._mask(mask)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_ctrl_set_disturbance(self._h, gt.data_ptr(), kt.data_ptr(), m.data_ptr() if m is not None else None,
+                                                      self._stream()))
+
     def reset_envs(self, mask=None):
         """Put the masked envs (None: all) back into the state a fresh env of their own initial state has -- clock, queues,
         noise states, counters, the episode record (``age``, ``cost``) and the controller's ``last_error`` 0; ``flags`` are
-        sticky and stay, and so do the gains -- and return the observations of all N envs.  (``reset()`` keeps the reference's meaning: it resets nothing.)"""
+        sticky and stay, and so do the gains and the disturbance (weights, key and count) -- and return the observations of all N envs.  (``reset()`` keeps the reference's meaning: it resets nothing.)"""
         torch = self._torch
         m = self._mask(mask)
         self._stepped = True                               # the observation buffer now holds what the GPU wrote
@@ -371,7 +412,8 @@ class VecControlLoopEnv(BaseEnv):
                "rx_power": ((4,), "f8"), "qlen": ((2,), "i4"), "received": ((2,), "u4"), "n_tx": ((), "u4"),
                "commands": ((), "u4"), "substeps": ((), "u4"), "flags": ((), "u4"),
                "age": ((), "u4"), "cost": ((), "f8"), "x_init": ((4,), "f8"), "u_init": ((), "f8"),
-               "gains": ((3,), "f8"), "last_error": ((), "f8")}
+               "gains": ((3,), "f8"), "last_error": ((), "f8"),
+               "disturbance": ((4,), "f8"), "noise_key": ((), "u8"), "noise_count": ((), "u8")}
 
     def get_state(self, field):
         import numpy as np

@@ -783,7 +783,8 @@ int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_
 /* host copies: "now","wake","u","angle_deg" f64[N] | "x" f64[N][4] | "rx_power" f64[N][4] | "qlen" int32[N][2] |
  *              "received" u32[N][2] (controller, actuator) | "n_tx","commands","substeps","flags" u32[N] |
  *              "age" u32[N], "cost" f64[N] (the running episode's record) | "x_init" f64[N][4], "u_init" f64[N] |
- *              "gains" f64[N][3] {kp, ki, kd}, "last_error" f64[N] (the controller, gw_ctrl_set_gains) */
+ *              "gains" f64[N][3] {kp, ki, kd}, "last_error" f64[N] (the controller, gw_ctrl_set_gains) |
+ *              "disturbance" f64[N][4], "noise_key" u64[N], "noise_count" u64[N] (the plant's, gw_ctrl_set_disturbance) */
 int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst_host, size_t bytes);
 
 /* Per-env initial state and reset.  Every env keeps an initial state of its own (x_init, u_init; cfg.x0 / cfg.u0 at create) and
@@ -792,7 +793,8 @@ int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst_host, size_t byte
  * it changes no env's running state.  gw_ctrl_reset puts the masked envs into exactly the state gw_ctrl_create leaves, with the
  * env's own initial state: clock, wake and tick 0, controller angle 0, both queues empty (head = len = 0), noise states 0,
  * received, n_tx, commands, substeps, age, cost and the controller's last_error 0.  flags are sticky and stay, and so do the
- * gains.  Envs outside the mask are untouched, bit for bit.  obs_dev (NULL ok) receives (int32) degrees(x[2]) of all N envs. */
+ * gains and the plant's disturbance record (g, key and the count n).  Envs outside the mask are untouched, bit for bit.
+ * obs_dev (NULL ok) receives (int32) degrees(x[2]) of all N envs. */
 int gw_ctrl_set_initial(gw_ctrl* c, const double* x0_dev, const double* u0_dev, const uint8_t* mask_dev, void* stream);
 int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* stream);
 
@@ -813,6 +815,31 @@ int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* s
  * no gains; its first call switches the handle, for good, to the kernels that read them.  Results do not depend on which
  * kernels run: a handle set to (1, 0, 0) computes what an unswitched one computes, and its last_error moves. */
 int gw_ctrl_set_gains(gw_ctrl* c, const double* gains_dev, const uint8_t* mask_dev, void* stream);
+
+/* Plant disturbance: seeded, counter-based noise on the plant's state, per env.  BUILDER-DEFINED, as the whole loop is.  Every
+ * env holds a record of 48 bytes {g[4] f64, key u64, n u64}, all 0 at create.  On a handle on which gw_ctrl_set_disturbance has
+ * been called, every counter tick runs the plant substep nx = A x + B u as before and then ends with, all integers mod 2^64:
+ *     z  = key ^ (n * 0xD1B54A32D192ED03)
+ *     z += 0x9E3779B97F4A7C15
+ *     z  = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z  = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z ^= z >> 31
+ *     w  = (double)(int32_t)(uint32_t)(z >> 32) * 0x1p-31          uniform on [-1, 1), a multiple of 2^-31, every operation exact
+ *     x[i] = nx[i] + g[i] * w      for i = 0..3                    the product rounded, then the sum; no contraction
+ *     n += 1
+ * n counts the substeps since the env's record was last set, and nothing else restarts it: gw_ctrl_reset and the reset at an
+ * episode's end inside a rollout leave g, key and n alone -- a reset env is a fresh env whose plant goes on drawing where the old
+ * one stopped (else every episode of an env would replay one noise sequence).  n lives in the handle: two calls of K / 2 steps
+ * equal one of K.  The draw depends on (key, n) alone, so two envs with equal key, g, gains, initial state and actions walk
+ * bit-identical trajectories wherever they sit in the batch; giving env j of every candidate the same key compares candidates on
+ * common random numbers.  With g = 0 the rule adds +-0: it may turn a -0.0 of the plant into +0.0 and changes nothing else.
+ * gw_ctrl_set_disturbance stores g_dev f64[N][4] and key_dev u64[N] and sets n = 0 for the envs with mask_dev[e] != 0 (NULL:
+ * all); other envs are untouched, bit for bit, and so is all other running state.  Stream-ordered; allocates nothing.  A NULL
+ * c, g_dev or key_dev: GW_EINVAL before any device call.  No value is validated: any f64 has the one meaning the rule gives it.
+ * A handle on which it has never been called launches exactly the kernels it launched before; its first call switches the
+ * handle, for good, to the disturbance instantiations of the step, rollout, schedule and both feedback kernels, which are PID
+ * instantiations as well (the gains are what gw_ctrl_set_gains last stored, {1, 0, 0} if it never did). */
+int gw_ctrl_set_disturbance(gw_ctrl* c, const double* g_dev, const uint64_t* key_dev, const uint8_t* mask_dev, void* stream);
 
 typedef struct gw_ctrl_episodes {
     int32_t max_steps;                      /* an episode ends when its age reaches this; 0: no limit */
