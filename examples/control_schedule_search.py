@@ -33,6 +33,14 @@ every plant substep (env.set_disturbance), something to hold the pendulum agains
 (actions.make_ctrl_disturbance(streams=arange(N) % envs_per_pair)): all cells face the same m noise sequences, so two cells'
 difference is a paired one.  Printed are both rankings side by side and, for the two best disturbed cells, in how many of the
 m sequences the better one wins.
+
+    python examples/control_schedule_search.py --loss 0.5 [--loss-links 1,1,1,1] [--disturbance 0.01] [--envs-per-pair 8]
+
+ranks the grid twice on the disturbed plant (weight --disturbance, default 0.01): on the PHY's own links, which drop nothing at
+this geometry, and with every transmission erased with probability P times its link's entry of --loss-links (announcement to the
+sensor, to the controller, sensor's data, controller's data; env.set_loss).  Env j of every cell gets noise stream j and loss
+stream j (actions.make_ctrl_loss(streams=arange(N) % envs_per_pair)): all cells lose the same transmissions, counted in the
+order they go on the air.  Printed are both rankings side by side, how the ranking moves, and the erasures per link.
 """
 import argparse
 import os
@@ -60,12 +68,19 @@ def main():
     ap.add_argument("--envs-per-pair", type=int, default=8, help="initial angles per (gain set, schedule) pair of --gains")
     ap.add_argument("--disturbance", type=float, default=None, metavar="A",
                     help="rank the gain x schedule grid with and without plant noise of weight A on x[3], common random numbers")
+    ap.add_argument("--loss", type=float, default=None, metavar="P",
+                    help="rank the gain x schedule grid on the disturbed plant with and without packet loss P, common random numbers")
+    ap.add_argument("--loss-links", default="1,1,1,1", help="a,b,c,d: P is multiplied by these per link "
+                    "(announcement to sensor, to controller, sensor -> controller, controller -> actuator)")
     ap.add_argument("--disturbance-steps", type=int, default=120, help="steps per env of --disturbance")
     args = ap.parse_args()
 
     import torch
     from gymwipe_amd import VecControlLoopEnv, actions
 
+    if args.loss is not None:
+        loss_grid(args, torch, VecControlLoopEnv, actions)
+        return
     if args.disturbance is not None:
         disturbance_grid(args, torch, VecControlLoopEnv, actions)
         return
@@ -277,6 +292,65 @@ def disturbance_grid(args, torch, VecControlLoopEnv, actions):
           " stream it wins in %d of %d" % (a.mean(), b.mean(), a.max() - a.min(), b.max() - b.min(), int((a < b).sum()), m))
     print("the exact plant's winner is rank %d of %d under disturbance; the disturbed winner is rank %d on the exact plant"
           % (rank_n[order_c[0]] + 1, P * G, rank_c[order_n[0]] + 1))
+
+
+def loss_grid(args, torch, VecControlLoopEnv, actions):
+    """disturbance_grid's layout and disturbed plant: the time-weighted mean |angle| of every (gain set, schedule) cell without
+    and with packet loss, m noise streams and m loss streams shared by all cells."""
+    closing = [(n, s) for n, s in SCHEDULES if any(d == 1 and u > 0 for d, u in s)]
+    G, P, m = len(GAIN_SETS), len(closing), args.envs_per_pair
+    if (G * m) % 64:
+        sys.exit("--envs-per-pair times %d gain sets must be a multiple of 64 (one schedule per 64-env block)" % G)
+    links = [float(v) for v in args.loss_links.split(",")]
+    if len(links) != 4:
+        sys.exit("--loss-links takes four factors a,b,c,d")
+    N = P * G * m
+    steps = args.disturbance_steps
+    names = [n for n, _ in closing]
+    sched, edges = actions.make_ctrl_feedback([[s] for _, s in closing], [[]] * P)
+    a = 0.01 if args.disturbance is None else args.disturbance
+    streams = np.arange(N) % m
+    weights, nkey = actions.make_ctrl_disturbance((0.0, 0.0, 0.0, a), N, seed=args.seed, streams=streams)
+    p_link = [args.loss * f for f in links]
+    _, lkey = actions.make_ctrl_loss(p_link, N, seed=args.seed + 1, streams=streams)
+
+    def run(lossy):
+        env = VecControlLoopEnv(N, x0=(0.0, 0.0, 0.0, 0.0), gains=actions.make_ctrl_gains(GAIN_SETS, N, envs_per_set=m))
+        env.set_disturbance(weights, nkey)
+        if lossy:
+            env.set_loss(p_link, lkey)
+        tally, _ = env.rollout_feedback(sched, edges, (0, 0.0), steps, abs_key=True)
+        t = tally.view(P, G, m, tally.shape[1]).cpu().numpy()
+        lost, sent = env.get_state("lost").sum(0), int(env.get_state("loss_count").sum())
+        env.close()
+        err = t[..., 6] / t[..., 5]
+        return np.where(np.isfinite(err), err, np.inf), lost, sent
+
+    (clean, _, _), (lossy, lost, sent) = run(False), run(True)
+    c, n = clean.mean(2), lossy.mean(2)
+    order_c, order_n = np.argsort(c, axis=None), np.argsort(n, axis=None)
+    rank_c, rank_n = np.empty(P * G, int), np.empty(P * G, int)
+    rank_c[order_c], rank_n[order_n] = np.arange(P * G), np.arange(P * G)
+
+    def cell(i):
+        p, g = np.unravel_index(i, c.shape)
+        return "%-16s %-18s" % (names[p], GAIN_SETS[g])
+    print("time-weighted mean |angle| in degrees over %d steps from upright, noise weight %g; loss probability per link %s;"
+          " %d noise and loss streams shared by all %d cells" % (steps, a, ["%g" % v for v in np.clip(p_link, 0, 1)], m, P * G))
+    print("%4s  %-35s %10s %10s %6s   |  %-35s %10s %10s %6s" % ("rank", "no loss: schedule, gains", "no loss", "lossy", "there",
+                                                               "lossy: schedule, gains", "lossy", "spread", "no loss"))
+    for r in range(min(10, P * G)):
+        i, j = order_c[r], order_n[r]
+        print("%4d  %s %10.4g %10.4g %6d   |  %s %10.4g %10.4g %6d"
+              % (r + 1, cell(i), c.flat[i], n.flat[i], rank_n[i] + 1, cell(j), n.flat[j],
+                 lossy.reshape(P * G, m)[j].max() - lossy.reshape(P * G, m)[j].min(), rank_c[j] + 1))
+    moved = np.abs(rank_c - rank_n)
+    print("how the ranking moves: the lossless winner is rank %d of %d under loss; the lossy winner is rank %d without loss; %d of %d cells"
+          " change rank, by %.1f places on average and %d at most" % (rank_n[order_c[0]] + 1, P * G, rank_c[order_n[0]] + 1,
+                                                                       int((moved > 0).sum()), P * G, moved.mean(), moved.max()))
+    best = np.array([n[p].min() for p in range(P)])
+    print("best cell per schedule under loss: " + ", ".join("%s %.3g (no loss %.3g)" % (names[p], best[p], c[p].min()) for p in range(P)))
+    print("erased of %d transmissions, per link: %s" % (sent, ", ".join("%s %d" % (l, v) for l, v in zip(actions.CTRL_LOSS_LINKS, lost))))
 
 
 if __name__ == "__main__":

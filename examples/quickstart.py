@@ -127,6 +127,10 @@ print("control loop: the same with kp = 0.1:", [round(v, 1) for v in (lambda s: 
 loop.set_disturbance((0.0, 0.0, 0.0, 0.01))           # seeded noise on the plant's state at every substep, one key per env (default: its own)
 loop.reset_envs()
 print("control loop: ... and a plant that is pushed:", [round(v, 1) for v in (lambda s: s[:, 3] / s[:, 0])(loop.rollout_schedules(scheds, (40, 0.0), 40)[1]).tolist()])
+loop.set_loss((0.3, 0.3, 0.3, 0.3))                   # seeded packet erasures: a loss probability per link (two announcements, two data links)
+loop.reset_envs()
+print("control loop: ... over links that lose 30 %:", [round(v, 1) for v in (lambda s: s[:, 3] / s[:, 0])(loop.rollout_schedules(scheds, (40, 0.0), 40)[1]).tolist()],
+      "erased per link:", loop.get_state("lost").sum(0).tolist())
 
 # 6. the reference's PHY-grid benchmark (tests/test_benchmark.py), 1 024 replicas of a 16-device grid
 import numpy as np

@@ -33,7 +33,7 @@ EXPORTS = (
     "gw_plant_config_default", "gw_plant_create", "gw_plant_destroy", "gw_plant_update", "gw_plant_set_input",
     "gw_plant_state_ptr", "gw_plant_get_state", "gw_plant_feedback", "gw_plant_update_feedback", "gw_now_ptr", "gw_pendulum_step",
     "gw_ctrl_config_default", "gw_ctrl_create", "gw_ctrl_destroy", "gw_ctrl_step", "gw_ctrl_get_state",
-    "gw_ctrl_set_initial", "gw_ctrl_set_gains", "gw_ctrl_set_disturbance", "gw_ctrl_reset", "gw_ctrl_rollout", "gw_ctrl_rollout_schedules", "gw_ctrl_rollout_feedback",
+    "gw_ctrl_set_initial", "gw_ctrl_set_gains", "gw_ctrl_set_disturbance", "gw_ctrl_set_loss", "gw_ctrl_reset", "gw_ctrl_rollout", "gw_ctrl_rollout_schedules", "gw_ctrl_rollout_feedback",
     "gw_grid_config_default", "gw_grid_create", "gw_grid_destroy", "gw_grid_run", "gw_grid_get_state", "gw_grid_set_position",
     "gw_grid_selftest_width",
 )
@@ -341,6 +341,7 @@ def lib():
     L.gw_ctrl_set_initial.argtypes, L.gw_ctrl_set_initial.restype = [vp, vp, vp, vp, vp], C.c_int
     L.gw_ctrl_set_gains.argtypes, L.gw_ctrl_set_gains.restype = [vp, vp, vp, vp], C.c_int
     L.gw_ctrl_set_disturbance.argtypes, L.gw_ctrl_set_disturbance.restype = [vp, vp, vp, vp, vp], C.c_int
+    L.gw_ctrl_set_loss.argtypes, L.gw_ctrl_set_loss.restype = [vp, vp, vp, vp, vp], C.c_int
     L.gw_ctrl_reset.argtypes, L.gw_ctrl_reset.restype = [vp, vp, vp, vp], C.c_int
     L.gw_ctrl_rollout.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(CtrlEpisodes), vp, vp, vp, vp, vp]
     L.gw_ctrl_rollout.restype = C.c_int

@@ -664,3 +664,49 @@ def ctrl_noise_numpy(key, n):
         z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
         z = z ^ (z >> u(31))
     return (z >> u(32)).astype(np.uint32).view(np.int32).astype(np.float64) * 2.0 ** -31
+
+
+# ---- control loop: seeded packet erasures per env and link (gw_ctrl_set_loss) --------------------------------------------------------------
+CTRL_LOSS_LINKS = ("rrm->sensor", "rrm->controller", "sensor->controller", "controller->actuator")
+CTRL_LOSS_DEFAULT_SEED = 0x10551055AA55AA55               # not the disturbance's 0: equal stream numbers, other keys
+
+
+def ctrl_loss_threshold(p):
+    """Loss probabilities -> the rule's uint32 thresholds (``gw_ctrl_set_loss`` in include/gymwipe_amd.h): ``p`` is clipped to
+    [0, 1] (NaN: 0) and ``thr = min(floor(p * 2^32), 2^32 - 1)``.  A transmission is erased when its draw, uniform on the 2^32
+    values of a uint32, is below ``thr``: probability ``thr * 2^-32``, so ``p = 0`` never erases and ``p = 1`` erases all but one
+    draw in 2^32.  Any shape; returns uint32 of that shape."""
+    q = np.nan_to_num(np.asarray(p, np.float64), nan=0.0)
+    q = np.clip(q, 0.0, 1.0)
+    return np.minimum(np.floor(q * 4294967296.0), 4294967295.0).astype(np.uint32)
+
+
+def make_ctrl_loss(p, num_envs, seed=CTRL_LOSS_DEFAULT_SEED, streams=None, envs_per_set=None):
+    """``(thr uint32[N][4], key uint64[N])``: what ``VecControlLoopEnv.set_loss`` uploads.  ``p`` is one vector of 4 loss
+    probabilities, one per link of ``CTRL_LOSS_LINKS`` -- the two announcements, then the two data links -- or G of them, laid
+    across the envs the way ``make_ctrl_disturbance`` lays ``g`` (env e gets set ``(e // envs_per_set) % G``) and converted by
+    ``ctrl_loss_threshold``.  The keys are that helper's formula, ``seed ^ (streams[e] * 0x9E3779B97F4A7C15 mod 2^64)``, from a
+    default seed of their own; ``streams = arange(N) % envs_per_policy`` makes env j of every candidate lose the same
+    transmissions, counted in the order they go on the air."""
+    sets = np.asarray(p, np.float64)
+    if sets.ndim == 1:
+        sets = sets[None]
+    if sets.ndim != 2 or sets.shape[1] != 4 or sets.shape[0] < 1:
+        raise ValueError("make_ctrl_loss: p is 4 loss probabilities, one per link, or G x 4")
+    laid, key = make_ctrl_disturbance(sets, num_envs, seed=seed, streams=streams, envs_per_set=envs_per_set)
+    return ctrl_loss_threshold(laid), key
+
+
+def ctrl_loss_numpy(key, n):
+    """The loss rule's draw ``r`` for key ``key`` at count ``n`` (``gw_ctrl_set_loss`` in include/gymwipe_amd.h), vectorised on
+    numpy uint64 (both broadcast); returns uint32.  The env's n-th transmission since its record was set is erased on link l
+    iff ``ctrl_loss_numpy(key, n) < thr[l]``."""
+    u = np.uint64
+    key, n = np.asarray(key).astype(np.uint64), np.asarray(n).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        z = key ^ (n * u(0xA0761D6478BD642F))
+        z = z + u(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+        z = z ^ (z >> u(31))
+    return (z >> u(32)).astype(np.uint32)

@@ -1,7 +1,7 @@
 // ctrl_common.hip.h -- what the control-loop kernels share: ctrl_step_kernel (ctrl_step.hip: one step per launch) and the fused
 // kernels of ctrl_rollout.hip (K steps per launch).  A lane's state, its two queues during a step, and the staging of a step's
-// appends, the controller's gains where a kernel reads them, and the plant's disturbance where a kernel draws it.  The step
-// itself is text: ctrl_step_body.h.
+// appends, the controller's gains where a kernel reads them, the plant's disturbance where a kernel draws it, and the links'
+// packet erasures where a kernel draws them.  The step itself is text: ctrl_step_body.h.
 #pragma once
 #include "ct_common.hip.h"
 
@@ -71,6 +71,48 @@ __device__ __forceinline__ double dist_draw(Dist& W)
     W.n += 1ull;
     W.nc += DIST_STEP;
     return (double)(int32_t)(uint32_t)(z >> 32) * 0x1p-31;
+}
+
+// The packet erasures of one env in the loss instantiations (ctrl_step_body.h under GW_CTRL_LOSS): the four links' thresholds,
+// the key, the count of draws and the four links' erasure counts, in registers across all steps of a launch.  GwCtrlLoss's
+// block holds {thr[4] u32, key u64, n u64, lost[4] u32}, 48 bytes per env: three 16-byte loads when a launch opens, one 8-byte
+// store of n and one 16-byte store of lost when it closes.  `nc` is n * LOSS_STEP mod 2^64 carried as a running sum, as
+// Dist::nc is.  thr and lost are only ever indexed by constants: the step selects its two thresholds from the device once and
+// adds its erasures to the right counters with selects (Lane says why).
+constexpr uint64_t LOSS_STEP = 0xA0761D6478BD642Full;
+
+struct Loss {
+    uint32_t thr[4], lost[4];
+    uint64_t key, n, nc;
+};
+
+__device__ __forceinline__ void loss_load(Loss& X, const GwCtrlLoss& x, int64_t e)
+{
+    const uint4* p = reinterpret_cast<const uint4*>(x.rec + e * 6);            // hipMalloc'ed, 48-byte records: 16-byte aligned
+    const uint4 a = p[0], c = p[2];
+    const ulonglong2 b = *reinterpret_cast<const ulonglong2*>(p + 1);
+    X.thr[0] = a.x; X.thr[1] = a.y; X.thr[2] = a.z; X.thr[3] = a.w;
+    X.lost[0] = c.x; X.lost[1] = c.y; X.lost[2] = c.z; X.lost[3] = c.w;
+    X.key = b.x; X.n = b.y;
+    X.nc = b.y * LOSS_STEP;
+}
+
+__device__ __forceinline__ void loss_store(const Loss& X, const GwCtrlLoss& x, int64_t e)
+{
+    x.rec[e * 6 + 3] = X.n;
+    *reinterpret_cast<uint4*>(x.rec + e * 6 + 4) = make_uint4(X.lost[0], X.lost[1], X.lost[2], X.lost[3]);
+}
+
+// one draw: dist_draw's mixer on key ^ (n * LOSS_STEP); the transmission is erased when the top 32 bits are below `thr`
+__device__ __forceinline__ bool loss_draw(Loss& X, uint32_t thr)
+{
+    uint64_t z = (X.key ^ X.nc) + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    X.n += 1ull;
+    X.nc += LOSS_STEP;
+    return (uint32_t)(z >> 32) < thr;
 }
 
 __device__ __forceinline__ uint32_t pick(const uint32_t (&a)[CR], int i)

@@ -1,7 +1,9 @@
 // ctrl_feedback_lane.hip.h -- the lane loop of the angle-feedback rollout kernels and the staging of a block's policy, shared by
 // ctrl_rollout_feedback.hip (the kernels with the default controller folded in), ctrl_rollout_feedback_pid.hip (their PID
-// instantiations: per-env gains) and ctrl_rollout_feedback_dist.hip (their disturbance instantiations: per-env plant noise).  What the loop does is stated at the top of ctrl_rollout_feedback.hip.  Everything here is
-// local to the including file (an unnamed namespace): each of the three compiles its own instantiations.
+// instantiations: per-env gains), ctrl_rollout_feedback_dist.hip (their disturbance instantiations: per-env plant noise) and
+// ctrl_rollout_feedback_loss.hip (their loss instantiations: per-env packet erasures as well).  What the loop does is stated at
+// the top of ctrl_rollout_feedback.hip.  Everything here is local to the including file (an unnamed namespace): each of the
+// four compiles its own instantiations.
 #pragma once
 #include "ctrl_common.hip.h"
 
@@ -25,12 +27,16 @@ struct FbRows {                                              // gw_ctrl_feedback
 // (A __forceinline__ template, not a kernel: the kernels below are plain functions.)
 // DIST (with PID): the plant is disturbed, as in that loop -- the env's record in registers, its count stored back once, a reset
 // leaves it alone.
-template <bool ROWS, bool PID, bool DIST>
+// LOSS (with PID and DIST): every transmission takes a draw of the env's own erasures, as in that loop -- the record in
+// registers, its count and erasure counts stored back once, a reset leaves it alone.  x is the last parameter, and defaulted.
+template <bool ROWS, bool PID, bool DIST, bool LOSS = false>
 __device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w,
                                                    const int steps, const uint32_t max_steps, const double fail_deg, const uint8_t* s_trans, const double* s_ber, double* col0,
                                                    double* col1, const int64_t e, const uint8_t* s_sched, const int32_t* s_edges,
-                                                   const uint32_t* s_par, const FbRows& r, double* __restrict__ tally)
+                                                   const uint32_t* s_par, const FbRows& r, double* __restrict__ tally,
+                                                   const GwCtrlLoss& x = GwCtrlLoss{nullptr})
 {
+    static_assert(DIST || !LOSS, "the loss instantiations are disturbance instantiations");
     const GwDevConst k = *(const GW_AS_CONST GwDevConst*)c.cst;
     Lane L;
     L.now = c.now[e]; L.wake = c.wake[e]; L.u = c.u[e]; L.ang = c.ang[e]; L.ktick = c.ktick[e];
@@ -48,6 +54,8 @@ __device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwC
     if (PID) pid_load(G, g, e);
     Dist W;
     if (DIST) dist_load(W, w, e);
+    Loss X;
+    if (LOSS) loss_load(X, x, e);
     uint32_t age = s.age[e];
     double cost = s.cost[e];
     const double deg_per_rad = 180.0 / 3.141592653589793;
@@ -73,7 +81,15 @@ __device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwC
         const double t_before = L.now;
         q_open(q0);
         q_open(q1);
-        if constexpr (DIST) {
+        if constexpr (LOSS) {
+#define GW_CTRL_PID
+#define GW_CTRL_DIST
+#define GW_CTRL_LOSS
+#include "ctrl_step_body.h"
+#undef GW_CTRL_LOSS
+#undef GW_CTRL_DIST
+#undef GW_CTRL_PID
+        } else if constexpr (DIST) {
 #define GW_CTRL_PID
 #define GW_CTRL_DIST
 #include "ctrl_step_body.h"
@@ -133,6 +149,7 @@ __device__ __forceinline__ void ctrl_feedback_lane(const GwCtrlDev& c, const GwC
     s.age[e] = age; s.cost[e] = cost;
     if (PID) pid_store(G, g, e);
     if (DIST) dist_store(W, w, e);
+    if (LOSS) loss_store(X, x, e);
     double* t = tally + e * GW_CTRL_FB_COLS;
     t[0] = (double)n_ended; t[1] = (double)n_failed; t[2] = (double)steps; t[3] = cost_ended;
     t[4] = airtime;         t[5] = elapsed;          t[6] = area;          t[7] = (double)n_bin0;

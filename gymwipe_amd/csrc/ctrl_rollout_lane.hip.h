@@ -1,7 +1,8 @@
 // ctrl_rollout_lane.hip.h -- the lane loop of the fused control-loop rollout kernels, shared by ctrl_rollout.hip (the kernels
-// with the default controller folded in and their PID instantiations) and ctrl_rollout_dist.hip (their disturbance
-// instantiations: per-env plant noise).  What fusion changes around the step is stated at the top of ctrl_rollout.hip.
-// Everything here is local to the including file (an unnamed namespace): each of the two compiles its own instantiations.
+// with the default controller folded in and their PID instantiations), ctrl_rollout_dist.hip (their disturbance
+// instantiations: per-env plant noise) and ctrl_rollout_loss.hip (their loss instantiations: per-env packet erasures as well).
+// What fusion changes around the step is stated at the top of ctrl_rollout.hip.
+// Everything here is local to the including file (an unnamed namespace): each of the three compiles its own instantiations.
 #pragma once
 #include "ctrl_common.hip.h"
 
@@ -20,17 +21,22 @@ constexpr int SCHED_MAX = 64;                                // entries of a sch
 // DIST (with PID): every plant substep ends with a draw of the env's own noise (the text under GW_CTRL_DIST as well), its record
 // loaded from w and held in registers, the count of draws stored back once; the in-launch reset leaves it alone -- a reset env's
 // plant goes on drawing where the old one stopped.  Else w is not read.
+// LOSS (with PID and DIST): every transmission takes a draw of the env's own erasures (the text under GW_CTRL_LOSS as well), the
+// record loaded from x and held in registers, the count of draws and the four erasure counts stored back once; the in-launch
+// reset leaves it alone, for the disturbance's reason.  Else x is not read: it is the last parameter, and defaulted.
 // (A __forceinline__ template, not a kernel: the kernels are plain functions.)
-template <bool SCHED, bool PID, bool DIST>
+template <bool SCHED, bool PID, bool DIST, bool LOSS = false>
 __device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w,
                                                   const int steps, const bool episodes, const uint32_t max_steps, const double fail_deg,
                                                   const uint8_t* s_trans, const double* s_ber, double* col0, double* col1, const int64_t e,
                                                   const int32_t* __restrict__ device, const int32_t* __restrict__ duration,
                                                   int32_t* __restrict__ obs, float* __restrict__ reward,
                                                   double* __restrict__ angle_deg, uint8_t* __restrict__ ended,
-                                                  const uint8_t* s_sched, const uint32_t Ls, double* __restrict__ tally)
+                                                  const uint8_t* s_sched, const uint32_t Ls, double* __restrict__ tally,
+                                                  const GwCtrlLoss& x = GwCtrlLoss{nullptr})
 {
     static_assert(PID || !DIST, "the disturbance instantiations are PID instantiations");
+    static_assert(DIST || !LOSS, "the loss instantiations are disturbance instantiations");
     const GwDevConst k = *(const GW_AS_CONST GwDevConst*)c.cst;
     Lane L;
     L.now = c.now[e]; L.wake = c.wake[e]; L.u = c.u[e]; L.ang = c.ang[e]; L.ktick = c.ktick[e];
@@ -48,6 +54,8 @@ __device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCt
     if (PID) pid_load(G, g, e);
     Dist W;
     if (DIST) dist_load(W, w, e);
+    Loss X;
+    if (LOSS) loss_load(X, x, e);
     uint32_t age = 0u;
     double cost = 0.0;
     if (episodes) { age = s.age[e]; cost = s.cost[e]; }
@@ -72,7 +80,15 @@ __device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCt
         const int d = d_now, du = du_now;
         q_open(q0);
         q_open(q1);
-        if constexpr (DIST) {
+        if constexpr (LOSS) {
+#define GW_CTRL_PID
+#define GW_CTRL_DIST
+#define GW_CTRL_LOSS
+#include "ctrl_step_body.h"
+#undef GW_CTRL_LOSS
+#undef GW_CTRL_DIST
+#undef GW_CTRL_PID
+        } else if constexpr (DIST) {
 #define GW_CTRL_PID
 #define GW_CTRL_DIST
 #include "ctrl_step_body.h"
@@ -128,6 +144,7 @@ __device__ __forceinline__ void ctrl_rollout_lane(const GwCtrlDev& c, const GwCt
     if (episodes) { s.age[e] = age; s.cost[e] = cost; }
     if (PID) pid_store(G, g, e);
     if (DIST) dist_store(W, w, e);
+    if (LOSS) loss_store(X, x, e);
     if (SCHED) {
         tally[e * 4 + 0] = (double)n_ended; tally[e * 4 + 1] = (double)n_failed;
         tally[e * 4 + 2] = (double)steps;   tally[e * 4 + 3] = cost_ended;

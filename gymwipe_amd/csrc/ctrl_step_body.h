@@ -18,6 +18,11 @@
         const StepMath m(k);
         const double slot = k.slot, br = k.bit_rate, hd = k.hdr_dur, hdr_bits = k.hdr_bits, interval = k.counter_interval;
         const int mh = k.mac_hdr;
+#ifdef GW_CTRL_LOSS
+        // the step's two links, selected once: the announcement's (0 or 1) and the data packets' (2 or 3); X is never indexed by d
+        const uint32_t thr_an = d == 0 ? X.thr[0] : X.thr[1], thr_da = d == 0 ? X.thr[2] : X.thr[3];
+        uint32_t lost_an = 0u, lost_da = 0u;
+#endif
         double* ringd = d == 0 ? ring0 : ring1;
         // the first PRE values at the head of the addressed queue, issued now: they land during the announcement
         double pre[PRE];
@@ -94,8 +99,16 @@
         const TxTimes an = tx_times(m, t_a, hd, m.over_rate((double)(Ld * 8)));
         L.ntx++;
         all_hear(CRRM);
+#ifdef GW_CTRL_LOSS
+        const bool heard = receive(m, s_ber[(d * CR + CRRM) * S + pick(L.rxs, d)], an, br, hdr_bits,
+                                   (double)(Ld * 8) * k.coded_factor, L.fl);
+        const bool erased_an = loss_draw(X, thr_an);                            // drawn whatever the PHY decided: no short circuit
+        lost_an += erased_an ? 1u : 0u;
+        const bool granted = heard & !erased_an;                                // an erased announcement is an ungranted step
+#else
         const bool granted = receive(m, s_ber[(d * CR + CRRM) * S + pick(L.rxs, d)], an, br, hdr_bits,
                                      (double)(Ld * 8) * k.coded_factor, L.fl);
+#endif
         const double t_r = an.t_e;
         const double t_end = t_r + (double)(slots + 1) * slot;
         if (granted) {
@@ -134,8 +147,16 @@
                 const TxTimes x = tx_times(m, cur, hd, pd);
                 L.ntx++;
                 all_hear(d);
+#ifdef GW_CTRL_LOSS
+                const bool decoded = receive(m, s_ber[(dst * CR + d) * S + pick(L.rxs, dst)], x, br, hdr_bits,
+                                             (double)(((int)sz - mh) * 8) * k.coded_factor, L.fl);
+                const bool erased = loss_draw(X, thr_da);                       // popped, sent and heard by every radio; not delivered
+                lost_da += erased ? 1u : 0u;
+                const bool ok = decoded & !erased;
+#else
                 const bool ok = receive(m, s_ber[(dst * CR + d) * S + pick(L.rxs, dst)], x, br, hdr_bits,
                                         (double)(((int)sz - mh) * 8) * k.coded_factor, L.fl);
+#endif
                 if (!(x.t_e < t_end)) L.fl |= GW_FLAG_CARRY;
                 ticks_until(x.t_e, true);                                       // ticks during the transmission, one exactly on its end
                 if (ok) {                                                       // included; then the delivery at t_e
@@ -148,4 +169,8 @@
         }
         ticks_until(t_end, true);
         L.now = t_end;
+#ifdef GW_CTRL_LOSS
+        X.lost[0] += d == 0 ? lost_an : 0u; X.lost[1] += d == 0 ? 0u : lost_an;
+        X.lost[2] += d == 0 ? lost_da : 0u; X.lost[3] += d == 0 ? 0u : lost_da;
+#endif
     }

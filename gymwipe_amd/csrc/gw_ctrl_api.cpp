@@ -20,7 +20,9 @@ struct gw_ctrl {
     bool pid_on;                       // gw_ctrl_set_gains has been called: the launches take the PID instantiations, for good
     GwCtrlDist dist;                   // per-env plant disturbance {g[4], key, n}: all 0 from gw_ctrl_create on
     bool dist_on;                      // gw_ctrl_set_disturbance has been called: the disturbance instantiations, for good (pid_on too)
-    void* blocks[24];
+    GwCtrlLoss loss;                   // per-env packet erasures {thr[4], key, n, lost[4]}: all 0 from gw_ctrl_create on
+    bool loss_on;                      // gw_ctrl_set_loss has been called: the loss instantiations, for good (dist_on and pid_on too)
+    void* blocks[32];
     int nblocks;
 };
 
@@ -136,6 +138,7 @@ int gw_ctrl_create(const gw_ctrl_config* cfg, gw_ctrl** out)
     CA(c->epi.x_init, N * 4); CA(c->epi.u_init, N); CA(c->epi.cost, N); CA(c->epi.age, N);
     CA(c->pid.pid, N * 4);
     CA(c->dist.rec, N * 6);
+    CA(c->loss.rec, N * 6);
 #undef CA
     d.cst = d_cst; d.trans = d_trans; d.ber = d_ber;
     CTRL_HIP(hipMemcpy(d_cst, &k, sizeof k, hipMemcpyHostToDevice), gw_ctrl_destroy(c));
@@ -143,6 +146,7 @@ int gw_ctrl_create(const gw_ctrl_config* cfg, gw_ctrl** out)
     CTRL_HIP(hipMemcpy(d_ber, c->tab.ber, tcount * sizeof(double), hipMemcpyHostToDevice), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemset(d.pay, 0, (size_t)N * 2 * GW_RING_PHYS * sizeof(double)), gw_ctrl_destroy(c));
     CTRL_HIP(hipMemset(c->dist.rec, 0, (size_t)N * 6 * sizeof(uint64_t)), gw_ctrl_destroy(c));    // g = 0, key = 0, n = 0
+    CTRL_HIP(hipMemset(c->loss.rec, 0, (size_t)N * 6 * sizeof(uint64_t)), gw_ctrl_destroy(c));    // thr = 0, key = 0, n = 0, lost = 0
     {
         const double def[4] = {1.0, 0.0, 0.0, 0.0};          // the reference's shipped gains, and a fresh controller's last error
         std::vector<double> fill((size_t)N * 4);
@@ -164,7 +168,9 @@ int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_
     if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
     if (!device_dev || !duration_dev || !obs_dev || !reward_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_step: NULL device pointer");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (c->dist_on ? gw_ctrl_launch_step_dist(c->dev, c->pid, c->dist, device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream)
+    if (c->loss_on ? gw_ctrl_launch_step_loss(c->dev, c->pid, c->dist, c->loss, device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev,
+                                              stream)
+        : c->dist_on ? gw_ctrl_launch_step_dist(c->dev, c->pid, c->dist, device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream)
                    : gw_ctrl_launch_step(c->dev, pid_of(c), device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop step launch failed");
     return GW_OK;
@@ -204,6 +210,20 @@ int gw_ctrl_set_disturbance(gw_ctrl* c, const double* g_dev, const uint64_t* key
     return GW_OK;
 }
 
+int gw_ctrl_set_loss(gw_ctrl* c, const uint32_t* thr_dev, const uint64_t* key_dev, const uint8_t* mask_dev, void* stream)
+{
+    if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
+    if (!thr_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_set_loss: thr_dev is NULL");
+    if (!key_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_set_loss: key_dev is NULL");
+    CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
+    if (gw_ctrl_launch_set_loss(c->dev, c->loss, thr_dev, key_dev, mask_dev, stream))
+        return gw_set_error(GW_EHIP, "control-loop set_loss launch failed");
+    c->loss_on = true;                 // the loss instantiations are disturbance and PID instantiations: the plant runs the
+    c->dist_on = true;                 // disturbance rule at the g last stored (0 if never) and a reset clears last_error
+    c->pid_on = true;                  // from here on
+    return GW_OK;
+}
+
 int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* stream)
 {
     if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
@@ -223,7 +243,9 @@ int gw_ctrl_rollout(gw_ctrl* c, int32_t steps, const int32_t* device_dev, const 
     if (steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout: steps < 0");
     if (steps == 0) return GW_OK;
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (c->dist_on ? gw_ctrl_launch_rollout_dist(c->dev, c->epi, c->pid, c->dist, steps, device_dev, duration_dev, ep, obs_dev, reward_dev,
+    if (c->loss_on ? gw_ctrl_launch_rollout_loss(c->dev, c->epi, c->pid, c->dist, c->loss, steps, device_dev, duration_dev, ep, obs_dev,
+                                                 reward_dev, angle_deg_dev, ended_dev, stream)
+        : c->dist_on ? gw_ctrl_launch_rollout_dist(c->dev, c->epi, c->pid, c->dist, steps, device_dev, duration_dev, ep, obs_dev, reward_dev,
                                                  angle_deg_dev, ended_dev, stream)
                    : gw_ctrl_launch_rollout(c->dev, c->epi, pid_of(c), steps, device_dev, duration_dev, ep, obs_dev, reward_dev, angle_deg_dev,
                                             ended_dev, stream))
@@ -246,7 +268,8 @@ int gw_ctrl_rollout_schedules(gw_ctrl* c, int32_t steps, const uint8_t* sched_de
     if (N % P != 0 || (N / P) % 64 != 0)
         return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_schedules: num_envs / P must be a whole multiple of 64 (one schedule per block)");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (c->dist_on ? gw_ctrl_launch_rollout_schedules_dist(c->dev, c->epi, c->pid, c->dist, steps, sched_dev, P, L, *ep, tally_dev, stream)
+    if (c->loss_on ? gw_ctrl_launch_rollout_schedules_loss(c->dev, c->epi, c->pid, c->dist, c->loss, steps, sched_dev, P, L, *ep, tally_dev, stream)
+        : c->dist_on ? gw_ctrl_launch_rollout_schedules_dist(c->dev, c->epi, c->pid, c->dist, steps, sched_dev, P, L, *ep, tally_dev, stream)
                    : gw_ctrl_launch_rollout_schedules(c->dev, c->epi, pid_of(c), steps, sched_dev, P, L, *ep, tally_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop schedule rollout launch failed");
     return GW_OK;
@@ -274,7 +297,8 @@ int gw_ctrl_rollout_feedback(gw_ctrl* c, int32_t steps, const gw_ctrl_feedback* 
     if (N % P != 0 || (N / P) % 64 != 0)
         return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_feedback: num_envs / P must be a whole multiple of 64 (one policy per block)");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (c->dist_on ? gw_ctrl_launch_rollout_feedback_dist(c->dev, c->epi, c->pid, c->dist, steps, *fb, *ep, rows, tally_dev, stream)
+    if (c->loss_on ? gw_ctrl_launch_rollout_feedback_loss(c->dev, c->epi, c->pid, c->dist, c->loss, steps, *fb, *ep, rows, tally_dev, stream)
+        : c->dist_on ? gw_ctrl_launch_rollout_feedback_dist(c->dev, c->epi, c->pid, c->dist, steps, *fb, *ep, rows, tally_dev, stream)
                    : gw_ctrl_launch_rollout_feedback(c->dev, c->epi, pid_of(c), steps, *fb, *ep, rows, tally_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop feedback rollout launch failed");
     return GW_OK;
@@ -327,6 +351,14 @@ int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst, size_t bytes)
         const size_t cols = field[0] == 'd' ? 4 : 1, first = field[0] == 'd' ? 0 : (field[6] == 'k' ? 4 : 5);
         if (bytes != (size_t)N * cols * 8) return gw_set_error(GW_EFIELD, "field %s needs %zu bytes", field, (size_t)N * cols * 8);
         CTRL_HIP(hipMemcpy2D(dst, cols * 8, c->dist.rec + first, 6 * 8, cols * 8, (size_t)N, hipMemcpyDeviceToHost), (void)0);
+        return GW_OK;
+    }
+    if (!strcmp(field, "loss") || !strcmp(field, "loss_key") || !strcmp(field, "loss_count") || !strcmp(field, "lost")) {
+        // u32[N][4] / u64[N] / u64[N] / u32[N][4]: columns of the {thr[4], key, n, lost[4]} records
+        const bool wide = !field[4];
+        const size_t width = wide ? 16 : 8, first = !strcmp(field, "loss") ? 0 : (field[3] == 't' ? 32 : (field[5] == 'k' ? 16 : 24));
+        if (bytes != (size_t)N * width) return gw_set_error(GW_EFIELD, "field %s needs %zu bytes", field, (size_t)N * width);
+        CTRL_HIP(hipMemcpy2D(dst, width, (const char*)c->loss.rec + first, 48, width, (size_t)N, hipMemcpyDeviceToHost), (void)0);
         return GW_OK;
     }
     if (!strcmp(field, "rx_power")) {                      // f64[N][4]

@@ -312,6 +312,26 @@ int gw_ctrl_launch_step_dist(const GwCtrlDev& c, const GwCtrlPid& g, const GwCtr
 int gw_ctrl_launch_rollout_feedback_dist(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, int32_t steps,
                                          const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
                                          double* tally, void* stream);                  // ctrl_rollout_feedback_dist.hip
+// Per-env packet erasures (the rule: include/gymwipe_amd.h, gw_ctrl_set_loss).  One block of 48-byte records
+// {thr[4] u32, key u64, n u64, lost[4] u32}, addressed as u64[N][6]; a struct of its own for GwCtrlEpi's reason, and the
+// kernels' last argument.  A handle that has set a loss launches the *_loss launchers below and no other step or rollout
+// launcher: their kernels are the disturbance instantiations with one draw per transmission.
+struct GwCtrlLoss {
+    uint64_t* rec;                             // [N][6]
+};
+int gw_ctrl_launch_set_loss(const GwCtrlDev& c, const GwCtrlLoss& x, const uint32_t* thr, const uint64_t* key, const uint8_t* mask,
+                            void* stream);                                              // ctrl_rollout_loss.hip, as the next two
+int gw_ctrl_launch_rollout_loss(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, const GwCtrlLoss& x,
+                                int32_t steps, const int32_t* device, const int32_t* duration, const gw_ctrl_episodes* ep, int32_t* obs,
+                                float* reward, double* angle_deg, uint8_t* ended, void* stream);
+int gw_ctrl_launch_rollout_schedules_loss(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, const GwCtrlLoss& x,
+                                          int32_t steps, const uint8_t* sched, int32_t P, int32_t L, const gw_ctrl_episodes& ep, double* tally,
+                                          void* stream);
+int gw_ctrl_launch_step_loss(const GwCtrlDev& c, const GwCtrlPid& g, const GwCtrlDist& w, const GwCtrlLoss& x, const int32_t* device,
+                             const int32_t* duration, int32_t* obs, float* reward, double* angle_deg, void* stream);   // ctrl_step_loss.hip
+int gw_ctrl_launch_rollout_feedback_loss(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, const GwCtrlLoss& x,
+                                         int32_t steps, const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep,
+                                         const gw_ctrl_feedback_rows* rows, double* tally, void* stream);   // ctrl_rollout_feedback_loss.hip
 int gw_fill_dev_const(const gw_config& cfg, const GwHostTables& tab, GwDevConst& k);   // gw_api.cpp
 int gw_validate_config(const gw_config& cfg);                                           // gw_api.cpp
 

@@ -151,11 +151,14 @@ class VecControlLoopEnv(BaseEnv):
     the default, the reference's shipped (1, 0, 0), commands ``-angle``.  Gains laid across the envs of each schedule
     (``actions.make_ctrl_gains``) make the rollout calls rank controllers and schedulers together.
     The plant is exact unless ``set_disturbance`` (or ``disturbance=`` here) gives envs seeded noise on their plant's state:
-    something to hold the pendulum against after the transient, keyed per env so that candidates can face the same noise."""
+    something to hold the pendulum against after the transient, keyed per env so that candidates can face the same noise.
+    The radio links are the PHY's deterministic ones unless ``set_loss`` (or ``loss=`` here) gives each of the four links a loss
+    probability: every transmission then takes one seeded draw and an erased packet is sent and not delivered, an erased
+    announcement an ungranted step; keyed per env as the disturbance is."""
     SENSOR, CONTROLLER, ACTUATOR = 0, 1, 2
 
     def __init__(self, num_envs, device="cuda:0", ctrl_start_tick=None, ctrl_period_ticks=None, positions=None, x0=None,
-                 A=None, B=None, u0=None, counter_interval=None, gains=None, disturbance=None):
+                 A=None, B=None, u0=None, counter_interval=None, gains=None, disturbance=None, loss=None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gymwipe_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -203,6 +206,8 @@ class VecControlLoopEnv(BaseEnv):
             self.set_gains(gains)
         if disturbance is not None:                        # (None: the plant is exact and the handle's kernels draw nothing)
             self.set_disturbance(disturbance)
+        if loss is not None:                               # (None: no packet is erased and the handle's kernels draw nothing for it)
+            self.set_loss(loss)
 
     def reset(self):
         """envs/inverted_pendulum.py:95-99: returns an observation, resets nothing."""
@@ -308,10 +313,53 @@ class VecControlLoopEnv(BaseEnv):
             nat.check(self._L.gw_ctrl_set_disturbance(self._h, gt.data_ptr(), kt.data_ptr(), m.data_ptr() if m is not None else None,
                                                       self._stream()))
 
+    def set_loss(self, p, key=None, mask=None):
+        """Erase packets of the masked envs (None: all): ``p`` f64[N][4], one loss probability per link -- the RRM's announcement
+        to the sensor, its announcement to the controller, sensor -> controller, controller -> actuator (4 values are
+        broadcast) -- clipped to [0, 1] and converted by ``actions.ctrl_loss_threshold``; and ``key``, one 64-bit key per env
+        as in ``set_disturbance`` (None: ``actions.make_ctrl_loss``'s default keys).  From then on every transmission of those
+        envs takes one draw (``actions.ctrl_loss_numpy`` of the env's key and of the count of transmissions since this call),
+        whatever the PHY decides about it.  An erased announcement is an ungranted step; an erased data packet leaves its queue,
+        goes on the air and is not delivered.  ``get_state("lost")`` counts the erasures per link, ``"loss_count"`` the draws.
+        The counts restart here and nowhere else: a reset keeps thresholds, key and counts.  No other running state is touched.
+        From the first call on the handle launches the kernels that draw, which are the disturbance's kernels as well: with
+        ``p = 0`` they compute what a handle that called ``set_disturbance`` computes (at ``g = 0`` if it never did)."""
+        import numpy as np
+        from .. import actions
+        torch = self._torch
+        pa = p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
+        if pa.dtype.kind not in "fiu":
+            raise ValueError("p holds loss probabilities (float64)")
+        pa = pa.astype(np.float64)
+        if pa.shape == (4,):
+            pa = np.broadcast_to(pa, (self.num_envs, 4))
+        if pa.shape != (self.num_envs, 4):
+            raise ValueError("p must be 4 loss probabilities, one per link, or float64[num_envs][4]")
+        thr = actions.ctrl_loss_threshold(pa)
+        tt = torch.from_numpy(np.ascontiguousarray(thr).view(np.int32)).to(self.device).contiguous()
+        if key is None:
+            key = actions.make_ctrl_loss(np.zeros(4), self.num_envs)[1]
+        if isinstance(key, torch.Tensor):
+            if key.dtype != torch.int64:
+                raise ValueError("key as a tensor is int64[num_envs] holding the keys' bit patterns")
+            kt = key.to(self.device)
+        else:
+            ka = np.asarray(key)
+            if ka.dtype != np.uint64:
+                raise ValueError("key is numpy uint64[num_envs] (or an int64 tensor holding the bit patterns)")
+            kt = torch.from_numpy(np.ascontiguousarray(ka).view(np.int64)).to(self.device)
+        if tuple(kt.shape) != (self.num_envs,):
+            raise ValueError("key holds one key per env")
+        kt = kt.contiguous()
+        m = self._mask(mask)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.gw_ctrl_set_loss(self._h, tt.data_ptr(), kt.data_ptr(), m.data_ptr() if m is not None else None,
+                                               self._stream()))
+
     def reset_envs(self, mask=None):
         """Put the masked envs (None: all) back into the state a fresh env of their own initial state has -- clock, queues,
         noise states, counters, the episode record (``age``, ``cost``) and the controller's ``last_error`` 0; ``flags`` are
-        sticky and stay, and so do the gains and the disturbance (weights, key and count) -- and return the observations of all N envs.  (``reset()`` keeps the reference's meaning: it resets nothing.)"""
+        sticky and stay, and so do the gains, the disturbance (weights, key and count) and the loss (thresholds, key and counts) -- and return the observations of all N envs.  (``reset()`` keeps the reference's meaning: it resets nothing.)"""
         torch = self._torch
         m = self._mask(mask)
         self._stepped = True                               # the observation buffer now holds what the GPU wrote
@@ -413,7 +461,8 @@ class VecControlLoopEnv(BaseEnv):
                "commands": ((), "u4"), "substeps": ((), "u4"), "flags": ((), "u4"),
                "age": ((), "u4"), "cost": ((), "f8"), "x_init": ((4,), "f8"), "u_init": ((), "f8"),
                "gains": ((3,), "f8"), "last_error": ((), "f8"),
-               "disturbance": ((4,), "f8"), "noise_key": ((), "u8"), "noise_count": ((), "u8")}
+               "disturbance": ((4,), "f8"), "noise_key": ((), "u8"), "noise_count": ((), "u8"),
+               "loss": ((4,), "u4"), "loss_key": ((), "u8"), "loss_count": ((), "u8"), "lost": ((4,), "u4")}
 
     def get_state(self, field):
         import numpy as np

@@ -784,7 +784,8 @@ int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_
  *              "received" u32[N][2] (controller, actuator) | "n_tx","commands","substeps","flags" u32[N] |
  *              "age" u32[N], "cost" f64[N] (the running episode's record) | "x_init" f64[N][4], "u_init" f64[N] |
  *              "gains" f64[N][3] {kp, ki, kd}, "last_error" f64[N] (the controller, gw_ctrl_set_gains) |
- *              "disturbance" f64[N][4], "noise_key" u64[N], "noise_count" u64[N] (the plant's, gw_ctrl_set_disturbance) */
+ *              "disturbance" f64[N][4], "noise_key" u64[N], "noise_count" u64[N] (the plant's, gw_ctrl_set_disturbance) |
+ *              "loss" u32[N][4], "loss_key" u64[N], "loss_count" u64[N], "lost" u32[N][4] (the links', gw_ctrl_set_loss) */
 int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst_host, size_t bytes);
 
 /* Per-env initial state and reset.  Every env keeps an initial state of its own (x_init, u_init; cfg.x0 / cfg.u0 at create) and
@@ -793,7 +794,8 @@ int gw_ctrl_get_state(gw_ctrl* c, const char* field, void* dst_host, size_t byte
  * it changes no env's running state.  gw_ctrl_reset puts the masked envs into exactly the state gw_ctrl_create leaves, with the
  * env's own initial state: clock, wake and tick 0, controller angle 0, both queues empty (head = len = 0), noise states 0,
  * received, n_tx, commands, substeps, age, cost and the controller's last_error 0.  flags are sticky and stay, and so do the
- * gains and the plant's disturbance record (g, key and the count n).  Envs outside the mask are untouched, bit for bit.
+ * gains, the plant's disturbance record (g, key and the count n) and the links' loss record (thr, key, n and lost).  Envs
+ * outside the mask are untouched, bit for bit.
  * obs_dev (NULL ok) receives (int32) degrees(x[2]) of all N envs. */
 int gw_ctrl_set_initial(gw_ctrl* c, const double* x0_dev, const double* u0_dev, const uint8_t* mask_dev, void* stream);
 int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* stream);
@@ -840,6 +842,43 @@ int gw_ctrl_set_gains(gw_ctrl* c, const double* gains_dev, const uint8_t* mask_d
  * handle, for good, to the disturbance instantiations of the step, rollout, schedule and both feedback kernels, which are PID
  * instantiations as well (the gains are what gw_ctrl_set_gains last stored, {1, 0, 0} if it never did). */
 int gw_ctrl_set_disturbance(gw_ctrl* c, const double* g_dev, const uint64_t* key_dev, const uint8_t* mask_dev, void* stream);
+
+/* Packet loss: seeded, counter-based erasures per env and link.  BUILDER-DEFINED, as the whole loop is.  Every env holds a loss
+ * record of 48 bytes, 16-byte aligned, all 0 at create:
+ *     struct { uint32_t thr[4]; uint64_t key; uint64_t n; uint32_t lost[4]; }
+ *     links: 0 RRM -> sensor (the announcement of a step with device 0)     2 sensor -> controller (data)
+ *            1 RRM -> controller (the announcement, device 1)               3 controller -> actuator (data)
+ * On a handle on which gw_ctrl_set_loss has been called, every transmission of a step -- the announcement first, then each data
+ * packet, in the order they go on the air -- takes exactly one draw, whatever the PHY decides about the transmission; all
+ * integers mod 2^64:
+ *     z  = key ^ (n * 0xA0761D6478BD642F)       an odd constant of its own: the disturbance and the loss under one key do not
+ *     z += 0x9E3779B97F4A7C15                   draw the same sequence; then the disturbance's mixer
+ *     z  = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z  = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z ^= z >> 31
+ *     r  = (uint32_t)(z >> 32)
+ *     erased = r < thr[link]                    probability thr * 2^-32: thr = 0 never, thr = 0xFFFFFFFF all but one draw in 2^32
+ *     if (erased) lost[link] += 1               wraps; counted whatever the PHY decided
+ *     n += 1
+ *     outcome = (what the PHY decided) && !erased
+ * An erased announcement is an ungranted step: nothing is sent, the counter ticks run to the step's end and the queues keep
+ * their packets.  An erased data packet has been popped and sent -- n_tx counts it and every other radio's noise state moves as
+ * before -- and is not delivered: neither the controller's angle nor the plant's input, neither count of "received" moves.  The
+ * flags the PHY's decision sets are set as before; a step flagged GW_FLAG_BADACT sends nothing and draws nothing.
+ * n counts the transmissions since the env's record was last set, and nothing else restarts it: gw_ctrl_reset and the reset at
+ * an episode's end inside a rollout leave thr, key, n and lost alone, for the disturbance's reason.  n lives in the handle: two
+ * calls of K / 2 steps equal one of K.  Two envs with equal loss records, disturbance, gains, initial state and actions walk
+ * bit-identical trajectories wherever they sit in the batch.
+ * gw_ctrl_set_loss stores thr_dev u32[N][4] and key_dev u64[N] and sets n = 0 and lost = 0 for the envs with mask_dev[e] != 0
+ * (NULL: all); other envs are untouched, bit for bit, and so is all other running state.  Stream-ordered; allocates nothing.  A
+ * NULL c, thr_dev or key_dev: GW_EINVAL before any device call.  No value is validated.
+ * A handle on which it has never been called launches exactly the kernels it launched before; its first call switches the
+ * handle, for good, to the loss instantiations of the step, rollout, schedule and both feedback kernels, which are disturbance
+ * and PID instantiations as well: gains and g stay at what was last stored ({1, 0, 0} and 0 if never).  So a handle switched by
+ * gw_ctrl_set_loss alone runs the disturbance rule at g = 0, which may turn a -0.0 of the plant into +0.0 and changes nothing
+ * else.  At thr = 0 a switched handle computes, bit for bit, what a handle switched by gw_ctrl_set_disturbance computes; its n
+ * still counts transmissions. */
+int gw_ctrl_set_loss(gw_ctrl* c, const uint32_t* thr_dev, const uint64_t* key_dev, const uint8_t* mask_dev, void* stream);
 
 typedef struct gw_ctrl_episodes {
     int32_t max_steps;                      /* an episode ends when its age reaches this; 0: no limit */

@@ -2,7 +2,7 @@
 """
 The control loop's fused rollout beside what it replaces (profiles/ctrl_rollout/README.md).
 
-VecControlLoopEnv, N envs, calls of K = 64 steps, every env with an initial angle of its own.  Up to nineteen legs in ONE process,
+VecControlLoopEnv, N envs, calls of K = 64 steps, every env with an initial angle of its own.  Up to twenty-five legs in ONE process,
 alternated call by call so that clock and thermal drift hit all alike, each leg on a handle of its own:
   a   K x env.step                                      the only form there was; ctrl_step_kernel is unchanged
   b   env.rollout, no episodes                          the same actions in one launch
@@ -25,11 +25,15 @@ alternated call by call so that clock and thermal drift hit all alike, each leg 
   cz, dz, fz   legs cg, dg and fg on a handle on which     what the switch to the disturbance instantiations costs
       env.set_disturbance(0) has been called as well    (profiles/ctrl_disturbance/README.md): the same trajectory, one draw per substep
   cw, dw, fw   the same with weights --noise on x[3]     a trajectory of their own: the disturbed plant, every env its own key
+  cl, dl, fl   legs cz, dz and fz on a handle on which     what the switch to the loss instantiations costs
+      env.set_loss(0) has been called as well           (profiles/ctrl_loss/README.md): the same trajectory, one draw per transmission
+  cp, dp, fp   the same with probability --loss on all    a trajectory of their own: packets and announcements erased, every env
+      four links                                        its own key
 A timed unit is one call of K steps between two HIP events and two wall-clock reads, the second after a synchronise; units are
 repeated until every leg has at least `--seconds` of stream time and at least `--min-repeats` units.  Before the timing, b's
 outputs are checked against a's, c's `ended` against cs's, d's tally against dc's `ended`, f's state against fn's, f1's
-tally against d's, cg's, dg's and fg's state against c's, d's and f's, and cz's, dz's and fz's against cg's, dg's and fg's, each
-pair from one state.
+tally against d's, cg's, dg's and fg's state against c's, d's and f's, cz's, dz's and fz's against cg's, dg's and fg's, and cl's,
+dl's and fl's against cz's, dz's and fz's, each pair from one state.
 Reported per leg: median, min and max of the wall-clock and event microseconds per step; the ratios of the wall-clock medians;
 and the run-to-run spread of leg a ((max - min) / median), against which b/a is to be read.  One JSON line; --out appends it to
 a file.
@@ -57,7 +61,8 @@ def main():
     ap.add_argument("--min-repeats", type=int, default=5)
     ap.add_argument("--bins", type=int, default=3, help="B of legs f and fn")
     ap.add_argument("--noise", type=float, default=0.01, help="the weight on x[3] of legs cw, dw and fw")
-    ap.add_argument("--legs", default="a,b,c,cs,cn,d,dc,f,fn,f1,cg,dg,fg,cz,dz,fz,cw,dw,fw")
+    ap.add_argument("--loss", type=float, default=0.25, help="the loss probability on every link of legs cp, dp and fp")
+    ap.add_argument("--legs", default="a,b,c,cs,cn,d,dc,f,fn,f1,cg,dg,fg,cz,dz,fz,cw,dw,fw,cl,dl,fl,cp,dp,fp")
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -88,17 +93,21 @@ def main():
     x_dev = torch.empty((K, N), dtype=torch.int32, device=dev)         # d's schedules expanded: filled in below
     x_dur = torch.empty((K, N), dtype=torch.int32, device=dev)
 
-    def new_env(gains=None, noise=None):
+    def new_env(gains=None, noise=None, loss=None):
         env = VecControlLoopEnv(N, device=dev, gains=gains)
         env.set_initial_state(torch.from_numpy(x0))
         env.reset_envs()
         if noise is not None:
             env.set_disturbance((0.0, 0.0, 0.0, noise))                 # default keys: a sequence of its own for every env
+        if loss is not None:
+            env.set_loss((loss,) * 4)                                   # default keys, as above
         return env
 
     names = [x for x in args.legs.split(",") if x]
     SWITCHED = {"cg": None, "dg": None, "fg": None, "cz": 0.0, "dz": 0.0, "fz": 0.0, "cw": args.noise, "dw": args.noise, "fw": args.noise}
-    envs = {n: new_env((1.0, 0.0, 0.0), SWITCHED[n]) if n in SWITCHED else new_env() for n in names}
+    LOSSY = {"cl": 0.0, "dl": 0.0, "fl": 0.0, "cp": args.loss, "dp": args.loss, "fp": args.loss}     # on a handle as cz's, dz's, fz's
+    envs = {n: new_env((1.0, 0.0, 0.0), 0.0, LOSSY[n]) if n in LOSSY else new_env((1.0, 0.0, 0.0), SWITCHED[n]) if n in SWITCHED else new_env()
+            for n in names}
     out = (torch.empty((K, N), dtype=torch.int32, device=dev), torch.empty((K, N), dtype=torch.float32, device=dev),
            torch.empty((K, N), dtype=torch.uint8, device=dev), torch.empty((K, N), dtype=torch.float64, device=dev))
     age = {n: torch.zeros(N, dtype=torch.int32, device=dev) for n in ("cs", "cn")}
@@ -195,7 +204,8 @@ def main():
             tally[n] = tally.pop(leg.__name__[4:])
         return run
 
-    legs = {"cz": leg_c, "cw": leg_c, "dz": tallied("dz", leg_dg), "dw": tallied("dw", leg_dg), "fz": tallied("fz", leg_fg),
+    legs = {"cl": leg_c, "cp": leg_c, "dl": tallied("dl", leg_dg), "dp": tallied("dp", leg_dg), "fl": tallied("fl", leg_fg),
+            "fp": tallied("fp", leg_fg), "cz": leg_c, "cw": leg_c, "dz": tallied("dz", leg_dg), "dw": tallied("dw", leg_dg), "fz": tallied("fz", leg_fg),
             "fw": tallied("fw", leg_fg), "cg": leg_c, "dg": leg_dg, "fg": leg_fg, "f": leg_f, "fn": leg_fn, "f1": leg_f1, "a": leg_a, "b": leg_b, "c": leg_c, "cs": composed("cs", True), "cn": composed("cn", False), "d": leg_d, "dc": leg_dc}
 
     # the legs mean what they say: from one state b gives a's last rows, and c ends the envs its composition ends
@@ -252,6 +262,24 @@ def main():
                 envs[n].reset_envs()
                 legs[n](envs[n])
             assert (envs[x].get_state("x") != envs[y].get_state("x")).any(), "leg %s is not disturbed" % x
+    for x, y in (("cl", "cz"), ("dl", "dz"), ("fl", "fz")):             # zero thresholds on a switched handle walk the disturbance's trajectory
+        if x in names and y in names:
+            for n in (x, y):
+                envs[n].reset_envs()
+                legs[n](envs[n])
+            for field in ("x", "now", "u", "angle_deg", "n_tx", "commands", "age", "cost", "last_error"):       # (the counts of draws
+                # survive reset_envs and the legs have run different numbers of calls by now: they are not compared)
+                assert (envs[x].get_state(field) == envs[y].get_state(field)).all(), "leg %s leaves another %s than leg %s" % (x, field, y)
+            assert (envs[x].get_state("loss_count") != 0).all() and (envs[y].get_state("loss_count") == 0).all()
+            assert (envs[x].get_state("lost") == 0).all()
+            if x != "cl":
+                assert torch.equal(tally[x], tally[y]), "leg %s tallies other episodes than leg %s" % (x, y)
+    for x, y in (("cp", "cz"), ("dp", "dz"), ("fp", "fz")):             # ... and thresholds that are not zero leave it
+        if x in names and y in names:
+            for n in (x, y):
+                envs[n].reset_envs()
+                legs[n](envs[n])
+            assert (envs[x].get_state("lost") != 0).any() and (envs[x].get_state("x") != envs[y].get_state("x")).any(), "leg %s loses nothing" % x
     for n in names:                                                     # warm-up: first launches, allocator, caches
         legs[n](envs[n])
     torch.cuda.synchronize(dev)
@@ -283,7 +311,8 @@ def main():
     med = {n: res[n]["wall_us_per_step"]["median"] for n in names}
     res["ratios"] = {"%s/%s" % (x, y): round(med[x] / med[y], 3)
                      for x, y in (("b", "a"), ("c", "cs"), ("c", "cn"), ("c", "b"), ("d", "dc"), ("d", "c"), ("f", "fn"), ("f1", "d"), ("f", "c"), ("cg", "c"), ("dg", "d"), ("fg", "f"),
-                                  ("cz", "cg"), ("dz", "dg"), ("fz", "fg"), ("cw", "cg"), ("dw", "dg"), ("fw", "fg")) if x in med and y in med}
+                                  ("cz", "cg"), ("dz", "dg"), ("fz", "fg"), ("cw", "cg"), ("dw", "dg"), ("fw", "fg"),
+                                  ("cl", "cz"), ("dl", "dz"), ("fl", "fz"), ("cp", "cz"), ("dp", "dz"), ("fp", "fz")) if x in med and y in med}
     if "a" in names:
         w = res["a"]["wall_us_per_step"]
         res["spread_a"] = round((w["max"] - w["min"]) / w["median"], 3)
