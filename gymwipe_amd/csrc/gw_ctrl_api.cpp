@@ -48,8 +48,15 @@ int calloc_dev(gw_ctrl* c, T** out, size_t count)
     return GW_OK;
 }
 
-// the launchers' controller argument: NULL (the kernels with the default rule compiled in) until gains have been set
-inline const GwCtrlPid* pid_of(const gw_ctrl* c) { return c->pid_on ? &c->pid : nullptr; }
+// the launchers' variant argument: the blocks of the switches that have been set on the handle (each sets the ones before it)
+inline GwCtrlBlocks blocks_of(const gw_ctrl* c)
+{
+    GwCtrlBlocks v = {nullptr, nullptr, nullptr};
+    if (c->pid_on) v.g = &c->pid;
+    if (c->dist_on) v.w = &c->dist;
+    if (c->loss_on) v.x = &c->loss;
+    return v;
+}
 
 } // namespace
 
@@ -168,10 +175,7 @@ int gw_ctrl_step(gw_ctrl* c, const int32_t* device_dev, const int32_t* duration_
     if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
     if (!device_dev || !duration_dev || !obs_dev || !reward_dev) return gw_set_error(GW_EINVAL, "gw_ctrl_step: NULL device pointer");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (c->loss_on ? gw_ctrl_launch_step_loss(c->dev, c->pid, c->dist, c->loss, device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev,
-                                              stream)
-        : c->dist_on ? gw_ctrl_launch_step_dist(c->dev, c->pid, c->dist, device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream)
-                   : gw_ctrl_launch_step(c->dev, pid_of(c), device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream))
+    if (gw_ctrl_launch_step(c->dev, blocks_of(c), device_dev, duration_dev, obs_dev, reward_dev, angle_deg_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop step launch failed");
     return GW_OK;
 }
@@ -228,7 +232,7 @@ int gw_ctrl_reset(gw_ctrl* c, const uint8_t* mask_dev, int32_t* obs_dev, void* s
 {
     if (!c) return gw_set_error(GW_EINVAL, "handle is NULL");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (gw_ctrl_launch_reset(c->dev, c->epi, pid_of(c), mask_dev, obs_dev, stream))
+    if (gw_ctrl_launch_reset(c->dev, c->epi, blocks_of(c), mask_dev, obs_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop reset launch failed");
     return GW_OK;
 }
@@ -243,12 +247,8 @@ int gw_ctrl_rollout(gw_ctrl* c, int32_t steps, const int32_t* device_dev, const 
     if (steps < 0) return gw_set_error(GW_EINVAL, "gw_ctrl_rollout: steps < 0");
     if (steps == 0) return GW_OK;
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (c->loss_on ? gw_ctrl_launch_rollout_loss(c->dev, c->epi, c->pid, c->dist, c->loss, steps, device_dev, duration_dev, ep, obs_dev,
-                                                 reward_dev, angle_deg_dev, ended_dev, stream)
-        : c->dist_on ? gw_ctrl_launch_rollout_dist(c->dev, c->epi, c->pid, c->dist, steps, device_dev, duration_dev, ep, obs_dev, reward_dev,
-                                                 angle_deg_dev, ended_dev, stream)
-                   : gw_ctrl_launch_rollout(c->dev, c->epi, pid_of(c), steps, device_dev, duration_dev, ep, obs_dev, reward_dev, angle_deg_dev,
-                                            ended_dev, stream))
+    if (gw_ctrl_launch_rollout(c->dev, c->epi, blocks_of(c), steps, device_dev, duration_dev, ep, obs_dev, reward_dev, angle_deg_dev, ended_dev,
+                               stream))
         return gw_set_error(GW_EHIP, "control-loop rollout launch failed");
     return GW_OK;
 }
@@ -268,9 +268,7 @@ int gw_ctrl_rollout_schedules(gw_ctrl* c, int32_t steps, const uint8_t* sched_de
     if (N % P != 0 || (N / P) % 64 != 0)
         return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_schedules: num_envs / P must be a whole multiple of 64 (one schedule per block)");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (c->loss_on ? gw_ctrl_launch_rollout_schedules_loss(c->dev, c->epi, c->pid, c->dist, c->loss, steps, sched_dev, P, L, *ep, tally_dev, stream)
-        : c->dist_on ? gw_ctrl_launch_rollout_schedules_dist(c->dev, c->epi, c->pid, c->dist, steps, sched_dev, P, L, *ep, tally_dev, stream)
-                   : gw_ctrl_launch_rollout_schedules(c->dev, c->epi, pid_of(c), steps, sched_dev, P, L, *ep, tally_dev, stream))
+    if (gw_ctrl_launch_rollout_schedules(c->dev, c->epi, blocks_of(c), steps, sched_dev, P, L, *ep, tally_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop schedule rollout launch failed");
     return GW_OK;
 }
@@ -297,9 +295,7 @@ int gw_ctrl_rollout_feedback(gw_ctrl* c, int32_t steps, const gw_ctrl_feedback* 
     if (N % P != 0 || (N / P) % 64 != 0)
         return gw_set_error(GW_EUNSUPPORTED, "gw_ctrl_rollout_feedback: num_envs / P must be a whole multiple of 64 (one policy per block)");
     CTRL_HIP(hipSetDevice(c->cfg.net.hip_device), (void)0);
-    if (c->loss_on ? gw_ctrl_launch_rollout_feedback_loss(c->dev, c->epi, c->pid, c->dist, c->loss, steps, *fb, *ep, rows, tally_dev, stream)
-        : c->dist_on ? gw_ctrl_launch_rollout_feedback_dist(c->dev, c->epi, c->pid, c->dist, steps, *fb, *ep, rows, tally_dev, stream)
-                   : gw_ctrl_launch_rollout_feedback(c->dev, c->epi, pid_of(c), steps, *fb, *ep, rows, tally_dev, stream))
+    if (gw_ctrl_launch_rollout_feedback(c->dev, c->epi, blocks_of(c), steps, *fb, *ep, rows, tally_dev, stream))
         return gw_set_error(GW_EHIP, "control-loop feedback rollout launch failed");
     return GW_OK;
 }

@@ -248,7 +248,7 @@ int gw_grid_launch_init(const GwGridDev& g, const double* delays_dev, const doub
 
 struct GwHostTables;
 
-// Closed control loop (ctrl_step.hip, gw_ctrl_api.cpp)
+// Closed control loop (ctrl_step.hip, ctrl_rollout.hip, ctrl_rollout_feedback.hip, gw_ctrl_api.cpp)
 struct GwCtrlDev {
     int64_t N;
     double *now, *wake, *x, *u, *ang;          // [N], [N], [N][4], [N], [N]
@@ -269,69 +269,49 @@ struct GwCtrlEpi {
     uint32_t* age;                             // [N]
 };
 // Per-env controller: the PID gains and the controller's last error (the rule: include/gymwipe_amd.h, gw_ctrl_set_gains).  One
-// block f64[N][4] = {kp, ki, kd, last_error}; a struct of its own for GwCtrlEpi's reason.  The launchers below take it by pointer:
-// NULL launches the kernels with the default rule compiled in (no gains read), else their PID instantiations.
+// block f64[N][4] = {kp, ki, kd, last_error}; a struct of its own for GwCtrlEpi's reason.
 struct GwCtrlPid {
     double* pid;                               // [N][4]
 };
-int gw_ctrl_launch_step(const GwCtrlDev& c, const GwCtrlPid* g, const int32_t* device, const int32_t* duration, int32_t* obs,
-                        float* reward, double* angle_deg, void* stream);
-int gw_ctrl_launch_init(const GwCtrlDev& c, const double* x0, double u0, void* stream);
-int gw_ctrl_launch_fill_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, double u0, void* stream);
-int gw_ctrl_launch_set_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, const double* u0, const uint8_t* mask,
-                               void* stream);
-int gw_ctrl_launch_set_gains(const GwCtrlDev& c, const GwCtrlPid& g, const double* gains, const uint8_t* mask, void* stream);
-int gw_ctrl_launch_reset(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, const uint8_t* mask, int32_t* obs, void* stream);
-int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, int32_t steps, const int32_t* device,
-                           const int32_t* duration, const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg,
-                           uint8_t* ended, void* stream);
-int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, int32_t steps, const uint8_t* sched,
-                                     int32_t P, int32_t L, const gw_ctrl_episodes& ep, double* tally, void* stream);
-int gw_ctrl_launch_rollout_feedback(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid* g, int32_t steps,
-                                    const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
-                                    double* tally, void* stream);                       // ctrl_rollout_feedback.hip
-int gw_ctrl_launch_rollout_feedback_pid(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, int32_t steps,
-                                        const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
-                                        double* tally, void* stream);                   // ctrl_rollout_feedback_pid.hip
 // Per-env plant disturbance (the rule: include/gymwipe_amd.h, gw_ctrl_set_disturbance).  One block of 48-byte records
-// {g[4] f64, key u64, n u64}, addressed as u64[N][6]; a struct of its own for GwCtrlEpi's reason.  A handle that has set a
-// disturbance launches the *_dist launchers below and no other step or rollout launcher: their kernels are the PID
-// instantiations with the rule at the end of every plant substep.
+// {g[4] f64, key u64, n u64}, addressed as u64[N][6]; a struct of its own for GwCtrlEpi's reason.
 struct GwCtrlDist {
     uint64_t* rec;                             // [N][6]
 };
-int gw_ctrl_launch_set_disturbance(const GwCtrlDev& c, const GwCtrlDist& w, const double* g, const uint64_t* key, const uint8_t* mask,
-                                   void* stream);                                       // ctrl_rollout_dist.hip, as the next two
-int gw_ctrl_launch_rollout_dist(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, int32_t steps,
-                                const int32_t* device, const int32_t* duration, const gw_ctrl_episodes* ep, int32_t* obs, float* reward,
-                                double* angle_deg, uint8_t* ended, void* stream);
-int gw_ctrl_launch_rollout_schedules_dist(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, int32_t steps,
-                                          const uint8_t* sched, int32_t P, int32_t L, const gw_ctrl_episodes& ep, double* tally, void* stream);
-int gw_ctrl_launch_step_dist(const GwCtrlDev& c, const GwCtrlPid& g, const GwCtrlDist& w, const int32_t* device, const int32_t* duration,
-                             int32_t* obs, float* reward, double* angle_deg, void* stream);      // ctrl_step_dist.hip
-int gw_ctrl_launch_rollout_feedback_dist(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, int32_t steps,
-                                         const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
-                                         double* tally, void* stream);                  // ctrl_rollout_feedback_dist.hip
 // Per-env packet erasures (the rule: include/gymwipe_amd.h, gw_ctrl_set_loss).  One block of 48-byte records
-// {thr[4] u32, key u64, n u64, lost[4] u32}, addressed as u64[N][6]; a struct of its own for GwCtrlEpi's reason, and the
-// kernels' last argument.  A handle that has set a loss launches the *_loss launchers below and no other step or rollout
-// launcher: their kernels are the disturbance instantiations with one draw per transmission.
+// {thr[4] u32, key u64, n u64, lost[4] u32}, addressed as u64[N][6]; a struct of its own for GwCtrlEpi's reason.
 struct GwCtrlLoss {
     uint64_t* rec;                             // [N][6]
 };
+// The variant of its kernels a handle launches, named by the blocks they read.  The set pointers form a prefix: none (the
+// kernels with the default rule compiled in, no block read), g (their PID instantiations), g and w (the plant disturbed at the
+// end of every substep as well), all three (one erasure draw per transmission as well).  The step and rollout launchers below
+// pick the kernel from it and pass the set blocks as the kernel's last arguments, in this order.
+struct GwCtrlBlocks {
+    const GwCtrlPid* g;
+    const GwCtrlDist* w;
+    const GwCtrlLoss* x;
+};
+int gw_ctrl_launch_init(const GwCtrlDev& c, const double* x0, double u0, void* stream);                   // ctrl_step.hip, as the next
+int gw_ctrl_launch_step(const GwCtrlDev& c, const GwCtrlBlocks& v, const int32_t* device, const int32_t* duration, int32_t* obs,
+                        float* reward, double* angle_deg, void* stream);
+int gw_ctrl_launch_fill_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, double u0, void* stream);   // ctrl_rollout.hip
+int gw_ctrl_launch_set_initial(const GwCtrlDev& c, const GwCtrlEpi& s, const double* x0, const double* u0, const uint8_t* mask,
+                               void* stream);
+int gw_ctrl_launch_set_gains(const GwCtrlDev& c, const GwCtrlPid& g, const double* gains, const uint8_t* mask, void* stream);
+int gw_ctrl_launch_set_disturbance(const GwCtrlDev& c, const GwCtrlDist& w, const double* g, const uint64_t* key, const uint8_t* mask,
+                                   void* stream);
 int gw_ctrl_launch_set_loss(const GwCtrlDev& c, const GwCtrlLoss& x, const uint32_t* thr, const uint64_t* key, const uint8_t* mask,
-                            void* stream);                                              // ctrl_rollout_loss.hip, as the next two
-int gw_ctrl_launch_rollout_loss(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, const GwCtrlLoss& x,
-                                int32_t steps, const int32_t* device, const int32_t* duration, const gw_ctrl_episodes* ep, int32_t* obs,
-                                float* reward, double* angle_deg, uint8_t* ended, void* stream);
-int gw_ctrl_launch_rollout_schedules_loss(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, const GwCtrlLoss& x,
-                                          int32_t steps, const uint8_t* sched, int32_t P, int32_t L, const gw_ctrl_episodes& ep, double* tally,
-                                          void* stream);
-int gw_ctrl_launch_step_loss(const GwCtrlDev& c, const GwCtrlPid& g, const GwCtrlDist& w, const GwCtrlLoss& x, const int32_t* device,
-                             const int32_t* duration, int32_t* obs, float* reward, double* angle_deg, void* stream);   // ctrl_step_loss.hip
-int gw_ctrl_launch_rollout_feedback_loss(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlPid& g, const GwCtrlDist& w, const GwCtrlLoss& x,
-                                         int32_t steps, const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep,
-                                         const gw_ctrl_feedback_rows* rows, double* tally, void* stream);   // ctrl_rollout_feedback_loss.hip
+                            void* stream);
+int gw_ctrl_launch_reset(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlBlocks& v, const uint8_t* mask, int32_t* obs, void* stream);
+int gw_ctrl_launch_rollout(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlBlocks& v, int32_t steps, const int32_t* device,
+                           const int32_t* duration, const gw_ctrl_episodes* ep, int32_t* obs, float* reward, double* angle_deg,
+                           uint8_t* ended, void* stream);
+int gw_ctrl_launch_rollout_schedules(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlBlocks& v, int32_t steps, const uint8_t* sched,
+                                     int32_t P, int32_t L, const gw_ctrl_episodes& ep, double* tally, void* stream);
+int gw_ctrl_launch_rollout_feedback(const GwCtrlDev& c, const GwCtrlEpi& s, const GwCtrlBlocks& v, int32_t steps,
+                                    const gw_ctrl_feedback& fb, const gw_ctrl_episodes& ep, const gw_ctrl_feedback_rows* rows,
+                                    double* tally, void* stream);                       // ctrl_rollout_feedback.hip
 int gw_fill_dev_const(const gw_config& cfg, const GwHostTables& tab, GwDevConst& k);   // gw_api.cpp
 int gw_validate_config(const gw_config& cfg);                                           // gw_api.cpp
 

@@ -223,12 +223,19 @@ def test_a_reset_that_restarted_the_count_would_be_caught(case):
 
 
 # ---- the disturbance instantiations use no scratch memory -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("source,kernels", [("ctrl_step_dist.hip", ("ctrl_step_dist_kernel",)),
-                                            ("ctrl_rollout_dist.hip", ("ctrl_rollout_dist_kernel", "ctrl_rollout_sched_dist_kernel",
-                                                                       "ctrl_set_disturbance_kernel")),
-                                            ("ctrl_rollout_feedback_dist.hip", ("ctrl_rollout_fb_dist_kernel", "ctrl_rollout_fb_rows_dist_kernel"))])
+_VARIANTS = ("", "_pid", "_dist", "_loss")                                # of every step and rollout kernel: default, + gains, + disturbance, + loss
+
+
+@pytest.mark.parametrize("source,kernels", [
+    ("ctrl_step.hip", tuple("ctrl_step%s_kernel" % v for v in _VARIANTS) + ("ctrl_init_kernel",)),
+    ("ctrl_rollout.hip", tuple("ctrl_rollout%s%s_kernel" % (shape, v) for shape in ("", "_sched") for v in _VARIANTS)
+     + ("ctrl_fill_initial_kernel", "ctrl_set_initial_kernel", "ctrl_set_gains_kernel", "ctrl_set_disturbance_kernel",
+        "ctrl_set_loss_kernel", "ctrl_reset_pid_kernel", "ctrl_reset_kernel")),
+    ("ctrl_rollout_feedback.hip", tuple("ctrl_rollout_fb%s%s_kernel" % (shape, v) for shape in ("", "_rows") for v in _VARIANTS))])
 def test_the_disturbance_kernels_use_no_scratch_memory(tmp_path, source, kernels):
-    """Every kernel of the three new files has a private segment of 0 bytes, compiled as the product build compiles them."""
+    """Every kernel of the three files that hold the control loop -- the disturbance instantiations and, since they share their
+    files, every other variant (the loss instantiations included) and the small kernels -- has a private segment of 0 bytes,
+    compiled as the product build compiles them; and the files hold exactly the kernels listed."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")

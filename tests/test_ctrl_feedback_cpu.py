@@ -259,9 +259,10 @@ def test_the_feedback_kernels_use_no_scratch_memory_and_are_plain_functions(tmp_
     names = re.findall(r"^\s+\.name:\s+(\S+)", text, re.M)
     assert sizes and len(sizes) == len(names)
     kernels = dict(zip(names, map(int, sizes)))
-    for want in ("ctrl_rollout_fb_kernel", "ctrl_rollout_fb_rows_kernel"):
+    variants = ("", "_pid", "_dist", "_loss")                            # default, + gains, + disturbance, + loss: all in this file
+    for want in ["ctrl_rollout_fb%s%s_kernel" % (shape, v) for shape in ("", "_rows") for v in variants]:
         assert any(want in n for n in kernels), (want, sorted(kernels))
-    assert len(kernels) == 2 and all(v == 0 for v in kernels.values()), kernels
+    assert len(kernels) == 2 * len(variants) and all(v == 0 for v in kernels.values()), kernels
     source = open(os.path.join(csrc, "ctrl_rollout_feedback.hip")).read()
     source = re.sub(r"//[^\n]*", "", source)
     assert len(re.findall(r"__global__", source)) == len(kernels)

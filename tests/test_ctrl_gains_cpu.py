@@ -185,9 +185,9 @@ def test_a_reset_that_kept_the_last_error_would_be_caught(case):
 
 # ---- the PID instantiations use no scratch memory -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("source,kernels", [("ctrl_step.hip", ("ctrl_step_kernel", "ctrl_step_pid_kernel")),
-                                            ("ctrl_rollout_feedback_pid.hip", ("ctrl_rollout_fb_pid_kernel", "ctrl_rollout_fb_rows_pid_kernel"))])
+                                            ("ctrl_rollout_feedback.hip", ("ctrl_rollout_fb_pid_kernel", "ctrl_rollout_fb_rows_pid_kernel"))])
 def test_the_pid_kernels_use_no_scratch_memory(tmp_path, source, kernels):
-    """Every kernel of the two files the older tests of this kind do not compile has a private segment of 0 bytes
+    """Every kernel of the two files that hold the PID instantiations beside ctrl_rollout.hip has a private segment of 0 bytes
     (ctrl_rollout.hip's, the PID instantiations included, are held to it by tests/test_ctrl_rollout_cpu.py)."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
