@@ -241,6 +241,24 @@ class VecControlLoopEnv(BaseEnv):
         assert m.shape == (self.num_envs,)
         return m
 
+    def _keys(self, key):
+        """One 64-bit key per env -- numpy uint64[N], or an int64 tensor holding the bit patterns -- as a contiguous int64[N]
+        tensor on the env's GPU, to be kept alive across the call."""
+        import numpy as np
+        torch = self._torch
+        if isinstance(key, torch.Tensor):
+            if key.dtype != torch.int64:
+                raise ValueError("key as a tensor is int64[num_envs] holding the keys' bit patterns")
+            kt = key.to(self.device)
+        else:
+            ka = np.asarray(key)
+            if ka.dtype != np.uint64:
+                raise ValueError("key is numpy uint64[num_envs] (or an int64 tensor holding the bit patterns)")
+            kt = torch.from_numpy(np.ascontiguousarray(ka).view(np.int64)).to(self.device)
+        if tuple(kt.shape) != (self.num_envs,):
+            raise ValueError("key holds one key per env")
+        return kt.contiguous()
+
     def set_initial_state(self, x0, u0=None, mask=None):
         """Give the masked envs (None: all) initial states of their own: ``x0`` f64[N][4] (a single state of 4 is broadcast),
         ``u0`` f64[N] or a number (None: keep).  Takes effect at the env's next reset -- ``reset_envs`` or the end of an
@@ -296,18 +314,7 @@ class VecControlLoopEnv(BaseEnv):
         if key is None:
             from .. import actions
             key = actions.make_ctrl_disturbance(np.zeros(4), self.num_envs)[1]
-        if isinstance(key, torch.Tensor):
-            if key.dtype != torch.int64:
-                raise ValueError("key as a tensor is int64[num_envs] holding the keys' bit patterns")
-            kt = key.to(self.device)
-        else:
-            ka = np.asarray(key)
-            if ka.dtype != np.uint64:
-                raise ValueError("key is numpy uint64[num_envs] (or an int64 tensor holding the bit patterns)")
-            kt = torch.from_numpy(np.ascontiguousarray(ka).view(np.int64)).to(self.device)
-        if tuple(kt.shape) != (self.num_envs,):
-            raise ValueError("key holds one key per env")
-        kt = kt.contiguous()
+        kt = self._keys(key)
         m = self._mask(mask)
         with torch.cuda.device(self.device):
             nat.check(self._L.gw_ctrl_set_disturbance(self._h, gt.data_ptr(), kt.data_ptr(), m.data_ptr() if m is not None else None,
@@ -339,18 +346,7 @@ class VecControlLoopEnv(BaseEnv):
         tt = torch.from_numpy(np.ascontiguousarray(thr).view(np.int32)).to(self.device).contiguous()
         if key is None:
             key = actions.make_ctrl_loss(np.zeros(4), self.num_envs)[1]
-        if isinstance(key, torch.Tensor):
-            if key.dtype != torch.int64:
-                raise ValueError("key as a tensor is int64[num_envs] holding the keys' bit patterns")
-            kt = key.to(self.device)
-        else:
-            ka = np.asarray(key)
-            if ka.dtype != np.uint64:
-                raise ValueError("key is numpy uint64[num_envs] (or an int64 tensor holding the bit patterns)")
-            kt = torch.from_numpy(np.ascontiguousarray(ka).view(np.int64)).to(self.device)
-        if tuple(kt.shape) != (self.num_envs,):
-            raise ValueError("key holds one key per env")
-        kt = kt.contiguous()
+        kt = self._keys(key)
         m = self._mask(mask)
         with torch.cuda.device(self.device):
             nat.check(self._L.gw_ctrl_set_loss(self._h, tt.data_ptr(), kt.data_ptr(), m.data_ptr() if m is not None else None,

@@ -120,7 +120,7 @@ def fixture_arrays(name, L=None):
 
 
 def wrapper(s, **kw):
-    import test_ctrl_rollout as g
+    import ctrl_fixtures as g
     return FeedbackControlLoop(x0=g.X0S[s], u0=g.U0S[s], start=g.START, period=g.PERIOD, **kw)
 
 
@@ -133,7 +133,7 @@ def fixture_streams(name, abs_key=None, max_steps=MAX_STEPS, steps=STEPS):
 
 @functools.lru_cache(maxsize=None)
 def _fixture_streams(name, key, max_steps, steps):
-    import test_ctrl_rollout as g
+    import ctrl_fixtures as g
     sched, edges, _ = fixture_arrays(name)
     tally = np.empty((g.STREAMS, COLS), np.float64)
     rows, states, reset_bins = None, [], []
@@ -146,7 +146,7 @@ def _fixture_streams(name, key, max_steps, steps):
             rows[f][:, s] = v
         states.append(env.state())
         reset_bins += rb
-    final = g._rows(states)
+    final = g.rows_of(states)
     for v in (tally,) + tuple(rows.values()) + tuple(final.values()):
         v.setflags(write=False)
     return tally, rows, final, tuple(reset_bins)

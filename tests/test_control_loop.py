@@ -6,8 +6,9 @@ import functools
 import numpy as np
 import pytest
 
+from ctrl_fixtures import DENSE_CTRL, STREAMS, stream_of          # the streams' layout and the dense plant: shared with the references
 from oracle import des_model as dm
-from util import PLANT_MODELS, assert_dense
+from util import assert_dense
 
 
 def test_control_loop_model_closes_the_loop():
@@ -80,17 +81,6 @@ def test_control_loop_env_surface():
 
 
 # ---- more than one block, and another plant ----------------------------------------------------------------------------
-STREAMS = 8
-DENSE_CTRL = {"A": PLANT_MODELS["dense0"]["A"], "B": PLANT_MODELS["dense0"]["B"] * 1e-2, "x0": PLANT_MODELS["dense0"]["x0"],
-              "u0": -0.37}                   # B scaled down: the controller commands u = -angle in DEGREES
-
-
-def stream_of(N):
-    """Env e follows action stream (5 e + e // 64) % 8: equal lanes of different 64-env blocks follow different streams."""
-    e = np.arange(N)
-    return (5 * e + e // 64) % STREAMS
-
-
 @functools.lru_cache(maxsize=None)
 def model_streams(plant, K, seed, start, period):
     """STREAMS action streams of K steps through one ControlLoopModel each: the actions, and per step and stream the model's

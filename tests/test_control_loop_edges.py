@@ -19,24 +19,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ctrl_episodes_model import FIELDS, EpisodicControlLoop, run_schedule
-from test_control_loop import STREAMS, stream_of
-from test_ctrl_rollout import ALL_FIELDS, T, X0S, U0S, assert_same, assert_states_equal, state_of
+from ctrl_fixtures import ALL_FIELDS, LAYOUTS, STREAMS, T, U0S, X0S, assert_same, stream_of
+from test_ctrl_rollout import assert_states_equal, state_of
 
 from oracle import des_model as dm
 
 N, K = 70, 24
 START, PERIOD, SEED = 5, 3, 20
-# sensor, controller, actuator / RRM
-LAYOUTS = {
-    # the RRM 3.45 - 3.6 m from sensor and controller: a 4-digit slot count is granted, a 5-digit one refused (banker's rounding)
-    "rrm_edge": (((0.0, 0.0), (0.0, -1.0), (0.5, 0.0)), (3.45, -0.5)),
-    # sensor -> controller 3.46 m: no sensor packet decodes, so the controller never has an angle to answer
-    "sensor_link_dead": (((0.0, 0.0), (0.0, -3.46), (0.5, -3.46)), (0.7, -1.73)),
-    # controller -> actuator 3.43 m: every sensor packet arrives, no command does
-    "actuator_link_dead": (((0.0, 0.0), (0.0, -1.0), (3.43, -1.0)), (0.5, 0.2)),
-    # both hops 3.43 m: the 14-byte sensor payloads decode, the 13-byte commands do not
-    "same_distance": (((0.0, 0.0), (0.0, -3.43), (3.43, -3.43)), (0.5, -1.7)),
-}
 TIE_ACTS = [(0, 19), (1, 7), (0, 3), (1, 19), (0, 0), (1, 12)]
 TIE_CASES = ("t_e1", "t_e1/2", "t_end/8")
 GATE_INTERVAL = 0.00097                                    # the issue's figure: just above the smallest interval admitted

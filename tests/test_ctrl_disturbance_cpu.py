@@ -4,9 +4,6 @@ motivate the feature, ``actions.make_ctrl_disturbance``, and the fixtures of the
 must be able to tell a kernel that drops a weight, or restarts the count at a reset, from a right one."""
 import math
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +12,10 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ctrl_dist_model as dm
 import ctrl_pid_model as pm
+import ctrl_tiers as ct
+from ctrl_fixtures import STREAMS
+from ctrl_tiers import DIST, PID
+from util import private_segments
 
 
 def bits(a):
@@ -73,8 +74,8 @@ def test_zero_weights_give_the_undisturbed_model_snapshot_for_snapshot(plant):
     rule as written may turn a -0.0 of the plant into +0.0; the fixture holds no -0.0, which is asserted, so bits are compared."""
     K, seed, start, period = 70, 1, 20, 10
     assert dm.G_SETS[0] == (0.0, 0.0, 0.0, 0.0) and pm.GAIN_SETS[0] == pm.DEFAULT_GAINS
-    dev, dur, want = pm.step_streams(plant, K, seed, start, period)
-    dev2, dur2, got = dm.step_streams(plant, K, seed, start, period)
+    dev, dur, want, _ = ct.step_streams(PID, plant, K, seed, start, period)
+    dev2, dur2, got, _ = ct.step_streams(DIST, plant, K, seed, start, period)
     assert (dev == dev2).all() and (dur == dur2).all()
     for k in range(K):
         for f, w in want[k].items():
@@ -140,7 +141,7 @@ def test_make_ctrl_disturbance_lays_sets_and_keys_across_envs():
     assert (key.reshape(4, 128) == key[:128]).all() and len(set(key[:128].tolist())) == 128
     p, gi, b, _ = pm.fused_layout()                                             # the fused fixture's keys through the helper
     _, key = actions.make_ctrl_disturbance(np.zeros(4), 512, seed=dm.SEED, streams=(p * dm.G + gi) * 2 + b)
-    assert (key == dm.fused_keys()).all()
+    assert (key == ct.fused_keys(dm.SEED64)).all()
     for bad in (lambda: actions.make_ctrl_disturbance(dm.G_SETS, 100), lambda: actions.make_ctrl_disturbance(dm.G_SETS, 512, envs_per_set=48),
                 lambda: actions.make_ctrl_disturbance(dm.G_SETS, 512, envs_per_set=0), lambda: actions.make_ctrl_disturbance([(1.0, 0.0, 0.0)], 8),
                 lambda: actions.make_ctrl_disturbance([], 8), lambda: actions.make_ctrl_disturbance(np.zeros(4), 8, streams=np.arange(7)),
@@ -151,24 +152,22 @@ def test_make_ctrl_disturbance_lays_sets_and_keys_across_envs():
 
 # ---- the fixtures of the GPU tests ---------------------------------------------------------------------------------------------------------
 def test_step_fixture_is_bounded_and_every_pair_walks_its_own_way():
-    from test_control_loop import STREAMS
-    _, _, steps = dm.step_streams(None, 70, 1, 20, 10)
+    steps = ct.step_streams(DIST, None, 70, 1, 20, 10).steps
     x = np.array([w["x"] for w in steps])
     ang = np.array([w["ang"] for w in steps])
     assert np.isfinite(x).all() and np.isfinite(ang).all() and np.abs(ang).max() < 2000.0, np.abs(ang).max()      # nothing the
     last = steps[-1]                                                            # int32 observation would have to clamp
     assert (last["commands"] > 0).all() and (last["noise_count"] == last["substeps"]).all()
     assert len({last["x"][g, s].tobytes() for g in range(dm.G) for s in range(STREAMS)}) == dm.G * STREAMS
-    _, _, calm = pm.step_streams(None, 70, 1, 20, 10)
+    calm = ct.step_streams(PID, None, 70, 1, 20, 10).steps
     assert (bits(last["x"][1:]) != bits(calm[-1]["x"][1:])).any(axis=-1).all()  # every disturbed pair left the calm trajectory
 
 
 def test_fused_fixtures_are_bounded_and_end_by_both_causes_under_the_noise():
-    _, tally, final, ang, ended = dm.schedule_streams(dm.MAX_STEPS)
-    fb_tally, rows, fb_final = dm.feedback_streams(dm.MAX_STEPS)
-    _, _, ep_ang, ep_ended, ep_final = dm.episode_streams(dm.SHORT_MAX_STEPS)
-    for what, a, e, f in (("schedules", ang, ended, final), ("feedback", rows["angle"], rows["ended"], fb_final),
-                          ("staged", ep_ang, ep_ended, ep_final)):
+    sch, fb, ep = ct.schedule_streams(DIST, dm.MAX_STEPS), ct.feedback_streams(DIST, dm.MAX_STEPS), ct.episode_streams(DIST, dm.SHORT_MAX_STEPS)
+    tally, fb_tally = sch.tally, fb.tally
+    for what, a, e, f in (("schedules", sch.ang, sch.ended, sch.final), ("feedback", fb.rows["angle"], fb.rows["ended"], fb.final),
+                          ("staged", ep.ang, ep.ended, ep.final)):
         assert np.isfinite(a).all() and np.abs(a).max() < 2000.0, (what, np.abs(a).max())
         assert np.isfinite(f["x"]).all() and np.isfinite(f["last_error"]).all(), what
         assert ((e & 1) != 0).sum() >= 20 and ((e & 2) != 0).sum() >= 20, what           # the step limit, and the failure angle
@@ -178,8 +177,8 @@ def test_fused_fixtures_are_bounded_and_end_by_both_causes_under_the_noise():
 
 
 def test_the_noise_changes_actions_the_feedback_fixture_takes():
-    _, rows, _ = dm.feedback_streams(dm.MAX_STEPS)
-    _, calm, _ = dm.feedback_streams(dm.MAX_STEPS, disturbed=False)
+    rows = ct.feedback_streams(DIST, dm.MAX_STEPS).rows
+    calm = ct.feedback_streams(DIST, dm.MAX_STEPS, g=(0.0, 0.0, 0.0, 0.0)).rows       # the same models with all weights 0
     moved = (rows["device"] != calm["device"]) | (rows["duration"] != calm["duration"])
     assert moved[:, :, 1:].any() and not moved[:, :, 0].any()                   # (weight set 0 is the calm one)
     assert moved.reshape(dm.STEPS, -1).any(0).sum() >= 8, moved.sum()           # in at least 8 of the 56 disturbed models
@@ -189,7 +188,7 @@ def test_the_noise_changes_actions_the_feedback_fixture_takes():
 def test_each_weight_alone_changes_where_the_fixtures_end(which):
     """A kernel that ignored one component of g would be caught: zeroing it moves the final x of at least 3 models of the
     schedule case."""
-    _, _, final, _, _ = dm.schedule_streams(dm.MAX_STEPS)
+    final = ct.schedule_streams(DIST, dm.MAX_STEPS).final
     moved = 0
     for gi in range(dm.G):
         g = list(dm.G_SETS[gi])
@@ -197,7 +196,7 @@ def test_each_weight_alone_changes_where_the_fixtures_end(which):
             continue
         g[which] = 0.0
         for p in range(dm.P):
-            _, _, _, env = dm.run_schedule(p, gi, 0, dm.MAX_STEPS, g=tuple(g))
+            _, _, _, env = ct.run_schedule(DIST, p, gi, 0, dm.MAX_STEPS, g=tuple(g))
             moved += bits(env.state()["x"]).tolist() != bits(final["x"][p, gi, 0]).tolist()
         if moved >= 3:
             break
@@ -207,13 +206,13 @@ def test_each_weight_alone_changes_where_the_fixtures_end(which):
 @pytest.mark.parametrize("case", ["schedules", "staged"])
 def test_a_reset_that_restarted_the_count_would_be_caught(case):
     moved = 0
-    final = dm.schedule_streams(dm.MAX_STEPS)[2] if case == "schedules" else dm.episode_streams(dm.SHORT_MAX_STEPS)[4]
+    final = ct.schedule_streams(DIST, dm.MAX_STEPS).final if case == "schedules" else ct.episode_streams(DIST, dm.SHORT_MAX_STEPS).final
     for gi in range(1, dm.G):
         for p in range(dm.P):
             if case == "schedules":
-                env = dm.run_schedule(p, gi, 1, dm.MAX_STEPS, restart_n=True)[3]
+                env = ct.run_schedule(DIST, p, gi, 1, dm.MAX_STEPS, restart_n=True)[3]
             else:
-                env = dm.run_episodes(p, gi, 1, dm.SHORT_MAX_STEPS, restart_n=True)[1]
+                env = ct.run_episodes(DIST, p, gi, 1, dm.SHORT_MAX_STEPS, restart_n=True)[1]
             st = env.state()
             assert st["noise_count"] <= st["substeps"]
             moved += bits(st["x"]).tolist() != bits(final["x"][p, gi, 1]).tolist()
@@ -236,20 +235,8 @@ def test_the_disturbance_kernels_use_no_scratch_memory(tmp_path, source, kernels
     """Every kernel of the three files that hold the control loop -- the disturbance instantiations and, since they share their
     files, every other variant (the loss instantiations included) and the small kernels -- has a private segment of 0 bytes,
     compiled as the product build compiles them; and the files hold exactly the kernels listed."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gymwipe_amd", "csrc")
-    flags = subprocess.run(["make", "-s", "-C", csrc, "print-flags"], check=True, capture_output=True, text=True).stdout.split()
-    assert "--offload-arch=gfx950" in flags and "-ffp-contract=off" in flags, flags
-    out = tmp_path / "listing.s"
-    subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", "-o", str(out), "-x", "hip", os.path.join(csrc, source)],
-                   check=True, capture_output=True, timeout=900, cwd=csrc)
-    text = out.read_text()
-    sizes = re.findall(r"^\s+\.private_segment_fixed_size:\s+(\d+)", text, re.M)
-    names = re.findall(r"^\s+\.name:\s+(\S+)", text, re.M)
-    assert sizes and len(sizes) == len(names) == len(kernels)
-    found = dict(zip(names, map(int, sizes)))
+    found = private_segments(tmp_path, source)
+    assert len(found) == len(kernels)
     for want in kernels:
         assert any(want in n for n in found), (want, sorted(found))
     assert all(v == 0 for v in found.values()), found

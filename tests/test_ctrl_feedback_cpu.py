@@ -9,8 +9,6 @@ import ctypes as C
 import math
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -20,6 +18,7 @@ from gymwipe_amd import actions
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ctrl_feedback_model as fm
+from util import private_segments
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -245,20 +244,8 @@ def test_a_feedback_scheduler_trades_airtime_against_time_weighted_error():
 
 # ---- 5. no scratch -------------------------------------------------------------------------------------------------------------------
 def test_the_feedback_kernels_use_no_scratch_memory_and_are_plain_functions(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
+    kernels = private_segments(tmp_path, "ctrl_rollout_feedback.hip")
     csrc = os.path.join(ROOT, "gymwipe_amd", "csrc")
-    flags = subprocess.run(["make", "-s", "-C", csrc, "print-flags"], check=True, capture_output=True, text=True).stdout.split()
-    assert "--offload-arch=gfx950" in flags and "-ffp-contract=off" in flags, flags
-    out = tmp_path / "ctrl_rollout_feedback.s"
-    subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", "-o", str(out), "-x", "hip", os.path.join(csrc, "ctrl_rollout_feedback.hip")],
-                   check=True, capture_output=True, timeout=900, cwd=csrc)
-    text = out.read_text()
-    sizes = re.findall(r"^\s+\.private_segment_fixed_size:\s+(\d+)", text, re.M)
-    names = re.findall(r"^\s+\.name:\s+(\S+)", text, re.M)
-    assert sizes and len(sizes) == len(names)
-    kernels = dict(zip(names, map(int, sizes)))
     variants = ("", "_pid", "_dist", "_loss")                            # default, + gains, + disturbance, + loss: all in this file
     for want in ["ctrl_rollout_fb%s%s_kernel" % (shape, v) for shape in ("", "_rows") for v in variants]:
         assert any(want in n for n in kernels), (want, sorted(kernels))

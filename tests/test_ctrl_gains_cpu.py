@@ -4,9 +4,6 @@ restatement of the rule against the model's controller, and the fixtures of the 
 they must be able to tell a kernel that drops a gain, or keeps the last error across a reset, from a right one."""
 import math
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -14,7 +11,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ctrl_pid_model as pm
+import ctrl_tiers as ct
+from ctrl_tiers import PID
 from test_control_loop import STREAMS, model_streams
+from util import private_segments
 
 
 def bits(a):
@@ -26,7 +26,7 @@ def bits(a):
 def test_default_gains_give_the_oracle_snapshot_for_snapshot(plant):
     K, seed, start, period = 70, 1, 20, 10
     dev, dur, want = model_streams(plant, K, seed, start, period)
-    dev2, dur2, got = pm.step_streams(plant, K, seed, start, period, gains=(pm.DEFAULT_GAINS,))
+    dev2, dur2, got, _ = ct.step_streams(PID, plant, K, seed, start, period, gains=(pm.DEFAULT_GAINS,))
     assert (dev == dev2).all() and (dur == dur2).all()
     for k in range(K):
         for f, w in want[k].items():
@@ -104,7 +104,7 @@ def test_make_ctrl_gains_lays_sets_across_envs():
 
 # ---- the fixtures of the GPU tests ------------------------------------------------------------------------------------------------------
 def test_step_fixture_is_bounded_and_commands_of_both_signs_are_delivered():
-    _, _, steps = pm.step_streams(None, 70, 1, 20, 10)
+    steps = ct.step_streams(PID, None, 70, 1, 20, 10).steps
     x = np.array([w["x"] for w in steps])
     ang = np.array([w["ang"] for w in steps])
     assert np.isfinite(x).all() and np.isfinite(ang).all() and np.abs(ang).max() < 2000.0, np.abs(ang).max()
@@ -119,11 +119,10 @@ def test_step_fixture_is_bounded_and_commands_of_both_signs_are_delivered():
 
 @pytest.mark.parametrize("max_steps", [pm.MAX_STEPS, pm.SHORT_MAX_STEPS])
 def test_fused_fixtures_are_bounded_and_end_by_both_causes(max_steps):
-    _, tally, final, ang, ended = pm.schedule_streams(max_steps)
-    fb_tally, rows, fb_final = pm.feedback_streams(max_steps)
-    _, _, _, _, ep_ang, ep_ended, ep_final = pm.episode_streams(max_steps)
-    for what, a, e, f in (("schedules", ang, ended, final), ("feedback", rows["angle"], rows["ended"], fb_final),
-                          ("staged", ep_ang, ep_ended, ep_final)):
+    sch, fb, ep = ct.schedule_streams(PID, max_steps), ct.feedback_streams(PID, max_steps), ct.episode_streams(PID, max_steps)
+    tally, fb_tally = sch.tally, fb.tally
+    for what, a, e, f in (("schedules", sch.ang, sch.ended, sch.final), ("feedback", fb.rows["angle"], fb.rows["ended"], fb.final),
+                          ("staged", ep.ang, ep.ended, ep.final)):
         assert np.isfinite(a).all() and np.abs(a).max() < 2000.0, (what, np.abs(a).max())
         assert np.isfinite(f["x"]).all() and np.isfinite(f["last_error"]).all(), what
         assert ((e & 1) != 0).sum() >= 20 and ((e & 2) != 0).sum() >= 20, what           # the step limit, and the failure angle
@@ -131,24 +130,23 @@ def test_fused_fixtures_are_bounded_and_end_by_both_causes(max_steps):
     assert (tally[..., 0] > 0).all() and (fb_tally[..., 0] > 0).all()
 
 
-def _pairs():
-    """(p, gain set index, stream) of the schedule case, sets with the gain in question first."""
-    return [(p, g, pm.fused_stream(p, g, b)) for g in range(pm.G) for p in range(pm.P) for b in range(2)]
+def _models():
+    """(p, gain set index, b) of the schedule case, sets with the gain in question first."""
+    return [(p, g, b) for g in range(pm.G) for p in range(pm.P) for b in range(2)]
 
 
 @pytest.mark.parametrize("which", [0, 1, 2])
 def test_each_gain_alone_changes_where_the_fixtures_end(which):
     """A kernel that ignored kp, ki or kd would be caught: zeroing that one gain moves the final x of at least 3 (gain set,
     stream) pairs of the schedule case."""
-    _, _, final, _, _ = pm.schedule_streams(pm.MAX_STEPS)
+    final = ct.schedule_streams(PID, pm.MAX_STEPS).final
     moved = 0
-    for p, g, s in _pairs():
+    for p, g, b in _models():
         gains = list(pm.GAIN_SETS[g])
         if gains[which] == 0.0:
             continue
         gains[which] = 0.0
-        _, _, _, env = pm.run_schedule(p, s, tuple(gains), pm.MAX_STEPS)
-        b = [b for b in range(2) if pm.fused_stream(p, g, b) == s][0]
+        _, _, _, env = ct.run_schedule(PID, p, g, b, pm.MAX_STEPS, gains=tuple(gains))
         moved += bits(env.state()["x"]).tolist() != bits(final["x"][p, g, b]).tolist()
         if moved >= 3:
             break
@@ -159,22 +157,23 @@ def test_each_gain_alone_changes_where_the_fixtures_end(which):
 def test_a_reset_that_kept_the_last_error_would_be_caught(case):
     moved = 0
     if case == "schedules":
-        _, _, final, _, _ = pm.schedule_streams(pm.MAX_STEPS)
-        for p, g, s in _pairs():
+        final = ct.schedule_streams(PID, pm.MAX_STEPS).final
+        for p, g, b in _models():
             if pm.GAIN_SETS[g][1] == 0.0 and pm.GAIN_SETS[g][2] == 0.0:
                 continue                                 # kp alone never reads the last error
-            _, _, _, env = pm.run_schedule(p, s, pm.GAIN_SETS[g], pm.MAX_STEPS, keep_last=True)
-            b = [b for b in range(2) if pm.fused_stream(p, g, b) == s][0]
+            _, _, _, env = ct.run_schedule(PID, p, g, b, pm.MAX_STEPS, keep_last=True)
             moved += bits(env.state()["x"]).tolist() != bits(final["x"][p, g, b]).tolist()
             if moved >= 3:
                 break
     else:
-        final = pm.episode_streams(pm.SHORT_MAX_STEPS)[6]
+        final = ct.episode_streams(PID, pm.SHORT_MAX_STEPS).final
+        where = {(g, pm.fused_stream(p, g, b)): (p, b) for p, g, b in _models()}      # the staged case is laid out by (set, stream)
         for g in range(pm.G):
             if pm.GAIN_SETS[g][1] == 0.0 and pm.GAIN_SETS[g][2] == 0.0:
                 continue
             for s in range(STREAMS):
-                _, env = pm.run_episodes(s, pm.GAIN_SETS[g], pm.SHORT_MAX_STEPS, keep_last=True)
+                p, b = where[g, s]
+                _, env = ct.run_episodes(PID, p, g, b, pm.SHORT_MAX_STEPS, keep_last=True)
                 moved += bits(env.state()["x"]).tolist() != bits(final["x"][g, s]).tolist()
                 if moved >= 3:
                     break
@@ -189,19 +188,7 @@ def test_a_reset_that_kept_the_last_error_would_be_caught(case):
 def test_the_pid_kernels_use_no_scratch_memory(tmp_path, source, kernels):
     """Every kernel of the two files that hold the PID instantiations beside ctrl_rollout.hip has a private segment of 0 bytes
     (ctrl_rollout.hip's, the PID instantiations included, are held to it by tests/test_ctrl_rollout_cpu.py)."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gymwipe_amd", "csrc")
-    flags = subprocess.run(["make", "-s", "-C", csrc, "print-flags"], check=True, capture_output=True, text=True).stdout.split()
-    out = tmp_path / "listing.s"
-    subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", "-o", str(out), "-x", "hip", os.path.join(csrc, source)],
-                   check=True, capture_output=True, timeout=900, cwd=csrc)
-    text = out.read_text()
-    sizes = re.findall(r"^\s+\.private_segment_fixed_size:\s+(\d+)", text, re.M)
-    names = re.findall(r"^\s+\.name:\s+(\S+)", text, re.M)
-    assert sizes and len(sizes) == len(names)
-    found = dict(zip(names, map(int, sizes)))
+    found = private_segments(tmp_path, source)
     for want in kernels:
         assert any(want in n for n in found), (want, sorted(found))
     assert all(v == 0 for v in found.values()), found

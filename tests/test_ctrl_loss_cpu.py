@@ -14,6 +14,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ctrl_dist_model as cd
 import ctrl_loss_model as lm
 import ctrl_pid_model as pm
+import ctrl_tiers as ct
+from ctrl_tiers import DIST, LOSS
 
 
 def bits(a):
@@ -71,7 +73,7 @@ def test_make_ctrl_loss_lays_sets_and_keys_as_the_disturbance_helper_does():
     assert (thr == lm.thr_array()[pm.fused_layout()[1]]).all()
     assert key.tolist() == [cd.key_of(lm.SEED64, e) for e in range(512)]
     p, gi, b, _ = pm.fused_layout()                                             # the fused fixture's keys through the helper
-    assert (actions.make_ctrl_loss(np.zeros(4), 512, seed=lm.SEED, streams=(p * lm.G + gi) * 2 + b)[1] == lm.fused_keys()).all()
+    assert (actions.make_ctrl_loss(np.zeros(4), 512, seed=lm.SEED, streams=(p * lm.G + gi) * 2 + b)[1] == ct.fused_keys(lm.SEED64)).all()
     thr, key = actions.make_ctrl_loss((0.5, 0.0, 1.0, 0.25), 6)
     assert (thr == [0x80000000, 0, 0xFFFFFFFF, 0x40000000]).all()
     _, dkey = actions.make_ctrl_disturbance(np.zeros(4), 6)
@@ -89,8 +91,8 @@ def test_make_ctrl_loss_lays_sets_and_keys_as_the_disturbance_helper_does():
 def test_zero_thresholds_give_the_disturbance_model_field_for_field(plant):
     K, seed, start, period = 70, 1, 20, 10
     assert lm.THR_SETS[0] == (0, 0, 0, 0)
-    dev, dur, want = cd.step_streams(plant, K, seed, start, period)
-    dev2, dur2, got, _ = lm.step_streams(plant, K, seed, start, period)
+    dev, dur, want, _ = ct.step_streams(DIST, plant, K, seed, start, period)
+    dev2, dur2, got, _ = ct.step_streams(LOSS, plant, K, seed, start, period)
     assert (dev == dev2).all() and (dur == dur2).all()
     for k in range(K):
         for f, w in want[k].items():
@@ -101,23 +103,23 @@ def test_zero_thresholds_give_the_disturbance_model_field_for_field(plant):
 
 def test_zero_thresholds_give_the_disturbance_models_fused_references():
     zero = (0, 0, 0, 0)
-    a, b = lm.schedule_streams(lm.MAX_STEPS, thr=zero), cd.schedule_streams(cd.MAX_STEPS)
-    assert same(a[1], b[1]) and same(a[3], b[3]) and same(a[4], b[4])
-    for f, w in b[2].items():
-        assert same(a[2][f], w), f
-    assert (a[2]["lost"] == 0).all() and (a[2]["loss_count"] >= a[2]["n_tx"].astype(np.uint64)).all()
+    a, b = ct.schedule_streams(LOSS, lm.MAX_STEPS, thr=zero), ct.schedule_streams(DIST, cd.MAX_STEPS)
+    assert same(a.tally, b.tally) and same(a.ang, b.ang) and same(a.ended, b.ended)
+    for f, w in b.final.items():
+        assert same(a.final[f], w), f
+    assert (a.final["lost"] == 0).all() and (a.final["loss_count"] >= a.final["n_tx"].astype(np.uint64)).all()
 
 
 # ---- 4. conditions on the fixtures ---------------------------------------------------------------------------------------------------------
 def _fused(case):
     if case == "staged":
-        r = lm.episode_streams(lm.SHORT_MAX_STEPS)
-        return r[2], r[3], r[4], r[5]
+        r = ct.episode_streams(LOSS, lm.SHORT_MAX_STEPS)
+        return r.ang, r.ended, r.final, r.envs
     if case == "schedules":
-        r = lm.schedule_streams(lm.MAX_STEPS)
-        return r[3], r[4], r[2], r[5]
-    r = lm.feedback_streams(lm.MAX_STEPS)
-    return r[1]["angle"], r[1]["ended"], r[2], r[3]
+        r = ct.schedule_streams(LOSS, lm.MAX_STEPS)
+        return r.ang, r.ended, r.final, r.envs
+    r = ct.feedback_streams(LOSS, lm.MAX_STEPS)
+    return r.rows["angle"], r.rows["ended"], r.final, r.envs
 
 
 @pytest.mark.parametrize("case", ["staged", "schedules", "feedback"])
@@ -147,7 +149,7 @@ def test_fused_fixtures_lose_and_deliver_on_every_link_and_end_by_both_causes(ca
 
 def test_failing_link_step_fixture_draws_for_transmissions_the_phy_rejected():
     from test_control_loop_edges import K, PERIOD, SEED, START
-    _, _, steps, models = lm.step_streams(None, K, SEED, START, PERIOD, layout=lm.FAILING_LAYOUT)
+    _, _, steps, models = ct.step_streams(LOSS, None, K, SEED, START, PERIOD, layout=lm.FAILING_LAYOUT)
     rejected = sum(m.loss.rejected_draws for row in models for m in row)
     commands = sum(1 for row in models for m in row for p in m.loss.sent if p.loss_link == 3)
     print("draws on rejected transmissions", rejected, "commands sent", commands)
@@ -158,7 +160,7 @@ def test_failing_link_step_fixture_draws_for_transmissions_the_phy_rejected():
 
 
 def test_step_fixture_is_bounded_and_loses_on_every_link():
-    _, _, steps, models = lm.step_streams(None, 70, 1, 20, 10)
+    _, _, steps, models = ct.step_streams(LOSS, None, 70, 1, 20, 10)
     ang = np.array([w["ang"] for w in steps])
     assert np.isfinite(ang).all() and np.abs(ang).max() < 2000.0, np.abs(ang).max()
     last = steps[-1]
@@ -180,12 +182,12 @@ def test_a_wrong_rule_would_be_caught(wrong):
     (on the default geometry every packet decodes and it is the right rule), the others on the schedule case."""
     if wrong == "phy_only":
         from test_control_loop_edges import K, PERIOD, SEED, START
-        right = lm.step_streams(None, K, SEED, START, PERIOD, layout=lm.FAILING_LAYOUT)[2][-1]
-        other = lm.step_streams(None, K, SEED, START, PERIOD, layout=lm.FAILING_LAYOUT, mode="phy_only")[2][-1]
+        right = ct.step_streams(LOSS, None, K, SEED, START, PERIOD, layout=lm.FAILING_LAYOUT).steps[-1]
+        other = ct.step_streams(LOSS, None, K, SEED, START, PERIOD, layout=lm.FAILING_LAYOUT, mode="phy_only").steps[-1]
     else:
-        right = lm.schedule_streams(lm.MAX_STEPS)[2]
+        right = ct.schedule_streams(LOSS, lm.MAX_STEPS).final
         kw = {"restart_loss_n": True} if wrong == "restart_n" else {"mode": wrong}
-        other = lm.schedule_streams(lm.MAX_STEPS, **kw)[2]
+        other = ct.schedule_streams(LOSS, lm.MAX_STEPS, **kw).final
     fields = _differs(other, right)
     print(wrong, "moves", fields)
     assert fields, wrong

@@ -15,44 +15,17 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ctrl_episodes_model import FIELDS, EpisodicControlLoop, run_schedule
-from test_control_loop import DENSE_CTRL, STREAMS, model_streams, stream_of
+from ctrl_fixtures import (ALL_FIELDS, DENSE_CTRL, EP_SEED, PERIOD, START, STREAMS, U0S, X0S, T, assert_same, same_bits, schedules_of,
+                           stream_of)
+from ctrl_fixtures import rows_of as _rows
+from test_control_loop import model_streams
 
-START, PERIOD = 5, 3
-# 8 initial states {wagon pos, wagon vel, angle, angle rate} and inputs: small and large angles of both signs, some already moving
-X0S = np.array([[0.0, 0.0, 0.05, 0.0], [0.1, 0.0, -0.3, 0.0], [0.0, 0.2, 0.8, 0.0], [0.0, 0.0, 1.55, 1.0],
-                [-0.2, 0.0, -1.45, 0.0], [0.0, -0.1, -1.56, -0.8], [0.0, 0.0, 0.02, 3.0], [0.3, 0.0, -1.0, -4.5]])
-U0S = np.array([0.1, -0.2, 0.0, 0.3, 0.1, -0.1, 0.25, 0.05])
-EP_STEPS, EP_MAX, EP_FAIL, EP_SEED = 60, 7, 90.0, 31            # test 3: max_steps does not divide the step count
+EP_STEPS, EP_MAX, EP_FAIL = 60, 7, 90.0                         # test 3: max_steps does not divide the step count
 SCHED_STEPS, SCHED_MAX, SCHED_FAIL = 60, 25, 90.0               # test 4
-ALL_FIELDS = FIELDS + ("wake", "flags", "age", "cost", "x_init", "u_init")
-
-
-def schedules_of(P, L):
-    """The P schedules of length L of test 4, as uint8[P][L][2]; every set holds bytes outside the action space."""
-    from gymwipe_amd import actions
-    if L == 1:
-        rows = [[(0, 19)], [(1, 250)], [(0, 0)], [(9, 19)]]
-    elif L == 3:
-        rows = [[(0, 19), (1, 19), (0, 7)], [(0, 0)], [(1, 5), (7, 200), (0, 20)], [(0, 19)]]
-    else:
-        rng = np.random.default_rng(100 + L)
-        rows = [list(zip(rng.integers(0, 2, L).tolist(), rng.integers(0, 20, L).tolist())) for _ in range(4)]
-        rows[1] = [(0, 19), (1, 19)]                             # padded cyclically to L
-        rows[2][5], rows[2][40 % L] = (255, 255), (2, 19)
-    return actions.make_ctrl_schedules(rows[:P], L)
 
 
 def wrapper(s, **kw):
     return EpisodicControlLoop(x0=X0S[s], u0=U0S[s], start=START, period=PERIOD, **kw)
-
-
-def _rows(states):
-    """[{field: value}] of STREAMS (or more) models -> {field: array}, in get_state's dtypes."""
-    out = {}
-    for f in states[0]:
-        a = np.array([st[f] for st in states])
-        out[f] = a.astype(np.float64) if f in ("now", "x", "u", "angle_deg", "rx_power", "cost") else a.astype(np.int64)
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,21 +69,6 @@ def schedule_streams(P, L):
     return sch, tally, dev, dur, final, worst
 
 
-def same_bits(g, w):
-    g, w = np.asarray(g), np.asarray(w)
-    if w.dtype == np.float64:
-        return np.asarray(g, np.float64).view(np.uint64) == w.view(np.uint64)
-    if w.dtype == np.float32:
-        return np.asarray(g, np.float32).view(np.uint32) == w.view(np.uint32)
-    return g.astype(np.int64) == w.astype(np.int64)
-
-
-def assert_same(got, want, what):
-    same = same_bits(got, want)
-    assert same.all(), (what, np.argwhere(~same)[:4].tolist())
-    return True
-
-
 def state_of(env, fields=ALL_FIELDS):
     return {f: env.get_state(f) for f in fields}
 
@@ -131,11 +89,6 @@ def make_env(N, plant=None, own_states=False):
         env.set_initial_state(torch.from_numpy(X0S[so]), torch.from_numpy(U0S[so]))
         env.reset_envs()
     return env
-
-
-def T(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a))
 
 
 # ---- 1. reset --------------------------------------------------------------------------------------------------------------------------

@@ -7,8 +7,6 @@ by both causes and stays inside the int32 observation's range -- and the fused k
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -18,6 +16,7 @@ from gymwipe_amd import actions
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ctrl_episodes_model import EpisodicControlLoop, run_schedule
+from util import private_segments
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -178,20 +177,8 @@ def test_the_wrapper_restates_the_episode_rule():
 
 # ---- 4. no scratch -------------------------------------------------------------------------------------------------------------------
 def test_the_fused_control_loop_kernels_use_no_scratch_memory_and_are_plain_functions(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
+    kernels = private_segments(tmp_path, "ctrl_rollout.hip")
     csrc = os.path.join(ROOT, "gymwipe_amd", "csrc")
-    flags = subprocess.run(["make", "-s", "-C", csrc, "print-flags"], check=True, capture_output=True, text=True).stdout.split()
-    assert "--offload-arch=gfx950" in flags and "-ffp-contract=off" in flags, flags
-    out = tmp_path / "ctrl_rollout.s"
-    subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", "-o", str(out), "-x", "hip", os.path.join(csrc, "ctrl_rollout.hip")],
-                   check=True, capture_output=True, timeout=900, cwd=csrc)
-    text = out.read_text()
-    sizes = re.findall(r"^\s+\.private_segment_fixed_size:\s+(\d+)", text, re.M)
-    names = re.findall(r"^\s+\.name:\s+(\S+)", text, re.M)
-    assert sizes and len(sizes) == len(names)
-    kernels = dict(zip(names, map(int, sizes)))
     for want in ("ctrl_rollout_kernel", "ctrl_rollout_sched_kernel", "ctrl_reset_kernel", "ctrl_set_initial_kernel"):
         assert any(want in n for n in kernels), (want, sorted(kernels))
     assert all(v == 0 for v in kernels.values()), kernels

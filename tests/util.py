@@ -63,6 +63,29 @@ def kernel_instantiations(path, family):
     return names
 
 
+def private_segments(tmp_path, source):
+    """Cross-compile ``gymwipe_amd/csrc/<source>`` for the device alone with the product build's own flags (``make
+    print-flags``: they change register allocation) and return {kernel symbol: private_segment_fixed_size}: a kernel that uses
+    no scratch memory has 0.  Needs hipcc and no GPU; skips the test where there is no hipcc."""
+    import os
+    import shutil
+    import pytest
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gymwipe_amd", "csrc")
+    flags = subprocess.run(["make", "-s", "-C", csrc, "print-flags"], check=True, capture_output=True, text=True).stdout.split()
+    assert "--offload-arch=gfx950" in flags and "-ffp-contract=off" in flags, flags
+    out = tmp_path / (source + ".s")
+    subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", "-o", str(out), "-x", "hip", os.path.join(csrc, source)],
+                   check=True, capture_output=True, timeout=900, cwd=csrc)
+    text = out.read_text()
+    sizes = re.findall(r"^\s+\.private_segment_fixed_size:\s+(\d+)", text, re.M)
+    names = re.findall(r"^\s+\.name:\s+(\S+)", text, re.M)
+    assert sizes and len(sizes) == len(names)
+    return dict(zip(names, map(int, sizes)))
+
+
 # ---- linear plant: models, the substep schedule, a long-double reference and a float64 emulation of the tabulated form ----
 # Test infrastructure in numpy alone: nothing here imports the library.
 PLANT_KMAX = 32                                                # GW_PLANT_KMAX: the largest tabulated substep count
